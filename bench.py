@@ -169,14 +169,52 @@ def lane_utilisation(st: dict) -> dict:
                 "2x2 blocks on the headline view)"}
 
 
+DUMP_BYTES = 60 * 10**6  # --dump-outputs writes at most this many bytes of array data (the limit is 64 MB)
+
+
+def dump_outputs(path, out, grads):
+    """--dump-outputs: what the last timed step handed its caller -- the images render() returned and the gradients the backward
+    left in the parameters -- as float32 .npy files, so that two builds can be compared output for output.  When everything
+    does not fit in DUMP_BYTES, a fixed seeded sample: the same pixels of every image ([C, n]) and the same Gaussians of every
+    per-Gaussian array ([n, ...]), chosen from the image size and the Gaussian count alone and written beside them
+    (pixel_index.npy, gaussian_index.npy, float64).  A gradient that is None is not written."""
+    images = {k: out[k].detach() for k in ("render", "semantics", "depth", "alpha")}
+    per_gaussian = {"radii": out["radii"], "grad_means2D": out["viewspace_points"].grad, **grads}
+    per_gaussian = {k: v.detach() for k, v in per_gaussian.items() if v is not None}
+    H, W = images["render"].shape[-2:]
+    HW, P = H * W, out["radii"].shape[0]
+    dev = out["radii"].device
+
+    def sample(total, floats_per_item, seed):
+        n = min(total, (DUMP_BYTES // 2) // (4 * floats_per_item + 8))
+        idx = np.arange(total) if n == total else np.sort(np.random.default_rng(seed).choice(total, n, replace=False))
+        return idx, torch.from_numpy(idx).to(dev)
+
+    pix, pix_d = sample(HW, sum(t.shape[0] for t in images.values()), 1)
+    gid, gid_d = sample(P, sum(t.numel() // P for t in per_gaussian.values()), 2)
+    arrays = {"pixel_index": pix.astype(np.float64), "gaussian_index": gid.astype(np.float64)}
+    for k, t in images.items():
+        arrays[k] = t.reshape(t.shape[0], HW).index_select(1, pix_d).float().cpu().numpy()
+    for k, t in per_gaussian.items():
+        arrays[k] = t.reshape(P, -1).index_select(0, gid_d).float().cpu().numpy().reshape((-1,) + tuple(t.shape[1:]))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {"dir": path, "bytes": total, "pixels": int(pix.size), "gaussians": int(gid.size)}
+
+
 def main():
     from goi_hyperplane_amd.scene import HEADLINE
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)  # >= 50: one host hiccup is < 2 % of the timed region
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the timed region (exactly --steps steps) is run this many times; value = the median repeat")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--P", type=int, default=HEADLINE["P"])
     ap.add_argument("--S", type=int, default=HEADLINE["S"])
     ap.add_argument("--W", type=int, default=HEADLINE["W"])
@@ -470,18 +508,21 @@ def main():
     # host time of every step's enqueue (a clock read per step, no synchronisation: the timed region is unchanged).
     # Informational only -- `value` is K steps over the barrier-bracketed time -- it separates a host stall
     # (max >> median; see profiles/r01_n0_bench_anomalous.json) from a run that is uniformly slow.
-    # The timed region (exactly K steps between barrier + synchronize) is run `--repeats` times back to back and `value`
-    # is the MEDIAN repeat: with the driver's --steps 20 one region is ~30 ms of GPU time, and a single 3 ms host hiccup
-    # is 10 % of it.  Every repeat is listed in the JSON line (`repeats_ms_per_step`); the events around the dominant
-    # kernel, the enqueue marks and the speculation counters below are those of the median repeat's siblings as well.
+    # The timed region (exactly K steps between barrier + synchronize) is run once, so that --steps is the number of timed
+    # steps.  --repeats N runs it N times back to back and `value` is the MEDIAN repeat: with --steps 20 one region is
+    # ~30 ms of GPU time, and a single 3 ms host hiccup is 10 % of it.  Every repeat is listed in the JSON line
+    # (`repeats_ms_per_step`); the events around the dominant kernel, the enqueue marks and the speculation counters below
+    # are those of the median repeat's siblings as well.
     spec0 = rasterizer.speculation_stats()
     runs = []
     for rep in range(max(1, args.repeats)):
         marks = [0.0] * (args.steps + 1)
         t0 = marks[0] = time.perf_counter()
         for i in range(args.steps):
-            step(args.warmup + i)
+            last_out = step(args.warmup + i)
             marks[i + 1] = time.perf_counter()
+            if i + 1 < args.steps:
+                last_out = None  # (only the last step's outputs outlive their step)
         drain()  # the last step's exchange completes inside the timed region
         barrier()
         el = time.perf_counter() - t0
@@ -491,6 +532,12 @@ def main():
             runs.append((float(t_.item()), el, marks, t0))
         else:
             runs.append((el, el, marks, t0))
+    dumped = None
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dumped = dump_outputs(args.dump_outputs, last_out, {
+            "grad_means3D": pc._xyz.grad, "grad_sh": pc._features.grad, "grad_semantics": pc._semantics.grad,
+            "grad_opacity": pc._opacity.grad, "grad_scales": pc._scaling.grad, "grad_rotations": pc._rotation.grad})
+    last_out = None
     order_ = sorted(range(len(runs)), key=lambda r_: runs[r_][0])
     elapsed_max, elapsed, marks, t0 = runs[order_[len(order_) // 2]]  # the median repeat (by the max-over-ranks time)
     repeats_ms = [round(r_[0] / args.steps * 1e3, 5) for r_ in runs]
@@ -1082,7 +1129,7 @@ def main():
         res = {
             "metric": "training views/sec (rasterizer fwd+bwd), 1M Gaussians @1600x1056 RGB+16-d feat",
             "value": args.steps * world / elapsed, "unit": "views/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "repeats_ms_per_step": repeats_ms,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "repeats_ms_per_step": repeats_ms, "dumped_outputs": dumped,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not args.ply else "ply scene, synthetic cameras",
             "config": {"workload": f"{args.scene}: {args.P} Gaussians @{args.W}x{args.H}, SH deg 3 RGB + {args.S}-d semantic, fwd+bwd"

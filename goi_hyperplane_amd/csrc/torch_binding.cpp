@@ -208,9 +208,12 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> 
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------
-// grow-only scratch per (device, stream): 4*R*129 bytes, dead when the call returns (same stream)
+// grow-only scratch per (device, stream): 4*R*129 bytes, dead when the call returns (same stream).
+// This map and g_pool below hold device tensors and are never destroyed: a destructor run at process exit would free them into
+// a HIP runtime and caching allocator that may already be torn down (they are when this library was loaded before the process
+// first used the GPU), and the process dies with SIGSEGV after its work is done.  The driver reclaims the memory at exit.
 std::mutex g_scratch_mu;
-std::map<std::pair<int, void*>, Tensor> g_scratch;
+std::map<std::pair<int, void*>, Tensor>& g_scratch = *new std::map<std::pair<int, void*>, Tensor>;
 
 void* backward_scratch(size_t bytes, const c10::Device& dev, void* stream, const torch::TensorOptions& byte_opts) {
     std::lock_guard<std::mutex> lk(g_scratch_mu);
@@ -248,7 +251,7 @@ struct PoolKey {
     }
 };
 std::mutex g_pool_mu;
-std::map<PoolKey, std::vector<PoolEntry>> g_pool;
+std::map<PoolKey, std::vector<PoolEntry>>& g_pool = *new std::map<PoolKey, std::vector<PoolEntry>>;  // (never destroyed: see g_scratch)
 bool g_pool_on = []() {
     const char* e = std::getenv("GOI_GRAD_POOL");
     return !(e && (e[0] == '0' || e[0] == 'n' || e[0] == 'f'));

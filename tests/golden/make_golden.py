@@ -375,7 +375,38 @@ def kmeans_pins():
     print("wrote ref_kmeans_pins")
 
 
+def caller_pins():
+    """ref_caller_pins.json -- how the reference's own caller (gaussian_renderer/__init__.py, render() and trace()) drives the
+    drop-in module, read from its AST: the parameters of each function, the keywords of its GaussianRasterizationSettings(...),
+    GaussianRasterizer(...) and rasterizer(...) / rasterizer.trace(...) calls, and the attributes it reads off the camera, the
+    model and the pipeline object.  tests/test_reference_callers_cpu.py makes those calls on this package."""
+    import ast
+    import json
+    tree = _ref_ast("gaussian_renderer/__init__.py")
+    pins = {}
+    for fn in tree.body:
+        if not (isinstance(fn, ast.FunctionDef) and fn.name in ("render", "trace")):
+            continue
+        calls, reads = {}, {"viewpoint_camera": set(), "pc": set(), "pipe": set()}
+        for node in ast.walk(fn):
+            if isinstance(node, ast.Call):
+                f = node.func
+                name = f.id if isinstance(f, ast.Name) else (
+                    f.value.id + "." + f.attr if isinstance(f, ast.Attribute) and isinstance(f.value, ast.Name) else None)
+                if name in ("GaussianRasterizationSettings", "GaussianRasterizer", "rasterizer", "rasterizer.trace"):
+                    calls[name] = [k.arg for k in node.keywords]
+            elif isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in reads:
+                reads[node.value.id].add(node.attr)
+        pins[fn.name] = {"parameters": [a.arg for a in fn.args.args], "calls": calls,
+                         "reads": {k: sorted(v) for k, v in reads.items()}}
+    with open(os.path.join(HERE, "ref_caller_pins.json"), "w") as fh:
+        json.dump(pins, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote ref_caller_pins")
+
+
 if __name__ == "__main__":
+    caller_pins()
     knn_golden()
     kmeans_pins()
     ref_python_pins()

@@ -1,74 +1,59 @@
-"""The reference's OWN caller, executed unchanged against this repository's drop-in package (runs only where
-/root/reference exists, i.e. in the authoring container; the GPU box has no reference and skips).
+"""The reference's own caller, replayed against this repository's drop-in package.
 
-gaussian_renderer/__init__.py:14 does `from diff_gaussian_rasterization import GaussianRasterizationSettings,
-GaussianRasterizer` and, in render() (:18-105) and trace() (:107-190), builds the settings tuple and calls the module with
-keyword arguments.  Here that file is imported as it is -- only `scene.gaussian_model` (needed for a type annotation;
-its own imports want plyfile and a CUDA device) is replaced by an empty stand-in module -- and its render() / trace() are
-called on CPU tensors.  There is no GPU in this container, so the call must travel through the reference's code, bind every
-field and keyword of this package's API, and stop at the one place this package refuses: "no CPU fallback".  Any mismatch
-in names, field order or keywords would raise something else (TypeError) first."""
-import importlib
+tests/golden/ref_caller_pins.json records, from the AST of the reference's gaussian_renderer/__init__.py (make_golden.py:
+caller_pins), how its render() and trace() drive `diff_gaussian_rasterization`: the keywords of their
+GaussianRasterizationSettings(...), GaussianRasterizer(...) and rasterizer(...) / rasterizer.trace(...) calls, and the attributes
+they read off the camera, the model and the pipeline object.  Here those calls are made on CPU tensors with exactly the
+recorded keywords, on this package's camera, model and pipeline objects: with the rasterizer's own SH and covariance paths and
+with the Python-side ones (colours and cov3D precomputed).  There is no GPU in this container, so the call must bind every field
+and keyword of this package's API and stop at the one place this package refuses: "no CPU fallback".  Any mismatch in names or
+keywords raises something else (AttributeError, TypeError, KeyError) first."""
+import json
+import math
 import os
-import sys
-import types
 
 import pytest
 import torch
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "gaussian_renderer")),
-                                reason="the reference checkout is only present in the authoring container")
+with open(os.path.join(ROOT, "tests", "golden", "ref_caller_pins.json")) as _fh:
+    PINS = json.load(_fh)
 
 
-@pytest.fixture()
-def ref_renderer(monkeypatch):
-    for name in ("scene", "scene.gaussian_model"):
-        m = types.ModuleType(name)
-        m.__path__ = []  # a package without content
-        monkeypatch.setitem(sys.modules, name, m)
-    sys.modules["scene.gaussian_model"].GaussianModel = object
-    monkeypatch.syspath_prepend(REF)
-    monkeypatch.syspath_prepend(ROOT)  # this repository's diff_gaussian_rasterization wins
-    for name in ("gaussian_renderer", "utils", "utils.sh_utils"):
-        sys.modules.pop(name, None)
-    mod = importlib.import_module("gaussian_renderer")
-    assert mod.__file__.startswith(REF)
+def _replay(fn, python_paths=False):
     import diff_gaussian_rasterization as dgr
-    assert dgr.__file__.startswith(ROOT) and mod.GaussianRasterizer is dgr.GaussianRasterizer
-    # the reference allocates its screen-space placeholder with device="cuda" (:26); there is none here
-    real = torch.zeros_like
-    monkeypatch.setattr(torch, "zeros_like", lambda t, **k: real(t, **{kk: v for kk, v in k.items() if kk != "device"}))
-    yield mod
-    for name in ("gaussian_renderer", "utils", "utils.sh_utils"):
-        sys.modules.pop(name, None)
-
-
-def _model_and_camera():
-    from goi_hyperplane_amd.render import GaussianSet, TorchCamera
+    from goi_hyperplane_amd.render import GaussianSet, PipelineParams, TorchCamera
     from goi_hyperplane_amd.scene import make_camera, make_scene
+    pins = PINS[fn]
     pc = GaussianSet.from_scene(make_scene(50, S=10, seed=0), torch.device("cpu"))
     cam = TorchCamera(make_camera(64, 48), torch.device("cpu"))
-    return pc, cam
-
-
-class _Pipe:
-    convert_SHs_python = False
-    compute_cov3D_python = False
-    debug = False
+    pipe = PipelineParams()
+    pipe.convert_SHs_python = pipe.compute_cov3D_python = python_paths
+    for obj, name in ((cam, "viewpoint_camera"), (pc, "pc"), (pipe, "pipe")):
+        missing = [a for a in pins["reads"][name] if not hasattr(obj, a)]
+        assert not missing, (name, missing)
+    settings = {"image_height": int(cam.image_height), "image_width": int(cam.image_width),
+                "tanfovx": math.tan(cam.FoVx * 0.5), "tanfovy": math.tan(cam.FoVy * 0.5), "bg": torch.zeros(3),
+                "scale_modifier": 1.0, "viewmatrix": cam.world_view_transform, "projmatrix": cam.full_proj_transform,
+                "sh_degree": pc.active_sh_degree, "campos": cam.camera_center, "prefiltered": False, "debug": pipe.debug}
+    rs = dgr.GaussianRasterizationSettings(**{k: settings[k] for k in pins["calls"]["GaussianRasterizationSettings"]})
+    rasterizer = dgr.GaussianRasterizer(**{k: rs for k in pins["calls"]["GaussianRasterizer"]})
+    xyz = pc.get_xyz
+    values = {"means3D": xyz, "means2D": torch.zeros_like(xyz, requires_grad=True) + 0, "opacities": pc.get_opacity,
+              "shs": None if python_paths else pc.get_features,
+              "colors_precomp": torch.full_like(xyz, 0.5) if python_paths else None,
+              "scales": None if python_paths else pc.get_scaling, "rotations": None if python_paths else pc.get_rotation,
+              "cov3D_precomp": pc.get_covariance(1.0) if python_paths else None,
+              "semantics": pc.get_semantics, "img_sem": torch.zeros(10, 48, 64)}
+    call, name = (rasterizer.trace, "rasterizer.trace") if fn == "trace" else (rasterizer, "rasterizer")
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        call(**{k: values[k] for k in pins["calls"][name]})
 
 
 @pytest.mark.parametrize("python_paths", [False, True])
-def test_reference_render_reaches_this_packages_operator(ref_renderer, python_paths):
-    pc, cam = _model_and_camera()
-    pipe = _Pipe()
-    pipe.convert_SHs_python = pipe.compute_cov3D_python = python_paths
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        ref_renderer.render(cam, pc, pipe, torch.zeros(3))
+def test_reference_render_reaches_this_packages_operator(python_paths):
+    _replay("render", python_paths)
 
 
-def test_reference_trace_reaches_this_packages_operator(ref_renderer):
-    pc, cam = _model_and_camera()
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        ref_renderer.trace(cam, pc, torch.zeros(10, 48, 64), _Pipe(), torch.zeros(3))
+def test_reference_trace_reaches_this_packages_operator():
+    _replay("trace")
