@@ -40,6 +40,7 @@ UNITS = {
     "knn.hip": ["-ffp-contract=off"],
     "adam.hip": ["-ffp-contract=off"],
     "codebook_loss.hip": [],
+    "osh.hip": [],
 }
 
 

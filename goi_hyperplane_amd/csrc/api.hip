@@ -883,6 +883,35 @@ int goi_semantic_decode(const float* sem, int S, long long HW, const float* W, c
     return 0;
 }
 
+int goi_semantic_osh_counts(const int* idx, const uint8_t* positive, long long HW, int n_codes, int* counts, void* stream) {
+    if (HW < 0) return fail("goi_semantic_osh_counts: bad HW");
+    if (n_codes < 1 || n_codes > osh_max_codes()) return fail("goi_semantic_osh_counts: need 1 <= n_codes <= 1000");
+    if (!counts) return fail("goi_semantic_osh_counts: counts is NULL");
+    if (HW == 0) return 0;
+    if (!idx || !positive) return fail("goi_semantic_osh_counts: NULL input");
+    launch_osh_counts(idx, positive, HW, n_codes, counts, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts, long long HW, int K, float* w, float* b,
+                         float lr, int max_epochs, double target_iou, int* epochs_out, float* loss_out, double* iou_out,
+                         double* init_iou_out, double* trace, void* stream) {
+    refresh_options();
+    if (n_codes < 1 || n_codes > osh_max_codes()) return fail("goi_semantic_osh_fit: need 1 <= n_codes <= 1000");
+    if (D < 1 || D > osh_max_dim()) return fail("goi_semantic_osh_fit: need 1 <= D <= 1024");
+    if (HW < 1 || HW >= (1ll << 31)) return fail("goi_semantic_osh_fit: need 1 <= HW < 2^31");
+    if (K < 0 || K > 65535) return fail("goi_semantic_osh_fit: need 0 <= K <= 65535");
+    if (max_epochs < 1 || max_epochs > GOI_OSH_MAX_EPOCHS) return fail("goi_semantic_osh_fit: need 1 <= max_epochs <= 1000000");
+    if (K == 0) return 0;
+    if (!lut || !counts || !w || !b || !epochs_out || !loss_out || !iou_out || !init_iou_out)
+        return fail("goi_semantic_osh_fit: a required pointer is NULL");
+    launch_osh_fit(lut, n_codes, D, counts, HW, K, w, b, lr, max_epochs, target_iou, epochs_out, loss_out, iou_out,
+                   init_iou_out, trace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
 int goi_codebook_loss_partial_rows(void) { return codebook_loss_waves(); }
 
 int goi_codebook_loss_rows(const float* sim_raw, const float* inv_gnorm, const float* sem, const float* W,
@@ -1022,6 +1051,10 @@ int goi_raster_set_option(const char* name, int value) {
     else if (!strcmp(name, "bwd_records")) {
         if (value < 0 || value > 2) return fail("bwd_records must be 0, 1 or 2");
         g_options.bwd_records = value;
+    }
+    else if (!strcmp(name, "osh_path")) {
+        if (value < 0 || value > 1) return fail("osh_path must be 0 or 1");
+        g_options.osh_path = value;
     }
     else return fail(std::string("unknown option ") + name);
     return 0;

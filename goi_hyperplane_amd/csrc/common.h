@@ -136,6 +136,8 @@ struct Options {
                            // reduce_rows_k; 128-byte rows), 1 the per-Gaussian sums stay in the row scratch as records and
                            // preprocess_bwd_k writes every per-id output (default), 0 reduce_rows_k writes six per-id arrays
                            // (and zeros for the unlisted Gaussians) that preprocess_bwd_k reads back.  Same gradients, bit for bit.
+    int osh_path = 0;      // goi_semantic_osh_fit: 0 the register path where the shape allows it (D = 256, n_codes <= 320), 1 always
+                           // the generic path (z re-formed from the LUT every epoch).  Same results, bit for bit.
 };
 // The switches an entry point works with are a per-THREAD snapshot taken when the call starts (refresh_options):
 // goi_raster_set_option changes the process-wide set under a mutex, and a call that is already running on another host
@@ -262,6 +264,13 @@ int launch_codebook_fused(const float* g, const float* l1, const float* sem, con
                           int C, int D, int S, float t, float* dsem, float* partials, float* dl1_partial, void* workspace,
                           hipStream_t s);
 int launch_codebook_dlut(const float* dsim, const float* g, long long HW, int C, int D, float* partial, hipStream_t s);
+int osh_max_codes();
+int osh_max_dim();
+bool osh_register_path(int n_codes, int D);
+void launch_osh_counts(const int* idx, const uint8_t* positive, long long HW, int n_codes, int* counts, hipStream_t s);
+void launch_osh_fit(const float* lut, int n_codes, int D, const int* counts, long long HW, int K, float* w, float* b,
+                    float lr, int max_epochs, double target_iou, int* epochs_out, float* loss_out, double* iou_out,
+                    double* init_iou_out, double* trace, hipStream_t s);
 int launch_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
                      const uint8_t* nograd_mask, const uint32_t* skip_flag, hipStream_t s);
 size_t knn_workspace_bytes(int P);

@@ -5,7 +5,9 @@ rendered S-dim feature into one of `tab_len` codes, the 256-d code book (LUT), t
 Mirrors, with the same names / constructor arguments / file formats so that the reference's
 checkpoints load unchanged:
     SemanticModel            scene/semantic_model.py:13-63   ({"args", "state_dict"} save format)
-    LinearSVM.forward        networks.py:12-59               (x / 0.3438 -> Linear(256, 1))
+    LinearSVM                networks.py:12-67               (x / 0.3438 -> Linear(256, 1), hinge loss, SGD)
+    fit_hyperplane           gui/main.py:1673-1763           (the OSH fine-tune against a mask: one HIP kernel)
+    select_gaussians         gui/main.py:400-405             (Gaussians of interest)
     compute_similarity       gui/main.py:364-386             (inference decode)
     codebook_losses          train.py:142-163                (training losses)
 
@@ -23,6 +25,7 @@ from __future__ import annotations
 
 import ctypes as C
 import ctypes as C_
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -69,16 +72,62 @@ class SemanticModel(torch.nn.Module):
 
 
 class LinearSVM(torch.nn.Module):
-    """The hyperplane of the paper: one Linear(input_dim -> 1) applied to x / 0.3438 (networks.py:12-59)."""
+    """The hyperplane of the paper: one Linear(input_dim -> 1) applied to x / 0.3438, trained with hinge loss and plain
+    SGD (networks.py:12-59).  `step` is the reference's per-pixel epoch -- it runs wherever torch runs and is the parity
+    reference of `fit_hyperplane`, which runs every epoch of the fit in one HIP kernel."""
 
-    def __init__(self, set_bias=0.86, input_dim=256):
+    def __init__(self, set_bias=0.86, input_dim=256, lr=0.01):
         super().__init__()
         self.linear = torch.nn.Linear(input_dim, 1)
         b = torch.tensor(set_bias)
         torch.nn.init.constant_(self.linear.bias, float(2 - torch.log(b / (1 - b))))
+        self.optimizer = torch.optim.SGD(self.parameters(), lr=lr)
+
+    def weight_set(self, weights):
+        with torch.no_grad():
+            self.linear.weight.copy_(weights)
+
+    @torch.no_grad()
+    def eval_forward(self, x, y):
+        """IoU of (output > 0) against (y > 0) over the rows of x."""
+        self.optimizer.zero_grad()
+        output = self.forward(x).squeeze()
+        return calculate_iou(y.squeeze() > 0, output > 0)
+
+    def step(self, x, y):
+        """One epoch: hinge loss on x [n, D] against y [n] (or [n, 1]) in {0, 1}, backward, SGD step; returns the loss
+        (before the step) and the IoU after it."""
+        self.optimizer.zero_grad()
+        y = y.squeeze()
+        output = self.forward(x).squeeze()
+        loss = hinge_loss(output, y)
+        loss.backward()
+        self.optimizer.step()
+        with torch.no_grad():
+            output = self.forward(x).squeeze()
+            iou = calculate_iou(y > 0, output > 0)
+        return loss, iou
 
     def forward(self, x):
         return self.linear(x / 0.3438)
+
+
+def hinge_loss(outputs, labels):
+    """mean(max(0, 1 - o * (2 y - 1))) (networks.py:62-67)."""
+    labels = 2 * labels - 1
+    return torch.mean(torch.clamp(1 - outputs * labels, min=0))
+
+
+def calculate_iou(label, pred):
+    """|pred & label| / |pred | label| of two boolean masks as a Python float, NaN for an empty union
+    (utils/image_utils.py:59-70)."""
+    pred_inds = pred == 1
+    label_inds = label == 1
+    intersection = torch.logical_and(pred_inds, label_inds).sum()
+    union = torch.logical_or(pred_inds, label_inds).sum()
+    if union == 0:
+        return float("nan")
+    return float(intersection) / float(max(union, 1))
 
 
 @torch.no_grad()
@@ -282,3 +331,183 @@ def fused_codebook_losses(sem_feature_chw: torch.Tensor, semantic_mlp: SemanticM
     t = 1.0 if iteration < 1000 else 2.0
     loss, terms = _FusedCodebookLoss.apply(sem_feature_chw, lin.weight, lin.bias, lut1, gtl_chw, t)
     return loss, {"lab": terms[0], "sl": terms[1], "sl1": terms[2], "recc": terms[3]}
+
+
+# ---- the optimisable semantic-space hyperplane (OSH) fine-tune: gui/main.py:1673-1763 (finetune_prompt_with_res) ---------
+# Every pixel's feature is one of n_codes normalised LUT rows, so the reference's per-pixel loop (hinge loss, SGD, IoU per
+# epoch) depends on the frame only through P[c] / N[c], the mask-positive / -negative pixel counts per code.
+# csrc/osh.hip counts them in one pass and runs every epoch of the fit, with its stop test, in one workgroup.
+
+OSH_MAX_CODES = 1000
+OSH_MAX_DIM = 1024
+OSH_MAX_EPOCHS = 1_000_000
+
+OSHFit = namedtuple("OSHFit", ["epochs", "loss", "iou", "init_iou", "trace"])
+OSHFit.__doc__ = ("Result of fit_hyperplane: epochs run, the last epoch's loss (before its step), the IoU after the last "
+                  "step and that of the initial hyperplane (Python floats; NaN for an empty union), and with return_trace "
+                  "a float64 [epochs, 2] tensor of (loss, IoU) per epoch (else None).")
+
+_NO_CPU = "goi_hyperplane_amd.semantic: tensors must live on a ROCm GPU; there is no CPU fallback"
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+@torch.no_grad()
+def osh_counts(idx: torch.Tensor, positive: torch.Tensor, n_codes: int) -> torch.Tensor:
+    """int32 [2, n_codes]: row 0 the pixels with idx == c and positive != 0, row 1 those with positive == 0 (one HIP
+    kernel over idx [HW] int32 and positive [HW] bool / uint8).  Codes outside [0, n_codes) are not counted."""
+    n_codes = int(n_codes)
+    if not 1 <= n_codes <= OSH_MAX_CODES:
+        raise ValueError(f"osh_counts: n_codes must be in 1..{OSH_MAX_CODES}, got {n_codes}")
+    if idx.numel() != positive.numel():
+        raise ValueError("osh_counts: idx and positive must have the same number of elements")
+    if not (idx.is_cuda and positive.is_cuda):
+        raise RuntimeError(_NO_CPU)
+    dev = idx.device
+    idx = idx.reshape(-1).to(torch.int32).contiguous()
+    pos = positive.reshape(-1)
+    pos = (pos if pos.dtype == torch.uint8 else (pos != 0).to(torch.uint8)).contiguous()
+    counts = torch.zeros((2, n_codes), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        r = lib.goi_semantic_osh_counts(C.c_void_p(idx.data_ptr()), C.c_void_p(pos.data_ptr()), idx.numel(), n_codes,
+                                        C.c_void_p(counts.data_ptr()), _stream(dev))
+    if r < 0:
+        raise RuntimeError(_lib.last_error())
+    return counts
+
+
+def _osh_launch(lut, counts, HW, w, b, lr, max_epochs, target_iou, return_trace):
+    """Launches goi_semantic_osh_fit on copies of w [K, D] / b [K]; returns (w, b, packed result buffer, trace view).
+    Nothing is synchronised: the packed buffer holds epochs (int32 [K]), loss (fp32 [K]), iou and init_iou (fp64 [K])."""
+    n_codes, D = int(lut.shape[0]), int(lut.shape[1])
+    if not 1 <= n_codes <= OSH_MAX_CODES:
+        raise ValueError(f"the hyperplane fit covers 1..{OSH_MAX_CODES} codes, got {n_codes}")
+    if not 1 <= D <= OSH_MAX_DIM:
+        raise ValueError(f"the hyperplane fit covers features of 1..{OSH_MAX_DIM} dimensions, got {D}")
+    max_epochs = int(max_epochs)
+    if not 1 <= max_epochs <= OSH_MAX_EPOCHS:
+        raise ValueError(f"max_epochs must be in 1..{OSH_MAX_EPOCHS}, got {max_epochs}")
+    HW = int(HW)
+    if not 1 <= HW < 2 ** 31:
+        raise ValueError(f"HW must be in 1..2^31-1, got {HW}")
+    K = int(w.shape[0])
+    if counts.shape != (K, 2, n_codes) or w.shape != (K, D) or b.shape != (K,):
+        raise ValueError(f"shapes: counts {tuple(counts.shape)} must be ({K}, 2, {n_codes}), w {tuple(w.shape)} ({K}, {D}), "
+                         f"b {tuple(b.shape)} ({K},)")
+    if not (lut.is_cuda and counts.is_cuda and w.is_cuda and b.is_cuda):
+        raise RuntimeError(_NO_CPU)
+    dev = lut.device
+    lut = lut.detach().float().contiguous()
+    counts = counts.to(torch.int32).contiguous()
+    w = w.detach().float().clone().contiguous()
+    b = b.detach().float().clone().contiguous()
+    buf = torch.empty(24 * K + (16 * K * max_epochs if return_trace else 0), dtype=torch.uint8, device=dev)
+    epochs, loss = buf[: 4 * K].view(torch.int32), buf[4 * K: 8 * K].view(torch.float32)
+    iou, init_iou = buf[8 * K: 16 * K].view(torch.float64), buf[16 * K: 24 * K].view(torch.float64)
+    trace = buf[24 * K:].view(torch.float64).view(K, max_epochs, 2) if return_trace else None
+    if trace is not None:
+        trace.fill_(float("nan"))
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        r = lib.goi_semantic_osh_fit(p(lut), n_codes, D, p(counts), HW, K, p(w), p(b), float(lr), max_epochs,
+                                     float(target_iou), p(epochs), p(loss), p(iou), p(init_iou), p(trace), _stream(dev))
+    if r < 0:
+        raise RuntimeError(_lib.last_error())
+    return w, b, buf, trace
+
+
+def _osh_unpack(buf_cpu, K, max_epochs, return_trace):
+    epochs = buf_cpu[: 4 * K].view(torch.int32)
+    if (epochs < 0).any():
+        raise ValueError("a code present in the frame has an all-zero LUT row (the reference's fit would be NaN)")
+    loss = buf_cpu[4 * K: 8 * K].view(torch.float32)
+    iou, init_iou = buf_cpu[8 * K: 16 * K].view(torch.float64), buf_cpu[16 * K: 24 * K].view(torch.float64)
+    trace = buf_cpu[24 * K: 24 * K + 16 * K * max_epochs].view(torch.float64).view(K, max_epochs, 2) if return_trace else None
+    return epochs, loss, iou, init_iou, trace
+
+
+@torch.no_grad()
+def fit_hyperplanes_counts(lut: torch.Tensor, counts: torch.Tensor, HW: int, w: torch.Tensor, b: torch.Tensor, lr: float = 0.01,
+                           max_epochs: int = 8000, target_iou: float = 0.9, return_trace: bool = False):
+    """K independent hyperplane fits over one code book, all in one launch (one workgroup each): lut [n_codes, D],
+    counts [K, 2, n_codes] (osh_counts of each mask), HW the pixels per frame, initial w [K, D] and b [K].  Returns
+    (w [K, D], b [K], [OSHFit per fit]) after one device synchronisation; each OSHFit's trace is [epochs, 2] or None."""
+    K = int(w.shape[0])
+    w, b, buf, _ = _osh_launch(lut, counts, HW, w, b, lr, max_epochs, target_iou, return_trace)
+    epochs, loss, iou, init_iou, trace = _osh_unpack(buf.cpu(), K, int(max_epochs), return_trace)
+    fits = [OSHFit(int(epochs[i]), float(loss[i]), float(iou[i]), float(init_iou[i]),
+                   trace[i, : int(epochs[i])].clone() if return_trace else None) for i in range(K)]
+    return w, b, fits
+
+
+def _decode_idx(sem_chw, mlp, n_codes):
+    """argmax code per pixel (goi_semantic_decode's idx_out), int32 [HW]."""
+    lin = mlp.layers[0]
+    S, HW, dev = int(sem_chw.shape[0]), int(sem_chw[0].numel()), sem_chw.device
+    sem = sem_chw.detach().contiguous().float()
+    W = lin.weight.detach().contiguous().float()
+    bias = (lin.bias.detach() if lin.bias is not None else torch.zeros(n_codes, device=dev)).contiguous().float()
+    idx = torch.empty(HW, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        r = _lib.load().goi_semantic_decode(C.c_void_p(sem.data_ptr()), S, HW, C.c_void_p(W.data_ptr()),
+                                            C.c_void_p(bias.data_ptr()), n_codes, None, 0.0, None, C.c_void_p(idx.data_ptr()),
+                                            None, _stream(dev))
+    if r < 0:
+        raise RuntimeError(_lib.last_error())
+    return idx
+
+
+@torch.no_grad()
+def fit_hyperplane(sem_chw: torch.Tensor, mlp: SemanticModel, lut: torch.Tensor, positive: torch.Tensor, svm: LinearSVM,
+                   max_epochs: int = 8000, target_iou: float = 0.9, return_trace: bool = False) -> OSHFit:
+    """The fine-tune of gui/main.py:1673-1763 on the GPU: decode the rendered map sem_chw [S, H, W] to codes, count the
+    mask `positive` (H*W elements in sem_chw's pixel order; bool, uint8 or float with values 0 / 1) per code, and fit
+    `svm` (hinge loss, SGD with its optimizer's lr) until the IoU is no longer below target_iou or max_epochs have run.
+    svm.linear is updated in place.  One device synchronisation, at the end."""
+    if mlp.num_layer != 1:
+        raise NotImplementedError("the fused decode covers the reference's configuration: one Linear(S -> tab_len)")
+    lin = mlp.layers[0]
+    n_codes, S = int(lin.weight.shape[0]), int(sem_chw.shape[0])
+    if lin.weight.shape[1] != S or lut.shape[0] != n_codes:
+        raise ValueError("shape mismatch between features, MLP and LUT")
+    if n_codes > OSH_MAX_CODES:
+        raise ValueError(f"the hyperplane fit covers up to {OSH_MAX_CODES} codes (the reference slices the decode to "
+                         f"[:, :1000]), got {n_codes}")
+    HW = int(sem_chw[0].numel())
+    if positive.numel() != HW:
+        raise ValueError(f"positive has {positive.numel()} elements, the frame {HW} pixels")
+    weight, bias = svm.linear.weight, svm.linear.bias
+    if weight.shape[1] != lut.shape[1]:
+        raise ValueError("LinearSVM input_dim differs from the LUT's feature size")
+    if not sem_chw.is_cuda or not positive.is_cuda or not lut.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    lr = svm.optimizer.param_groups[0]["lr"]
+    pos = positive.reshape(-1)
+    bad = None if pos.dtype == torch.bool else ((pos != 0) & (pos != 1)).any()
+    idx = _decode_idx(sem_chw, mlp, n_codes)
+    counts = osh_counts(idx, pos, n_codes)
+    w, b, buf, _ = _osh_launch(lut, counts.unsqueeze(0), HW, weight.detach().reshape(1, -1), bias.detach().reshape(1),
+                               lr, max_epochs, target_iou, return_trace)
+    if bad is not None:
+        buf = torch.cat([buf, bad.reshape(1).to(torch.uint8)])
+    host = buf.cpu()  # the one synchronisation
+    if bad is not None and bool(host[-1]):
+        raise ValueError("positive must hold only 0 and 1")
+    epochs, loss, iou, init_iou, trace = _osh_unpack(host, 1, int(max_epochs), return_trace)
+    weight.copy_(w.reshape(weight.shape))
+    bias.copy_(b.reshape(bias.shape))
+    n = int(epochs[0])
+    return OSHFit(n, float(loss[0]), float(iou[0]), float(init_iou[0]), trace[0, :n].clone() if return_trace else None)
+
+
+@torch.no_grad()
+def select_gaussians(pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float = 0.5) -> torch.Tensor:
+    """The Gaussians of interest (gui/main.py:400-405, compute_relative_gs_index): the fused decode of every Gaussian's
+    own semantic feature pc.get_semantics [P, S], scored by score_fn and thresholded; bool [P], ready for
+    render(..., gaussian_mask=...)."""
+    sem = pc.get_semantics.detach().float().t().contiguous()  # [S, P]: the decode's channel-major layout, one "pixel" per Gaussian
+    return compute_similarity(sem, mlp, lut, score_fn, thresh) > 0

@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-/* 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats
+/* 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
+ *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -272,6 +273,29 @@ int goi_semantic_decode(const float* sem, int S, long long HW, const float* W, c
                         const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
                         void* stream);
 
+/* ---- semantic-space hyperplane fine-tune (gui/main.py:1673-1763, finetune_prompt_with_res; csrc/osh.hip) -------------
+ * The reference trains its LinearSVM (networks.py:12-59: o = w . (x / 0.3438) + b) with hinge loss and SGD against a binary
+ * mask, one epoch per step, until IoU >= target_iou or max_epochs.  Every pixel's feature is a normalised code-book row, so
+ * the fit depends on the frame only through two histograms over the decoded codes.
+ *
+ * goi_semantic_osh_counts ADDS into counts [2][n_codes] (int32, the caller zeroes it): row 0 the pixels with idx = c and
+ * positive != 0, row 1 those with positive == 0.  idx [HW] (int32: goi_semantic_decode's idx_out), positive [HW] (bytes).
+ * Codes outside [0, n_codes) are not counted.  1 <= n_codes <= 1000.
+ *
+ * goi_semantic_osh_fit runs K independent fits in one launch (one workgroup each), all epochs on the device:
+ *   lut [n_codes][D] fp32 (z_c = (lut[c] / |lut[c]|) / 0.3438), counts [K][2][n_codes] (as above), HW = pixels per frame
+ *   (the mean's divisor), w [K][D] and b [K] (in: initial hyperplane, out: fitted), lr (SGD), max_epochs (1 .. 1e6),
+ *   target_iou (stop after the first epoch whose IoU is not below it; a NaN IoU also stops).
+ *   Writes, per fit: epochs_out (epochs run, >= 1; -1 if a code present in counts has an all-zero LUT row, and then w / b
+ *   are left as they were), loss_out (the last epoch's loss, taken before its step), iou_out (IoU after the last step,
+ *   double, NaN for an empty union), init_iou_out (IoU of the initial hyperplane); trace (NULL or [K][max_epochs][2]
+ *   doubles): (loss, IoU) of every epoch run.  1 <= D <= 1024, 1 <= n_codes <= 1000, 1 <= HW < 2^31. */
+#define GOI_OSH_MAX_EPOCHS 1000000
+int goi_semantic_osh_counts(const int* idx, const uint8_t* positive, long long HW, int n_codes, int* counts, void* stream);
+int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts, long long HW, int K, float* w, float* b,
+                         float lr, int max_epochs, double target_iou, int* epochs_out, float* loss_out, double* iou_out,
+                         double* init_iou_out, double* trace, void* stream);
+
 /* ---- measurement hooks (bench.py): per-stage HIP-event timing on the launch stream ---------- */
 enum {
     GOI_STAGE_PREPROCESS = 0,   /* forward per-Gaussian kernel */
@@ -334,7 +358,9 @@ int goi_raster_profile_collect(double* ms, int* calls);
  *                  listed Gaussian and the per-Gaussian pass writes every per-id output; 0 they go through six per-id
  *                  arrays (dL_dconic, dL_ddepth, ... and zeros for the Gaussians that are not listed); same gradients, bit for bit;
  *                  2 EXPERIMENT (128-byte rows: S = 5 .. 20): the per-Gaussian pass sums its Gaussians' rows itself -- no record,
- *                  no reduce_rows_k; bit-identical, measured slower (285 -> 437 us on the headline view: DESIGN.md 9.3)
+ *                  no reduce_rows_k; bit-identical, measured slower
+ *   "osh_path"     goi_semantic_osh_fit: 0 (default) z in registers where the shape allows it (D = 256, n_codes <= 320),
+ *                  1 always the generic path (z re-formed from the LUT every epoch); bit-identical (285 -> 437 us on the headline view: DESIGN.md 9.3)
  * Thread safety: the set is changed under a mutex; an entry point snapshots it when it starts. */
 int goi_raster_set_option(const char* name, int value);
 

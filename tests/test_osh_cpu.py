@@ -1,0 +1,121 @@
+"""The hyperplane fine-tune without a GPU: the restated LinearSVM (step / eval_forward / hinge_loss / calculate_iou of
+networks.py:12-67 and utils/image_utils.py:59-70) replays the reference's own loop pinned in
+tests/golden/ref_osh_pins.npz, the float64 per-code form (tests/osh_reference.py) agrees with it, and the OSH entry
+points reject bad input."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests.osh_reference import counts_of, fit_per_code, iou_flips
+
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+CASES = ("a", "b", "c", "d")
+
+
+@pytest.fixture(scope="module")
+def pins():
+    return np.load(os.path.join(GOLD, "ref_osh_pins.npz"))
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_restated_linear_svm_replays_reference(pins, name):
+    """Same statements, same CPU fp32 arithmetic: epochs, init IoU and IoU trace exactly; the loss trace and the final
+    w / b to 1e-6 relative (the CPU GEMM's blocking may depend on the thread count, so bit equality is not promised)."""
+    from goi_hyperplane_amd.semantic import LinearSVM
+    lut = torch.tensor(pins[f"{name}_lut"])
+    idx = torch.tensor(pins[f"{name}_idx"]).long()
+    gt = torch.tensor(pins[f"{name}_gt"]).float().reshape(-1, 1)
+    svm = LinearSVM(set_bias=float(pins[f"{name}_set_bias"]), input_dim=lut.shape[1])
+    svm.weight_set(torch.tensor(pins[f"{name}_w0"]).reshape(1, -1))
+    assert float(svm.linear.bias.detach()) == float(pins[f"{name}_b0"])
+    sem_feature = lut[idx]
+    normed = sem_feature / sem_feature.norm(dim=-1, keepdim=True)
+    init_iou = svm.eval_forward(normed, gt)
+    np.testing.assert_array_equal(np.asarray(init_iou), pins[f"{name}_init_iou"])
+    trace, epoch, iou = [], 0, 0
+    while epoch < 8000 and iou < 0.9:
+        loss, iou = svm.step(normed, gt)
+        trace.append((loss.item(), iou))
+        epoch += 1
+    trace = np.array(trace)
+    ref = pins[f"{name}_trace"]
+    assert epoch == int(pins[f"{name}_epochs"])
+    np.testing.assert_array_equal(trace[:, 1], ref[:, 1])
+    np.testing.assert_allclose(trace[:, 0], ref[:, 0], rtol=1e-6, atol=0)
+    np.testing.assert_allclose(svm.linear.weight.detach().numpy().reshape(-1), pins[f"{name}_w"], rtol=1e-6, atol=1e-7)
+    np.testing.assert_allclose(float(svm.linear.bias.detach()), float(pins[f"{name}_b"]), rtol=1e-6, atol=1e-7)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_per_code_float64_matches_reference(pins, name):
+    lut = pins[f"{name}_lut"]
+    res = fit_per_code(lut, counts_of(pins[f"{name}_idx"], pins[f"{name}_gt"], lut.shape[0]), int(np.prod(pins[f"{name}_hw"])),
+                       pins[f"{name}_w0"], float(pins[f"{name}_b0"]))
+    epochs = int(pins[f"{name}_epochs"])
+    assert res["epochs"] == epochs
+    assert iou_flips(res["trace"][:, 1], pins[f"{name}_trace"][:, 1]) <= max(2, epochs // 200)
+    np.testing.assert_array_equal(np.asarray(res["init_iou"]), pins[f"{name}_init_iou"])
+    w_ref = pins[f"{name}_w"]
+    assert np.abs(res["w"] - w_ref).max() <= 1e-3 * np.abs(w_ref).max()
+    if name == "c":
+        assert epochs == 1 and np.isnan(pins["c_trace"][0, 1])
+    if name == "a":
+        assert epochs < 8000 and pins["a_trace"][-1, 1] >= 0.9
+    if name == "b":
+        assert epochs == 8000
+
+
+def test_hinge_loss_and_iou_helpers():
+    from goi_hyperplane_amd.semantic import calculate_iou, hinge_loss
+    o = torch.tensor([2.0, 0.5, -0.5, -2.0, 1.0])
+    y = torch.tensor([1.0, 1.0, 0.0, 0.0, 0.0])
+    assert hinge_loss(o, y).item() == pytest.approx((0 + 0.5 + 0.5 + 0 + 2.0) / 5)
+    assert calculate_iou(y > 0, o > 0) == 2 / 3
+    assert np.isnan(calculate_iou(torch.zeros(3, dtype=torch.bool), torch.zeros(3, dtype=torch.bool)))
+    # clamp(min=0)'s gradient passes at the kink (1 - o * label == 0)
+    from goi_hyperplane_amd.semantic import LinearSVM
+    svm = LinearSVM(input_dim=2)
+    assert "optimizer" not in svm.state_dict() and set(svm.state_dict()) == {"linear.weight", "linear.bias"}
+    assert svm.optimizer.param_groups[0]["lr"] == 0.01
+    o = torch.tensor([1.0], requires_grad=True)
+    hinge_loss(o, torch.tensor([1.0])).backward()
+    assert o.grad.item() == -1.0
+
+
+def test_osh_entry_points_reject_bad_input():
+    from goi_hyperplane_amd.semantic import (LinearSVM, SemanticModel, fit_hyperplane, fit_hyperplanes_counts,
+                                             osh_counts)
+    mlp = SemanticModel(dim_in=4, dim_out=1001, num_layer=1, use_bias=True, device="cpu")
+    sem = torch.zeros(4, 3, 5)
+    with pytest.raises(ValueError):  # more codes than the reference's [:, :1000] slice keeps
+        fit_hyperplane(sem, mlp, torch.rand(1001, 256), torch.zeros(15), LinearSVM())
+    mlp = SemanticModel(dim_in=4, dim_out=30, num_layer=1, use_bias=True, device="cpu")
+    with pytest.raises(ValueError):  # mask size
+        fit_hyperplane(sem, mlp, torch.rand(30, 256), torch.zeros(16), LinearSVM())
+    with pytest.raises(ValueError):  # LUT / LinearSVM feature size
+        fit_hyperplane(sem, mlp, torch.rand(30, 128), torch.zeros(15), LinearSVM())
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        fit_hyperplane(sem, mlp, torch.rand(30, 256), torch.zeros(15), LinearSVM())
+    with pytest.raises(ValueError):
+        osh_counts(torch.zeros(5, dtype=torch.int32), torch.zeros(5, dtype=torch.bool), 1001)
+    with pytest.raises(ValueError):
+        osh_counts(torch.zeros(5, dtype=torch.int32), torch.zeros(6, dtype=torch.bool), 10)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        osh_counts(torch.zeros(5, dtype=torch.int32), torch.zeros(5, dtype=torch.bool), 10)
+    lut, counts = torch.rand(30, 256), torch.zeros(1, 2, 30, dtype=torch.int32)
+    w, b = torch.zeros(1, 256), torch.zeros(1)
+    for kw in (dict(max_epochs=0), dict(max_epochs=1_000_001)):
+        with pytest.raises(ValueError):
+            fit_hyperplanes_counts(lut, counts, 15, w, b, **kw)
+    with pytest.raises(ValueError):
+        fit_hyperplanes_counts(lut, counts, 0, w, b)
+    with pytest.raises(ValueError):
+        fit_hyperplanes_counts(torch.rand(30, 1025), counts, 15, torch.zeros(1, 1025), b)
+    with pytest.raises(ValueError):
+        fit_hyperplanes_counts(lut, torch.zeros(1, 2, 29, dtype=torch.int32), 15, w, b)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        fit_hyperplanes_counts(lut, counts, 15, w, b)
