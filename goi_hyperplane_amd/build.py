@@ -41,6 +41,7 @@ UNITS = {
     "adam.hip": ["-ffp-contract=off"],
     "codebook_loss.hip": [],
     "osh.hip": [],
+    "dbscan.hip": ["-ffp-contract=off"],
 }
 
 

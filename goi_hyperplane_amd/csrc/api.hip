@@ -1,5 +1,6 @@
 // extern "C" entry points of libgoi_raster.so (see include/goi_raster.h): workspace layout,
 // stage orchestration on the caller's HIP stream, per-stage event timing.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -908,6 +909,32 @@ int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts
         return fail("goi_semantic_osh_fit: a required pointer is NULL");
     launch_osh_fit(lut, n_codes, D, counts, HW, K, w, b, lr, max_epochs, target_iou, epochs_out, loss_out, iou_out,
                    init_iou_out, trace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_semantic_dbscan_workspace_bytes(long long n) {
+    return (n > 0 && n < (1ll << 31)) ? dbscan_workspace_bytes((size_t)n) : 0;
+}
+
+int goi_semantic_dbscan(long long n, const float* points, float eps, int min_samples, int* labels, uint8_t* core, int* result,
+                        void* workspace, void* stream) {
+    if (n < 0 || n >= (1ll << 31)) return fail("goi_semantic_dbscan: need 0 <= n < 2^31");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail("goi_semantic_dbscan: eps must be a finite number > 0");
+    if (min_samples < 1) return fail("goi_semantic_dbscan: min_samples must be >= 1");
+    if (!result) return fail("goi_semantic_dbscan: result is NULL");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    GOI_HIP(hipMemsetAsync(result, 0, 2 * sizeof(int), s));
+    if (n == 0) return 0;
+    if (!points || !labels || !workspace) return fail("goi_semantic_dbscan: a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("goi_semantic_dbscan: workspace must be 256-byte aligned");
+    if (!(eps >= 0x1p-40f && eps <= 0x1p40f)) {  // outside the range of the grid's exactness argument (csrc/dbscan.hip)
+        GOI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(result + 1), DBSCAN_FLAG_RANGE, 1, s));
+        return 0;
+    }
+    const float eps2 = eps * eps;
+    const double h = (double)eps / std::sqrt(3.0) * (1.0 - 1.0 / 4096.0);  // cell side: eps / sqrt(3) less a margin
+    launch_dbscan((int)n, points, eps2, h, min_samples, labels, core, result, workspace, s);
     GOI_HIP(hipGetLastError());
     return 0;
 }

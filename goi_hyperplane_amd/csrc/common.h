@@ -275,6 +275,9 @@ int launch_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, dou
                      const uint8_t* nograd_mask, const uint32_t* skip_flag, hipStream_t s);
 size_t knn_workspace_bytes(int P);
 int launch_knn(int P, const float* points, float* mean_dist2, void* workspace, hipStream_t s);
+size_t dbscan_workspace_bytes(size_t n);
+void launch_dbscan(int n, const float* pts, float eps2, double h, int min_samples, int* labels, uint8_t* core, int* result,
+                   void* workspace, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).

@@ -8,6 +8,7 @@ checkpoints load unchanged:
     LinearSVM                networks.py:12-67               (x / 0.3438 -> Linear(256, 1), hinge loss, SGD)
     fit_hyperplane           gui/main.py:1673-1763           (the OSH fine-tune against a mask: one HIP kernel)
     select_gaussians         gui/main.py:400-405             (Gaussians of interest)
+    group_points             gui/main.py:1595-1665           (DBSCAN refinement of the selection: cluster.py)
     compute_similarity       gui/main.py:364-386             (inference decode)
     codebook_losses          train.py:142-163                (training losses)
 
@@ -511,3 +512,60 @@ def select_gaussians(pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh
     render(..., gaussian_mask=...)."""
     sem = pc.get_semantics.detach().float().t().contiguous()  # [S, P]: the decode's channel-major layout, one "pixel" per Gaussian
     return compute_similarity(sem, mlp, lut, score_fn, thresh) > 0
+
+
+@torch.no_grad()
+def group_points(pc, selected: torch.Tensor, viewpoint_camera, bg_color: torch.Tensor, mlp: SemanticModel, lut: torch.Tensor,
+                 score_fn, res_mask: torch.Tensor, eps: float = 0.35, min_samples: int = 600, keep_ratio: float = 0.7,
+                 thresh: float = 0.5, scaling_modifier: float = 1.0, gaussian_mask: torch.Tensor | None = None) -> torch.Tensor:
+    """The cluster refinement of the retrieved Gaussians (gui/main.py:1595-1665, group_points) on the device.
+
+    `selected` (bool [P], e.g. select_gaussians' result) picks the Gaussians whose positions pc.get_xyz are clustered with
+    the exact DBSCAN(eps, min_samples) of cluster.dbscan.  For every cluster, in ascending label order and noise skipped, the
+    semantics of all other Gaussians are masked out (pc.set_semantic_masks), the view is rendered with render_gui
+    (scaling_modifier, gaussian_mask) and decoded with compute_similarity(thresh); a cluster that shows no semantic pixel is
+    dropped (the reference's cos_sim.sum() == 0), and one is kept when |sem & res| / |sem| > keep_ratio, sem = (decoded
+    similarity > 0) and res = (res_mask != 0).  That ratio is compute_mask_ratio's elementwise definition
+    (utils/image_utils.py:36-48), evaluated as the reference does (fp32 quotient, compared in fp64); res_mask is any tensor
+    with H*W elements in the frame's pixel order, as `positive` is in fit_hyperplane (the reference's [1,H,W]-against-[H,W,1]
+    comment would broadcast and cannot be meant literally).
+
+    Returns the refined selection, bool [P]: the union of the kept clusters.  Unlike the reference, pc's semantic mask is
+    left as it was found and the caller applies the result (gui/main.py:1664 stores it as rel_gs_index).  The ratios are
+    accumulated on the device: host synchronisations are the index gather of `selected` and dbscan's one read of the
+    cluster count, none per cluster.  With rasterizer.set_geometry_cache on, the K renders of one camera share the
+    geometry: renders 2..K are blend-only."""
+    from . import cluster
+    from .render import render_gui
+
+    P = int(pc.get_xyz.shape[0])
+    if selected.numel() != P:
+        raise ValueError(f"selected has {selected.numel()} elements, the model {P} Gaussians")
+    H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
+    if res_mask.numel() != H * W:
+        raise ValueError(f"res_mask has {res_mask.numel()} elements, the frame {H * W} pixels")
+    if not (selected.is_cuda and res_mask.is_cuda and pc.get_xyz.is_cuda):
+        raise RuntimeError(_NO_CPU)
+    dev = pc.get_xyz.device
+    sel_idx = torch.nonzero(selected.reshape(-1)).reshape(-1)
+    labels = cluster.dbscan(pc.get_xyz.detach()[sel_idx].float().contiguous(), eps, min_samples)
+    K = cluster.dbscan.last_n_clusters
+    res = (res_mask.reshape(-1) != 0)
+    keep = torch.zeros(K, dtype=torch.bool, device=dev)
+    saved = pc._semantics_masks
+    try:
+        for k in range(K):
+            member = torch.zeros(P, dtype=torch.bool, device=dev)
+            member.index_put_((sel_idx,), labels == k)
+            pc.set_semantic_masks(member)
+            out = render_gui(viewpoint_camera, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask)
+            sem = compute_similarity(out["semantics"], mlp, lut, score_fn, thresh).reshape(-1) > 0
+            n_sem = sem.sum()
+            ratio = (sem & res).sum().float() / n_sem.float()
+            keep[k] = (n_sem > 0) & (ratio.double() > keep_ratio)
+    finally:
+        pc._semantics_masks = saved
+    picked = (labels >= 0) & keep[labels.clamp(min=0)] if K else torch.zeros_like(labels, dtype=torch.bool)
+    result = torch.zeros(P, dtype=torch.bool, device=dev)
+    result.index_put_((sel_idx,), picked)
+    return result

@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
- *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit
+ *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -295,6 +295,26 @@ int goi_semantic_osh_counts(const int* idx, const uint8_t* positive, long long H
 int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts, long long HW, int K, float* w, float* b,
                          float lr, int max_epochs, double target_iou, int* epochs_out, float* loss_out, double* iou_out,
                          double* init_iou_out, double* trace, void* stream);
+
+/* ---- exact DBSCAN of a point set (gui/main.py:1595-1665 runs sklearn.cluster.DBSCAN(eps=0.35, min_samples=600) on the
+ * selected Gaussians' positions; csrc/dbscan.hip).  labels [n] (int32) equal sklearn's DBSCAN(eps, min_samples).fit(X).labels_
+ * for the neighbour test d2 <= eps*eps evaluated in fp32 as dx = xi - xj (y, z alike), d2 = fma(dz,dz, fma(dy,dy, dx*dx)):
+ * core points have >= min_samples neighbours (themselves included), clusters are the connected components of the core points
+ * numbered by their smallest core index, a border point takes the smallest label among its core neighbours, noise is -1.
+ * core [n] (bytes, may be NULL) receives the core flags.  result (device, 2 ints): result[0] = number of clusters,
+ * result[1] = DBSCAN_FLAG_* bits; when result[1] != 0 the labels are not to be used.  points [n][3] fp32, device.
+ * workspace: goi_semantic_dbscan_workspace_bytes(n) bytes of device memory, 256-byte aligned.  Asynchronous on `stream`, no
+ * host read-back; bit-identical from run to run.  Returns < 0 (goi_raster_last_error) for eps <= 0 or non-finite,
+ * min_samples < 1, n < 0 or n >= 2^31; eps outside [2^-40, 2^40] (where the grid's exactness argument stops) is reported
+ * as DBSCAN_FLAG_RANGE.  n = 0 gives 0 clusters. */
+#define DBSCAN_FLAG_NONFINITE 1 /* a coordinate is NaN or infinite (sklearn raises ValueError) */
+#define DBSCAN_FLAG_SORT 2      /* a radix-sort look-back ran out of its spin budget (a wedged device) */
+#define DBSCAN_FLAG_RANGE 4     /* the extent needs more than 2^21 grid cells on an axis, or eps is outside [2^-40, 2^40] */
+#define DBSCAN_FLAG_GRID 8      /* a grid cell failed its clique check (cannot happen inside the range; never silent) */
+#define DBSCAN_FLAG_UNION 16    /* a union-find loop reached its bound (cannot happen; never silent) */
+size_t goi_semantic_dbscan_workspace_bytes(long long n);
+int goi_semantic_dbscan(long long n, const float* points, float eps, int min_samples, int* labels, uint8_t* core, int* result,
+                        void* workspace, void* stream);
 
 /* ---- measurement hooks (bench.py): per-stage HIP-event timing on the launch stream ---------- */
 enum {
