@@ -90,6 +90,10 @@ SYMBOLS = {
     "goi_semantic_dbscan_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "goi_semantic_dbscan": (C.c_int, [C.c_longlong, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "goi_semantic_mask_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "goi_semantic_mask_dilate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "goi_semantic_mask_unpack": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
+    "goi_semantic_mask_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "goi_raster_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "goi_raster_blend_stats": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 5),
     "goi_raster_debug_views": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_void_p] * 8 + [C.c_void_p]),

@@ -42,6 +42,7 @@ UNITS = {
     "codebook_loss.hip": [],
     "osh.hip": [],
     "dbscan.hip": ["-ffp-contract=off"],
+    "masks.hip": [],
 }
 
 

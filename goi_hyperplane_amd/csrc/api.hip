@@ -939,6 +939,57 @@ int goi_semantic_dbscan(long long n, const float* points, float eps, int min_sam
     return 0;
 }
 
+static int mask_dims(const char* fn, int H, int W) {
+    if (H < 1 || W < 1) return fail(std::string(fn) + ": need H >= 1 and W >= 1");
+    if ((long long)H * W >= (1ll << 31)) return fail(std::string(fn) + ": need H * W < 2^31");
+    return 0;
+}
+
+int goi_semantic_mask_pack(const void* src, int src_dtype, int n_views, int H, int W, int first_view, uint64_t* packed, long long* counts,
+                  void* stream) {
+    if (mask_dims("goi_semantic_mask_pack", H, W) < 0) return -1;
+    if (src_dtype != GOI_MASK_F32 && src_dtype != GOI_MASK_U8) return fail("goi_semantic_mask_pack: src_dtype must be GOI_MASK_F32 or GOI_MASK_U8");
+    if (n_views < 0 || n_views > 65535 || first_view < 0) return fail("goi_semantic_mask_pack: need 0 <= n_views <= 65535, first_view >= 0");
+    if (n_views == 0) return 0;
+    if (!src || !packed) return fail("goi_semantic_mask_pack: NULL src or packed");
+    launch_mask_pack(src, src_dtype, n_views, H, W, first_view, packed, counts, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_semantic_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, int W, int radius, void* stream) {
+    if (mask_dims("goi_semantic_mask_dilate", H, W) < 0) return -1;
+    if (radius < 0 || radius > GOI_MASK_MAX_RADIUS) return fail("goi_semantic_mask_dilate: need 0 <= radius <= 63");
+    if (n_views < 0) return fail("goi_semantic_mask_dilate: need n_views >= 0");
+    if (n_views == 0) return 0;
+    if (!src || !dst) return fail("goi_semantic_mask_dilate: NULL src or dst");
+    if (src == dst) return fail("goi_semantic_mask_dilate: dst must not be src");
+    launch_mask_dilate(src, dst, n_views, H, W, radius, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_semantic_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
+                             void* stream) {
+    if (mask_dims("goi_semantic_mask_unpack", H, W) < 0) return -1;
+    if (n_out < 0 || n_views < 0) return fail("goi_semantic_mask_unpack: need n_out >= 0 and n_views >= 0");
+    if (n_out == 0) return 0;
+    if (!packed || !out) return fail("goi_semantic_mask_unpack: NULL packed or out");
+    launch_mask_unpack(packed, n_views, H, W, n_out, index, out, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_semantic_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, void* stream) {
+    if (mask_dims("goi_semantic_mask_confusion", H, W) < 0) return -1;
+    if (n_views < 0) return fail("goi_semantic_mask_confusion: need n_views >= 0");
+    if (n_views == 0) return 0;
+    if (!pred || !gt || !out) return fail("goi_semantic_mask_confusion: NULL pred, gt or out");
+    launch_mask_confusion(pred, gt, n_views, H, W, out, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
 int goi_codebook_loss_partial_rows(void) { return codebook_loss_waves(); }
 
 int goi_codebook_loss_rows(const float* sim_raw, const float* inv_gnorm, const float* sem, const float* W,

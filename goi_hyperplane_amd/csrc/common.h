@@ -278,6 +278,12 @@ int launch_knn(int P, const float* points, float* mean_dist2, void* workspace, h
 size_t dbscan_workspace_bytes(size_t n);
 void launch_dbscan(int n, const float* pts, float eps2, double h, int min_samples, int* labels, uint8_t* core, int* result,
                    void* workspace, hipStream_t s);
+void launch_mask_pack(const void* src, int src_dtype, int n_views, int H, int W, int first_view, uint64_t* packed,
+                      long long* counts, hipStream_t s);
+void launch_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, int W, int radius, hipStream_t s);
+void launch_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
+                        hipStream_t s);
+void launch_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).

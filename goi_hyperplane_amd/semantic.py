@@ -9,6 +9,8 @@ checkpoints load unchanged:
     fit_hyperplane           gui/main.py:1673-1763           (the OSH fine-tune against a mask: one HIP kernel)
     select_gaussians         gui/main.py:400-405             (Gaussians of interest)
     group_points             gui/main.py:1595-1665           (DBSCAN refinement of the selection: cluster.py)
+    relevant_cameras         gui/main.py:407-478             (relevant-camera precompute: masks.py on the device)
+    evaluate_cameras         gui/main.py:1957-2016           (eval_epoch's IoU / mPA / mP, utils/image_utils.py:59-102)
     compute_similarity       gui/main.py:364-386             (inference decode)
     codebook_losses          train.py:142-163                (training losses)
 
@@ -569,3 +571,121 @@ def group_points(pc, selected: torch.Tensor, viewpoint_camera, bg_color: torch.T
     result = torch.zeros(P, dtype=torch.bool, device=dev)
     result.index_put_((sel_idx,), picked)
     return result
+
+
+RelevantCameras = namedtuple("RelevantCameras", ["index", "counts", "semantic_mask", "semantic_mask_dilated"])
+RelevantCameras.__doc__ = ("Result of relevant_cameras: index (list of the kept camera numbers, in camera order), counts "
+                           "(int64 [V] on the device: count_nonzero of every camera's decoded similarity, the reference's "
+                           "relative_pixel_number), semantic_mask and semantic_mask_dilated (bool [K, 1, H, W], kept cameras "
+                           "only, in index order).")
+
+SegEvaluation = namedtuple("SegEvaluation", ["iou", "mpa", "mp", "mean_iou", "mean_mpa", "mean_mp"])
+SegEvaluation.__doc__ = ("Result of evaluate_cameras: per-view iou (float64 [V]), mpa and mp (float32 [V]) as CPU tensors, "
+                         "and their means (Python floats: iou summed in float64, mpa / mp in float32, each divided by V).")
+
+
+def _sweep_frame(cameras):
+    cams = list(cameras)
+    if not cams:
+        raise ValueError("the camera set is empty")
+    H, W = int(cams[0].image_height), int(cams[0].image_width)
+    for i, cam in enumerate(cams):
+        if (int(cam.image_height), int(cam.image_width)) != (H, W):
+            raise ValueError(f"all cameras must share one frame size: camera 0 is {H}x{W}, camera {i} "
+                             f"{int(cam.image_height)}x{int(cam.image_width)}")
+    return cams, H, W
+
+
+def _sweep_pack(cams, H, W, pc, mlp, lut, score_fn, thresh, bg_color, scaling_modifier):
+    """Renders and decodes every camera and packs `sim > 0` into slot v of one buffer, with the two counts (masks.pack_into).
+    No synchronisation of its own."""
+    from . import masks
+    from .render import render_gui
+    dev = pc.get_xyz.device
+    packed = torch.empty((len(cams), H, masks.words(W)), dtype=torch.int64, device=dev)
+    counts = torch.zeros((len(cams), 2), dtype=torch.int64, device=dev)
+    for v, cam in enumerate(cams):
+        out = render_gui(cam, pc, bg_color, scaling_modifier)
+        sim = compute_similarity(out["semantics"], mlp, lut, score_fn, thresh)
+        masks.pack_into(sim.reshape(H, W), packed, counts, v)
+    return packed, counts
+
+
+def relevant_keep(count: torch.Tensor, min_ratio: float = 0.1) -> torch.Tensor:
+    """The camera filter of gui/main.py:470-477 as one tensor expression on the per-camera count_nonzero values (int64
+    [V], any device, no synchronisation): kept iff count > 0 (the cos_sim.any() guard of :433) and not
+    count < count.max() * min_ratio.  int64 times a Python float is float32, and the comparison is made in float32, as in
+    the reference."""
+    return (count > 0) & ~(count < count.max() * min_ratio)
+
+
+@torch.no_grad()
+def relevant_cameras(cameras, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float, bg_color: torch.Tensor,
+                     kernel_size: int = 3, iterations: int = 5, min_ratio: float = 0.1,
+                     scaling_modifier: float = 1.0) -> RelevantCameras:
+    """The relevant-camera precompute (gui/main.py:407-478, pre_compute_relative_cameras; gui/main_edit.py:320-394) on the
+    device.  With pc's semantic masks cleared (set_semantic_masks() as at :410), every camera in order is rendered with
+    render_gui, decoded with compute_similarity(thresh), and its mask cos_sim > 0 and count torch.count_nonzero(cos_sim)
+    go into slot v of one packed buffer (masks.pack_into).  After the loop: one batched dilation by
+    np.ones((kernel_size, kernel_size)) with `iterations` (the reference's cv2.dilate(...) >= 0.5, masks.dilate), and the
+    filter on the device with the reference's expression, so with its dtype promotion (int64 count times a Python float
+    is float32): camera v is kept iff count[v] > 0 (the cos_sim.any() guard) and not count[v] < count.max() * min_ratio.
+    Then ONE host read-back (the kept flags) and the unpacking of the kept views only.  The renders take whatever forward
+    mode is set; the mask stage adds no synchronisation.
+
+    All cameras must share one H x W (ValueError otherwise).  Unlike the reference nothing is written onto the camera
+    objects, and pc's semantic mask is restored on exit.  A GUI port attaches the masks itself:
+        for k, i in enumerate(res.index):
+            cams[i].semantic_mask, cams[i].semantic_mask_dilated = res.semantic_mask[k], res.semantic_mask_dilated[k]
+    and keeps relative_cameras = [cams[i] for i in res.index]."""
+    from . import masks
+    r = masks.radius(kernel_size, iterations)
+    cams, H, W = _sweep_frame(cameras)
+    if not pc.get_xyz.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    saved = pc._semantics_masks
+    try:
+        pc.set_semantic_masks()
+        packed, counts = _sweep_pack(cams, H, W, pc, mlp, lut, score_fn, thresh, bg_color, scaling_modifier)
+    finally:
+        pc._semantics_masks = saved
+    dilated = masks.dilate_packed(packed, W, r)
+    count = counts[:, 0]
+    keep = relevant_keep(count, min_ratio)
+    keep_host = keep.cpu()  # the one read-back
+    index = torch.nonzero(keep_host).reshape(-1).tolist()
+    kept = torch.sort((~keep).to(torch.uint8), stable=True).indices[: len(index)]  # the same indices, on the device
+    return RelevantCameras(index, count, masks.unpack(packed, W, kept), masks.unpack(dilated, W, kept))
+
+
+@torch.no_grad()
+def evaluate_cameras(cameras, gt_masks: torch.Tensor, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float,
+                     bg_color: torch.Tensor, scaling_modifier: float = 1.0) -> SegEvaluation:
+    """The segmentation evaluation of gui/main.py:1957-2016 (eval_epoch) on the device: every camera is rendered with
+    render_gui, decoded with compute_similarity(thresh) and its prediction cos_sim > 0 packed; gt_masks ([V, H, W], or
+    any CUDA tensor of V*H*W elements in pixel order; positive where != 0) is packed in one launch, one confusion launch
+    counts TP / FP / FN / TN per view, and the [V, 4] counts are read back once for masks.segmentation_metrics.  The
+    formulas are those of utils/image_utils.py:59-102 on same-shape masks (eval_epoch itself passes a [H, W, C] ground
+    truth against a [H, W, 1] prediction, which calculate_mean_pixel_accuracy's shape assert rejects).  The means are the
+    sums over the views divided by V, so a NaN view makes its mean NaN, as in eval_epoch.  pc is rendered as it is (the
+    reference does not touch its semantic mask here)."""
+    from . import masks
+    cams, H, W = _sweep_frame(cameras)
+    V = len(cams)
+    if gt_masks.numel() != V * H * W:
+        raise ValueError(f"gt_masks has {gt_masks.numel()} elements, {V} views of {H}x{W} need {V * H * W}")
+    if not (gt_masks.is_cuda and pc.get_xyz.is_cuda):
+        raise RuntimeError(_NO_CPU)
+    gt = gt_masks.reshape(V, H, W)
+    if gt.dtype != torch.uint8:
+        gt = gt != 0
+    pred, _ = _sweep_pack(cams, H, W, pc, mlp, lut, score_fn, thresh, bg_color, scaling_modifier)
+    gt_packed = torch.empty_like(pred)
+    masks.pack_into(gt, gt_packed)
+    m = masks.segmentation_metrics(masks.confusion_packed(pred, gt_packed, W).cpu())
+    total_iou, total_mpa, total_mp = 0.0, torch.zeros((), dtype=torch.float32), torch.zeros((), dtype=torch.float32)
+    for v in range(V):  # eval_epoch's running sums, in its order and precision
+        total_iou += float(m.iou[v])
+        total_mpa = total_mpa + m.mpa[v]
+        total_mp = total_mp + m.mp[v]
+    return SegEvaluation(m.iou, m.mpa, m.mp, total_iou / V, float(total_mpa / V), float(total_mp / V))

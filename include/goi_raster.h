@@ -50,7 +50,8 @@ extern "C" {
 #endif
 
 /* 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
- *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan
+ *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan,
+ *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -315,6 +316,34 @@ int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts
 size_t goi_semantic_dbscan_workspace_bytes(long long n);
 int goi_semantic_dbscan(long long n, const float* points, float eps, int min_samples, int* labels, uint8_t* core, int* result,
                         void* workspace, void* stream);
+
+/* ---- bit-packed binary masks of a camera sweep (csrc/masks.hip): the mask stage of the relevant-camera precompute
+ * (gui/main.py:407-478: torch.count_nonzero(cos_sim), cos_sim > 0, cv2.dilate(mask, ones((3,3)), iterations=5) >= 0.5 on
+ * the host) and of the segmentation evaluation (gui/main.py:1957-2016 with utils/image_utils.py:59-102).
+ * A packed mask buffer is [V][H][Wwords] uint64, Wwords = ceil(W / 64): bit j of word w of row y is pixel (y, 64 w + j);
+ * bits past W are zero.  Every call is asynchronous on `stream`: no allocation, copy or synchronisation.  Returns < 0
+ * (goi_raster_last_error) for bad sizes or NULL pointers; pointers are device memory; H * W < 2^31.
+ *
+ * goi_semantic_mask_pack packs n_views maps src [n_views][H][W] (GOI_MASK_F32: bit = x > 0, a NaN clears it;
+ *   GOI_MASK_U8: bit = x != 0) into views first_view .. first_view + n_views - 1 of `packed`.  counts (NULL or [V][2]
+ *   int64) is ADDED to (the caller zeroes it): counts[v][0] += pixels with x != 0 (count_nonzero: a NaN counts),
+ *   counts[v][1] += set bits.  1 <= n_views <= 65535.
+ * goi_semantic_mask_dilate: dst = src dilated by the square of radius `radius` clipped at the border (cv2.dilate with
+ *   ones((k,k)) and n iterations is radius n(k-1)/2; its default border never contributes).  0 <= radius <=
+ *   GOI_MASK_MAX_RADIUS, dst != src.
+ * goi_semantic_mask_unpack: out [n_out][H][W] bytes (0 / 1) from views index[0 .. n_out-1] of the n_views views of
+ *   packed (index NULL: views 0 .. n_out-1); an index outside 0 .. n_views-1 gives an all-zero mask.
+ * goi_semantic_mask_confusion: out [n_views][4] int64 = TP, FP, FN, TN of pred against gt per view (one workgroup per
+ *   view, deterministic). */
+#define GOI_MASK_F32 0
+#define GOI_MASK_U8 1
+#define GOI_MASK_MAX_RADIUS 63
+int goi_semantic_mask_pack(const void* src, int src_dtype, int n_views, int H, int W, int first_view, uint64_t* packed, long long* counts,
+                  void* stream);
+int goi_semantic_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, int W, int radius, void* stream);
+int goi_semantic_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
+                             void* stream);
+int goi_semantic_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, void* stream);
 
 /* ---- measurement hooks (bench.py): per-stage HIP-event timing on the launch stream ---------- */
 enum {
