@@ -57,11 +57,11 @@ def dbscan(points: torch.Tensor, eps: float, min_samples: int, return_core: bool
         raise TypeError(f"dbscan: points must be float32, got {points.dtype}")
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError(f"dbscan: points must be [n, 3], got {tuple(points.shape)}")
+    n = int(points.shape[0])
+    if n >= 2 ** 30:  # (the radix sort of the cell keys is exact below 2^30 keys: csrc/common.h)
+        raise ValueError("dbscan: at most 2^30 - 1 points")
     if not points.is_cuda:
         raise RuntimeError(_NO_CPU)
-    n = int(points.shape[0])
-    if n >= 2 ** 31:
-        raise ValueError("dbscan: at most 2^31 - 1 points")
     dev = points.device
     pts = points.contiguous()
     lib = _lib.load()

@@ -914,12 +914,13 @@ int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts
 }
 
 size_t goi_semantic_dbscan_workspace_bytes(long long n) {
-    return (n > 0 && n < (1ll << 31)) ? dbscan_workspace_bytes((size_t)n) : 0;
+    return (n > 0 && n < SORT_MAX_KEYS) ? dbscan_workspace_bytes((size_t)n) : 0;
 }
 
 int goi_semantic_dbscan(long long n, const float* points, float eps, int min_samples, int* labels, uint8_t* core, int* result,
                         void* workspace, void* stream) {
-    if (n < 0 || n >= (1ll << 31)) return fail("goi_semantic_dbscan: need 0 <= n < 2^31");
+    // (the cell keys go through radix_sort_pairs, exact below 2^30 keys: common.h)
+    if (n < 0 || n >= SORT_MAX_KEYS) return fail("goi_semantic_dbscan: need 0 <= n < 2^30");
     if (!(eps > 0.f) || !std::isfinite(eps)) return fail("goi_semantic_dbscan: eps must be a finite number > 0");
     if (min_samples < 1) return fail("goi_semantic_dbscan: min_samples must be >= 1");
     if (!result) return fail("goi_semantic_dbscan: result is NULL");
@@ -1081,10 +1082,12 @@ int goi_adam_step_guarded(const GoiAdamGroup* groups, int n_groups, double beta1
     return 0;
 }
 
-size_t goi_knn_workspace_bytes(int P) { return P > 0 ? knn_workspace_bytes(P) : 0; }
+size_t goi_knn_workspace_bytes(int P) { return P > 0 && P < SORT_MAX_KEYS ? knn_workspace_bytes(P) : 0; }
 
 int goi_knn_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream) {
     if (P < 0) return fail("goi_knn_dist2: bad P");
+    // (the Morton codes go through radix_sort_pairs, exact below 2^30 keys: common.h)
+    if (P >= SORT_MAX_KEYS) return fail("goi_knn_dist2: need P < 2^30");
     if (P == 0) return 0;
     if (!points || !mean_dist2 || !workspace) return fail("goi_knn_dist2: a required pointer is NULL");
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("goi_knn_dist2: workspace must be 256-byte aligned");
@@ -1208,6 +1211,64 @@ int goi_raster_debug_views(int P, int W, int H, int R, const void* geom_buffer, 
         const int fin = tile_sort_result_index(W, H, R);
         GOI_HIP(hipMemcpyAsync(point_list, bv.vals[fin], sizeof(uint32_t) * (size_t)R, hipMemcpyDeviceToDevice, s));
     }
+    return 0;
+}
+
+static int debug_sort_args(const char* fn, long long n, int lo, int hi) {
+    if (n < 0 || n >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need 0 <= n < 2^30");
+    if (lo < 0 || hi > 32 || lo >= hi) return fail(std::string(fn) + ": need 0 <= lo < hi <= 32");
+    return 0;
+}
+
+size_t goi_raster_debug_sort_workspace_bytes(long long n, int lo, int hi) {
+    if (n < 0 || n >= SORT_MAX_KEYS || lo < 0 || hi > 32 || lo >= hi) return 0;
+    return sort_scratch_words((size_t)(n > 0 ? n : 1)) * sizeof(uint32_t) + 256;
+}
+
+int goi_raster_debug_sort_pairs(uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, uint32_t* vals1, long long n, int lo, int hi,
+                                const uint32_t* n_dev, const uint32_t* ghist, int flags, uint32_t* error_out, void* workspace,
+                                void* stream) {
+    refresh_options();
+    const char* fn = "goi_raster_debug_sort_pairs";
+    if (debug_sort_args(fn, n, lo, hi) < 0) return -1;
+    if (flags & ~1) return fail(std::string(fn) + ": unknown flags");
+    const bool onesweep = g_options.sort_variant == 1;
+    if ((n_dev || ghist) && !onesweep) return fail(std::string(fn) + ": n_dev and ghist need the onesweep sort (sort_variant 1)");
+    if (n == 0) return 0;
+    if (!keys0 || !vals0 || !keys1 || !vals1 || !workspace) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": workspace must be 256-byte aligned");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t* scratch = static_cast<uint32_t*>(workspace);
+    bool cleared = (flags & 1) != 0;
+    if (ghist) {  // the rasterizer's convention: control words cleared, then the histograms written by the caller's own kernel
+        const size_t passes = (size_t)(hi - lo + 7) / 8;
+        GOI_HIP(hipMemsetAsync(scratch, 0, radix_sort_control_words((size_t)n, lo, hi) * sizeof(uint32_t), s));
+        GOI_HIP(hipMemcpyAsync(radix_sort_ghist(scratch, (size_t)n, lo, hi), ghist, passes * 256 * sizeof(uint32_t),
+                               hipMemcpyDeviceToDevice, s));
+        cleared = true;
+    }
+    uint32_t* keys[2] = {keys0, keys1};
+    uint32_t* vals[2] = {vals0, vals1};
+    const int fin = radix_sort_pairs(keys, vals, (size_t)n, lo, hi, scratch, s, cleared, ghist != nullptr, n_dev, error_out);
+    GOI_HIP(hipGetLastError());
+    if (error_out) radix_sort_report_error(scratch, (size_t)n, lo, hi, error_out, s);
+    GOI_HIP(hipGetLastError());
+    return fin;
+}
+
+size_t goi_raster_debug_scan_workspace_bytes(long long n) {
+    return (n >= 0 && n < (1ll << 32)) ? scan_scratch_words((size_t)n) * sizeof(uint32_t) + 256 : 0;
+}
+
+int goi_raster_debug_exclusive_scan(const uint32_t* in, const uint32_t* gather, uint32_t* out, long long n, const uint32_t* n_dev,
+                                    uint32_t* total, void* workspace, void* stream) {
+    refresh_options();
+    if (n < 0 || n >= (1ll << 32)) return fail("goi_raster_debug_exclusive_scan: need 0 <= n < 2^32");
+    if (gather && out == in) return fail("goi_raster_debug_exclusive_scan: out == in with a gather is a data race");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n > 0 && (!in || !out || !workspace)) return fail("goi_raster_debug_exclusive_scan: a required pointer is NULL");
+    exclusive_scan_u32(in, gather, out, (size_t)n, total, static_cast<uint32_t*>(workspace), s, n_dev);
+    GOI_HIP(hipGetLastError());
     return 0;
 }
 

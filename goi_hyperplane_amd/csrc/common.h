@@ -148,12 +148,16 @@ void refresh_options();
 // ---- device-wide primitives (scan_sort.hip) ----------------------------------------------------
 size_t scan_scratch_words(size_t n);
 size_t sort_scratch_words(size_t n);
-// out[i] = sum_{j<i} f(j), f(j) = gather ? in[gather[j]] : in[j]; *total (device, may be NULL) = sum.
-// n_dev (may be NULL): the count lives on the device, `n` is a capacity (grids cover n; min(*n_dev, n) elements are scanned).
+// out[i] = sum_{j<i} f(j), f(j) = gather ? in[gather[j]] : in[j]; *total (device, may be NULL) = sum.  Sums wrap mod 2^32.
+// n_dev (may be NULL): the count lives on the device, `n` is a capacity (grids cover n; min(*n_dev, n) elements are scanned,
+// out[count .. n) is not written).
+// out == in is allowed only WITHOUT a gather: with one, a block would write out[i] while another still reads in[gather[j]].
 void exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* out, size_t n, uint32_t* total,
                         uint32_t* scratch, hipStream_t s, const uint32_t* n_dev = nullptr);
 // Stable LSD radix sort of (key,val) pairs on key bits [lo, hi).  Data start in keys[0]/vals[0];
 // returns the index (0/1) of the buffers holding the sorted result.
+// n < SORT_MAX_KEYS = 2^30: the onesweep look-back publishes per-digit counts in 30-bit fields of its status words, so a digit
+// holding 2^30 keys or more would be mis-sorted without any error.  Entry points that sort caller-sized input refuse larger n.
 // Onesweep control words (status, global digit histograms, tickets, error) sit at the start of `scratch`:
 //   cleared     : the caller has zeroed the first radix_sort_control_words(n, lo, hi) words (e.g. together with
 //                 neighbouring counters in one memset) -- otherwise the sort clears them itself;
@@ -169,6 +173,9 @@ int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], size_t n, int lo, int
                      uint32_t* frame_error = nullptr);
 size_t radix_sort_control_words(size_t n, int lo, int hi);
 uint32_t* radix_sort_ghist(uint32_t* scratch, size_t n, int lo, int hi);
+// ORs the onesweep sort's own error word (in `scratch`, after a radix_sort_pairs of the same n, lo, hi) into *out (device)
+void radix_sort_report_error(const uint32_t* scratch, size_t n, int lo, int hi, uint32_t* out, hipStream_t s);
+constexpr long long SORT_MAX_KEYS = 1ll << 30;
 
 // ---- stages ---------------------------------------------------------------------------------------
 void launch_preprocess_fwd(const GoiRasterScene& sc, const GeomView& g, int* radii, uint2* ranges, int n_tiles,

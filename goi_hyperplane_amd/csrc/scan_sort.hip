@@ -27,8 +27,8 @@ constexpr int SCAN_CHUNK = SCAN_THREADS * SCAN_ITEMS;  // 2048
 #endif
 constexpr int SORT_THREADS = GOI_SORT_THREADS;
 constexpr int SORT_ITEMS = 16;
-constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;  // 4096
-constexpr int SORT_WAVES = SORT_THREADS / WAVE;        // 4
+constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;  // 8192
+constexpr int SORT_WAVES = SORT_THREADS / WAVE;        // 8
 constexpr int SORT_WAVE_ITEMS = SORT_TILE / SORT_WAVES;  // 1024
 constexpr int RADIX_MAX = 256;
 
@@ -610,7 +610,7 @@ static int sweep_min_items(size_t n) { return sweep_min_items_for(n, g_options.s
 static size_t sweep_min_tile_keys(size_t n) { return sweep_adaptive(n) ? (size_t)512 * sweep_min_items(n) : 4096; }
 
 size_t sort_scratch_words(size_t n) {
-    size_t nblk = div_up(n, 4096);  // the smallest tile of the three-kernel variant
+    size_t nblk = div_up(n, 4096);  // blocks of the three-kernel variant (SORT_TILE keys each): counted generously
     size_t table = (size_t)RADIX_MAX * nblk;
     size_t three_kernel = table + scan_scratch_words(table) + 16;
     // (laid out for the smallest tile ANY setting of sort_small may choose: a workspace outlives the option)
@@ -648,6 +648,16 @@ size_t radix_sort_control_words(size_t n, int lo, int hi) {
 }
 uint32_t* radix_sort_ghist(uint32_t* scratch, size_t n, int lo, int hi) {
     return scratch + sweep_status_words(n, lo, hi);
+}
+
+namespace {
+__global__ void or_word_k(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) { *dst |= *src; }
+}  // namespace
+
+void radix_sort_report_error(const uint32_t* scratch, size_t n, int lo, int hi, uint32_t* out, hipStream_t s) {
+    if (n == 0 || g_options.sort_variant != 1 || (hi - lo + 7) / 8 > MAX_PASSES) return;  // (no look-back, no error word)
+    const uint32_t* error = scratch + sweep_status_words(n, lo, hi) + GH_WORDS + MAX_PASSES;  // (layout: radix_sort_pairs)
+    or_word_k<<<dim3(1), dim3(1), 0, s>>>(error, out);
 }
 
 int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], size_t n, int lo, int hi, uint32_t* scratch,

@@ -12,6 +12,8 @@ from . import _lib
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
+    if points.dim() >= 1 and points.size(0) >= 2 ** 30:  # (the radix sort of the Morton codes is exact below 2^30 keys)
+        raise RuntimeError("distCUDA2: at most 2^30 - 1 points")
     if not points.is_cuda:
         raise RuntimeError("distCUDA2: points must live on a ROCm GPU (cuda device); there is no CPU fallback")
     if points.dtype != torch.float32:

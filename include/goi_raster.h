@@ -51,7 +51,9 @@ extern "C" {
 
 /* 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
  *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan,
- *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion
+ *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion,
+ *    goi_raster_debug_sort_workspace_bytes, goi_raster_debug_sort_pairs, goi_raster_debug_scan_workspace_bytes,
+ *    goi_raster_debug_exclusive_scan; goi_knn_dist2 and goi_semantic_dbscan refuse 2^30 points or more
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -306,7 +308,7 @@ int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts
  * result[1] = DBSCAN_FLAG_* bits; when result[1] != 0 the labels are not to be used.  points [n][3] fp32, device.
  * workspace: goi_semantic_dbscan_workspace_bytes(n) bytes of device memory, 256-byte aligned.  Asynchronous on `stream`, no
  * host read-back; bit-identical from run to run.  Returns < 0 (goi_raster_last_error) for eps <= 0 or non-finite,
- * min_samples < 1, n < 0 or n >= 2^31; eps outside [2^-40, 2^40] (where the grid's exactness argument stops) is reported
+ * min_samples < 1, n < 0 or n >= 2^30 (the radix sort of the cell keys is exact below 2^30 keys); eps outside [2^-40, 2^40] (where the grid's exactness argument stops) is reported
  * as DBSCAN_FLAG_RANGE.  n = 0 gives 0 clusters. */
 #define DBSCAN_FLAG_NONFINITE 1 /* a coordinate is NaN or infinite (sklearn raises ValueError) */
 #define DBSCAN_FLAG_SORT 2      /* a radix-sort look-back ran out of its spin budget (a wedged device) */
@@ -427,7 +429,8 @@ int goi_raster_sh_grad_from_views(int P, int D, int M, int V, const float* means
  * mean_dist2[i] = (d0 + d1 + d2) / 3 in fp32.  points [P,3] and mean_dist2 [P] are device pointers;
  * workspace holds goi_knn_workspace_bytes(P) bytes of device memory (256-byte aligned).  With fewer
  * than 4 points the missing neighbours count as FLT_MAX, as in the reference.  Asynchronous on
- * `stream`; no host read-back. */
+ * `stream`; no host read-back.  P >= 2^30 is refused (returns < 0; the workspace size is 0): the
+ * radix sort of the Morton codes is exact below 2^30 keys. */
 size_t goi_knn_workspace_bytes(int P);
 int goi_knn_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream);
 
@@ -522,6 +525,27 @@ int goi_raster_debug_views(int P, int W, int H, int R, const void* geom_buffer, 
                            float* depths /*[P]*/, float* means2D /*[P,2]*/, float* conic_opacity /*[P,4]*/,
                            float* rgb /*[P,3]*/, uint32_t* tiles_touched /*[P]*/, uint32_t* point_list /*[R]*/,
                            uint32_t* ranges /*[T,2]*/, uint32_t* n_contrib /*[H*W]*/, void* stream);
+
+/* The device-wide radix sort and scan every stage sorts and scans with (tests only).  Both follow the option snapshot
+ * (goi_raster_set_option "sort_variant" / "sort_small" / "sort_lookback") and are asynchronous on `stream`.
+ * Sort: stable ascending sort of (keys0, vals0) on key bits [lo, hi), 0 <= lo < hi <= 32, n < 2^30; keys1 / vals1 are the
+ * ping-pong buffers.  Returns the index (0/1) of the buffers that hold the result, or < 0 (goi_raster_last_error).
+ *   n_dev    (device, may be NULL): the count; n is then a capacity and min(*n_dev, n) keys are sorted.  Onesweep only.
+ *   ghist    (device, may be NULL): [passes][256] digit histograms of the keys sorted, passes = ceil((hi - lo) / 8) over
+ *            [lo, hi) split as evenly as possible, low digits first.  The sort's histogram kernel is then skipped.  Onesweep only.
+ *   flags    bit 0: the caller has zeroed the workspace's control words (the whole workspace will do).
+ *   error_out (device, may be NULL): gets the sort's error bits OR-ed in (non-zero: the result is not to be used).
+ *   workspace: goi_raster_debug_sort_workspace_bytes(n, lo, hi) bytes, 256-byte aligned.
+ * Scan: out[i] = sum of f(j) over j < i, f(j) = gather ? in[gather[j]] : in[j], mod 2^32; *total (device, may be NULL) =
+ * the sum.  n_dev as above (out[count .. n) is not written).  out == in is allowed only without a gather.
+ *   workspace: goi_raster_debug_scan_workspace_bytes(n) bytes. */
+size_t goi_raster_debug_sort_workspace_bytes(long long n, int lo, int hi);
+int goi_raster_debug_sort_pairs(uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, uint32_t* vals1, long long n, int lo, int hi,
+                                const uint32_t* n_dev, const uint32_t* ghist, int flags, uint32_t* error_out, void* workspace,
+                                void* stream);
+size_t goi_raster_debug_scan_workspace_bytes(long long n);
+int goi_raster_debug_exclusive_scan(const uint32_t* in, const uint32_t* gather, uint32_t* out, long long n, const uint32_t* n_dev,
+                                    uint32_t* total, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
