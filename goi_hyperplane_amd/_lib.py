@@ -102,6 +102,9 @@ SYMBOLS = {
                                     + [C.c_void_p] * 3),
     "goi_raster_debug_scan_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "goi_raster_debug_exclusive_scan": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong] + [C.c_void_p] * 4),
+    "goi_raster_debug_reduce_row_floats": (C.c_int, [C.c_int, C.c_int]),
+    "goi_raster_debug_reduce_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "goi_raster_debug_reduce_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 14),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 // extern "C" entry points of libgoi_raster.so (see include/goi_raster.h): workspace layout,
 // stage orchestration on the caller's HIP stream, per-stage event timing.
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -453,8 +454,7 @@ size_t bwd_scratch_layout(int N, int S, char* base, BwdScratchView* v) {
     BwdScratchView& b = v ? *v : tmp;
     carve(p, b.rows, n * (size_t)bwd_row_floats(S));
     carve(p, b.flags, n);
-    // big Gaussians (more than REDUCE_BIG_INST instances each): at most N / REDUCE_BIG_INST of them
-    b.cap_big = n / 4 / REDUCE_BIG_INST + 2;
+    b.cap_big = reduce_cap_big(n / 4);
     carve(p, b.big_ctl, 8);
     carve(p, b.big_desc, b.cap_big);
     return (size_t)(p - base) + 256;
@@ -840,7 +840,7 @@ int goi_raster_backward_semantics(const GoiRasterScene* scene, int R, const void
     if (R > 0) binning_layout(R, const_cast<char*>(static_cast<const char*>(binning_buffer)), &bv);
     BwdScratchView scr;  // same allocation as the full backward; rows are narrower here
     bwd_scratch_layout(R, sc.S, static_cast<char*>(scratch), &scr);
-    const int row_floats = ((4 * ((sc.S + 3) / 4) + 15) / 16) * 16;
+    const int row_floats = bwd_sem_row_floats(sc.S);
     {
         StageTimer t(GOI_STAGE_BLEND_BWD, s);
         if (R > 0) {
@@ -1268,6 +1268,79 @@ int goi_raster_debug_exclusive_scan(const uint32_t* in, const uint32_t* gather, 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (n > 0 && (!in || !out || !workspace)) return fail("goi_raster_debug_exclusive_scan: a required pointer is NULL");
     exclusive_scan_u32(in, gather, out, (size_t)n, total, static_cast<uint32_t*>(workspace), s, n_dev);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+// The row reduction's workspace: a counter block (the frame words at COUNTER_N / COUNTER_V / COUNTER_OVF, where the launchers
+// read them), big_ctl, big_desc[cap_big] -- the tail of bwd_scratch_layout, with cap_big from the same helper.
+static size_t debug_reduce_layout(long long n_cap, char* base, uint32_t** counters, BwdScratchView* v) {
+    char* p = base;
+    uint32_t* c;
+    carve(p, c, 64);
+    BwdScratchView tmp;
+    BwdScratchView& b = v ? *v : tmp;
+    b.cap_big = reduce_cap_big((size_t)n_cap);
+    carve(p, b.big_ctl, 8);
+    carve(p, b.big_desc, b.cap_big);
+    if (counters) *counters = c;
+    return (size_t)(p - base);
+}
+
+int goi_raster_debug_reduce_row_floats(int mode, int S) {
+    if (mode < 0 || mode > 3) return fail("goi_raster_debug_reduce_rows: unknown mode");
+    if (S < 1 || S > 32) return fail("goi_raster_debug_reduce_rows: need 1 <= S <= 32");
+    if (mode == 3) return bwd_sem_row_floats(S);
+    const int rf = bwd_row_floats(S);
+    if (mode == 2 && rf != 32) return fail("goi_raster_debug_reduce_rows: mode 2 sums 128-byte rows only (S = 5 .. 20)");
+    return rf;
+}
+
+size_t goi_raster_debug_reduce_workspace_bytes(long long n_cap) {
+    if (n_cap < 0 || n_cap > INT_MAX) return 0;
+    return debug_reduce_layout(n_cap, nullptr, nullptr, nullptr) + 256;
+}
+
+int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const uint32_t* frame, const uint32_t* order,
+                                 const uint32_t* offsets, const uint32_t* tiles_touched, float* rows, const uint8_t* flags,
+                                 float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
+                                 float* dL_ddepth, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_debug_reduce_rows";
+    const int rf = goi_raster_debug_reduce_row_floats(mode, S);
+    if (rf < 0) return -1;
+    if (P < 0 || n_cap < 0 || n_cap > INT_MAX) return fail(fn + ": need P >= 0 and 0 <= n_cap < 2^31");
+    if (P == 0) return 0;
+    const bool arrays = mode == 0, per_id = mode == 0 || mode == 3;
+    if (!frame || !order || !offsets || !rows || !flags || !workspace || (per_id && (!tiles_touched || !dL_dsemantic)) ||
+        (arrays && (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_ddepth)))
+        return fail(fn + ": a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + ": workspace must be 256-byte aligned");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    GoiRasterScene sc{};
+    sc.P = P;
+    sc.S = S;
+    GeomView g{};
+    BwdScratchView scr{};
+    debug_reduce_layout(n_cap, static_cast<char*>(workspace), &g.counters, &scr);
+    g.sort_vals[depth_sort_result_index()] = const_cast<uint32_t*>(order);
+    g.offsets = const_cast<uint32_t*>(offsets);
+    g.tiles_touched = const_cast<uint32_t*>(tiles_touched);
+    scr.rows = rows;
+    scr.flags = const_cast<uint8_t*>(flags);
+    // frame = {count, listed V, overflow}; big_ctl cleared as launch_quad_order's extra workgroups (or the memset) do
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_N, frame + 0, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_V, frame + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_OVF, frame + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
+    const int N = (int)n_cap;
+    if (mode == 0)
+        launch_reduce_rows(sc, g, N, scr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, s, false);
+    else if (mode == 1)
+        launch_reduce_rows(sc, g, N, scr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s, true);
+    else if (mode == 2)
+        launch_reduce_big_only(sc, g, N, scr, s);
+    else
+        launch_reduce_sem_rows(sc, g, N, scr, rf, dL_dsemantic, s);
     GOI_HIP(hipGetLastError());
     return 0;
 }

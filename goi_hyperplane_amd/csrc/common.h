@@ -63,6 +63,8 @@ struct ImageView {
 // (emit-order instance, quadrant) and one validity byte per row.
 // row = [sem 0..4*ceil(S/4)) | r g b depth | mean2D.x .y conic.a .b .c opacity | pad], 64-byte multiple
 inline int bwd_row_floats(int S) { return ((4 * ((S + 3) / 4) + 4 + 6 + 15) / 16) * 16; }
+// the semantics-only backward (goi_raster_backward_semantics): rows of the padded semantic channels alone
+inline int bwd_sem_row_floats(int S) { return ((4 * ((S + 3) / 4) + 15) / 16) * 16; }
 #ifndef GOI_REDUCE_BIG_INST
 #define GOI_REDUCE_BIG_INST 384
 #endif
@@ -77,6 +79,9 @@ inline int bwd_row_floats(int S) { return ((4 * ((S + 3) / 4) + 4 + 6 + 15) / 16
 // on the device, from its own counters); 64 quarter waves beyond REDUCE_HUGE_INST instances, 16 up to there.
 constexpr uint32_t REDUCE_BIG_INST = GOI_REDUCE_BIG_INST, REDUCE_HUGE_INST = GOI_REDUCE_HUGE_INST,
                    REDUCE_DENSE_RATIO = GOI_REDUCE_DENSE_RATIO;
+// Descriptors of big Gaussians a row scratch laid out for n_cap instances can receive: each has more than REDUCE_BIG_INST
+// instances (the smaller of the two thresholds), so there are at most n_cap / REDUCE_BIG_INST of them (+ 2 spare).
+inline size_t reduce_cap_big(size_t n_cap) { return (n_cap > 0 ? n_cap : 1) / REDUCE_BIG_INST + 2; }
 struct BwdScratchView {
     float* rows;     // [4N][bwd_row_floats(S)]: slot = (emit-order instance) * 4 + quadrant
     uint8_t* flags;  // [4N] validity bytes

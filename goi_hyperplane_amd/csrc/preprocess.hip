@@ -516,7 +516,7 @@ constexpr bool BWD_HOIST = GOI_PBWD_HOIST != 0;
 // SRC: where the blend gradients of a Gaussian come from -- 0 the six per-id arrays, 1 its RECORD in the row scratch
 // (reduce_rows_k<.., RECORD>), 2 the kernel SUMS THE ROWS ITSELF (bwd_records 2; 128-byte rows): before a tile's chain, the
 // workgroup's sixteen quarter waves walk the tile's Gaussians, each summing one Gaussian's rows exactly as reduce_rows_k does
-// (same function, same slot order: bit-identical sums; slot range two Gaussians ahead, validity bytes one ahead); the 16
+// (same function, same order of the rows: bit-identical sums; slot range two Gaussians ahead, validity bytes one ahead); the 16
 // semantic sums leave for dL/dsemantics at once, the ten values the chain needs go to LDS.  No record is written or read back,
 // no second kernel walks the listed Gaussians; only the BIG ones (reduce_big_k) still pass through a record.
 template <bool WITH_DSH, int SRC>

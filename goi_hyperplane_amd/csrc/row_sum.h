@@ -1,5 +1,7 @@
 // Row summation of the atomic-free backward, shared by reduce_rows.hip (reduce_rows_k, reduce_big_k) and preprocess.hip (the
-// per-Gaussian backward that sums its Gaussians' rows itself: bwd_records 2).  Pure fp32 additions in slot order.
+// per-Gaussian backward that sums its Gaussians' rows itself: bwd_records 2).  Pure fp32 additions in a fixed order: the
+// instances in chunks of 16 counted from the first one, inside a chunk QUADRANT-major (the quadrant-0 rows of the chunk's
+// instances in instance order, then quadrant 1, ..) -- not slot order (slot = instance * 4 + quadrant).
 #pragma once
 #include "common.h"
 
@@ -10,7 +12,7 @@ namespace goi {
 #endif
 
 // Sums the rows of `cnt` consecutive instances starting at instance `inst0` (their validity words at flags32[inst0 ..]) into
-// sum[] -- the lane's elements of the row -- in slot order.  Wave-synchronous: the four quarter waves of a wave call it
+// sum[] -- the lane's elements of the row -- in the order above.  Wave-synchronous: the four quarter waves of a wave call it
 // together, each for its own (inst0, cnt); w_first = the validity word of instance inst0 + e (prefetched by the caller).
 // COMPENSATED (reduce_big_k): Kahan summation -- the lost low bits of every addition are carried in comp[] and fed back.  A big
 // Gaussian's sum runs over ten thousand rows of both signs: the plain fp32 sum's error grows with their number and depends on
@@ -56,8 +58,9 @@ __device__ __forceinline__ void sum_instances(const float* __restrict__ rows, co
                 m |= ((bal >> (16 * quarter)) & 0xFFFFull) << (16 * q);
             }
             const float* chunk = rows + (inst0 + cc) * 4 * RF;
-            // NF rows requested back to back, then added in slot order (absent slots add +0: the sums do not depend on
-            // NF).  Most Gaussians own a handful of rows -- 6 on average, half of them at most 4 -- and the 16-slot trip
+            // NF rows requested back to back, then added in mask order, bit 16q + i lowest first: quadrant-major (absent
+            // slots add +0: the sums do not depend on NF).  Most Gaussians own a handful of rows -- 6 on average, half of
+            // them at most 4 -- and the 16-slot trip
             // costs ~160 vector instructions whatever it finds (the kernel issued 60 M of them: 44 % VALU-busy on top
             // of its memory waits): when no quarter of the wave has more than 4 rows left, a 4-slot trip does.
             auto trip = [&](auto nf_c) {

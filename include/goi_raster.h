@@ -53,7 +53,8 @@ extern "C" {
  *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan,
  *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion,
  *    goi_raster_debug_sort_workspace_bytes, goi_raster_debug_sort_pairs, goi_raster_debug_scan_workspace_bytes,
- *    goi_raster_debug_exclusive_scan; goi_knn_dist2 and goi_semantic_dbscan refuse 2^30 points or more
+ *    goi_raster_debug_exclusive_scan; goi_knn_dist2 and goi_semantic_dbscan refuse 2^30 points or more;
+ *    goi_raster_debug_reduce_row_floats, goi_raster_debug_reduce_workspace_bytes, goi_raster_debug_reduce_rows
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -546,6 +547,29 @@ int goi_raster_debug_sort_pairs(uint32_t* keys0, uint32_t* vals0, uint32_t* keys
 size_t goi_raster_debug_scan_workspace_bytes(long long n);
 int goi_raster_debug_exclusive_scan(const uint32_t* in, const uint32_t* gather, uint32_t* out, long long n, const uint32_t* n_dev,
                                     uint32_t* total, void* workspace, void* stream);
+
+/* The backward's row reduction (tests only): sums the partial-gradient rows of a frame with the product's launchers, on caller
+ * buffers, asynchronously on `stream`.  Slot = (emit-order instance) * 4 + quadrant; rows [4 n_cap][row_floats], validity bytes
+ * flags [4 n_cap] (non-zero: the row is added).  The listed Gaussian of depth rank i (i < V <= P) is order[i] and owns the
+ * instances [offsets[i], offsets[i + 1]) -- the last one up to the count --, clamped to min(count, n_cap); a frame whose overflow
+ * word is non-zero owns none.  A Gaussian's rows are added in 16-instance chunks counted from its first instance, inside a
+ * chunk quadrant-major (all quadrant-0 rows of the chunk's instances, then quadrant 1, ...).
+ *   mode 0: the six per-id arrays of goi_raster_backward (bwd_records 0), every element of all P Gaussians written
+ *   mode 1: one record per listed Gaussian that owns an instance, over its first slot's row (bwd_records 1)
+ *   mode 2: records of the big Gaussians only (bwd_records 2; 128-byte rows, S = 5 .. 20)
+ *   mode 3: dL_dsemantic of the semantics-only backward (rows of the padded semantic channels only)
+ * frame (device): {count, listed V, overflow}.  tiles_touched [P] (non-zero: listed) is read by modes 0 and 3, the arrays by
+ * modes 0 (all six) and 3 (dL_dsemantic); the other pointers may be NULL there.
+ * goi_raster_debug_reduce_row_floats: the row width the mode lays out for S, or < 0 (goi_raster_last_error).
+ * workspace: goi_raster_debug_reduce_workspace_bytes(n_cap) bytes, 256-byte aligned: a 256-byte counter block, then the
+ * 8 control words of the big Gaussians (at byte 256; word 1: huge ones registered, word 2: the other big ones), then their
+ * descriptors. */
+int goi_raster_debug_reduce_row_floats(int mode, int S);
+size_t goi_raster_debug_reduce_workspace_bytes(long long n_cap);
+int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const uint32_t* frame, const uint32_t* order,
+                                 const uint32_t* offsets, const uint32_t* tiles_touched, float* rows, const uint8_t* flags,
+                                 float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
+                                 float* dL_ddepth, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
