@@ -43,6 +43,7 @@ UNITS = {
     "osh.hip": [],
     "dbscan.hip": ["-ffp-contract=off"],
     "masks.hip": [],
+    "codebook_init.hip": [],
 }
 
 

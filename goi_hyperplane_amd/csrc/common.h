@@ -296,6 +296,14 @@ void launch_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, 
 void launch_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
                         hipStream_t s);
 void launch_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, hipStream_t s);
+size_t uniq_workspace_bytes(int V, int D, uint32_t HW);
+uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW);  // [V] counts, then the flag word
+void launch_uniq_dedup(const float* const* maps, int V, int D, uint32_t HW, void* ws, hipStream_t s);
+// true when the view went through the radix sorts (whose error bit lands in the flag word)
+bool launch_uniq_sort(const float* map, int v, int V, int D, uint32_t HW, uint32_t N, float* out, void* ws, hipStream_t s);
+size_t kmeans_workspace_bytes(long long rows, int K, int k, int D);
+void launch_kmeans(float* x, const long long* off, int K, long long max_rows, long long total_rows, int D, int k, int niter,
+                   const int* perms, float* centers, int* status, void* ws, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).

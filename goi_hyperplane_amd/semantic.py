@@ -689,3 +689,202 @@ def evaluate_cameras(cameras, gt_masks: torch.Tensor, pc, mlp: SemanticModel, lu
         total_mpa = total_mpa + m.mpa[v]
         total_mp = total_mp + m.mp[v]
     return SegEvaluation(m.iou, m.mpa, m.mp, total_iou / V, float(total_mpa / V), float(total_mp / V))
+
+
+# ---- code-book initialisation (train.py:78-86) -------------------------------------------------------------------------
+# How unique_rows moves maps that start on the host: "pageable" is a plain .to(device) per map; "pinned" stages them
+# through two reusable pinned buffers, the host copy into one overlapping the DMA out of the other.  Measured on 25 maps
+# of 432 MB: pageable 0.282 s, pinned staging 0.293 s for the whole stage, so pageable is the default.
+# Maps the caller has pinned already are copied asynchronously either way.
+CODEBOOK_STAGING = "pageable"
+_STAGING = {}
+_CODEBOOK_FLAG_NONFINITE = 1  # GOI_CODEBOOK_FLAG_NONFINITE (include/goi_raster.h)
+
+
+class _RowsAlloc:
+    def __init__(self, dev):
+        self.dev, self.tensor, self.error = dev, None, None
+        self.cb = _lib.ALLOC_FN(self._alloc)
+
+    def _alloc(self, _user, nbytes):
+        try:
+            self.tensor = torch.empty(int(nbytes), dtype=torch.uint8, device=self.dev)
+            return self.tensor.data_ptr()
+        except Exception as ex:  # never let an exception cross the C boundary
+            self.error = ex
+            return None
+
+
+def _staging_buffers(nbytes):
+    bufs = _STAGING.get("bufs")
+    if bufs is None or bufs[0].numel() < nbytes:
+        bufs = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        _STAGING["bufs"] = bufs
+    return bufs
+
+
+def _maps_to_device(maps, dev):
+    """fp32 device copies (or the maps themselves) of [D, H, W] maps on the host or the device."""
+    out = [None] * len(maps)
+    host = [i for i, m in enumerate(maps) if not m.is_cuda]
+    for i, m in enumerate(maps):
+        if m.is_cuda:
+            out[i] = m.float().contiguous()
+    if not host:
+        return out
+    main = torch.cuda.current_stream(dev)
+    staged = [i for i in host if not maps[i].is_pinned()] if CODEBOOK_STAGING == "pinned" else []
+    for i in host:
+        if i not in staged:
+            out[i] = maps[i].to(dev, non_blocking=maps[i].is_pinned())
+    if staged:
+        nbytes = max(maps[i].numel() * maps[i].element_size() for i in staged)
+        bufs = _staging_buffers(nbytes)
+        copy = _STAGING.setdefault(("stream", dev), torch.cuda.Stream(dev))
+        copy.wait_stream(main)
+        done = [None, None]
+        for n, i in enumerate(staged):
+            m, b = maps[i].contiguous(), n & 1
+            if done[b] is not None:
+                done[b].synchronize()  # the DMA out of this buffer has finished
+            buf = bufs[b][:m.numel() * m.element_size()].view(m.dtype).view(m.shape)
+            buf.copy_(m)
+            with torch.cuda.stream(copy):
+                out[i] = torch.empty(m.shape, dtype=m.dtype, device=dev)
+                out[i].copy_(buf, non_blocking=True)
+                done[b] = torch.cuda.Event()
+                done[b].record(copy)
+        main.wait_stream(copy)
+        for i in staged:
+            out[i].record_stream(main)
+    return [o.float().contiguous() for o in out]
+
+
+@torch.no_grad()
+def unique_rows(maps):
+    """x.permute(1, 2, 0).reshape(-1, D).unique(dim=0) of each [D, H, W] map (train.py:80), on the device: a list of
+    [N_v, D] float32 CUDA tensors (a single map gives a list of one).  Exact: rows are compared by value (-0 == +0) and
+    come out in ascending lexicographic order, as torch.unique(dim=0) on the CPU orders them.  Maps may live on the host
+    or the device, in float32, float16 or bfloat16 (conversion to float32 is exact and keeps the order).  One read-back
+    of the counts of all views of a shape; NaN or Inf in a map raises ValueError (the reference's order is undefined
+    there).  Maps on the host are copied per view (CODEBOOK_STAGING)."""
+    lst = [maps] if torch.is_tensor(maps) else list(maps)
+    if not lst:
+        return []
+    for m in lst:
+        if not torch.is_tensor(m) or m.dim() != 3:
+            raise ValueError("unique_rows: every map must be a [D, H, W] tensor")
+        if m.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"unique_rows: maps must be float32, float16 or bfloat16, got {m.dtype}")
+    dev = next((m.device for m in lst if m.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+    dmaps = _maps_to_device(lst, dev)
+    groups = {}
+    for i, m in enumerate(dmaps):
+        groups.setdefault(tuple(m.shape), []).append(i)
+    lib = _lib.load()
+    out = [None] * len(lst)
+    for (D, H, W), idx in groups.items():
+        V = len(idx)
+        ws = torch.empty(max(int(lib.goi_codebook_unique_rows_workspace_bytes(V, D, H, W)), 1), dtype=torch.uint8, device=dev)
+        ptrs = (C.c_void_p * V)(*[dmaps[i].data_ptr() for i in idx])
+        counts = (C.c_longlong * V)()
+        flags = C.c_uint(0)
+        alloc = _RowsAlloc(dev)
+        with torch.cuda.device(dev):
+            r = lib.goi_codebook_unique_rows(ptrs, V, D, H, W, counts, C.byref(flags), alloc.cb, None, C.c_void_p(ws.data_ptr()),
+                                             _stream(dev))
+        if r < 0:
+            raise ValueError(_lib.last_error())
+        if alloc.error is not None:
+            raise alloc.error
+        if flags.value & _CODEBOOK_FLAG_NONFINITE:
+            raise ValueError("unique_rows: a map holds NaN or Inf values (the order of unique(dim=0) is undefined there)")
+        if flags.value:
+            raise RuntimeError(f"unique_rows: device flag word {flags.value:#x} (sort or table bound hit); the rows are not usable")
+        rows = alloc.tensor[:sum(counts) * D * 4].view(torch.float32).view(-1, D)
+        start = 0
+        for j, i in enumerate(idx):
+            out[i] = rows[start:start + counts[j]]
+            start += counts[j]
+    return out
+
+
+@torch.no_grad()
+def spherical_kmeans_batched(xs, ncluster: int, niter: int = 10):
+    """io.kmeans (train.py:36-56) of every [N_i, D] float32 CUDA tensor of xs in ONE set of launches: a list of
+    [ncluster, D] centres.  Same RNG draws as calling io.kmeans on each in list order (torch.randperm(N_i) on the CPU
+    default generator, 1 + niter times each, drawn up front), same in-place normalisation of every x, RuntimeError where
+    the reference raises (more dead centres than rows; the generator is then left as the reference leaves it).  fp32
+    arithmetic, deterministic means (bit-reproducible); the argmax can differ from a library matmul only at near-ties."""
+    xs = list(xs)
+    if not xs:
+        return []
+    ncluster, niter = int(ncluster), int(niter)
+    if ncluster < 1:
+        raise ValueError("spherical_kmeans: ncluster must be >= 1")
+    if niter < 0:
+        raise ValueError("spherical_kmeans: niter must be >= 0")
+    D = int(xs[0].shape[1]) if xs[0].dim() == 2 else -1
+    for x in xs:
+        if not torch.is_tensor(x) or x.dim() != 2 or int(x.shape[1]) != D:
+            raise ValueError("spherical_kmeans: every x must be [N, D] with the same D")
+        if x.dtype != torch.float32:
+            raise TypeError(f"spherical_kmeans: x must be float32, got {x.dtype}")
+        if not x.is_cuda:
+            raise RuntimeError(_NO_CPU)
+    sizes = [int(x.shape[0]) for x in xs]
+    dev = xs[0].device
+    state = torch.get_rng_state()
+    perms = []
+    for n in sizes:
+        if n == 0:
+            raise RuntimeError("spherical_kmeans: x has no rows (the reference's argmax of an empty tensor raises)")
+        perms.extend(torch.randperm(n) for _ in range(niter + 1))
+    perms = torch.cat(perms).to(torch.int32).to(dev)
+    xcat = torch.cat(xs).contiguous() if len(xs) > 1 else xs[0].contiguous()
+    offsets = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(dev)
+    centers = torch.empty(len(xs), ncluster, D, dtype=torch.float32, device=dev)
+    status = torch.empty(len(xs), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    rows = sum(sizes)
+    ws = torch.empty(max(int(lib.goi_codebook_kmeans_workspace_bytes(rows, len(xs), ncluster, D)), 1), dtype=torch.uint8, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    with torch.cuda.device(dev):
+        r = lib.goi_codebook_kmeans(p(xcat), p(offsets), len(xs), max(sizes), rows, D, ncluster, niter, p(perms), p(centers),
+                                    p(status), p(ws), _stream(dev))
+    if r < 0:
+        raise ValueError(_lib.last_error())
+    start = 0
+    for x, n in zip(xs, sizes):  # x /= x.norm(...) is in place in the reference
+        if xcat.data_ptr() != x.data_ptr():
+            x.copy_(xcat[start:start + n])
+        start += n
+    st = status.cpu().tolist()  # the one synchronisation
+    bad = next((i for i, s in enumerate(st) if s), None)
+    if bad is not None:
+        # the reference raises inside problem `bad` at iteration st[bad] - 1, after its seed draw and st[bad] more
+        torch.set_rng_state(state)
+        for n in sizes[:bad]:
+            for _ in range(niter + 1):
+                torch.randperm(n)
+        for _ in range(st[bad] + 1):
+            torch.randperm(sizes[bad])
+        raise RuntimeError(f"spherical_kmeans: more dead centres than the {sizes[bad]} rows at iteration {st[bad] - 1} "
+                           f"(the reference's centers[nanix] = x[randperm(N)[:ndead]] shape mismatch)")
+    return list(centers.unbind(0))
+
+
+def spherical_kmeans(x: torch.Tensor, ncluster: int, niter: int = 10) -> torch.Tensor:
+    """Device drop-in for io.kmeans (train.py:36-56) on a [N, D] float32 CUDA tensor: spherical_kmeans_batched of one."""
+    return spherical_kmeans_batched([x], ncluster, niter)[0]
+
+
+@torch.no_grad()
+def init_codebook(ape_maps, tab_len: int = 300, per_view: int = 80, niter: int = 10) -> torch.Tensor:
+    """The code-book initialisation of train.py:78-84 for the [ape_dim, H, W] APE maps given (the caller applies the
+    reference's [::8] to its cameras): unique rows per view, k-means of each into per_view centres (one batched launch
+    set), k-means of all of them into tab_len; returns the [tab_len, ape_dim] float32 LUT.  Same RNG draws and order as
+    the reference stage."""
+    uniq = unique_rows(ape_maps)
+    tot = torch.cat(spherical_kmeans_batched(uniq, per_view, niter), 0)
+    return spherical_kmeans(tot, tab_len, niter).float()

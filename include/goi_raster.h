@@ -54,7 +54,8 @@ extern "C" {
  *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion,
  *    goi_raster_debug_sort_workspace_bytes, goi_raster_debug_sort_pairs, goi_raster_debug_scan_workspace_bytes,
  *    goi_raster_debug_exclusive_scan; goi_knn_dist2 and goi_semantic_dbscan refuse 2^30 points or more;
- *    goi_raster_debug_reduce_row_floats, goi_raster_debug_reduce_workspace_bytes, goi_raster_debug_reduce_rows
+ *    goi_raster_debug_reduce_row_floats, goi_raster_debug_reduce_workspace_bytes, goi_raster_debug_reduce_rows,
+ *    goi_codebook_unique_rows_workspace_bytes, goi_codebook_unique_rows, goi_codebook_kmeans_workspace_bytes, goi_codebook_kmeans
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -347,6 +348,39 @@ int goi_semantic_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, in
 int goi_semantic_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
                              void* stream);
 int goi_semantic_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, void* stream);
+
+/* ---- code-book initialisation (train.py:78-86; csrc/codebook_init.hip) ----------------------------------------------
+ * goi_codebook_unique_rows: the rows of x.permute(1, 2, 0).reshape(-1, D).unique(dim=0) of each of n_views fp32 maps
+ *   maps[v] [D][H][W] (a host array of n_views device pointers; the maps are read in place), exact: rows are compared by
+ *   value (-0 == +0; the kept row is the first pixel's), written in ascending lexicographic order of their values.
+ *   The call synchronises `stream` once to read the per-view counts, then asks alloc(alloc_user, bytes) for the output
+ *   [sum counts][D] fp32 (views one after another) and fills it asynchronously; a view of more than
+ *   GOI_CODEBOOK_RANK_MAX distinct rows (or of D > 8192) is sorted by D radix sorts, after which the call synchronises once more to read
+ *   the sort's error bit.  counts (host, [n_views]) and flags (host, GOI_CODEBOOK_FLAG_* bits) are written; when
+ *   *flags != 0 nothing is allocated or written and the rows are not to be used.  1 <= D, H * W < 2^30.
+ *   workspace: goi_codebook_unique_rows_workspace_bytes(n_views, D, H, W) bytes of device memory, 256-byte aligned.
+ * goi_codebook_kmeans: spherical k-means (train.py:36-56) of n_problems problems at once.  Problem p owns rows
+ *   row_offsets[p] .. row_offsets[p+1]-1 (device, int64) of x [n_rows][D] fp32, which is normalised IN PLACE (a zero
+ *   row becomes NaN, as in the reference); max_rows = the largest problem's row count (host).  perms (device, int32)
+ *   holds, per problem from (niter + 1) * row_offsets[p] on, the niter + 1 permutations of 0 .. N_p-1 the reference
+ *   draws (torch.randperm(N_p): the seed order, then one per iteration).  centers [n_problems][ncluster][D] receives
+ *   the final centres (the last means with dead centres replaced, not normalised).  status (device, [n_problems]
+ *   int32): 0, or 1 + the iteration at which more centres died than the problem has rows (the reference raises
+ *   there).  fp32 throughout, no float atomics: bit-identical from run to run.  Asynchronous: no host synchronisation.
+ *   Every problem needs N_p >= 1.  1 <= ncluster <= GOI_CODEBOOK_KMEANS_MAX_K, 1 <= D <= GOI_CODEBOOK_KMEANS_MAX_DIM.
+ *   workspace: goi_codebook_kmeans_workspace_bytes(n_rows, n_problems, ncluster, D) bytes, 256-byte aligned. */
+#define GOI_CODEBOOK_FLAG_NONFINITE 1 /* a map holds a NaN or an Inf (the reference's order is undefined there) */
+#define GOI_CODEBOOK_FLAG_SORT 2      /* a radix-sort look-back ran out of its spin budget (a wedged device) */
+#define GOI_CODEBOOK_FLAG_TABLE 4     /* a hash probe reached its bound (cannot happen: the table is twice the pixels) */
+#define GOI_CODEBOOK_RANK_MAX 4096
+#define GOI_CODEBOOK_KMEANS_MAX_K 4096
+#define GOI_CODEBOOK_KMEANS_MAX_DIM 1024
+size_t goi_codebook_unique_rows_workspace_bytes(int n_views, int D, int H, int W);
+int goi_codebook_unique_rows(const float* const* maps, int n_views, int D, int H, int W, long long* counts, unsigned* flags,
+                             goi_alloc_fn alloc, void* alloc_user, void* workspace, void* stream);
+size_t goi_codebook_kmeans_workspace_bytes(long long n_rows, int n_problems, int ncluster, int D);
+int goi_codebook_kmeans(float* x, const long long* row_offsets, int n_problems, long long max_rows, long long n_rows, int D,
+                        int ncluster, int niter, const int* perms, float* centers, int* status, void* workspace, void* stream);
 
 /* ---- measurement hooks (bench.py): per-stage HIP-event timing on the launch stream ---------- */
 enum {
