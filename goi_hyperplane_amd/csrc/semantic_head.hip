@@ -351,9 +351,10 @@ int launch_semantic_decode(const float* sem, int S, long long HW, const float* W
     case N:                                  \
         GOI_LAUNCH((semantic_decode_k<N, 0>)); \
         break;
-    if (S <= 16 && g_options.decode_variant >= 1) {  // split-bf16 contraction (fp32 accuracy at the bf16 matrix rate)
-        const size_t lds3 = (size_t)ncp * 16 * 2 * 3 + (size_t)ncp * 4 * sizeof(float);
-        if (lds3 > 64 * 1024) return -1;
+    // split-bf16 contraction (fp32 accuracy at the bf16 matrix rate) while its code book fits the default 64 KiB of
+    // dynamic LDS (n_codes <= 576); larger code books go to the fp32 kernel below, whose 160 KiB hold 2400 codes at S = 16
+    const size_t lds3 = (size_t)ncp * 16 * 2 * 3 + (size_t)ncp * 4 * sizeof(float);
+    if (S <= 16 && g_options.decode_variant >= 1 && lds3 <= 64 * 1024) {
         // pixel blocks per operand fetch: 2 (default; 0.152 ms at 1600x1056, 300 codes), 4 (0.158) or 1 (0.165)
         const int npb = g_options.decode_variant == 1 ? 2 : g_options.decode_variant == 2 ? 4 : 1;
         // persistent grid: as many workgroups as are resident at once (W is split and staged once per workgroup)

@@ -150,7 +150,11 @@ def compute_similarity(sem_chw: torch.Tensor, mlp: SemanticModel, lut: torch.Ten
                        out_bg_mask: torch.Tensor | None = None, return_index: bool = False):
     """Fused decode of a rendered semantic map `sem_chw` [S, H, W] (the rasterizer's output, NOT
     permuted): returns sim[H*W] with background (sim < thresh) zeroed, like the reference's
-    compute_similarity(embedding_feature=[HW,S]).  Runs only on the GPU through libgoi_raster.so."""
+    compute_similarity(embedding_feature=[HW,S]).  Runs only on the GPU through libgoi_raster.so.
+
+    Shapes (include/goi_raster.h, goi_semantic_decode): 1 <= S <= 32 and 1 <= tab_len <= 16 * floor(10240 /
+    (16 * ceil(S / 4) + 4)), i.e. 2400 codes at S = 16 and 1232 at S = 32; a larger code book raises.  S <= 16 with
+    tab_len <= 576 decodes on the split-bf16 kernel, everything else on the fp32-MFMA kernel."""
     if mlp.num_layer != 1:
         raise NotImplementedError("the fused decode covers the reference's configuration: one Linear(S -> tab_len)")
     if not sem_chw.is_cuda:

@@ -273,7 +273,13 @@ int goi_raster_mark_visible(int P, const float* means3D, const float* viewmatrix
  * sim < thresh -> background (sim = 0).  `sem` is the rasterizer's semantic output [S, HW]
  * (channel-major, no permute); W is [n_codes, S] row-major (torch Linear.weight); code_score[n_codes]
  * is the host-folded tail (LUT lookup -> L2 normalise -> LinearSVM/VLM score).  Any of sim_out[HW],
- * idx_out[HW] (int32), bg_mask_out[HW] (bytes) may be NULL.  S <= 32. */
+ * idx_out[HW] (int32), bg_mask_out[HW] (bytes) may be NULL.  Ties go to the lowest code index.
+ * 1 <= S <= 32 and 1 <= n_codes <= 16 * floor(10240 / (16 * ceil(S / 4) + 4)) (the code book staged in 160 KiB of LDS:
+ * 8192 codes at S <= 4, 2400 at S = 13..16, 1232 at S = 29..32); a larger code book is refused with nothing written.
+ * Which kernel serves a call (csrc/semantic_head.hip): S <= 16 and n_codes <= 576 (64 KiB of LDS) under "decode_variant"
+ * 1 .. 3 the split-bf16 contraction semantic_decode3n_k; every other shape, and every shape under decode_variant 0, the
+ * fp32-MFMA semantic_decode_k (specialised for 289..304 codes at S = 13..16).  Both are accurate to fp32 rounding of
+ * the logits. */
 int goi_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
                         const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
                         void* stream);
