@@ -100,6 +100,11 @@ SYMBOLS = {
     "goi_codebook_kmeans_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
     "goi_codebook_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong] + [C.c_int] * 3
                             + [C.c_void_p] * 5),
+    "goi_raster_photometric_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_uint]),
+    "goi_raster_photometric_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          C.c_uint] + [C.c_void_p] * 4),
+    "goi_raster_photometric_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.c_uint] + [C.c_void_p] * 5),
     "goi_raster_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "goi_raster_blend_stats": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 5),
     "goi_raster_debug_views": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_void_p] * 8 + [C.c_void_p]),

@@ -44,6 +44,7 @@ UNITS = {
     "dbscan.hip": ["-ffp-contract=off"],
     "masks.hip": [],
     "codebook_init.hip": [],
+    "photometric.hip": [],
 }
 
 

@@ -1065,6 +1065,52 @@ int goi_codebook_kmeans(float* x, const long long* row_offsets, int n_problems, 
     return 0;
 }
 
+namespace {
+// the shape limits of goi_raster_photometric_*: "" when the call may go ahead
+std::string photometric_check(long long n, int c, int h, int w, int window_size) {
+    if (window_size != GOI_PHOTOMETRIC_WINDOW) return "window_size " + std::to_string(window_size) + " is not supported (only 11)";
+    if (n < 1 || c < 1 || h < 1 || w < 1) return "need n, c, h, w >= 1";
+    if ((long long)h * w >= (1ll << 31)) return "need h * w < 2^31";
+    if (n * c * ((h + 31) / 32) * (long long)((w + 31) / 32) >= (1ll << 31)) return "need n * c * ceil(h/32) * ceil(w/32) < 2^31";
+    return "";
+}
+}  // namespace
+
+size_t goi_raster_photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags) {
+    if (!photometric_check(n, c, h, w, GOI_PHOTOMETRIC_WINDOW).empty()) return 0;
+    return photometric_workspace_bytes(n, c, h, w, flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2));
+}
+
+int goi_raster_photometric_forward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
+                                   float lambda_dssim, unsigned flags, float* out, float* out_images, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_photometric_forward: ";
+    const std::string bad = photometric_check(n, c, h, w, window_size);
+    if (!bad.empty()) return fail(fn + bad);
+    if (!img1 || !img2 || !out || !workspace) return fail(fn + "a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    launch_photometric_forward(img1, img2, n, c, h, w, lambda_dssim, flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2), out,
+                               out_images, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_photometric_backward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
+                                    float lambda_dssim, unsigned flags, const float* grad_out, const void* workspace, float* grad1,
+                                    float* grad2, void* stream) {
+    const std::string fn = "goi_raster_photometric_backward: ";
+    const std::string bad = photometric_check(n, c, h, w, window_size);
+    if (!bad.empty()) return fail(fn + bad);
+    if (!(flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2))) return fail(fn + "no gradient asked for");
+    if (!img1 || !img2 || !grad_out || !workspace || ((flags & GOI_PHOTOMETRIC_GRAD1) && !grad1) ||
+        ((flags & GOI_PHOTOMETRIC_GRAD2) && !grad2))
+        return fail(fn + "a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    launch_photometric_backward(img1, img2, n, c, h, w, lambda_dssim, flags, grad_out, workspace, grad1, grad2,
+                                static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
 int goi_codebook_loss_partial_rows(void) { return codebook_loss_waves(); }
 
 int goi_codebook_loss_rows(const float* sim_raw, const float* inv_gnorm, const float* sem, const float* W,

@@ -305,6 +305,12 @@ size_t kmeans_workspace_bytes(long long rows, int K, int k, int D);
 void launch_kmeans(float* x, const long long* off, int K, long long max_rows, long long total_rows, int D, int k, int niter,
                    const int* perms, float* centers, int* status, void* ws, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
+constexpr int PHOTO_RADIUS = GOI_PHOTOMETRIC_WINDOW / 2;  // the only window instantiated (photometric.hip)
+size_t photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags);
+void launch_photometric_forward(const float* x, const float* y, long long n, int c, int h, int w, float lambda, unsigned flags,
+                                float* out, float* out_images, void* ws, hipStream_t s);
+void launch_photometric_backward(const float* x, const float* y, long long n, int c, int h, int w, float lambda, unsigned flags,
+                                 const float* grad_out, const void* ws, float* gx, float* gy, hipStream_t s);
 
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).
 __device__ __forceinline__ void tile_rect(float px, float py, int r, int gx, int gy, int& x0, int& y0, int& x1,

@@ -55,7 +55,8 @@ extern "C" {
  *    goi_raster_debug_sort_workspace_bytes, goi_raster_debug_sort_pairs, goi_raster_debug_scan_workspace_bytes,
  *    goi_raster_debug_exclusive_scan; goi_knn_dist2 and goi_semantic_dbscan refuse 2^30 points or more;
  *    goi_raster_debug_reduce_row_floats, goi_raster_debug_reduce_workspace_bytes, goi_raster_debug_reduce_rows,
- *    goi_codebook_unique_rows_workspace_bytes, goi_codebook_unique_rows, goi_codebook_kmeans_workspace_bytes, goi_codebook_kmeans
+ *    goi_codebook_unique_rows_workspace_bytes, goi_codebook_unique_rows, goi_codebook_kmeans_workspace_bytes, goi_codebook_kmeans,
+ *    goi_raster_photometric_workspace_bytes, goi_raster_photometric_forward, goi_raster_photometric_backward
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -387,6 +388,32 @@ int goi_codebook_unique_rows(const float* const* maps, int n_views, int D, int H
 size_t goi_codebook_kmeans_workspace_bytes(long long n_rows, int n_problems, int ncluster, int D);
 int goi_codebook_kmeans(float* x, const long long* row_offsets, int n_problems, long long max_rows, long long n_rows, int D,
                         int ncluster, int niter, const int* perms, float* centers, int* status, void* workspace, void* stream);
+
+/* ---- photometric loss and image metrics (train.py:137-140, utils/loss_utils.py, utils/image_utils.psnr; csrc/photometric.hip)
+ * img1, img2: [n][c][h][w] fp32 (a [c][h][w] image is n = 1).  SSIM is loss_utils._ssim: the 11x11 Gaussian window
+ *   (sigma 1.5), zero padding of 5 per (image, channel) plane, C1 = 0.01^2, C2 = 0.03^2.  window_size must be
+ *   GOI_PHOTOMETRIC_WINDOW; other sizes are refused.  1 <= h, w; h * w < 2^31; n * c * ceil(h/32) * ceil(w/32) < 2^31.
+ * goi_raster_photometric_forward: out (device, [3]) = loss = (1 - lambda_dssim) * L1 + lambda_dssim * (1 - SSIM), L1 = mean |img1 -
+ *   img2|, SSIM = mean of the SSIM map, all over every element.  out_images (device, [3][n], or NULL) = per image the SSIM
+ *   mean, the L1 mean and PSNR = 20 log10(1 / sqrt(mean (img1 - img2)^2)).  flags GOI_PHOTOMETRIC_GRAD1 / _GRAD2 keep in
+ *   the workspace what the backward needs for the gradient of img1 / img2.
+ * goi_raster_photometric_backward: after a forward with the same arguments, flags and workspace (untouched in between): grad1 =
+ *   dL/dimg1 (GRAD1), grad2 = dL/dimg2 (GRAD2), for L = the loss above (flags without GOI_PHOTOMETRIC_SSIM_ONLY) or the SSIM
+ *   mean itself (with it), times the upstream gradient grad_out (device): one value for the mean over every element, or
+ *   with GOI_PHOTOMETRIC_PER_IMAGE one value per image for per-image means.  The L1 term's gradient is 0 where img1 == img2.
+ *   workspace: goi_raster_photometric_workspace_bytes(n, c, h, w, flags) bytes of device memory, 256-byte aligned.
+ * Sums are formed in a fixed order without float atomics: bit-identical from call to call.  No host synchronisation. */
+#define GOI_PHOTOMETRIC_WINDOW 11
+#define GOI_PHOTOMETRIC_GRAD1 1u     /* the gradient of img1 is wanted */
+#define GOI_PHOTOMETRIC_GRAD2 2u     /* the gradient of img2 is wanted */
+#define GOI_PHOTOMETRIC_PER_IMAGE 4u /* backward: grad_out holds n values, of per-image means */
+#define GOI_PHOTOMETRIC_SSIM_ONLY 8u /* backward: the gradient of the SSIM mean, not of the loss */
+size_t goi_raster_photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags);
+int goi_raster_photometric_forward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
+                                   float lambda_dssim, unsigned flags, float* out, float* out_images, void* workspace, void* stream);
+int goi_raster_photometric_backward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
+                                    float lambda_dssim, unsigned flags, const float* grad_out, const void* workspace, float* grad1,
+                                    float* grad2, void* stream);
 
 /* ---- measurement hooks (bench.py): per-stage HIP-event timing on the launch stream ---------- */
 enum {
