@@ -1224,21 +1224,17 @@ int goi_raster_set_option(const char* name, int value) {
     if (!name) return fail("option name is NULL");
     std::lock_guard<std::mutex> lk(g_options_mu);
     Options& g_options = g_shared_options;  // (calls already running keep their own snapshot)
-    if (!strcmp(name, "fwd_variant")) g_options.fwd_variant = value;
+    if (!strcmp(name, "fwd_variant")) {
+        if (value < 0 || value > 1) return fail("fwd_variant must be 0 or 1");
+        g_options.fwd_variant = value;
+    }
     else if (!strcmp(name, "bwd_variant")) {
         if (value < 0 || value > 2) return fail("bwd_variant must be 0, 1 or 2");
         g_options.bwd_variant = value;
     }
     else if (!strcmp(name, "sort_variant")) g_options.sort_variant = value;
     else if (!strcmp(name, "sort_small")) g_options.sort_small = value;
-    else if (!strcmp(name, "pre_shdma")) g_options.pre_shdma = value;
     else if (!strcmp(name, "sort_lookback")) g_options.sort_lookback = value;
-    else if (!strcmp(name, "sort_tickets")) {
-        // 0 is an EXPERIMENT that is only safe while the hardware starts workgroups in index order (HIP promises no such thing: a
-        // tile could wait for a workgroup that never starts): refused unless the process opts in explicitly
-        if (value == 0 && !getenv("GOI_UNSAFE_EXPERIMENTS")) return fail("sort_tickets 0 is an unsafe experiment: set GOI_UNSAFE_EXPERIMENTS=1 to allow it");
-        g_options.sort_tickets = value;
-    }
     else if (!strcmp(name, "cull_variant")) g_options.cull_variant = value;
     else if (!strcmp(name, "bwd_order")) {
         if (value < 0 || value > 8) return fail("bwd_order must be 0 .. 8");

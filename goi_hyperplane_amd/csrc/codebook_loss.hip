@@ -554,7 +554,7 @@ __global__ __launch_bounds__(64 * SIM_NW) void codebook_sim_k(const float* __res
 //                     pixels are 8 bytes, a wave store is 512 contiguous bytes, and the layout is the A operand of the last
 //                     kernel.  Per pixel it records the code-book label (first arg-maximum, number of maxima; the full set
 //                     of maxima as a bit mask in the rare case of a tie).
-//   decoder_grad_k    z again, P from the recorded statistics, dz, and its two contractions:
+//   decoder_gd_k      z again, P from the recorded statistics, dz, and its two contractions, two code blocks at a time:
 //                       dL/dW[c][s] = sum_p dz[p][c] f[p][s]  over pixels: the dz tile in the D layout IS the A operand
 //                                     (M = code, k = 4 kq + r = pixel) -- persistent accumulators, one partial per wave;
 //                       dL/df[p][s] = sum_c dz[p][c] W[c][s]  over codes, the lane axis of the D layout: dz goes through a
@@ -575,9 +575,8 @@ constexpr int FU_NJ = (SIM_NCB + 1) / 2;      // 32-code K steps of the df contr
 constexpr int FU_WT_BYTES = 2 * FU_NJ * 16 * 64;  // decoder planes for df: [2][10][16 s][32 codes] bf16
 constexpr int FU_DCHUNK = 2 * SIM_NC * 16;    // uint16 elements of one 16-pixel block of the dsim planes
 constexpr int FU_TIE_WORDS = 10;              // 304 bits
-constexpr int DG_NW = 8;                      // decoder_grad_k: waves per workgroup (one workgroup per CU, persistent)
+constexpr int GD_NW = 8;                      // decoder_gd_k: waves per workgroup (one workgroup per CU, persistent)
 constexpr int DS_NW = 4;                      // decoder_stats_k
-constexpr int DF_NW = 12;                     // decoder_df_k: three waves per SIMD, one workgroup per CU
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
@@ -590,7 +589,7 @@ struct FusedArgs {
     const float* sem;        // [S][HW]
     uint16_t* dplanes;       // [blocks][2][304][16] bf16
     float* dsem;             // [S][HW]
-    float* partials;         // [decoder_grad waves][C (S + 1) + 4]
+    float* partials;         // [decoder_gd waves][C (S + 1) + 4]
     // per-pixel records, [16 * blocks] each
     float *r_mz, *r_rzp, *r_p2, *r_nl;
     int *r_arga, *r_args;
@@ -645,8 +644,8 @@ __device__ __forceinline__ int row_min(int v) {
 
 // z tiles of one 16-pixel block: A = f [pixel mm][s = 4 kq + i] (fv: this lane's four values), B = W [code mm][s = 4 kq + i]
 // from the LDS image (wz_l = image + 32 mm + 8 kq), C = bias (bias_l = s_bias + mm).  The three products of a tile are issued
-// term by term over groups of four tiles: no MFMA waits for the one before it.  decoder_stats_k and decoder_grad_k both call
-// this: the same instructions in the same order, the same z to the last bit.
+// term by term over groups of four tiles: no MFMA waits for the one before it.  decoder_stats_k calls this; decoder_gd_k forms
+// each tile with the same three products in the same order: the same z to the last bit.
 __device__ __forceinline__ void decoder_logits(f32x4 (&z)[SIM_NCB], const float (&fv)[4], const char* wz_l, const float* bias_l,
                                                bool vlast) {
     uint32_t fh[2], fl[2];
@@ -693,7 +692,7 @@ __global__ __launch_bounds__(64 * DS_NW, 3) void decoder_stats_k(const FusedArgs
     const bool vlast = 16 * (SIM_NCB - 1) + mm < a.C;
     const char* const wz_l = s_wz + 32 * mm + 8 * kq;
     const float* const bias_l = s_bias + mm;
-    auto fetch = [&](long long blk, float (&fv)[4]) {  // one block ahead: see decoder_grad_k
+    auto fetch = [&](long long blk, float (&fv)[4]) {  // one block ahead: see decoder_gd_k
         const long long p = min(16 * min(blk, a.blocks - 1) + mm, HW - 1);
 #pragma unroll
         for (int i = 0; i < 4; i++) fv[i] = (4 * kq + i < a.S) ? a.sem[(size_t)(4 * kq + i) * HW + p] : 0.f;
@@ -905,7 +904,7 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void codebook_simgrad_k(const FusedA
             o_nl[r] = nl;
             (&o_args.x)[r] = arg_s;
             // A tie (several codes share the maximum of sim: duplicate code-book rows) is the one case in which
-            // decoder_grad_k cannot rebuild the label from (arg_s, nl): the set of maxima goes out as a bit mask, bit c of the
+            // decoder_gd_k cannot rebuild the label from (arg_s, nl): the set of maxima goes out as a bit mask, bit c of the
             // pixel's 304.  (dL/dsim itself follows the FIRST maximum, as the row kernel and torch.max do.)
             if (__builtin_expect(__any(nl > 1.f), 0)) {
                 uint32_t* wd = a.r_tie + (size_t)(pbase + 4 * kq + r) * FU_TIE_WORDS;
@@ -959,48 +958,11 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void codebook_simgrad_k(const FusedA
     if (lane == 0) *reinterpret_cast<f32x4*>(a.sums_a + 4 * ((size_t)blockIdx.x * SG_NW + w)) = f32x4{t0, t1, t2, t3};
 }
 
-// dz of one 16-pixel block in place of its logits z: P from the recorded statistics, the label from (arg_s, nl) or, for a tie,
-// from the recorded bit mask.  Returns this lane's share of the lab loss sum (counted once per pixel row: lanes mm = 0).
+// the recorded statistics of a 16-pixel block's rows 4 kq .. 4 kq + 3 (decoder_stats_k, codebook_simgrad_k)
 struct DecIn {
     f32x4 mz, rzp, p2, nl;
     int4 args;
 };
-__device__ __forceinline__ float decoder_dz(f32x4 (&z)[SIM_NCB], const DecIn& in, const FusedArgs& a, long long pbase, int kq, int mm) {
-    float lab_sum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const bool valid = pbase + 4 * kq + r < a.HW;
-        const float mz = in.mz[r], rZ = in.rzp[r], P2 = in.p2[r], nl = in.nl[r];
-        const int arg_s = (&in.args.x)[r];
-        float sP = 0.f;
-        uint32_t labm = 0;  // bit cb: this lane's code of block cb is a maximum of sim
-        if (__builtin_expect(__any(nl > 1.f), 0)) {
-            const uint32_t* wd = a.r_tie + (size_t)(pbase + 4 * kq + r) * FU_TIE_WORDS;
-#pragma unroll
-            for (int cb = 0; cb < SIM_NCB; cb++) {
-                const bool lab = nl > 1.f ? ((wd[cb >> 1] >> (16 * (cb & 1) + mm)) & 1u) != 0 : (16 * cb + mm == arg_s);
-                labm |= lab ? (1u << cb) : 0u;
-            }
-        } else {
-            labm = (arg_s & 15) == mm ? 1u << (arg_s >> 4) : 0u;
-        }
-#pragma unroll
-        for (int cb = 0; cb < SIM_NCB; cb++) {
-            z[cb][r] = __expf(z[cb][r] - mz) * rZ;  // P
-            sP += (labm >> cb) & 1u ? z[cb][r] : 0.f;
-        }
-        const float Pl = row_sum(sP);
-        lab_sum += (valid && mm == 0) ? (P2 - 2.f * Pl) + nl : 0.f;
-        const float kap = valid ? a.kappa : 0.f;  // a pixel beyond the map has no gradient
-        const float Dsum = kap * (P2 - Pl);
-#pragma unroll
-        for (int cb = 0; cb < SIM_NCB; cb++) {
-            const float P = z[cb][r], lab = (labm >> cb) & 1u ? 1.f : 0.f;
-            z[cb][r] = P * (kap * (P - lab) - Dsum);  // dz
-        }
-    }
-    return lab_sum;
-}
 __device__ __forceinline__ void decoder_fetch(DecIn& in, const FusedArgs& a, long long pbase, int kq) {
     in.mz = *reinterpret_cast<const f32x4*>(a.r_mz + pbase + 4 * kq);
     in.rzp = *reinterpret_cast<const f32x4*>(a.r_rzp + pbase + 4 * kq);
@@ -1009,206 +971,19 @@ __device__ __forceinline__ void decoder_fetch(DecIn& in, const FusedArgs& a, lon
     in.args = *reinterpret_cast<const int4*>(a.r_args + pbase + 4 * kq);
 }
 
-// ---- dL/dW, dL/db: persistent, one 16-pixel block per wave and iteration.
+// ---- dL/dW, dL/db and dL/df in ONE pass over z: persistent, one 16-pixel block per wave and iteration.  dz[p][c] depends on
+// every code of the pixel through ONE number: Pl = sum of P over the pixel's label codes, which enters through Dsum.  With the
+// label a single code (arg_s: the only case when no two code-book rows coincide) Pl is P at that code, and its logit is a
+// 16-term dot product the 16 lanes of the pixel's row form from the decoder image in LDS and the feature values the lane
+// already holds -- a few instructions per pixel; for a tie the same dot product runs once per bit of the recorded mask.  With
+// Pl known up front the block STREAMS: two code blocks at a time -- logits (6 matrix instructions), dz in place, dL/db sums,
+// the dL/dW products, the transposition tile, the df products -- and what lives across the block is the 76 accumulator
+// registers and a handful of row scalars (two waves per SIMD).  Pl is an fp32 chain over the decoder's hi + lo planes where
+// the logits are the three split-bf16 products of the same planes: ~1e-6 relative on P.
 //   dL/dW[c][s] += sum_p dz[p][c] f[p][s]: A = dz [code mm][k = pixel 4 kq + r] (the D layout as it is), B = f [k = pixel 4 kq + i][s = mm]
-__global__ __launch_bounds__(64 * DG_NW, 1) void decoder_grad_k(const FusedArgs a) {
-    __shared__ __attribute__((aligned(16))) char s_wz[FU_WZ_BYTES];
-    __shared__ float s_bias[SIM_NC];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, kq = lane >> 4, mm = lane & 15;
-    const long long HW = a.HW;
-    const int C = a.C, S = a.S;
-    for (int i = tid; i < FU_WZ_BYTES / 16; i += 64 * DG_NW)
-        reinterpret_cast<uint4*>(s_wz)[i] = reinterpret_cast<const uint4*>(a.wz)[i];
-    for (int i = tid; i < SIM_NC; i += 64 * DG_NW) s_bias[i] = (a.bias && i < a.C) ? a.bias[i] : 0.f;
-    __syncthreads();
-    const bool vlast = 16 * (SIM_NCB - 1) + mm < C;
-    const char* const wz_l = s_wz + 32 * mm + 8 * kq;
-    const float* const bias_l = s_bias + mm;
-    f32x4 dWacc[SIM_NCB];  // D[code 16 cb + 4 kq + r][s = mm]
-    float dbr[SIM_NCB];    // lane (kq, mm): sum of dz[pixel rows 4 kq + r][code 16 cb + mm]
-#pragma unroll
-    for (int cb = 0; cb < SIM_NCB; cb++) {
-        dWacc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        dbr[cb] = 0.f;
-    }
-    float acc_lab = 0.f;
-    const long long wave = (long long)blockIdx.x * DG_NW + w, n_waves = (long long)gridDim.x * DG_NW;
-    // A block's inputs are requested a block ahead: the loop is short and only two waves share a SIMD, so a load issued where
-    // it is used costs its whole latency.
-    float fvz[4], fvw[4];  // the decoder's two views of the feature: f[s = 4 kq + i][pixel mm], f[s = mm][pixel 4 kq + i]
-    DecIn in;
-    auto fetch = [&](long long blk) {
-        const long long pbase = 16 * min(blk, a.blocks - 1);
-        const long long pz = min(pbase + mm, HW - 1);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            fvz[i] = (4 * kq + i < S) ? a.sem[(size_t)(4 * kq + i) * HW + pz] : 0.f;
-            fvw[i] = mm < S ? a.sem[(size_t)mm * HW + min(pbase + 4 * kq + i, HW - 1)] : 0.f;
-        }
-        decoder_fetch(in, a, pbase, kq);
-    };
-    fetch(wave);
-    for (long long blk = wave; blk < a.blocks; blk += n_waves) {
-        const long long pbase = 16 * blk;
-        f32x4 z[SIM_NCB];
-        decoder_logits(z, fvz, wz_l, bias_l, vlast);
-        acc_lab += decoder_dz(z, in, a, pbase, kq, mm);
-        uint32_t bh[2], bl[2];
-        split_pair(fvw[0], fvw[1], bh[0], bl[0]);
-        split_pair(fvw[2], fvw[3], bh[1], bl[1]);
-        const s16x4 fBh = __builtin_bit_cast(s16x4, uint2{bh[0], bh[1]}), fBl = __builtin_bit_cast(s16x4, uint2{bl[0], bl[1]});
-        fetch(blk + n_waves);  // the next block's inputs (this block's are consumed): they land under the products below
-#pragma unroll
-        for (int cb = 0; cb < SIM_NCB; cb++) {
-            uint32_t dh[2], dl[2];
-            split_pair(z[cb][0], z[cb][1], dh[0], dl[0]);
-            split_pair(z[cb][2], z[cb][3], dh[1], dl[1]);
-            dbr[cb] += (z[cb][0] + z[cb][1]) + (z[cb][2] + z[cb][3]);
-            const s16x4 Ah = __builtin_bit_cast(s16x4, uint2{dh[0], dh[1]}), Al = __builtin_bit_cast(s16x4, uint2{dl[0], dl[1]});
-            dWacc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Al, fBh, dWacc[cb], 0, 0, 0);
-            dWacc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Ah, fBl, dWacc[cb], 0, 0, 0);
-            dWacc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Ah, fBh, dWacc[cb], 0, 0, 0);
-        }
-    }
-    // ---- this wave's partial sums
-    float* out = a.partials + (size_t)wave * ((size_t)C * (S + 1) + 4);
-#pragma unroll
-    for (int cb = 0; cb < SIM_NCB; cb++) {
-        if (mm < S) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int c = 16 * cb + 4 * kq + r;
-                if (c < C) out[(size_t)c * (S + 1) + mm] = dWacc[cb][r];
-            }
-        }
-        float d = dbr[cb];
-        d += __shfl_xor(d, 16, 64);
-        d += __shfl_xor(d, 32, 64);
-        if (kq == 0 && 16 * cb + mm < C) out[(size_t)(16 * cb + mm) * (S + 1) + S] = d;
-    }
-    // the loss sums: this kernel's part (sum P^2 - 2 sum_label P + number of labels) and, folded in in a fixed order,
-    // codebook_simgrad_k's per-wave sums (rows wave, wave + n_waves, ...)
-    float t0 = wave_sum_u(acc_lab);
-    float t1 = 0.f, t2 = 0.f, t3 = 0.f;
-    for (long long i = wave + n_waves * lane; i < a.n_sums_a; i += 64 * n_waves) {  // lane partials, then the fixed DPP order
-        const f32x4 v = *reinterpret_cast<const f32x4*>(a.sums_a + 4 * i);
-        t1 += v[1];
-        t2 += v[2];
-        t3 += v[3];
-    }
-    t1 = wave_sum_u(t1);
-    t2 = wave_sum_u(t2);
-    t3 = wave_sum_u(t3);
-    if (lane == 0) {
-        float* lo = out + (size_t)C * (S + 1);
-        lo[0] = t0;
-        lo[1] = t1;
-        lo[2] = t2;
-        lo[3] = t3;
-    }
-}
-
-// ---- dL/df[p][s] = sum_c dz[p][c] W[c][s]: the contraction runs over the codes, the LANE axis of the D layout, so dz goes
-// through a wave-private LDS tile ([16 pixels][32 codes] bf16 hi and lo, 80-byte rows) to become the A operand
-// [pixel mm][k = code 8 kq + i]; tile j + 1 is written before tile j is read, and the three products keep separate
-// accumulators (no dependent MFMA chain).  One 16-pixel block per wave and iteration; z and dz are recomputed here rather than
-// shared with decoder_grad_k: together the two kernels need more registers than two waves per SIMD have.
-__global__ __launch_bounds__(64 * DF_NW, 1) void decoder_df_k(const FusedArgs a) {
-    __shared__ __attribute__((aligned(16))) char s_wz[FU_WZ_BYTES];
-    __shared__ __attribute__((aligned(16))) char s_wt[FU_WT_BYTES];
-    __shared__ __attribute__((aligned(16))) char s_tr[DF_NW][2][FU_TBUF];
-    __shared__ float s_bias[SIM_NC];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, kq = lane >> 4, mm = lane & 15;
-    const long long HW = a.HW;
-    const int C = a.C, S = a.S;
-    for (int i = tid; i < FU_WZ_BYTES / 16; i += 64 * DF_NW)
-        reinterpret_cast<uint4*>(s_wz)[i] = reinterpret_cast<const uint4*>(a.wz)[i];
-    for (int i = tid; i < FU_WT_BYTES / 16; i += 64 * DF_NW)
-        reinterpret_cast<uint4*>(s_wt)[i] = reinterpret_cast<const uint4*>(a.wt)[i];
-    for (int i = tid; i < SIM_NC; i += 64 * DF_NW) s_bias[i] = (a.bias && i < a.C) ? a.bias[i] : 0.f;
-    __syncthreads();
-    const bool vlast = 16 * (SIM_NCB - 1) + mm < C;
-    const char* const wz_l = s_wz + 32 * mm + 8 * kq;
-    const float* const bias_l = s_bias + mm;
-    const char* const wt_l = s_wt + 64 * mm + 16 * kq;
-    char* const tw_l = s_tr[w][0] + 2 * mm + FU_TROW * 4 * kq;     // tile writes: this lane's code column, its 4 pixel rows
-    const char* const tr_l = s_tr[w][0] + FU_TROW * mm + 16 * kq;  // tile reads: pixel row mm, codes 8 kq ..
-    const long long wave = (long long)blockIdx.x * DF_NW + w, n_waves = (long long)gridDim.x * DF_NW;
-    float fvz[4];
-    DecIn in;
-    auto fetch = [&](long long blk) {
-        const long long pbase = 16 * min(blk, a.blocks - 1);
-        const long long pz = min(pbase + mm, HW - 1);
-#pragma unroll
-        for (int i = 0; i < 4; i++) fvz[i] = (4 * kq + i < S) ? a.sem[(size_t)(4 * kq + i) * HW + pz] : 0.f;
-        decoder_fetch(in, a, pbase, kq);
-    };
-    fetch(wave);
-    for (long long blk = wave; blk < a.blocks; blk += n_waves) {
-        const long long pbase = 16 * blk;
-        f32x4 z[SIM_NCB];
-        decoder_logits(z, fvz, wz_l, bias_l, vlast);
-        (void)decoder_dz(z, in, a, pbase, kq, mm);
-        fetch(blk + n_waves);
-        f32x4 df0 = f32x4{0.f, 0.f, 0.f, 0.f}, df1 = df0, df2 = df0;
-        auto put = [&](int j) {  // dz of code blocks 2 j, 2 j + 1 -> tile j & 1
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int cb = 2 * j + h;
-                char* col = tw_l + FU_TBUF * (j & 1) + 32 * h;
-                uint32_t dh[2] = {0u, 0u}, dl[2] = {0u, 0u};
-                if (cb < SIM_NCB) {
-                    const f32x4 d = z[cb < SIM_NCB ? cb : 0];
-                    split_pair(d[0], d[1], dh[0], dl[0]);
-                    split_pair(d[2], d[3], dh[1], dl[1]);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    *reinterpret_cast<uint16_t*>(col + FU_TROW * r) = (uint16_t)((r & 1) ? dh[r >> 1] >> 16 : dh[r >> 1]);
-                    *reinterpret_cast<uint16_t*>(col + FU_TROW * r + FU_TPLANE) = (uint16_t)((r & 1) ? dl[r >> 1] >> 16 : dl[r >> 1]);
-                }
-            }
-        };
-        put(0);
-#pragma unroll
-        for (int j = 0; j < FU_NJ; j++) {
-            if (j + 1 < FU_NJ) put(j + 1);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const bf16x8 Ah = *reinterpret_cast<const bf16x8*>(tr_l + FU_TBUF * (j & 1));
-            const bf16x8 Al = *reinterpret_cast<const bf16x8*>(tr_l + FU_TBUF * (j & 1) + FU_TPLANE);
-            const bf16x8 Bh = *reinterpret_cast<const bf16x8*>(wt_l + 1024 * j);
-            const bf16x8 Bl = *reinterpret_cast<const bf16x8*>(wt_l + 1024 * j + FU_WT_BYTES / 2);
-            df0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, Bh, df0, 0, 0, 0);
-            df1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bl, df1, 0, 0, 0);
-            df2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bh, df2, 0, 0, 0);
-            asm volatile("" ::: "memory");  // or all ten K steps' decoder operands are read up front: 80 registers
-        }
-        // D[pixel 4 kq + r][s = mm]
-        if (mm < S) {
-            float* dst = a.dsem + (size_t)mm * HW + pbase + 4 * kq;
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-                if (pbase + 4 * kq + r < HW) dst[r] = (df0[r] + df1[r]) + df2[r];
-        }
-    }
-}
-
-// ---- decoder_grad_k and decoder_df_k in ONE pass over z (round 5).  The two kernels above each rebuild the block's logits, its
-// probabilities and dz (57 matrix instructions, an exponential and ~12 vector instructions per (pixel, code)) because held
-// together -- 76 registers of dz, 76 of dL/dW accumulators, the df products and their operands -- they do not fit two waves per
-// SIMD.  What forces all 19 code blocks of dz to exist at once is ONE number per pixel: Pl = sum of P over the pixel's label
-// codes, which enters every dz[p][c] through Dsum.  With the label a single code (arg_s: the only case when no two code-book
-// rows coincide) Pl is P at that code, and its logit is a 16-term dot product the 16 lanes of the pixel's row form from the
-// decoder image in LDS and the feature values the lane already holds -- a few instructions per pixel; for a tie the same dot
-// product runs once per bit of the recorded mask.  With Pl known up front the block STREAMS: two code blocks at a time --
-// logits (6 matrix instructions), dz in place, dL/db sums, the dL/dW products, the transposition tile, the df products -- and
-// what lives across the block is the 76 accumulator registers and a handful of row scalars.  Same wave -> partial-row mapping,
-// same partial layout and the same loss sums as decoder_grad_k (its launch shape is kept), same dL/df as decoder_df_k up to
-// the rounding of Pl (the dot product is an fp32 chain over the decoder's hi + lo planes, the logits it replaces the three
-// split-bf16 products of the same planes: ~1e-6 relative on P).
-constexpr int GD_NW = 8;
+//   dL/df[p][s] = sum_c dz[p][c] W[c][s]: the contraction runs over the codes, the LANE axis of the D layout, so dz goes
+//     through a wave-private LDS tile ([16 pixels][32 codes] bf16 hi and lo, 80-byte rows) to become the A operand
+//     [pixel mm][k = code 8 kq + i]; the three products keep separate accumulators (no dependent MFMA chain).
 __global__ __launch_bounds__(64 * GD_NW, 1) void decoder_gd_k(const FusedArgs a) {
     __shared__ __attribute__((aligned(16))) char s_wz[FU_WZ_BYTES];
     __shared__ __attribute__((aligned(16))) char s_wt[FU_WT_BYTES];
@@ -1239,6 +1014,8 @@ __global__ __launch_bounds__(64 * GD_NW, 1) void decoder_gd_k(const FusedArgs a)
     }
     float acc_lab = 0.f;
     const long long wave = (long long)blockIdx.x * GD_NW + w, n_waves = (long long)gridDim.x * GD_NW;
+    // A block's inputs are requested a block ahead: the loop is short and only two waves share a SIMD, so a load issued where
+    // it is used costs its whole latency.
     float fvz[4], fvw[4];  // the decoder's two views of the feature: f[s = 4 kq + i][pixel mm], f[s = mm][pixel 4 kq + i]
     DecIn in;
     auto fetch = [&](long long blk) {
@@ -1402,7 +1179,7 @@ __global__ __launch_bounds__(64 * GD_NW, 1) void decoder_gd_k(const FusedArgs a)
                 if (pbase + 4 * kq + r < HW) dst[r] = (df0[r] + df1[r]) + df2[r];
         }
     }
-    // ---- this wave's partial sums (decoder_grad_k's layout)
+    // ---- this wave's partial row: dL/dW[c][s] and dL/db[c] as [C][S + 1], then the four loss sums
     float* out = a.partials + (size_t)wave * ((size_t)C * (S + 1) + 4);
 #pragma unroll
     for (int cb = 0; cb < SIM_NCB; cb++) {
@@ -1418,6 +1195,8 @@ __global__ __launch_bounds__(64 * GD_NW, 1) void decoder_gd_k(const FusedArgs a)
         d += __shfl_xor(d, 32, 64);
         if (kq == 0 && 16 * cb + mm < C) out[(size_t)(16 * cb + mm) * (S + 1) + S] = d;
     }
+    // the loss sums: this kernel's part (sum P^2 - 2 sum_label P + number of labels) and, folded in in a fixed order,
+    // codebook_simgrad_k's per-wave sums (rows wave, wave + n_waves, ...)
     float t0 = wave_sum_u(acc_lab);
     float t1 = 0.f, t2 = 0.f, t3 = 0.f;
     for (long long i = wave + n_waves * lane; i < a.n_sums_a; i += 64 * n_waves) {  // lane partials, then the fixed DPP order
@@ -1572,11 +1351,6 @@ int launch_codebook_dlut(const float* dsim, const float* g, long long HW, int C,
     return 0;
 }
 
-// GOI_DECODER_ONE_PASS=0: the two-kernel decoder backward (decoder_grad_k + decoder_df_k) instead of decoder_gd_k (A/B, cross-check)
-static const bool g_decoder_one_pass = []() {
-    const char* e = getenv("GOI_DECODER_ONE_PASS");
-    return !(e && e[0] == '0');
-}();
 // ---- the training half in one call.  workspace: code-book planes | decoder images | per-pixel records | simgrad wave sums |
 // dsim planes (the only large part: 2 x 2 B per (pixel, code))
 static size_t fu_align(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1588,7 +1362,7 @@ size_t codebook_fused_workspace_bytes(long long HW) {
            fu_align(npad * FU_TIE_WORDS * 4) + fu_align((size_t)fu_simgrad_wgs(HW) * SG_NW * 16) +
            (size_t)fu_blocks(HW) * FU_DCHUNK * 2;
 }
-int codebook_fused_rows() { return 256 * DG_NW; }
+int codebook_fused_rows() { return 256 * GD_NW; }
 // returns -1 when the shape is not the kernels' (D = 256, C in 289..304, S <= 16, HW % 4 = 0, HW < 2^25)
 int launch_codebook_fused(const float* g, const float* l1, const float* sem, const float* W, const float* bias, long long HW,
                           int C, int D, int S, float t, float* dsem, float* partials, float* dl1_partial, void* workspace,
@@ -1626,14 +1400,7 @@ int launch_codebook_fused(const float* g, const float* l1, const float* sem, con
     const long long stat_wgs = (blocks + DS_NW - 1) / DS_NW;
     decoder_stats_k<<<dim3((unsigned)(stat_wgs < 2048 ? stat_wgs : 2048)), dim3(64 * DS_NW), 0, s>>>(a);
     codebook_simgrad_k<<<dim3((unsigned)fu_simgrad_wgs(HW)), dim3(64 * SG_NW), 0, s>>>(a);
-    static_assert(GD_NW == DG_NW, "decoder_gd_k writes decoder_grad_k's partial rows");
-    if (g_decoder_one_pass) {
-        decoder_gd_k<<<dim3(codebook_fused_rows() / GD_NW), dim3(64 * GD_NW), 0, s>>>(a);
-    } else {
-        decoder_grad_k<<<dim3(codebook_fused_rows() / DG_NW), dim3(64 * DG_NW), 0, s>>>(a);
-        const long long df_wgs = (blocks + DF_NW - 1) / DF_NW;
-        decoder_df_k<<<dim3((unsigned)(df_wgs < 1024 ? df_wgs : 1024)), dim3(64 * DF_NW), 0, s>>>(a);
-    }
+    decoder_gd_k<<<dim3(codebook_fused_rows() / GD_NW), dim3(64 * GD_NW), 0, s>>>(a);
     codebook_dlut2_k<<<dim3(codebook_dlut_blocks()), dim3(64 * DL2_NW), 0, s>>>(dplanes, g, HW, dl1_partial);
     return 0;
 }

@@ -116,21 +116,16 @@ size_t binning_layout(int N, char* base, BinView* v);
 
 // Tuning / experiment switches (goi_raster_set_option); defaults are the shipped configuration.
 struct Options {
-    int fwd_variant = 1;  // 0: one candidate per loop trip, 1: two candidates per trip (default); experiments (render_fwd.hip): 2 the
-                          // 16 pixels x 4 Gaussians mapping, 3 scalar-operand features (S = 16), 4 fp32 outer-product MFMA
+    int fwd_variant = 1;  // 0: one candidate per loop trip, 1: two candidates per trip (default)
     int bwd_variant = 0;  // low 4 bits: 0 atomic-free wave-per-quadrant backward (needs scratch) with the split-f16
                           // MFMA flush (fp32-grade), 2 the same with the exact-fp32 flush, 1 workgroup-per-tile + atomics
     int sort_variant = 1;  // 0: histogram / scan / scatter per pass, 1: onesweep (decoupled look-back, default)
     int sort_lookback = 1;  // onesweep: 1 grouped look-back (two round trips: group aggregates, group totals), 0 the chained decoupled look-back
-    int sort_tickets = 1;  // onesweep: 1 tiles are dealt by a ticket counter (a tile only waits for tiles that are running), 0 tile = workgroup index (experiment)
     int sort_small = 0;    // 1: sorts of up to 2 M keys also take the adaptive 512 x (2..16) tile (scan_sort.hip) instead of 1024 x 4
     int decode_variant = 1;  // semantic decode, S <= 16: 1 split-bf16 MFMA contraction, 2 pixel blocks per operand fetch (2: 4 blocks, 3: 1 block; bit-identical), 0 fp32 MFMA
     int cull_variant = 2;  // 0: a Gaussian is listed in every tile of its 3-sigma rectangle (the reference's lists),
                            // 1: only in the tiles its exact contribution box touches, 2: only in the tiles its contribution
                            // ELLIPSE reaches (rectangles of up to 64 tiles).  Same images and gradients, bit for bit.
-    int pre_shdma = 0;     // preprocess_fwd_k, SH colours with M = 16: 1 the wave moves the SH rows of its visible lanes to LDS by
-                           // DMA (EXPERIMENT, measured: 67 vs 63.5 us at 1 M, 190 vs 193 us at 3 M), 0 every lane fetches its own
-                           // row (default).  Bit-identical.
     int bwd_order = 1;     // backward blend: v >= 1 the quadrants of each XCD's band are launched longest-first (their cost is
                            // known from the forward's n_contrib; cost classes of 2^(3+v) list positions), 0 in tile order.
                            // Same rows, same gradients.
@@ -211,10 +206,6 @@ void launch_render_fwd(const GoiRasterScene& sc, const GeomView& g, const ImageV
                        uint32_t* host_words = nullptr,  // host_words: pinned, device-mapped words that get counters[0 .. 32) ...
                        uint32_t stamp = 0);  // ... and, behind a system-scope fence, `stamp` in word HOST_STAMP_WORD (api.hip: tickets)
 constexpr int HOST_STAMP_WORD = 33;
-// fwd_variant 2 (experiment): the 16 pixels x 4 Gaussians mapping of the forward blend (render_fwd_g4.hip); S <= 16, no depth cut
-void launch_render_fwd_g4(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
-                          float* out_color, float* out_sem, float* out_depth, float* out_alpha, hipStream_t s,
-                          unsigned long long* qmask, uint32_t* host_words, uint32_t stamp);
 // lane utilisation of the blend kernels counted from a forward's member masks / n_contrib (blend_stats.hip): out[GOI_BLEND_STATS_WORDS]
 void launch_blend_stats(int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                         const unsigned long long* qmask, unsigned long long* out, hipStream_t s);

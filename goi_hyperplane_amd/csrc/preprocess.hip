@@ -90,23 +90,6 @@ __device__ __forceinline__ Camera load_camera(const float* __restrict__ v, const
     return cam;
 }
 
-// SH rows by LDS-DMA (SHDMA: SH colours with M = 16, the degree-3 layout).  A lane's colour is a sequential fp32 sum over its
-// own 192-byte row (the reference's order: the clamp bits depend on it), so the arithmetic stays per lane -- but a lane FETCHING
-// its row (sixteen 12-byte or twelve 16-byte loads at a 192-byte lane stride) makes every load instruction of the wave touch 64
-// different lines, and with 20+ waves per CU a line is fetched from L2 again for most of them: SH -> RGB was 6-12 us of a wave's
-// ~20.  Now the WAVE moves the rows of its visible lanes: global_load_lds_dwordx4 sends 16 bytes per lane from
-// memory straight to LDS (no registers), consecutive lanes taking consecutive 16-byte quads of consecutive VISIBLE rows (ranked
-// by a ballot; a culled Gaussian's row is never requested), so an instruction reads ~5 rows as ~10 whole lines; the requests
-// are issued as soon as the visibility is known and travel under the contribution box / ellipse tile mask work; then every
-// visible lane reads its row from LDS (row stride 13 quads = 52 dwords: eight lanes of a ds_read_b128 cover the 32 banks once)
-// and runs the same statement sequence as before: bit-identical colours and clamp bits.  LDS holds SH_ROWS_CAP rows per wave
-// (7.3 KB: five waves per SIMD, what the registers allow); the ~1 in 6 waves with more visible lanes take a second trip.
-#ifndef GOI_PRE_SH_ROWS
-#define GOI_PRE_SH_ROWS 36
-#endif
-constexpr int SH_ROWS_CAP = GOI_PRE_SH_ROWS;
-constexpr int SH_ROW_QUADS = 13;  // 12 quads of coefficients + 1 of padding
-
 template <typename SHK_T>
 __device__ __forceinline__ V3 sh_to_rgb_sum(int D, const V3& dir, SHK_T SHK) {
     V3 res = kSH0 * SHK(0);
@@ -129,16 +112,9 @@ __device__ __forceinline__ V3 sh_to_rgb_sum(int D, const V3& dir, SHK_T SHK) {
     return res + V3{0.5f, 0.5f, 0.5f};
 }
 
-__device__ __forceinline__ void sh_dma16(const void* global_src, void* lds_base) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(global_src, lds_base, 16, 0, 0);
-#endif
-}
-
 #ifndef GOI_PRE_MINBLOCKS
 #define GOI_PRE_MINBLOCKS 1
 #endif
-template <bool SHDMA>
 __global__ __launch_bounds__(256, GOI_PRE_MINBLOCKS) void preprocess_fwd_k(const PreArgs args, GaussRec* __restrict__ rec,
                                                         float* __restrict__ cov3D_out,
                                                         uint32_t* __restrict__ tiles_touched,
@@ -148,8 +124,6 @@ __global__ __launch_bounds__(256, GOI_PRE_MINBLOCKS) void preprocess_fwd_k(const
                                                         unsigned long long* __restrict__ blk_coarse, int* __restrict__ radii,
                                                         uint32_t* __restrict__ counters, uint2* __restrict__ ranges,
                                                         int n_tiles) {
-    __shared__ __attribute__((aligned(16))) float4 s_sh[SHDMA ? 4 : 1][SHDMA ? SH_ROWS_CAP * SH_ROW_QUADS : 1];
-    __shared__ uint8_t s_rank[SHDMA ? 4 : 1][64];  // rank among the wave's visible lanes -> lane
     const int gtid = blockIdx.x * blockDim.x + threadIdx.x;
     // the tile ranges start from zero (emit accumulates per-tile counts into them): cleared here for free
     for (int t = gtid; t < n_tiles; t += gridDim.x * blockDim.x) ranges[t] = make_uint2(0u, 0u);
@@ -222,36 +196,8 @@ __global__ __launch_bounds__(256, GOI_PRE_MINBLOCKS) void preprocess_fwd_k(const
         int x0, y0, x1, y1;
         tile_rect(pix, piy, (int)my_radius, a.gx, a.gy, x0, y0, x1, y1);
         if ((x1 - x0) * (y1 - y0) == 0) break;
-        vis = live;  // (a lane past P has redone the last Gaussian up to here: it must neither rank among the wave's rows -- its
-                     // "row" would lie beyond the array -- nor store anything)
+        vis = live;  // (a lane past P has redone the last Gaussian up to here: it must not store anything)
     } while (false);
-
-    // ---- (SHDMA) the wave requests the SH rows of its visible lanes: rank r of the visible lanes -> row r of the wave's LDS area
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    unsigned long long vm = 0ull;
-    int nvis = 0, rank = 0;
-    const int wave_first = blockIdx.x * 256 + wv * 64;
-    auto request_rows = [&](int r0) {  // rows of ranks [r0, r0 + SH_ROWS_CAP): quad k of rank r travels to slot 13 r + k
-        const int nslots = min(SH_ROWS_CAP, nvis - r0) * SH_ROW_QUADS;
-#pragma unroll
-        for (int i = 0; i < (SH_ROWS_CAP * SH_ROW_QUADS + 63) / 64; i++) {
-            if (i * 64 >= nslots) break;  // (wave-uniform)
-            const int sl = i * 64 + lane;
-            const int r = (sl * 5042) >> 16, q = sl - SH_ROW_QUADS * r;  // sl / 13 (exact below 1100), sl % 13
-            if (sl < nslots && q < SH_ROW_QUADS - 1) {
-                const int src = s_rank[wv][r0 + r];
-                sh_dma16(a.shs + ((size_t)(wave_first + src) * 48 + 4 * q), &s_sh[wv][i * 64]);
-            }
-        }
-    };
-    if constexpr (SHDMA) {
-        vm = __ballot(vis);
-        nvis = __popcll(vm);
-        rank = __popcll(vm & ((1ull << lane) - 1ull));
-        if (vis) s_rank[wv][rank] = (uint8_t)lane;
-        __builtin_amdgcn_wave_barrier();
-        if (nvis > 0) request_rows(0);
-    }
 
     // ---- phase B: contribution box, listed rectangle, ellipse tile mask (nothing here needs the colour)
     float hx = -1.f, hy = -1.f, o = 0.f;
@@ -377,34 +323,13 @@ __global__ __launch_bounds__(256, GOI_PRE_MINBLOCKS) void preprocess_fwd_k(const
         cg = fmaxf(res.y, 0.0f);
         cb = fmaxf(res.z, 0.0f);
     };
-    if constexpr (SHDMA) {
-        for (int r0 = 0; r0 < nvis; r0 += SH_ROWS_CAP) {  // (wave-uniform: one trip for five waves in six)
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the rows are in LDS
-            __builtin_amdgcn_wave_barrier();
-            if (vis && rank >= r0 && rank < r0 + SH_ROWS_CAP) {
-                const float4* row = &s_sh[wv][(rank - r0) * SH_ROW_QUADS];
-                float rowf[48];
-#pragma unroll
-                for (int i = 0; i < 12; i++) {
-                    const float4 v = row[i];
-                    rowf[4 * i] = v.x;
-                    rowf[4 * i + 1] = v.y;
-                    rowf[4 * i + 2] = v.z;
-                    rowf[4 * i + 3] = v.w;
-                }
-                finish_colour(sh_to_rgb_sum(a.D, dir, [&](int k) { return V3{rowf[3 * k], rowf[3 * k + 1], rowf[3 * k + 2]}; }));
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (r0 + SH_ROWS_CAP < nvis) request_rows(r0 + SH_ROWS_CAP);
-        }
-    } else if (vis) {
+    if (vis) {
         if (a.colors_precomp) {
             cr = a.colors_precomp[3 * idx];
             cg = a.colors_precomp[3 * idx + 1];
             cb = a.colors_precomp[3 * idx + 2];
         } else {
             // A degree-3 row (M = 16: 192 bytes, 16-byte aligned) is fetched as TWELVE 16-byte loads instead of sixteen 12-byte ones
-            // (this instance only runs when the LDS-DMA path above is switched off, GOI_OPTIONS pre_shdma=0: the A/B of it).
             float rowf[48];
             const bool row16 = a.M == 16;
             if (row16) {
@@ -1185,13 +1110,8 @@ void launch_preprocess_fwd(const GoiRasterScene& sc, const GeomView& g, int* rad
     a.focal_x = sc.W / (2.0f * sc.tan_fovx);
     a.view_p = sc.viewmatrix; a.proj_p = sc.projmatrix; a.campos_p = sc.campos;
     static_assert(PRE_BLOCK == 256, "preprocess_fwd_k is written for 256-thread workgroups");
-    // SH colours in the degree-3 layout: the wave moves its visible lanes' rows by LDS-DMA (pre_shdma 0: every lane fetches its own)
-    if (sc.shs && !sc.colors_precomp && sc.M == 16 && g_options.pre_shdma)
-        preprocess_fwd_k<true><<<dim3((sc.P + PRE_BLOCK - 1) / PRE_BLOCK), dim3(PRE_BLOCK), 0, s>>>(
-            a, g.rec, g.cov3D, g.tiles_touched, g.clamped, g.sort_keys[1], g.aux, g.blk_agg, g.blk_coarse, radii, g.counters, ranges, n_tiles);
-    else
-        preprocess_fwd_k<false><<<dim3((sc.P + PRE_BLOCK - 1) / PRE_BLOCK), dim3(PRE_BLOCK), 0, s>>>(
-            a, g.rec, g.cov3D, g.tiles_touched, g.clamped, g.sort_keys[1], g.aux, g.blk_agg, g.blk_coarse, radii, g.counters, ranges, n_tiles);
+    preprocess_fwd_k<<<dim3((sc.P + PRE_BLOCK - 1) / PRE_BLOCK), dim3(PRE_BLOCK), 0, s>>>(
+        a, g.rec, g.cov3D, g.tiles_touched, g.clamped, g.sort_keys[1], g.aux, g.blk_agg, g.blk_coarse, radii, g.counters, ranges, n_tiles);
 }
 
 void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, float* dL_dmean2D,

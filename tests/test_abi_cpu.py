@@ -140,6 +140,35 @@ def test_argument_validation_messages_and_no_cpu_fallback():
         r(m, m, z(4, 1), colors_precomp=z(4, 3), scales=z(4, 3), rotations=z(4, 4), semantics=z(4, 10))
 
 
+@pytest.mark.parametrize("name,value,message", [("fwd_variant", 2, "fwd_variant must be 0 or 1"),
+                                                ("fwd_variant", 3, "fwd_variant must be 0 or 1"),
+                                                ("fwd_variant", 4, "fwd_variant must be 0 or 1"),
+                                                ("fwd_variant", -1, "fwd_variant must be 0 or 1"),
+                                                ("pre_shdma", 0, "unknown option pre_shdma"),
+                                                ("pre_shdma", 1, "unknown option pre_shdma"),
+                                                ("sort_tickets", 0, "unknown option sort_tickets"),
+                                                ("sort_tickets", 1, "unknown option sort_tickets")])
+def test_removed_options_are_refused_and_change_nothing(lib, name, value, message):
+    """The forward blend experiments (fwd_variant 2 .. 4), the SH rows by LDS-DMA (pre_shdma) and the ticketless onesweep
+    (sort_tickets) are gone: setting them fails and leaves the options in force as they were."""
+    from goi_hyperplane_amd import _lib
+    fake = C.c_void_p(1 << 20)  # never dereferenced: the sort call below is refused first
+    before = dict(_lib.OPTIONS)
+    try:
+        _lib.set_option("fwd_variant", 0)
+        _lib.set_option("sort_variant", 0)
+        with pytest.raises(RuntimeError, match=message):
+            _lib.set_option(name, value)
+        assert _lib.OPTIONS["fwd_variant"] == 0 and _lib.OPTIONS["sort_variant"] == 0
+        assert name == "fwd_variant" or name not in _lib.OPTIONS
+        # sort_variant 0 is still in force in the library: a device-side count needs the onesweep sort
+        assert lib.goi_raster_debug_sort_pairs(fake, fake, fake, fake, 100, 0, 32, fake, None, 0, None, fake, None) < 0
+        assert "onesweep" in lib.goi_raster_last_error().decode()
+    finally:
+        _lib.set_option("fwd_variant", before.get("fwd_variant", 1))
+        _lib.set_option("sort_variant", before.get("sort_variant", 1))
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "goi_hyperplane_amd")
     offenders = []
