@@ -256,23 +256,15 @@ def row_width(C: int, S: int) -> int:
     return C * (S + 1) + 4
 
 
-def _rows_chunk(sim, inv, sem, W, b, t, HW_total, C):
-    """Per-pixel float64 reference and tolerances of one pixel range."""
-    S = W.shape[1]
-    dev = sim.device
-    xs32 = sim.float() * inv.float()[:, None]             # the kernel's fp32 xs, exactly
-    xs = xs32.double()
-    f = sem.double().T                                    # [m, S]
-    W64 = W.double()
-    b64 = b.double() if b is not None else torch.zeros(C, dtype=torch.float64, device=dev)
-    z = b64[None, :] + f @ W64.T
-    zs = (b64.abs()[None, :] + f.abs() @ W64.abs().T).amax(1)
-    mz = z.amax(1, keepdim=True)
+def loss_terms(xs, lab, z, t, HW_total, C):
+    """The float64 mathematics of the row losses of one pixel range, shared by the row pass and the fused path
+    (tests/codebook_loss_reference.py): xs [m, C] the normalised sim, lab [m, C] the label set (0 / 1), z [m, C] the
+    decoder logits.  arg_s is the first member of the label set, arg_a the first maximum of z."""
+    dev = xs.device
     arg_a = z.argmax(1)                                   # first maximum
     P = torch.softmax(z, 1)
     ms = xs.amax(1, keepdim=True)
-    lab = (xs32 == xs32.amax(1, keepdim=True)).double()
-    arg_s = xs.argmax(1)
+    arg_s = (lab * torch.arange(C, 0, -1, device=dev, dtype=torch.float64)).argmax(1)  # first label
     nl = lab.sum(1)
     lx = t * (xs - ms)
     logZq = torch.logsumexp(lx, 1, keepdim=True)
@@ -287,11 +279,31 @@ def _rows_chunk(sim, inv, sem, W, b, t, HW_total, C):
     ar = torch.arange(C, device=dev)[None, :]
     ind = (ar == arg_s[:, None]).double() + (ar == arg_a[:, None]).double()
     gq = 0.3 * t * inv_hw * q
-    d = -gq * (lq + H[:, None]) - inv_hw * ind
+    d = -gq * (lq + H[:, None]) - inv_hw * ind          # dL/dxs
+    sim_a = xs.gather(1, arg_a[:, None])[:, 0]
+    return dict(arg_a=arg_a, arg_s=arg_s, P=P, ms=ms[:, 0], nl=nl, lq=lq, q=q, H=H, P2=P2, Pl=Pl, kappa=kappa,
+                inv_hw=inv_hw, dz=dz, ind=ind, gq=gq, d=d, sim_a=sim_a)
+
+
+def _rows_chunk(sim, inv, sem, W, b, t, HW_total, C):
+    """Per-pixel float64 reference and tolerances of one pixel range."""
+    S = W.shape[1]
+    dev = sim.device
+    xs32 = sim.float() * inv.float()[:, None]             # the kernel's fp32 xs, exactly
+    xs = xs32.double()
+    f = sem.double().T                                    # [m, S]
+    W64 = W.double()
+    b64 = b.double() if b is not None else torch.zeros(C, dtype=torch.float64, device=dev)
+    z = b64[None, :] + f @ W64.T
+    zs = (b64.abs()[None, :] + f.abs() @ W64.abs().T).amax(1)
+    lab = (xs32 == xs32.amax(1, keepdim=True)).double()
+    r = loss_terms(xs, lab, z, t, HW_total, C)
+    P, ms, nl, lq, q, H, P2, Pl = (r[k] for k in ("P", "ms", "nl", "lq", "q", "H", "P2", "Pl"))
+    kappa, inv_hw, dz, ind, gq, d, sim_a = (r[k] for k in ("kappa", "inv_hw", "dz", "ind", "gq", "d", "sim_a"))
+    ms = ms[:, None]
     inv64 = inv.double()
     dsim = d * inv64[:, None]
     dsem = dz @ W64                                        # [m, S]
-    sim_a = xs.gather(1, arg_a[:, None])[:, 0]
     # tolerances
     E_z = (S + 1) * U * zs
     span_z = (z.amax(1) - z.amin(1))
