@@ -105,6 +105,13 @@ SYMBOLS = {
                                           C.c_uint] + [C.c_void_p] * 4),
     "goi_raster_photometric_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                            C.c_uint] + [C.c_void_p] * 5),
+    "goi_raster_densify_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "goi_raster_densify_stats": (C.c_int, [C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_void_p] * 4),
+    "goi_raster_densify_plan": (C.c_int, [C.c_longlong] + [C.c_void_p] * 4 + [C.c_double] * 3 + [C.c_int, C.c_double, C.c_double]
+                                + [C.c_void_p] * 3),
+    "goi_raster_densify_prune_plan": (C.c_int, [C.c_longlong] + [C.c_void_p] * 4),
+    "goi_raster_densify_apply": (C.c_int, [C.c_longlong, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_longlong, C.c_longlong]
+                                 + [C.c_void_p] * 2),
     "goi_raster_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "goi_raster_blend_stats": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 5),
     "goi_raster_debug_views": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_void_p] * 8 + [C.c_void_p]),
@@ -163,6 +170,14 @@ class GoiAdamGroup(C.Structure):
 
 
 ADAM_MAX_GROUPS = 8
+
+
+class GoiDensifyRows(C.Structure):
+    """include/goi_raster.h: GoiDensifyRows"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_longlong), ("row_len", C.c_int), ("mode", C.c_int)]
+
+
+DENSIFY_MAX_GROUPS = 24
 
 
 OPTIONS = {}  # the switches set through set_option / GOI_OPTIONS in this process (name -> value)

@@ -1111,6 +1111,82 @@ int goi_raster_photometric_backward(const float* img1, const float* img2, long l
     return 0;
 }
 
+size_t goi_raster_densify_workspace_bytes(long long P) {
+    return (P >= 0 && P < (1ll << 30)) ? densify_layout(P, nullptr, nullptr) + 256 : 0;
+}
+
+int goi_raster_densify_stats(long long P, const float* grad, long long grad_stride, const unsigned char* filter, float* accum,
+                             float* denom, void* stream) {
+    const std::string fn = "goi_raster_densify_stats: ";
+    if (P < 0 || P >= (1ll << 31)) return fail(fn + "need 0 <= P < 2^31");
+    if (grad_stride < 2) return fail(fn + "grad_stride must be >= 2");
+    if (P > 0 && (!grad || !filter || !accum || !denom)) return fail(fn + "a required pointer is NULL");
+    launch_densify_stats(P, grad, grad_stride, filter, accum, denom, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_densify_plan(long long P, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                            double max_grad, double scale_threshold, double min_opacity, int screen_test, double max_screen_size,
+                            double big_threshold, unsigned* counts, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_densify_plan: ";
+    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
+    if (!counts || !workspace || (P > 0 && (!accum || !denom || !scaling || !opacity))) return fail(fn + "a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    refresh_options();
+    DensifyView v;
+    densify_layout(P, static_cast<char*>(workspace), &v);
+    DensifyThresholds t;
+    t.max_grad = (float)max_grad;  // a Python scalar meets an fp32 tensor: rounded to fp32 once
+    t.thr_scale = (float)scale_threshold;
+    t.min_opacity = (float)min_opacity;
+    t.big_world = (float)big_threshold;
+    t.split_inv = 1.0f / (float)(0.8 * 2);  // torch's reciprocal of the CPU scalar 0.8 * N
+    t.screen = screen_test != 0;
+    t.screen_all = 0.0f > (float)max_screen_size;  // max_radii2D is all zeros when the reference tests it
+    launch_densify_plan(P, accum, denom, scaling, opacity, t, counts, v, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_densify_prune_plan(long long P, const unsigned char* mask, unsigned* counts, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_densify_prune_plan: ";
+    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
+    if (!counts || !workspace || (P > 0 && !mask)) return fail(fn + "a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    refresh_options();
+    DensifyView v;
+    densify_layout(P, static_cast<char*>(workspace), &v);
+    launch_prune_plan(P, mask, counts, v, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_densify_apply(long long P, const GoiDensifyRows* groups, int n_groups, const float* rotation, const float* scaling,
+                             const float* z, long long n_split, long long kept_children, const void* workspace, void* stream) {
+    const std::string fn = "goi_raster_densify_apply: ";
+    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
+    if (n_groups < 0 || n_groups > GOI_DENSIFY_MAX_GROUPS) return fail(fn + "n_groups must be 0..24");
+    if (n_groups && !groups) return fail(fn + "groups is NULL");
+    if (n_split < 0 || n_split > P || kept_children < 0 || kept_children > n_split) return fail(fn + "bad n_split / kept_children");
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255)) return fail(fn + "workspace must be a 256-byte aligned pointer");
+    for (int k = 0; k < n_groups; k++) {
+        const GoiDensifyRows& g = groups[k];
+        if (g.row_len < 1 || g.rows < 0 || g.mode < GOI_DENSIFY_PARAM || g.mode > GOI_DENSIFY_ZERO) return fail(fn + "bad group");
+        if (g.mode != GOI_DENSIFY_ZERO && g.rows != P) return fail(fn + "a copied group must have P source rows");
+        if (g.rows > 0 && (!g.dst || (g.mode != GOI_DENSIFY_ZERO && !g.src))) return fail(fn + "a group pointer is NULL");
+        if ((g.mode == GOI_DENSIFY_XYZ || g.mode == GOI_DENSIFY_SCALING) && g.row_len != 3) return fail(fn + "xyz / scaling rows are 3 floats");
+        if (g.mode == GOI_DENSIFY_XYZ && kept_children > 0 && (!rotation || !scaling || !z))
+            return fail(fn + "children's xyz need rotation, scaling and z");
+    }
+    DensifyView v;
+    densify_layout(P, static_cast<char*>(const_cast<void*>(workspace)), &v);
+    launch_densify_apply(P, groups, n_groups, rotation, scaling, z, n_split, kept_children, 1.0f / (float)(0.8 * 2), v,
+                         static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
 int goi_codebook_loss_partial_rows(void) { return codebook_loss_waves(); }
 
 int goi_codebook_loss_rows(const float* sim_raw, const float* inv_gnorm, const float* sem, const float* W,

@@ -303,6 +303,27 @@ void launch_photometric_forward(const float* x, const float* y, long long n, int
 void launch_photometric_backward(const float* x, const float* y, long long n, int c, int h, int w, float lambda, unsigned flags,
                                  const float* grad_out, const void* ws, float* gx, float* gy, hipStream_t s);
 
+// densification (densify.hip): thresholds rounded to fp32 once, and the workspace of a plan
+struct DensifyThresholds {
+    float max_grad, thr_scale, min_opacity, big_world, split_inv;
+    int screen, screen_all;  // max_screen_size truthy; 0 > max_screen_size (the zeroed radii test prunes every row)
+};
+struct DensifyView {
+    uint8_t* flags;     // [P] plan byte per original Gaussian
+    uint32_t* rank;     // [4P] keep / clone / children / split streams, scanned in place: destination rows
+    uint32_t* scratch;  // scan partials
+    uint32_t* total;
+};
+size_t densify_layout(long long P, char* base, DensifyView* v);
+void launch_densify_stats(long long P, const float* grad, long long stride, const uint8_t* filter, float* accum, float* denom,
+                          hipStream_t s);
+void launch_densify_plan(long long P, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                         const DensifyThresholds& t, uint32_t* counts, const DensifyView& v, hipStream_t s);
+void launch_prune_plan(long long P, const uint8_t* mask, uint32_t* counts, const DensifyView& v, hipStream_t s);
+void launch_densify_apply(long long P, const GoiDensifyRows* groups, int n_groups, const float* rotation, const float* scaling,
+                          const float* z, long long n_split, long long kept_children, float split_inv, const DensifyView& v,
+                          hipStream_t s);
+
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).
 __device__ __forceinline__ void tile_rect(float px, float py, int r, int gx, int gy, int& x0, int& y0, int& x1,
                                           int& y1) {

@@ -558,6 +558,49 @@ int goi_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, double
 int goi_adam_step_guarded(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
                           const unsigned char* nograd_mask /*[P] or NULL*/, const uint32_t* skip_flag, void* stream);
 
+/* ---- densification and pruning of the Gaussian set (scene/gaussian_model.py:291-513; csrc/densify.hip).  P < 2^30.
+ * All pointers are device pointers to contiguous fp32 rows unless stated; everything is asynchronous on `stream`.
+ * goi_raster_densify_stats: add_densification_stats, for every i with filter[i] != 0: accum[i] += sqrt(gx^2 + gy^2),
+ *   denom[i] += 1, (gx, gy) = grad[i * grad_stride + 0 / 1] (the 2-D mean gradient, grad_stride >= 2 floats).
+ * goi_raster_densify_plan: the decisions of densify_and_prune for every ORIGINAL Gaussian from accum [P], denom [P],
+ *   scaling [P][3] (raw log-scales), opacity [P] (raw), each threshold as the reference forms it in double (max_grad,
+ *   scale_threshold = percent_dense * extent, min_opacity, big_threshold = 0.1 * extent) and rounded to fp32 here;
+ *   screen_test != 0 when max_screen_size is truthy (the reference compares max_screen_size with the ZEROED max_radii2D
+ *   then: 0 > max_screen_size prunes every row).  Writes counts (device, 4 words) = rows kept of {originals, clones, first
+ *   children, and -- the fourth -- Gaussians selected for a split} and fills the workspace for goi_raster_densify_apply.
+ * goi_raster_densify_prune_plan: prune_points: counts[0] = rows with mask[i] == 0 (mask: P bytes), counts[1..3] = 0.
+ * goi_raster_densify_apply: after a plan on the same workspace and P: every group reads `rows` = P source rows of row_len
+ *   floats and writes the new layout [originals kept][clones kept][first children kept][second children kept] (each block
+ *   in ascending original index; dst holds counts[0] + counts[1] + 2 counts[2] rows).  GOI_DENSIFY_PARAM copies a row to
+ *   each destination, _MOMENT copies kept originals and writes 0 for clones and children, _XYZ / _SCALING (row_len 3)
+ *   form the children's xyz = build_rotation(rotation) @ (Z exp(scaling)) + xyz and scaling = log(exp(s) / 1.6) from
+ *   rotation [P][4], scaling [P][3] and z [2 n_split][3] (row r: first child of the split Gaussian of rank r, row n_split + r:
+ *   its second child); _ZERO writes `rows` x row_len zeros to dst (src unused).  n_split = counts[3], kept_children =
+ *   counts[2].  Up to GOI_DENSIFY_MAX_GROUPS groups in one launch.  No float atomics: the result is deterministic.
+ * workspace: goi_raster_densify_workspace_bytes(P) bytes, 256-byte aligned (0: P out of range). */
+#define GOI_DENSIFY_MAX_GROUPS 24
+#define GOI_DENSIFY_PARAM 0
+#define GOI_DENSIFY_MOMENT 1
+#define GOI_DENSIFY_XYZ 2
+#define GOI_DENSIFY_SCALING 3
+#define GOI_DENSIFY_ZERO 4
+typedef struct GoiDensifyRows {
+    const float* src;
+    float* dst;
+    long long rows;
+    int row_len; /* >= 1 */
+    int mode;    /* GOI_DENSIFY_* */
+} GoiDensifyRows;
+size_t goi_raster_densify_workspace_bytes(long long P);
+int goi_raster_densify_stats(long long P, const float* grad, long long grad_stride, const unsigned char* filter, float* accum,
+                             float* denom, void* stream);
+int goi_raster_densify_plan(long long P, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                            double max_grad, double scale_threshold, double min_opacity, int screen_test, double max_screen_size,
+                            double big_threshold, unsigned* counts, void* workspace, void* stream);
+int goi_raster_densify_prune_plan(long long P, const unsigned char* mask, unsigned* counts, void* workspace, void* stream);
+int goi_raster_densify_apply(long long P, const GoiDensifyRows* groups, int n_groups, const float* rotation, const float* scaling,
+                             const float* z, long long n_split, long long kept_children, const void* workspace, void* stream);
+
 /* Lane utilisation of the blend kernels, counted on the device from what the forward of a frame left in its workspaces
  * (member masks, n_contrib, per-quadrant walk lengths): a diagnostic of the execution mapping, not part of the reference's
  * interface (its blend loops, one thread per pixel: CR/forward.cu:330-372, CR/backward.cu:523-589).  R / the three buffers:
