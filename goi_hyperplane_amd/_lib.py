@@ -123,6 +123,8 @@ SYMBOLS = {
     "goi_raster_debug_reduce_row_floats": (C.c_int, [C.c_int, C.c_int]),
     "goi_raster_debug_reduce_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "goi_raster_debug_reduce_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 14),
+    "goi_raster_debug_preprocess_backward": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int, C.c_int, C.c_longlong]
+                                             + [C.c_void_p] * 22),
 }
 
 _lib = None

@@ -1537,4 +1537,69 @@ int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const 
     return 0;
 }
 
+int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source, int flags, int max_blocks, long long n_cap,
+                                         const uint32_t* frame, const int* radii, const uint8_t* clamped, const float* cov3D,
+                                         const int* prev_radii, const uint32_t* aux, const uint32_t* tiles_touched,
+                                         const float* rows, const uint8_t* row_flags, float* dL_dmean2D, const float* dL_dconic,
+                                         float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, const float* dL_ddepth,
+                                         float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                         void* workspace, void* stream) {
+    const std::string fn = "goi_raster_debug_preprocess_backward";
+    if (!scene) return fail(fn + ": scene is NULL");
+    const GoiRasterScene& sc = *scene;
+    if (sc.P < 0 || sc.W <= 0 || sc.H <= 0) return fail(fn + ": bad P/W/H");
+    if (sc.S < 1 || sc.S > 32) return fail(fn + ": need 1 <= S <= 32");
+    if (source < 0 || source > 2) return fail(fn + ": unknown source (0 per-id arrays, 1 records, 2 rows summed in the kernel)");
+    if (flags & ~GOI_BACKWARD_ACCUMULATE) return fail(fn + ": unknown flag bits");
+    if (max_blocks < 0) return fail(fn + ": max_blocks must be >= 0 (0: the product's grid)");
+    if (n_cap < 0 || n_cap > INT_MAX) return fail(fn + ": need 0 <= n_cap < 2^31");
+    if (source == 2 && bwd_row_floats(sc.S) != 32) return fail(fn + ": source 2 sums 128-byte rows only (S = 5 .. 20)");
+    if (sc.P == 0) return 0;
+    if (!(sc.tan_fovx > 0.f) || !(sc.tan_fovy > 0.f)) return fail(fn + ": tan_fovx / tan_fovy must be positive");
+    if (!sc.means3D || !sc.viewmatrix || !sc.projmatrix || !sc.campos) return fail(fn + ": a required scene pointer is NULL");
+    if (sc.shs && sc.colors_precomp) return fail(fn + ": shs and colors_precomp are both given");
+    if (sc.shs && (sc.D < 0 || sc.D > 3 || sc.M < (sc.D + 1) * (sc.D + 1) || sc.M > 16))
+        return fail(fn + ": SH degree must be 0..3 and (D+1)^2 <= M <= 16");
+    if (sc.shs && (3 * sc.M) % 4 == 0 && (reinterpret_cast<uintptr_t>(sc.shs) & 15u) != 0)
+        return fail(fn + ": shs must be 16-byte aligned when 3 M is a multiple of 4");
+    if (!sc.shs && dL_dsh) return fail(fn + ": dL_dsh without shs");
+    if ((sc.scales == nullptr) != (sc.rotations == nullptr)) return fail(fn + ": scales and rotations go together");
+    if ((sc.scales != nullptr) == (sc.cov3D_precomp != nullptr))
+        return fail(fn + ": exactly one of the scale/rotation pair and cov3D_precomp");
+    if (sc.scales && !cov3D) return fail(fn + ": cov3D (what the forward computed from scale/rotation) is NULL");
+    if (sc.rotations && (reinterpret_cast<uintptr_t>(sc.rotations) & 15u) != 0) return fail(fn + ": rotations must be 16-byte aligned");
+    const bool accumulate = (flags & GOI_BACKWARD_ACCUMULATE) != 0;
+    if (accumulate && source != 1) return fail(fn + ": accumulate needs source 1 (the records)");
+    if (accumulate && prev_radii) return fail(fn + ": accumulate with prev_radii");
+    if (accumulate && sc.shs && !dL_dsh) return fail(fn + ": accumulate with factored SH (dL_dsh NULL)");
+    if (!frame || !radii || !workspace || !dL_dmean2D || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
+        (sc.shs && !clamped))
+        return fail(fn + ": a required pointer is NULL");
+    if (source == 0 && (!dL_dconic || !dL_ddepth)) return fail(fn + ": source 0 reads dL_dconic and dL_ddepth");
+    if (source != 0 && (!aux || !tiles_touched || !rows || !dL_dopacity || !dL_dsemantic))
+        return fail(fn + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic");
+    if (source == 2 && !row_flags) return fail(fn + ": source 2 needs the validity bytes");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + ": workspace must be 256-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(dL_drot) & 15u) || (aux && (reinterpret_cast<uintptr_t>(aux) & 15u)) ||
+        (rows && (reinterpret_cast<uintptr_t>(rows) & 15u)) || (row_flags && (reinterpret_cast<uintptr_t>(row_flags) & 3u)) ||
+        (dL_dsemantic && (reinterpret_cast<uintptr_t>(dL_dsemantic) & 15u)))
+        return fail(fn + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    GeomView g{};
+    g.counters = static_cast<uint32_t*>(workspace);  // a 256-byte counter block: the frame words where the kernel reads them
+    g.cov3D = const_cast<float*>(cov3D);
+    g.clamped = const_cast<uint8_t*>(clamped);
+    g.aux = reinterpret_cast<uint4*>(const_cast<uint32_t*>(aux));
+    g.tiles_touched = const_cast<uint32_t*>(tiles_touched);
+    static_assert(COUNTER_N < 64 && COUNTER_V < 64 && COUNTER_OVF < 64, "the frame words fit the 256-byte counter block");
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_N, frame + 0, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_V, frame + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_OVF, frame + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                          dL_drot, s, source != 0 ? rows : nullptr, dL_dopacity, dL_dsemantic, prev_radii,
+                          source == 2 ? row_flags : nullptr, (int)n_cap, accumulate, max_blocks);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"

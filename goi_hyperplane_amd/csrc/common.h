@@ -250,7 +250,8 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
                            const float* record_rows = nullptr, float* dL_dopacity = nullptr, float* dL_dsemantic = nullptr,
                            const int* prev_radii = nullptr,  // prev_radii: BwdArgs (rows that already hold zeros)
                            const uint8_t* row_flags = nullptr, int N_cap = 0,  // row_flags: the kernel sums the rows itself (bwd_records 2)
-                           bool accumulate = false);  // add to the outputs instead of writing them (record path only: BwdArgs::accumulate)
+                           bool accumulate = false,  // add to the outputs instead of writing them (record path only: BwdArgs::accumulate)
+                           int max_blocks = 0);  // > 0: cap on the persistent grid (the test entry; the product passes 0: its own choice)
 int launch_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
                            const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
                            hipStream_t s);

@@ -1118,7 +1118,7 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
                            const float* dL_dconic, float* dL_dcolor, const float* dL_ddepth, float* dL_dmean3D,
                            float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, hipStream_t s,
                            const float* record_rows, float* dL_dopacity, float* dL_dsemantic, const int* prev_radii,
-                           const uint8_t* row_flags, int N_cap, bool accumulate) {
+                           const uint8_t* row_flags, int N_cap, bool accumulate, int max_blocks) {
     BwdArgs a;
     a.prev_radii = prev_radii;
     a.accumulate = accumulate ? 1 : 0;
@@ -1147,7 +1147,10 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n > 0 ? n : 256;
     }();
-    const dim3 grid((unsigned)std::min((sc.P + 255) / 256, n_cu * BWD_BLOCKS_PER_CU));
+    // max_blocks > 0 (goi_raster_debug_preprocess_backward only): fewer persistent workgroups, each walking more segments
+    int blocks = std::min((sc.P + 255) / 256, n_cu * BWD_BLOCKS_PER_CU);
+    if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+    const dim3 grid((unsigned)blocks);
 #define GOI_PBWD(DSH, SRC, LDS)                                                                                             \
     preprocess_bwd_k<DSH, SRC><<<grid, dim3(256), LDS, s>>>(a, radii, g.counters, g.clamped, dL_dmean2D, dL_dconic, dL_dcolor, \
                                                             dL_ddepth, ra, dL_dmean3D, dL_dcov3D, DSH ? dL_dsh : nullptr,      \

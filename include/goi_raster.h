@@ -56,7 +56,8 @@ extern "C" {
  *    goi_raster_debug_exclusive_scan; goi_knn_dist2 and goi_semantic_dbscan refuse 2^30 points or more;
  *    goi_raster_debug_reduce_row_floats, goi_raster_debug_reduce_workspace_bytes, goi_raster_debug_reduce_rows,
  *    goi_codebook_unique_rows_workspace_bytes, goi_codebook_unique_rows, goi_codebook_kmeans_workspace_bytes, goi_codebook_kmeans,
- *    goi_raster_photometric_workspace_bytes, goi_raster_photometric_forward, goi_raster_photometric_backward
+ *    goi_raster_photometric_workspace_bytes, goi_raster_photometric_forward, goi_raster_photometric_backward,
+ *    goi_raster_debug_preprocess_backward
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -668,6 +669,37 @@ int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const 
                                  const uint32_t* offsets, const uint32_t* tiles_touched, float* rows, const uint8_t* flags,
                                  float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
                                  float* dL_ddepth, void* workspace, void* stream);
+
+/* The per-Gaussian backward (tests only): the product's own launch of preprocess_bwd_k on caller buffers, asynchronously on
+ * `stream`; nothing comes from a forward pass.  From `scene`: P, D, M, S, W, H, means3D, shs (or NULL: no SH path), scales +
+ * rotations (or NULL: no scale / rotation path; cov3D_precomp is then the covariance), scale_modifier, the camera.  All arrays
+ * are DEVICE arrays:
+ *   radii [P] (> 0: visible -- the caller's choice), clamped [P] (bit 0..2: r, g, b clamped; read with shs only), cov3D [P,6]
+ *   (what the forward computed from scale / rotation; unused with cov3D_precomp), prev_radii [P] or NULL (the radii of the
+ *   backward that last wrote these output buffers: a Gaussian invisible then and now is left untouched),
+ *   frame {count, listed, overflow}: copied into the counter block at the start of `workspace` (256 bytes, 256-byte aligned);
+ *   a non-zero overflow word makes every Gaussian invisible.
+ * source: where the blend gradients of a Gaussian come from
+ *   0  the per-id arrays dL_dmean2D [P,3], dL_dconic [P,4] (a, b, -, c), dL_dcolor [P,3], dL_ddepth [P] (inputs; dL_dcolor is
+ *      rewritten in factored mode);
+ *   1  its RECORD in `rows` over the slot 4 * aux[4 g] (aux [P,4] words, word 0: first emit-order instance) when
+ *      tiles_touched[g] != 0, zeros otherwise; the kernel writes dL_dmean2D, dL_dcolor, dL_dopacity [P], dL_dsemantic [P,S];
+ *      record = [sem 0 .. 4 ceil(S/4)) | r g b depth | mean2D x y | conic a b c | opacity], row width as
+ *      goi_raster_debug_reduce_row_floats(1, S);
+ *   2  the kernel sums the rows of the Gaussian's tiles_touched[g] instances from aux[4 g] on (validity bytes row_flags
+ *      [4 n_cap], order as goi_raster_debug_reduce_rows), or reads its record when it has more instances than the frame's
+ *      big-Gaussian threshold; 128-byte rows only.  Every instance must lie below n_cap.
+ * flags: GOI_BACKWARD_ACCUMULATE (source 1, prev_radii NULL, dL_dsh given with shs): visible rows are added to, the others kept.
+ * dL_dsh NULL with shs: factored mode (the clamp-masked colour gradient goes to dL_dcolor).  max_blocks > 0 caps the persistent
+ * grid (0: the product's choice).  Outputs: dL_dmean3D [P,3], dL_dcov3D [P,6], dL_dsh [P,M,3], dL_dscale [P,3], dL_drot [P,4].
+ * Invalid combinations fail by name (goi_raster_last_error). */
+int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source, int flags, int max_blocks, long long n_cap,
+                                         const uint32_t* frame, const int* radii, const uint8_t* clamped, const float* cov3D,
+                                         const int* prev_radii, const uint32_t* aux, const uint32_t* tiles_touched,
+                                         const float* rows, const uint8_t* row_flags, float* dL_dmean2D, const float* dL_dconic,
+                                         float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, const float* dL_ddepth,
+                                         float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                         void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -632,6 +632,138 @@ static void cov3D_backward(int idx, V3 scale_, float mod, const float* rot, cons
     dL_drots[4 * idx + 3] = qw;
 }
 
+// The per-Gaussian half of the backward (CR/backward.cu:144-274 computeCov2DCUDA, 346-412 preprocessCUDA): the blend's per-id
+// gradients -> dL/dmean3D, dL/dcov3D, dL/dSH, dL/dscale, dL/drotation of every Gaussian with radii > 0.  The outputs of the
+// other Gaussians are left as they are (the caller zero-fills).
+static void preprocess_backward_loop(const GoiOracleScene* sc, const int* radii, const uint8_t* clamped /*[P,3]*/,
+                                     const float* cov3Ds, const float* dL_dmean2D, const float* dL_dconic,
+                                     const float* dL_dcolor, const float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D,
+                                     float* dL_dsh, float* dL_dscale, float* dL_drot, int nt) {
+    const int P = sc->P, W = sc->W, H = sc->H, M = sc->M;
+    const float focal_y = H / (2.0f * sc->tan_fovy);
+    const float focal_x = W / (2.0f * sc->tan_fovx);
+    const V3 campos = {sc->campos[0], sc->campos[1], sc->campos[2]};
+    const float* view = sc->viewmatrix;
+    const float* proj = sc->projmatrix;
+
+#pragma omp parallel for num_threads(nt) schedule(static)
+    for (int idx = 0; idx < P; idx++) {
+        if (!(radii[idx] > 0)) continue;
+        // ---- CR/backward.cu:144-274 computeCov2DCUDA
+        {
+            const float* cov3D = cov3Ds + (size_t)6 * idx;
+            V3 mean = {sc->means3D[3 * idx], sc->means3D[3 * idx + 1], sc->means3D[3 * idx + 2]};
+            V3 dL_dcon = {dL_dconic[4 * idx], dL_dconic[4 * idx + 1], dL_dconic[4 * idx + 3]};
+            Cov2DCtx c;
+            M3 cov2D;
+            cov2D_common(mean, focal_x, focal_y, sc->tan_fovx, sc->tan_fovy, cov3D, view, c, cov2D);
+            const float x_grad_mul = (c.txtz < -c.limx || c.txtz > c.limx) ? 0.f : 1.f;
+            const float y_grad_mul = (c.tytz < -c.limy || c.tytz > c.limy) ? 0.f : 1.f;
+            const auto& T = c.T.c;
+            const auto& Vrk = c.Vrk.c;
+            const auto& Wm = c.W.c;
+            float a = cov2D.c[0][0] += 0.3f;
+            float b = cov2D.c[0][1];
+            float cc = cov2D.c[1][1] += 0.3f;
+            float denom = a * cc - b * b;
+            float dL_da = 0, dL_db = 0, dL_dc = 0;
+            float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+            float* dcov = dL_dcov3D + (size_t)6 * idx;
+            if (denom2inv != 0) {
+                dL_da = denom2inv * (-cc * cc * dL_dcon.x + 2 * b * cc * dL_dcon.y + (denom - a * cc) * dL_dcon.z);
+                dL_dc = denom2inv * (-a * a * dL_dcon.z + 2 * a * b * dL_dcon.y + (denom - a * cc) * dL_dcon.x);
+                dL_db = denom2inv * 2 * (b * cc * dL_dcon.x - (denom + 2 * b * b) * dL_dcon.y + a * b * dL_dcon.z);
+                dcov[0] = (T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc);
+                dcov[3] = (T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc);
+                dcov[5] = (T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc);
+                dcov[1] = 2 * T[0][0] * T[0][1] * dL_da + (T[0][0] * T[1][1] + T[0][1] * T[1][0]) * dL_db +
+                          2 * T[1][0] * T[1][1] * dL_dc;
+                dcov[2] = 2 * T[0][0] * T[0][2] * dL_da + (T[0][0] * T[1][2] + T[0][2] * T[1][0]) * dL_db +
+                          2 * T[1][0] * T[1][2] * dL_dc;
+                dcov[4] = 2 * T[0][2] * T[0][1] * dL_da + (T[0][1] * T[1][2] + T[0][2] * T[1][1]) * dL_db +
+                          2 * T[1][1] * T[1][2] * dL_dc;
+            } else {
+                for (int i = 0; i < 6; i++) dcov[i] = 0;
+            }
+            float dL_dT00 = 2 * (T[0][0] * Vrk[0][0] + T[0][1] * Vrk[0][1] + T[0][2] * Vrk[0][2]) * dL_da +
+                            (T[1][0] * Vrk[0][0] + T[1][1] * Vrk[0][1] + T[1][2] * Vrk[0][2]) * dL_db;
+            float dL_dT01 = 2 * (T[0][0] * Vrk[1][0] + T[0][1] * Vrk[1][1] + T[0][2] * Vrk[1][2]) * dL_da +
+                            (T[1][0] * Vrk[1][0] + T[1][1] * Vrk[1][1] + T[1][2] * Vrk[1][2]) * dL_db;
+            float dL_dT02 = 2 * (T[0][0] * Vrk[2][0] + T[0][1] * Vrk[2][1] + T[0][2] * Vrk[2][2]) * dL_da +
+                            (T[1][0] * Vrk[2][0] + T[1][1] * Vrk[2][1] + T[1][2] * Vrk[2][2]) * dL_db;
+            float dL_dT10 = 2 * (T[1][0] * Vrk[0][0] + T[1][1] * Vrk[0][1] + T[1][2] * Vrk[0][2]) * dL_dc +
+                            (T[0][0] * Vrk[0][0] + T[0][1] * Vrk[0][1] + T[0][2] * Vrk[0][2]) * dL_db;
+            float dL_dT11 = 2 * (T[1][0] * Vrk[1][0] + T[1][1] * Vrk[1][1] + T[1][2] * Vrk[1][2]) * dL_dc +
+                            (T[0][0] * Vrk[1][0] + T[0][1] * Vrk[1][1] + T[0][2] * Vrk[1][2]) * dL_db;
+            float dL_dT12 = 2 * (T[1][0] * Vrk[2][0] + T[1][1] * Vrk[2][1] + T[1][2] * Vrk[2][2]) * dL_dc +
+                            (T[0][0] * Vrk[2][0] + T[0][1] * Vrk[2][1] + T[0][2] * Vrk[2][2]) * dL_db;
+            float dL_dJ00 = Wm[0][0] * dL_dT00 + Wm[0][1] * dL_dT01 + Wm[0][2] * dL_dT02;
+            float dL_dJ02 = Wm[2][0] * dL_dT00 + Wm[2][1] * dL_dT01 + Wm[2][2] * dL_dT02;
+            float dL_dJ11 = Wm[1][0] * dL_dT10 + Wm[1][1] * dL_dT11 + Wm[1][2] * dL_dT12;
+            float dL_dJ12 = Wm[2][0] * dL_dT10 + Wm[2][1] * dL_dT11 + Wm[2][2] * dL_dT12;
+            float tz = 1.f / c.t.z;
+            float tz2 = tz * tz;
+            float tz3 = tz2 * tz;
+            float dL_dtx = x_grad_mul * -focal_x * tz2 * dL_dJ02;
+            float dL_dty = y_grad_mul * -focal_y * tz2 * dL_dJ12;
+            float dL_dtz = -focal_x * tz2 * dL_dJ00 - focal_y * tz2 * dL_dJ11 + (2 * focal_x * c.t.x) * tz3 * dL_dJ02 +
+                           (2 * focal_y * c.t.y) * tz3 * dL_dJ12;
+            V3 dL_dmean = transformVec4x3Transpose({dL_dtx, dL_dty, dL_dtz}, view);
+            dL_dmean3D[3 * idx + 0] = dL_dmean.x;  // assigns (CR/backward.cu:273)
+            dL_dmean3D[3 * idx + 1] = dL_dmean.y;
+            dL_dmean3D[3 * idx + 2] = dL_dmean.z;
+        }
+        // ---- CR/backward.cu:346-412 preprocessCUDA
+        {
+            V3 m = {sc->means3D[3 * idx], sc->means3D[3 * idx + 1], sc->means3D[3 * idx + 2]};
+            V4 m_hom = transformPoint4x4(m, proj);
+            float m_w = 1.0f / (m_hom.w + 0.0000001f);
+            float mul1 = (proj[0] * m.x + proj[4] * m.y + proj[8] * m.z + proj[12]) * m_w * m_w;
+            float mul2 = (proj[1] * m.x + proj[5] * m.y + proj[9] * m.z + proj[13]) * m_w * m_w;
+            const float d2x = dL_dmean2D[3 * idx], d2y = dL_dmean2D[3 * idx + 1];
+            V3 dL_dmean;
+            dL_dmean.x = (proj[0] * m_w - proj[3] * mul1) * d2x + (proj[1] * m_w - proj[3] * mul2) * d2y;
+            dL_dmean.y = (proj[4] * m_w - proj[7] * mul1) * d2x + (proj[5] * m_w - proj[7] * mul2) * d2y;
+            dL_dmean.z = (proj[8] * m_w - proj[11] * mul1) * d2x + (proj[9] * m_w - proj[11] * mul2) * d2y;
+            dL_dmean3D[3 * idx + 0] += dL_dmean.x;
+            dL_dmean3D[3 * idx + 1] += dL_dmean.y;
+            dL_dmean3D[3 * idx + 2] += dL_dmean.z;
+            float mul3 = view[2] * m.x + view[6] * m.y + view[10] * m.z + view[14];
+            V3 dL_dmean2;
+            dL_dmean2.x = (view[2] - view[3] * mul3) * dL_ddepth[idx];
+            dL_dmean2.y = (view[6] - view[7] * mul3) * dL_ddepth[idx];
+            dL_dmean2.z = (view[10] - view[11] * mul3) * dL_ddepth[idx];
+            dL_dmean3D[3 * idx + 0] += dL_dmean2.x;
+            dL_dmean3D[3 * idx + 1] += dL_dmean2.y;
+            dL_dmean3D[3 * idx + 2] += dL_dmean2.z;
+            if (sc->shs)
+                sh_backward(idx, sc->D, M, sc->means3D, campos, sc->shs, clamped, dL_dcolor, dL_dmean3D,
+                            dL_dsh);
+            if (sc->scales) {
+                V3 s = {sc->scales[3 * idx], sc->scales[3 * idx + 1], sc->scales[3 * idx + 2]};
+                cov3D_backward(idx, s, sc->scale_modifier, sc->rotations + (size_t)4 * idx, dL_dcov3D, dL_dscale,
+                               dL_drot);
+            }
+        }
+    }
+}
+
+int goi_oracle_preprocess_backward(const GoiOracleScene* sc, const int* radii, const uint8_t* clamped, const float* cov3D,
+                                   const float* dL_dmean2D, const float* dL_dconic, const float* dL_dcolor,
+                                   const float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                                   float* dL_drot, int num_threads) {
+    const int P = sc->P, M = sc->M;
+    if (sc->shs && (!dL_dsh || !clamped)) return -1;
+    std::fill(dL_dmean3D, dL_dmean3D + (size_t)3 * P, 0.f);
+    std::fill(dL_dcov3D, dL_dcov3D + (size_t)6 * P, 0.f);
+    if (dL_dsh && M > 0) std::fill(dL_dsh, dL_dsh + (size_t)3 * M * P, 0.f);
+    std::fill(dL_dscale, dL_dscale + (size_t)3 * P, 0.f);
+    std::fill(dL_drot, dL_drot + (size_t)4 * P, 0.f);
+    preprocess_backward_loop(sc, radii, clamped, sc->cov3D_precomp ? sc->cov3D_precomp : cov3D, dL_dmean2D, dL_dconic, dL_dcolor,
+                             dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, threads_or_default(num_threads));
+    return 0;
+}
+
 int goi_oracle_backward(const GoiOracleScene* sc, const GoiOracleState* st, const float* out_alpha,
                         const float* dL_dpix, const float* dL_dpixsem, const float* dL_dpix_depth,
                         const float* dL_dalphas, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
@@ -775,113 +907,9 @@ int goi_oracle_backward(const GoiOracleScene* sc, const GoiOracleState* st, cons
         dL_dopacity[g] = (float)a[9 + S];
     }
 
-    const float focal_y = H / (2.0f * sc->tan_fovy);
-    const float focal_x = W / (2.0f * sc->tan_fovx);
     const float* cov3Ds = sc->cov3D_precomp ? sc->cov3D_precomp : st->cov3D.data();  // CR/rasterizer_impl.cu:579
-    const V3 campos = {sc->campos[0], sc->campos[1], sc->campos[2]};
-    const float* view = sc->viewmatrix;
-    const float* proj = sc->projmatrix;
-
-#pragma omp parallel for num_threads(nt) schedule(static)
-    for (int idx = 0; idx < P; idx++) {
-        if (!(st->radii[idx] > 0)) continue;
-        // ---- CR/backward.cu:144-274 computeCov2DCUDA
-        {
-            const float* cov3D = cov3Ds + (size_t)6 * idx;
-            V3 mean = {sc->means3D[3 * idx], sc->means3D[3 * idx + 1], sc->means3D[3 * idx + 2]};
-            V3 dL_dcon = {dL_dconic[4 * idx], dL_dconic[4 * idx + 1], dL_dconic[4 * idx + 3]};
-            Cov2DCtx c;
-            M3 cov2D;
-            cov2D_common(mean, focal_x, focal_y, sc->tan_fovx, sc->tan_fovy, cov3D, view, c, cov2D);
-            const float x_grad_mul = (c.txtz < -c.limx || c.txtz > c.limx) ? 0.f : 1.f;
-            const float y_grad_mul = (c.tytz < -c.limy || c.tytz > c.limy) ? 0.f : 1.f;
-            const auto& T = c.T.c;
-            const auto& Vrk = c.Vrk.c;
-            const auto& Wm = c.W.c;
-            float a = cov2D.c[0][0] += 0.3f;
-            float b = cov2D.c[0][1];
-            float cc = cov2D.c[1][1] += 0.3f;
-            float denom = a * cc - b * b;
-            float dL_da = 0, dL_db = 0, dL_dc = 0;
-            float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-            float* dcov = dL_dcov3D + (size_t)6 * idx;
-            if (denom2inv != 0) {
-                dL_da = denom2inv * (-cc * cc * dL_dcon.x + 2 * b * cc * dL_dcon.y + (denom - a * cc) * dL_dcon.z);
-                dL_dc = denom2inv * (-a * a * dL_dcon.z + 2 * a * b * dL_dcon.y + (denom - a * cc) * dL_dcon.x);
-                dL_db = denom2inv * 2 * (b * cc * dL_dcon.x - (denom + 2 * b * b) * dL_dcon.y + a * b * dL_dcon.z);
-                dcov[0] = (T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc);
-                dcov[3] = (T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc);
-                dcov[5] = (T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc);
-                dcov[1] = 2 * T[0][0] * T[0][1] * dL_da + (T[0][0] * T[1][1] + T[0][1] * T[1][0]) * dL_db +
-                          2 * T[1][0] * T[1][1] * dL_dc;
-                dcov[2] = 2 * T[0][0] * T[0][2] * dL_da + (T[0][0] * T[1][2] + T[0][2] * T[1][0]) * dL_db +
-                          2 * T[1][0] * T[1][2] * dL_dc;
-                dcov[4] = 2 * T[0][2] * T[0][1] * dL_da + (T[0][1] * T[1][2] + T[0][2] * T[1][1]) * dL_db +
-                          2 * T[1][1] * T[1][2] * dL_dc;
-            } else {
-                for (int i = 0; i < 6; i++) dcov[i] = 0;
-            }
-            float dL_dT00 = 2 * (T[0][0] * Vrk[0][0] + T[0][1] * Vrk[0][1] + T[0][2] * Vrk[0][2]) * dL_da +
-                            (T[1][0] * Vrk[0][0] + T[1][1] * Vrk[0][1] + T[1][2] * Vrk[0][2]) * dL_db;
-            float dL_dT01 = 2 * (T[0][0] * Vrk[1][0] + T[0][1] * Vrk[1][1] + T[0][2] * Vrk[1][2]) * dL_da +
-                            (T[1][0] * Vrk[1][0] + T[1][1] * Vrk[1][1] + T[1][2] * Vrk[1][2]) * dL_db;
-            float dL_dT02 = 2 * (T[0][0] * Vrk[2][0] + T[0][1] * Vrk[2][1] + T[0][2] * Vrk[2][2]) * dL_da +
-                            (T[1][0] * Vrk[2][0] + T[1][1] * Vrk[2][1] + T[1][2] * Vrk[2][2]) * dL_db;
-            float dL_dT10 = 2 * (T[1][0] * Vrk[0][0] + T[1][1] * Vrk[0][1] + T[1][2] * Vrk[0][2]) * dL_dc +
-                            (T[0][0] * Vrk[0][0] + T[0][1] * Vrk[0][1] + T[0][2] * Vrk[0][2]) * dL_db;
-            float dL_dT11 = 2 * (T[1][0] * Vrk[1][0] + T[1][1] * Vrk[1][1] + T[1][2] * Vrk[1][2]) * dL_dc +
-                            (T[0][0] * Vrk[1][0] + T[0][1] * Vrk[1][1] + T[0][2] * Vrk[1][2]) * dL_db;
-            float dL_dT12 = 2 * (T[1][0] * Vrk[2][0] + T[1][1] * Vrk[2][1] + T[1][2] * Vrk[2][2]) * dL_dc +
-                            (T[0][0] * Vrk[2][0] + T[0][1] * Vrk[2][1] + T[0][2] * Vrk[2][2]) * dL_db;
-            float dL_dJ00 = Wm[0][0] * dL_dT00 + Wm[0][1] * dL_dT01 + Wm[0][2] * dL_dT02;
-            float dL_dJ02 = Wm[2][0] * dL_dT00 + Wm[2][1] * dL_dT01 + Wm[2][2] * dL_dT02;
-            float dL_dJ11 = Wm[1][0] * dL_dT10 + Wm[1][1] * dL_dT11 + Wm[1][2] * dL_dT12;
-            float dL_dJ12 = Wm[2][0] * dL_dT10 + Wm[2][1] * dL_dT11 + Wm[2][2] * dL_dT12;
-            float tz = 1.f / c.t.z;
-            float tz2 = tz * tz;
-            float tz3 = tz2 * tz;
-            float dL_dtx = x_grad_mul * -focal_x * tz2 * dL_dJ02;
-            float dL_dty = y_grad_mul * -focal_y * tz2 * dL_dJ12;
-            float dL_dtz = -focal_x * tz2 * dL_dJ00 - focal_y * tz2 * dL_dJ11 + (2 * focal_x * c.t.x) * tz3 * dL_dJ02 +
-                           (2 * focal_y * c.t.y) * tz3 * dL_dJ12;
-            V3 dL_dmean = transformVec4x3Transpose({dL_dtx, dL_dty, dL_dtz}, view);
-            dL_dmean3D[3 * idx + 0] = dL_dmean.x;  // assigns (CR/backward.cu:273)
-            dL_dmean3D[3 * idx + 1] = dL_dmean.y;
-            dL_dmean3D[3 * idx + 2] = dL_dmean.z;
-        }
-        // ---- CR/backward.cu:346-412 preprocessCUDA
-        {
-            V3 m = {sc->means3D[3 * idx], sc->means3D[3 * idx + 1], sc->means3D[3 * idx + 2]};
-            V4 m_hom = transformPoint4x4(m, proj);
-            float m_w = 1.0f / (m_hom.w + 0.0000001f);
-            float mul1 = (proj[0] * m.x + proj[4] * m.y + proj[8] * m.z + proj[12]) * m_w * m_w;
-            float mul2 = (proj[1] * m.x + proj[5] * m.y + proj[9] * m.z + proj[13]) * m_w * m_w;
-            const float d2x = dL_dmean2D[3 * idx], d2y = dL_dmean2D[3 * idx + 1];
-            V3 dL_dmean;
-            dL_dmean.x = (proj[0] * m_w - proj[3] * mul1) * d2x + (proj[1] * m_w - proj[3] * mul2) * d2y;
-            dL_dmean.y = (proj[4] * m_w - proj[7] * mul1) * d2x + (proj[5] * m_w - proj[7] * mul2) * d2y;
-            dL_dmean.z = (proj[8] * m_w - proj[11] * mul1) * d2x + (proj[9] * m_w - proj[11] * mul2) * d2y;
-            dL_dmean3D[3 * idx + 0] += dL_dmean.x;
-            dL_dmean3D[3 * idx + 1] += dL_dmean.y;
-            dL_dmean3D[3 * idx + 2] += dL_dmean.z;
-            float mul3 = view[2] * m.x + view[6] * m.y + view[10] * m.z + view[14];
-            V3 dL_dmean2;
-            dL_dmean2.x = (view[2] - view[3] * mul3) * dL_ddepth[idx];
-            dL_dmean2.y = (view[6] - view[7] * mul3) * dL_ddepth[idx];
-            dL_dmean2.z = (view[10] - view[11] * mul3) * dL_ddepth[idx];
-            dL_dmean3D[3 * idx + 0] += dL_dmean2.x;
-            dL_dmean3D[3 * idx + 1] += dL_dmean2.y;
-            dL_dmean3D[3 * idx + 2] += dL_dmean2.z;
-            if (sc->shs)
-                sh_backward(idx, sc->D, M, sc->means3D, campos, sc->shs, st->clamped.data(), dL_dcolor, dL_dmean3D,
-                            dL_dsh);
-            if (sc->scales) {
-                V3 s = {sc->scales[3 * idx], sc->scales[3 * idx + 1], sc->scales[3 * idx + 2]};
-                cov3D_backward(idx, s, sc->scale_modifier, sc->rotations + (size_t)4 * idx, dL_dcov3D, dL_dscale,
-                               dL_drot);
-            }
-        }
-    }
+    preprocess_backward_loop(sc, st->radii.data(), st->clamped.data(), cov3Ds, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth,
+                             dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nt);
     return 0;
 }
 

@@ -67,6 +67,16 @@ int goi_oracle_backward(const GoiOracleScene* sc, const GoiOracleState* st,
                         float* dL_dsh /*[P,M,3]*/, float* dL_dscale /*[P,3]*/,
                         float* dL_drot /*[P,4]*/, int num_threads);
 
+/* The per-Gaussian half of goi_oracle_backward on its own (the same function goi_oracle_backward calls): from the blend's
+ * per-id gradients dL_dmean2D [P,3], dL_dconic [P,4] (a, b, -, c), dL_dcolor [P,3], dL_ddepth [P] to the five outputs, for the
+ * Gaussians with radii > 0 (the caller's choice); the others get zeros.  Reads of `sc`: P, D, M, W, H, means3D, shs, scales,
+ * rotations, scale_modifier, cov3D_precomp, the camera.  clamped [P,3] bytes (with shs), cov3D [P,6] (unless cov3D_precomp). */
+int goi_oracle_preprocess_backward(const GoiOracleScene* sc, const int* radii, const uint8_t* clamped, const float* cov3D,
+                                   const float* dL_dmean2D, const float* dL_dconic, const float* dL_dcolor,
+                                   const float* dL_ddepth, float* dL_dmean3D /*[P,3]*/, float* dL_dcov3D /*[P,6]*/,
+                                   float* dL_dsh /*[P,M,3]*/, float* dL_dscale /*[P,3]*/, float* dL_drot /*[P,4]*/,
+                                   int num_threads);
+
 /* Trace (image -> Gaussian feature scatter), deterministic-sum restatement.
  * img_sem[S,H,W]; outputs out_color[3,H,W], gau_sem[P,S], num_gsem[P]. */
 int goi_oracle_trace(const GoiOracleScene* sc, GoiOracleState* st, const float* img_sem,

@@ -48,6 +48,8 @@ def _lib(variant: str = ""):
         lib.goi_oracle_forward.argtypes = [C.POINTER(_Scene), C.c_void_p] + [C.c_void_p] * 6 + [C.c_float, C.c_int]
         lib.goi_oracle_backward.restype = C.c_int
         lib.goi_oracle_backward.argtypes = [C.POINTER(_Scene), C.c_void_p] + [C.c_void_p] * 16 + [C.c_int]
+        lib.goi_oracle_preprocess_backward.restype = C.c_int
+        lib.goi_oracle_preprocess_backward.argtypes = [C.POINTER(_Scene)] + [C.c_void_p] * 12 + [C.c_int]
         lib.goi_oracle_trace.restype = C.c_int
         lib.goi_oracle_trace.argtypes = [C.POINTER(_Scene), C.c_void_p] + [C.c_void_p] * 5 + [C.c_int]
         lib.goi_oracle_mark_visible.argtypes = [C.c_int] + [C.c_void_p] * 4
@@ -183,6 +185,39 @@ class Oracle:
             "point_list_keys", "ranges", "n_contrib")])
         s.update(P=P, N=N, T=T)
         return s
+
+
+def preprocess_backward(*, W, H, means3D, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, dL_dmean2D, dL_dconic,
+                        dL_dcolor, dL_ddepth, shs=None, clamped=None, scales=None, rotations=None, cov3D=None,
+                        cov3D_precomp=None, sh_degree=3, scale_modifier=1.0, variant="", threads=0) -> dict:
+    """The per-Gaussian half of the backward alone (goi_oracle_preprocess_backward): from the blend's per-id gradients
+    dL_dmean2D [P,3], dL_dconic [P,4] (a, b, -, c), dL_dcolor [P,3], dL_ddepth [P] to means3D / cov3D / sh / scales /
+    rotations gradients of the Gaussians with radii > 0 (zeros elsewhere).  clamped: [P,3] bytes (with shs); cov3D: [P,6],
+    what the forward computed from scales / rotations (unused with cov3D_precomp)."""
+    a = dict(means3D=_f32(means3D).reshape(-1, 3), shs=_f32(shs), scales=_f32(scales), rotations=_f32(rotations),
+             cov3D_precomp=_f32(cov3D_precomp), viewmatrix=_f32(viewmatrix).reshape(16), projmatrix=_f32(projmatrix).reshape(16),
+             campos=_f32(campos).reshape(3), cov3D=_f32(cov3D), m2d=_f32(dL_dmean2D), conic=_f32(dL_dconic),
+             color=_f32(dL_dcolor), depth=_f32(dL_ddepth).reshape(-1),
+             radii=np.ascontiguousarray(radii, dtype=np.int32),
+             clamped=None if clamped is None else np.ascontiguousarray(clamped, dtype=np.uint8))
+    P = a["means3D"].shape[0]
+    M = 0 if a["shs"] is None else a["shs"].shape[1]
+    assert a["radii"].shape == (P,) and a["m2d"].shape == (P, 3) and a["conic"].shape == (P, 4) and a["color"].shape == (P, 3)
+    assert a["depth"].shape == (P,) and (a["shs"] is None or a["clamped"].shape == (P, 3))
+    assert (a["scales"] is None) == (a["rotations"] is None) and (a["scales"] is None) != (a["cov3D_precomp"] is None)
+    assert a["cov3D_precomp"] is not None or a["cov3D"].shape == (P, 6)
+    sc = _Scene(P, int(sh_degree), M, 1, int(W), int(H), None, _ptr(a["means3D"]), _ptr(a["shs"]), None, None, None,
+                _ptr(a["scales"]), float(scale_modifier), _ptr(a["rotations"]), _ptr(a["cov3D_precomp"]), _ptr(a["viewmatrix"]),
+                _ptr(a["projmatrix"]), _ptr(a["campos"]), float(tan_fovx), float(tan_fovy), 0)
+    o = dict(means3D=np.zeros((P, 3), np.float32), cov3D=np.zeros((P, 6), np.float32), sh=np.zeros((P, M, 3), np.float32),
+             scales=np.zeros((P, 3), np.float32), rotations=np.zeros((P, 4), np.float32))
+    r = _lib(variant).goi_oracle_preprocess_backward(
+        C.byref(sc), _ptr(a["radii"]), _ptr(a["clamped"]), _ptr(a["cov3D"]), _ptr(a["m2d"]), _ptr(a["conic"]), _ptr(a["color"]),
+        _ptr(a["depth"]), _ptr(o["means3D"]), _ptr(o["cov3D"]), _ptr(o["sh"]) if M > 0 else None, _ptr(o["scales"]),
+        _ptr(o["rotations"]), int(threads))
+    if r < 0:
+        raise RuntimeError(f"oracle preprocess_backward failed ({r})")
+    return o
 
 
 def mark_visible(means3D, viewmatrix, projmatrix) -> np.ndarray:

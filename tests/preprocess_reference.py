@@ -1,0 +1,211 @@
+"""Float64 (or float32) reference of the per-Gaussian backward (csrc/preprocess.hip: preprocess_bwd_k; the oracle's
+goi_oracle_preprocess_backward), written from the mathematics: the FORWARD of one Gaussian -- NDC mean, conic, SH colour
++ 0.5 under a given clamp mask, view depth -- is stated in torch for all Gaussians at once and the gradients of
+sum(upstream . outputs) come from autograd.  Nothing of the oracle's backward formulas is restated here.
+
+Conventions of the blend's per-id arrays (both confirmed against the oracle):
+  * dL_dmean2D is the gradient with respect to the NDC mean, ndc = hom.xy / (hom.w + 1e-7);
+  * dL_dconic[:, 1] holds HALF the gradient with respect to the conic's off-diagonal b (the blend accumulates
+    -0.5 gdx d.y dL_dG), so the loss is dca a + 2 dcb b + dcc c;
+  * a frustum-clamped t.x / t.y is a constant (tests/torch_reference.py: render);
+  * a colour channel whose clamp bit is set passes no gradient;
+  * dL_dscale is the gradient with respect to the MODIFIED scale scale_modifier * scale, not the scale: the reference's
+    computeCov3D backward (CR/backward.cu:295-325) forms s = mod * scale and writes dL/ds, without the factor mod (found
+    by tests/test_preprocess_bwd_cpu.py: with scale_modifier 0.7 / 1.6 every row of the true derivative differs from the
+    oracle's by 1/0.7 - 1 / 1 - 1/1.6).  The product follows the reference.
+Also here: the inputs shared by tests/test_preprocess_bwd_cpu.py and tests/test_gpu_preprocess_bwd.py (seeded upstream
+gradients, the classes of Gaussians, the row error).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from tests.torch_reference import quat_to_rot, sh_to_rgb
+
+TENSORS = ("means3D", "cov3D", "sh", "scales", "rotations")
+
+
+def gaussian_gradients(dtype, *, means3D, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, W, H, dL_dmean2D, dL_dconic,
+                       dL_dcolor, dL_ddepth, shs=None, sh_degree=3, clamp_mask=None, scales=None, rotations=None,
+                       scale_modifier=1.0, cov3D=None) -> dict:
+    """Gradients of sum_g (dL_dmean2D . ndc + dca a + 2 dcb b + dcc c + dL_dcolor . rgb + dL_ddepth depth) in `dtype`.
+    dL_dmean2D [P,>=2], dL_dconic [P,4] (a, b/2, -, c), clamp_mask [P] (bit 0..2: r, g, b passes no gradient).  With
+    scales / rotations the covariance is built from them (and dL/dcov3D is the gradient at that covariance); otherwise
+    `cov3D` [P,6] is the input.  Returns numpy arrays (means3D, cov3D, sh, scales, rotations; absent inputs: None) and the
+    classification clamp_x, clamp_y [P] bool, depth [P]."""
+    T = lambda a: torch.tensor(np.asarray(a), dtype=dtype)  # noqa: E731
+    mean = T(means3D).requires_grad_()
+    P = mean.shape[0]
+    V, PM = T(viewmatrix).reshape(4, 4), T(projmatrix).reshape(4, 4)
+    hom = torch.cat([mean, torch.ones(P, 1, dtype=dtype)], 1)
+    p_view = hom @ V
+    p_hom = hom @ PM
+    p_w = 1.0 / (p_hom[:, 3] + 1e-7)
+    ndc = p_hom[:, :2] * p_w[:, None]
+    tz = p_view[:, 2]
+
+    sc = rot = None
+    if scales is not None:
+        # (the leaf is the MODIFIED scale: see the module docstring)
+        sc, rot = (scale_modifier * T(scales)).requires_grad_(), T(rotations).requires_grad_()
+        L = quat_to_rot(rot) @ torch.diag_embed(sc)
+        Sg = L @ L.transpose(1, 2)
+        c6 = torch.stack([Sg[:, 0, 0], Sg[:, 0, 1], Sg[:, 0, 2], Sg[:, 1, 1], Sg[:, 1, 2], Sg[:, 2, 2]], -1)
+        c6.retain_grad()
+    else:
+        c6 = T(cov3D).requires_grad_()
+    Sigma = torch.stack([c6[:, 0], c6[:, 1], c6[:, 2], c6[:, 1], c6[:, 3], c6[:, 4], c6[:, 2], c6[:, 4], c6[:, 5]],
+                        -1).reshape(-1, 3, 3)
+
+    fx, fy = W / (2.0 * tan_fovx), H / (2.0 * tan_fovy)
+    limx, limy = 1.3 * tan_fovx, 1.3 * tan_fovy
+    txtz, tytz = p_view[:, 0] / tz, p_view[:, 1] / tz
+    cx = (txtz < -limx) | (txtz > limx)
+    cy = (tytz < -limy) | (tytz > limy)
+    tx = torch.where(cx, (txtz.clamp(-limx, limx) * tz).detach(), p_view[:, 0])
+    ty = torch.where(cy, (tytz.clamp(-limy, limy) * tz).detach(), p_view[:, 1])
+    zero = torch.zeros_like(tz)
+    J = torch.stack([fx / tz, zero, -(fx * tx) / (tz * tz), zero, fy / tz, -(fy * ty) / (tz * tz)], -1).reshape(-1, 2, 3)
+    A = J @ V[:3, :3].T
+    cov2 = A @ Sigma @ A.transpose(1, 2)
+    a, b, c = cov2[:, 0, 0] + 0.3, cov2[:, 0, 1], cov2[:, 1, 1] + 0.3
+    det = a * c - b * b
+    con_a, con_b, con_c = c / det, -b / det, a / det
+
+    up2, upc, upd = T(dL_dmean2D), T(dL_dconic), T(dL_ddepth).reshape(-1)
+    loss = (up2[:, 0] * ndc[:, 0] + up2[:, 1] * ndc[:, 1]).sum()
+    loss = loss + (upc[:, 0] * con_a + 2.0 * upc[:, 1] * con_b + upc[:, 3] * con_c).sum() + (upd * tz).sum()
+    sh = None
+    if shs is not None:
+        sh = T(shs).requires_grad_()
+        d = mean - T(campos).reshape(1, 3)
+        d = d / d.norm(dim=1, keepdim=True)
+        rgb = sh_to_rgb(sh_degree, sh, d) + 0.5
+        m = torch.tensor(np.asarray(clamp_mask, dtype=np.uint8).astype(np.int64))
+        keep = torch.stack([(m & 1) == 0, (m & 2) == 0, (m & 4) == 0], -1).to(dtype)
+        loss = loss + (T(dL_dcolor) * keep * rgb).sum()
+    loss.backward()
+    g = lambda t: None if t is None else t.grad.numpy()  # noqa: E731
+    return dict(means3D=g(mean), cov3D=g(c6), sh=g(sh), scales=g(sc), rotations=g(rot), clamp_x=cx.numpy(), clamp_y=cy.numpy(),
+                depth=tz.detach().numpy())
+
+
+def upstream(P: int, seed: int) -> dict:
+    """Seeded per-id blend gradients; each Gaussian's rows scaled by 10^k, k = -3 .. 1 (one k per Gaussian and array)."""
+    rng = np.random.default_rng(seed)
+
+    def arr(n):
+        return (rng.normal(size=(P, n)) * 10.0 ** rng.integers(-3, 2, size=(P, 1))).astype(np.float32)
+
+    m2d, con = arr(3), arr(4)
+    m2d[:, 2] = 0
+    con[:, 2] = 0
+    return dict(mean2D=m2d, conic=con, color=arr(3), depth=arr(1).reshape(-1), opacity=arr(1).reshape(-1))
+
+
+def clamp_bytes(mask: np.ndarray) -> np.ndarray:
+    """[P] bit mask (the kernel's form) -> [P,3] bytes (the oracle's form)."""
+    m = np.asarray(mask, dtype=np.uint8)
+    return np.stack([m & 1, (m >> 1) & 1, (m >> 2) & 1], -1).astype(np.uint8)
+
+
+def clamp_bits(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b).reshape(-1, 3) != 0
+    return (b[:, 0] * 1 + b[:, 1] * 2 + b[:, 2] * 4).astype(np.uint8)
+
+
+def row_error(got: np.ndarray, ref64: np.ndarray) -> np.ndarray:
+    """[P] max_j |got - ref| / max_j |ref| of every row (NaN where the reference row is all zero)."""
+    got = np.asarray(got, dtype=np.float64).reshape(len(ref64), -1)
+    ref = np.asarray(ref64, dtype=np.float64).reshape(len(ref64), -1)
+    den = np.abs(ref).max(1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(den > 0, np.abs(got - ref).max(1) / den, np.nan)
+
+
+def classes(ref: dict, visible: np.ndarray, scales=None) -> dict:
+    """Boolean [P] masks of the geometric classes of the visible Gaussians."""
+    cx, cy = ref["clamp_x"], ref["clamp_y"]
+    out = {"all": visible.copy(), "unclamped": visible & ~cx & ~cy, "x_only": visible & cx & ~cy, "y_only": visible & ~cx & cy,
+           "both": visible & cx & cy, "near": visible & (ref["depth"] < 0.4)}
+    if scales is not None:
+        s = np.asarray(scales, dtype=np.float64)
+        out["aspect100"] = visible & (s.max(1) / s.min(1) > 100.0)
+    return out
+
+
+# ---- the scenes both tests run -------------------------------------------------------------------------------------------
+# A box of half-extent (3, 2, 2) with the camera INSIDE the cloud (near-plane culls, frustum-clamped t.x / t.y, view depths
+# down to 0.2), at a corner of the box looking in, the same with a narrow field of view (nearly everything clamped), and the
+# canonical outside camera (distance 5: nothing clamped in x) at an odd image size.
+POSES = {
+    "inside": dict(width=200, height=152, yaw=0.3, pitch=-0.1, distance=0.6, target=(0.3, 0.1, 0.2)),
+    "corner": dict(width=200, height=152, yaw=2.159, pitch=-0.506, distance=3.92),
+    "narrow": dict(width=200, height=152, fovx=0.35, yaw=0.3, pitch=-0.1, distance=0.6, target=(0.3, 0.1, 0.2)),
+    "outside": dict(width=123, height=77),
+}
+
+
+def make_inputs(P: int, pose: str, *, seed: int = 3, sh_degree: int = 3, M: int = 16, qnorm: bool = False,
+                log_scale_std: float = 1.2, scale_modifier: float = 1.0, up_seed: int = 5) -> dict:
+    """Scene arrays, camera and upstream gradients of one run.  qnorm: quaternions of norm 0.5 .. 2 instead of 1."""
+    from goi_hyperplane_amd.scene import make_camera, make_scene
+    if pose == "outside":
+        sc = make_scene(P, S=4, seed=seed, sh_degree=sh_degree)
+    else:
+        sc = make_scene(P, S=4, seed=seed, sh_degree=sh_degree, log_scale_mean=-3.0, log_scale_std=log_scale_std, extent=(3, 2, 2))
+    cam = make_camera(**POSES[pose])
+    rot = sc.rotations
+    if qnorm:
+        rot = (rot * np.random.default_rng(seed + 77).uniform(0.5, 2.0, size=(P, 1))).astype(np.float32)
+    up = upstream(P, up_seed)
+    return dict(P=P, W=cam.image_width, H=cam.image_height, means3D=sc.means3D, shs=np.ascontiguousarray(sc.shs[:, :M]),
+                scales=sc.scales, rotations=rot, viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform,
+                campos=cam.camera_center, tan_fovx=cam.tanfovx, tan_fovy=cam.tanfovy, sh_degree=sh_degree,
+                scale_modifier=scale_modifier, opacities=sc.opacities, semantics=sc.semantics, up=up)
+
+
+def oracle_forward(oracle_mod, inp: dict, **kw) -> tuple:
+    """(radii [P], clamped [P,3] bytes, cov3D [P,6]) of the oracle's forward of the run's scene."""
+    o = oracle_mod.Oracle(W=inp["W"], H=inp["H"], bg=np.zeros(3, np.float32), means3D=inp["means3D"], opacities=inp["opacities"],
+                          semantics=inp["semantics"], viewmatrix=inp["viewmatrix"], projmatrix=inp["projmatrix"],
+                          campos=inp["campos"], tan_fovx=inp["tan_fovx"], tan_fovy=inp["tan_fovy"], shs=inp["shs"],
+                          scales=inp["scales"], rotations=inp["rotations"], sh_degree=inp["sh_degree"],
+                          scale_modifier=inp["scale_modifier"], **kw)
+    f = o.forward()
+    st = o.state()
+    return f.radii.copy(), st["clamped"].copy(), st["cov3D"].copy()
+
+
+def chain_kwargs(inp: dict) -> dict:
+    """What oracle.preprocess_backward and gaussian_gradients take alike."""
+    k = {n: inp[n] for n in ("W", "H", "means3D", "shs", "scales", "rotations", "viewmatrix", "projmatrix", "campos", "tan_fovx",
+                             "tan_fovy", "sh_degree", "scale_modifier")}
+    up = inp["up"]
+    k.update(dL_dmean2D=up["mean2D"], dL_dconic=up["conic"], dL_dcolor=up["color"], dL_ddepth=up["depth"])
+    return k
+
+
+def quantiles(e: np.ndarray) -> tuple:
+    """(median, p99, max) of the finite entries."""
+    e = e[~np.isnan(e)]
+    return float(np.median(e)), float(np.quantile(e, 0.99)), float(e.max())
+
+
+MIN_ROWS = 200                 # rows a class must hold to be judged
+FACTORS = (4.0, 4.0, 16.0)     # median, p99, max: the judged evaluation against the yardstick's
+
+
+def judge(errors: dict, yard: dict, what: str, log=print) -> list:
+    """errors / yard: {(tensor, class): row errors}.  A list of the misses: a quantile of `errors` above FACTORS x the
+    yardstick's.  Every pair of quantiles goes to `log`."""
+    bad = []
+    for key in sorted(errors):
+        e, y = quantiles(errors[key]), quantiles(yard[key])
+        n = int((~np.isnan(errors[key])).sum())
+        log("%-10s %-10s n=%5d  %s %.2e / %.2e / %.2e   yardstick %.2e / %.2e / %.2e" % (key[0], key[1], n, what, *e, *y))
+        for q, ev, yv, f in zip(("median", "p99", "max"), e, y, FACTORS):
+            if ev > f * yv:
+                bad.append(f"{what} {key[0]} [{key[1]}] {q} {ev:.3e} > {f:g} x {yv:.3e}")
+    return bad

@@ -172,16 +172,33 @@ def test_config1_exact_shape_forward_matches_oracle(oracle_mod, dev):
     assert abs(float(res["render"].astype(np.float64).sum()) - 129836.92) <= 0.03 * 129836.92
 
 
-@pytest.mark.parametrize("P,S,W,H,mu,deg", CASES)
-def test_forward_backward_match_oracle(oracle_mod, dev, P, S, W, H, mu, deg):
-    sc = make_scene(P, S=S, sh_degree=deg, seed=3, log_scale_mean=mu)
-    cam = make_camera(W, H, yaw=0.2, pitch=-0.1)
+# The camera INSIDE the cloud (every case above stands 5 units away from a box of half-depth 1: nothing behind the near plane,
+# no frustum-clamped t.x, view depths >= 3).  Counted with the oracle: Gaussians behind the near plane / visible / with a
+# clamped t.x / t.y / both / largest radius, fragile pixels (the gate allows 2 %), largest disagreement of the oracle's plain
+# and FMA builds on a gradient tensor (the gate is 1e-3 of its scale).
+INSIDE_CASES = [
+    # P, S, W, H, mu, deg, geometry
+    (3000, 16, 160, 120, -3.0, 3, dict(distance=1.0, target=(0.0, 0.0, 0.5), yaw=0.3, extent=(2.0, 1.5, 1.0))),   # 1043 / 379 / 85 / 125 / 47 / 721; 0.10 %; 1.4e-5
+    (3000, 10, 123, 77, -3.4, 2, dict(distance=0.6, target=(0.5, 0.2, 0.0), yaw=-0.7, extent=(2.0, 1.5, 1.0))),   # 1410 / 402 / 37 / 69 / 16 / 332; 0.06 %; 2.6e-4
+    (6000, 4, 200, 152, -3.6, 1, dict(distance=0.3, target=(0.0, 0.0, 0.0), yaw=1.2, extent=(3.0, 2.0, 2.0))),    # 2916 / 878 / 18 / 47 / 8 / 243; 0.02 %; 7.9e-6
+]
+_CASE_IDS = ["-".join(str(v) for v in c) for c in CASES] + ["-".join(str(v) for v in c[:6]) + "-inside" for c in INSIDE_CASES]
+
+
+@pytest.mark.parametrize("P,S,W,H,mu,deg,geom", [c + (None,) for c in CASES] + INSIDE_CASES, ids=_CASE_IDS)
+def test_forward_backward_match_oracle(oracle_mod, dev, P, S, W, H, mu, deg, geom):
+    if geom is None:
+        sc = make_scene(P, S=S, sh_degree=deg, seed=3, log_scale_mean=mu)
+        cam = make_camera(W, H, yaw=0.2, pitch=-0.1)
+    else:
+        sc = make_scene(P, S=S, sh_degree=deg, seed=3, log_scale_mean=mu, extent=geom["extent"])
+        cam = make_camera(W, H, yaw=geom["yaw"], pitch=-0.1, distance=geom["distance"], target=geom["target"])
     bg = np.array([0.1, 0.3, 0.6], np.float32)
     grads = upstream_grads(S, H, W, seed=5)
     o = oracle_mod.from_scene(sc, cam, bg=bg)
     f = o.forward()
     res = run_hip(sc, cam, bg, dev, grads=grads, debug_views=True)
-    tag = f"P{P}_S{S}_{W}x{H}"
+    tag = f"P{P}_S{S}_{W}x{H}" + ("" if geom is None else "_inside")
     # integer stages: bit-exact
     st = o.state()
     assert res["N"] == f.num_rendered, f"{tag}: num_rendered {res['N']} != {f.num_rendered}"
