@@ -125,6 +125,8 @@ SYMBOLS = {
     "goi_raster_debug_reduce_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 14),
     "goi_raster_debug_preprocess_backward": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int, C.c_int, C.c_longlong]
                                              + [C.c_void_p] * 22),
+    "goi_raster_debug_pair_eval": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_void_p] * 4),
+    "goi_raster_debug_backward_blend": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int] + [C.c_void_p] * 24),
 }
 
 _lib = None

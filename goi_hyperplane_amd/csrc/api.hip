@@ -1602,4 +1602,114 @@ int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source
     return 0;
 }
 
+int goi_raster_debug_pair_eval(int P, int W, int H, const void* geom_buffer, const uint32_t* requests, long long n_requests,
+                               float* E, float* alpha, uint8_t* guards, void* stream) {
+    const std::string fn = "goi_raster_debug_pair_eval";
+    if (P <= 0 || W <= 0 || H <= 0) return fail(fn + ": bad P/W/H");
+    if (n_requests < 0 || n_requests > (1ll << 31)) return fail(fn + ": need 0 <= n_requests <= 2^31");
+    if (n_requests == 0) return 0;
+    if (!geom_buffer || !requests || !E || !alpha || !guards) return fail(fn + ": a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(geom_buffer) & 255) return fail(fn + ": geom_buffer must be 256-byte aligned");
+    if (reinterpret_cast<uintptr_t>(requests) & 7u) return fail(fn + ": requests must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(E) & 3u) || (reinterpret_cast<uintptr_t>(alpha) & 3u))
+        return fail(fn + ": E and alpha must be 4-byte aligned");
+    GeomView g;
+    geom_layout(P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
+    launch_pair_eval(P, W, H, g, requests, n_requests, E, alpha, guards, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_debug_backward_blend(const GoiRasterScene* scene, int R, int mode, const void* geom_buffer,
+                                    const void* binning_buffer, const void* image_buffer, const int* radii,
+                                    const float* out_alpha, const float* dL_dout_color, const float* dL_dout_semantic,
+                                    const float* dL_dout_depth, const float* dL_dout_alpha, void* scratch, float* rows,
+                                    uint8_t* row_flags, uint32_t* aux, unsigned long long* qmask0, unsigned long long* qmask,
+                                    uint32_t* qcost, uint32_t* qorder, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                    float* dL_dcolor, float* dL_dsemantic, float* dL_ddepth, void* stream) {
+    const std::string fn = "goi_raster_debug_backward_blend";
+    refresh_options();
+    if (!scene) return fail(fn + ": scene is NULL");
+    const GoiRasterScene& sc = *scene;
+    if (sc.P <= 0 || sc.W <= 0 || sc.H <= 0) return fail(fn + ": bad P/W/H");
+    if (sc.S < 1 || sc.S > 32) return fail(fn + ": need 1 <= S <= 32");
+    if (R <= 0) return fail(fn + ": need R > 0 (the instance count the forward returned)");
+    if (mode < 0 || mode > 8)
+        return fail(fn + ": unknown mode (0..3 rows, 4..7 semantic rows: bit 0 exact-fp32 flush, bit 1 candidate testing; 8 per-tile kernel)");
+    const bool tile = mode == 8, sem = !tile && (mode & 4) != 0;
+    if (!sc.bg || !sc.semantics) return fail(fn + ": scene.bg and scene.semantics are required");
+    if ((sc.S & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.semantics) & 15u) != 0)
+        return fail(fn + ": semantics must be 16-byte aligned when S is a multiple of 4");
+    if (!geom_buffer || !binning_buffer || !image_buffer) return fail(fn + ": workspace pointer is NULL");
+    if ((reinterpret_cast<uintptr_t>(geom_buffer) & 255) || (reinterpret_cast<uintptr_t>(binning_buffer) & 255) ||
+        (reinterpret_cast<uintptr_t>(image_buffer) & 255))
+        return fail(fn + ": the workspaces must be 256-byte aligned");
+    if (!radii || !out_alpha) return fail(fn + ": radii and out_alpha are required");
+    if (sem && !dL_dout_semantic) return fail(fn + ": the semantic rows need dL_dout_semantic");
+    if (tile) {
+        if (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_dsemantic || !dL_ddepth)
+            return fail(fn + ": mode 8 writes the six per-id arrays");
+    } else {
+        if (!scratch) return fail(fn + ": modes 0..7 need the scratch of goi_raster_backward_scratch_bytes");
+        if (reinterpret_cast<uintptr_t>(scratch) & 255) return fail(fn + ": scratch must be 256-byte aligned");
+        if (!rows || !row_flags) return fail(fn + ": modes 0..7 copy out rows and row_flags");
+        if (reinterpret_cast<uintptr_t>(rows) & 15u) return fail(fn + ": rows must be 16-byte aligned");
+    }
+    if ((aux && (reinterpret_cast<uintptr_t>(aux) & 15u)) || (qmask0 && (reinterpret_cast<uintptr_t>(qmask0) & 7u)) ||
+        (qmask && (reinterpret_cast<uintptr_t>(qmask) & 7u)))
+        return fail(fn + ": aux must be 16-byte aligned, qmask0 and qmask 8-byte aligned");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    GeomView g;
+    ImageView im;
+    BinView bv;
+    geom_layout(sc.P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
+    image_layout(sc.W, sc.H, const_cast<char*>(static_cast<const char*>(image_buffer)), &im);
+    binning_layout(R, const_cast<char*>(static_cast<const char*>(binning_buffer)), &bv);
+    const int fin = tile_sort_result_index(sc.W, sc.H, R);
+    const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
+    const size_t n_quads = (size_t)gx * gy * 4;
+    bool ordered = false;
+    if (tile) {
+        const size_t P = (size_t)sc.P;
+        GOI_HIP(hipMemsetAsync(dL_dmean2D, 0, 3 * P * sizeof(float), s));
+        GOI_HIP(hipMemsetAsync(dL_dconic, 0, 4 * P * sizeof(float), s));
+        GOI_HIP(hipMemsetAsync(dL_dopacity, 0, P * sizeof(float), s));
+        GOI_HIP(hipMemsetAsync(dL_dcolor, 0, 3 * P * sizeof(float), s));
+        GOI_HIP(hipMemsetAsync(dL_dsemantic, 0, (size_t)sc.S * P * sizeof(float), s));
+        GOI_HIP(hipMemsetAsync(dL_ddepth, 0, P * sizeof(float), s));
+        launch_render_bwd_tile(sc, g, im, bv.vals[fin], out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha,
+                               dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, s);
+    } else {
+        // the form of the kernel is the mode's, whatever the process-wide switches say (this thread's snapshot only)
+        g_options.bwd_variant = (mode & 1) ? 2 : 0;
+        g_options.bwd_masks = (mode & 2) ? 0 : 1;
+        BwdScratchView scr;
+        bwd_scratch_layout(R, sc.S, static_cast<char*>(scratch), &scr);
+        ordered = launch_quad_order(sc, im, s, scr.flags, g.counters + COUNTER_N, (uint32_t)R, scr.big_ctl);
+        if (!ordered) {
+            GOI_HIP(hipMemsetAsync(scr.flags, 0, round_up_256((size_t)R * 4), s));
+            GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
+        }
+        const int row_floats = sem ? bwd_sem_row_floats(sc.S) : bwd_row_floats(sc.S);
+        if (sem)
+            launch_render_bwd_sem(sc, g, im, bv.vals[fin], radii, out_alpha, dL_dout_semantic, scr.rows, scr.flags, row_floats, s,
+                                  bv.qmask);
+        else
+            launch_render_bwd_rows(sc, g, im, bv.vals[fin], radii, out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth,
+                                   dL_dout_alpha, scr, s, bv.qmask);
+        GOI_HIP(hipGetLastError());
+        GOI_HIP(hipMemcpyAsync(rows, scr.rows, (size_t)R * 4 * row_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+        GOI_HIP(hipMemcpyAsync(row_flags, scr.flags, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
+    }
+    GOI_HIP(hipGetLastError());
+    if (aux) GOI_HIP(hipMemcpyAsync(aux, g.aux, (size_t)sc.P * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+    if (qmask0) GOI_HIP(hipMemcpyAsync(qmask0, im.qmask0, n_quads * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    if (qmask)
+        GOI_HIP(hipMemcpyAsync(qmask, bv.qmask, 4 * ((size_t)R / 64 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    if (qcost) GOI_HIP(hipMemcpyAsync(qcost, im.qcost, n_quads * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    if (qorder && ordered)
+        GOI_HIP(hipMemcpyAsync(qorder, im.qorder, 8 * ((n_quads + 7) / 8) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    return ordered ? 1 : 0;
+}
+
 }  // extern "C"

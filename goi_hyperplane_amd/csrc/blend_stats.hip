@@ -103,7 +103,49 @@ __global__ __launch_bounds__(64) void blend_stats_k(const uint2* __restrict__ ra
     }
 }
 
+// One (pixel, Gaussian) evaluation per lane, as the blend kernels do it, written out (tests only; goi_raster_debug_pair_eval).
+// One wave per request (Gaussian id, quadrant index 4 tile + q): the quadrant geometry comes from quad_geom_of, the centre and the
+// lane's (u, v) are formed as in render_fwd_k / render_bwd_rows_k, the coefficients by ONE call of poly_coefs (every lane forms
+// the same ones: which path a Gaussian takes depends on its own S only) and the pair by eval_poly.  Lanes outside the image
+// evaluate like any other: that is what the blend kernels' lanes do before `inside` masks them.  A request that names no
+// Gaussian or no quadrant writes NaN and guard byte 0x80.
+__global__ __launch_bounds__(64) void pair_eval_k(const uint2* __restrict__ req, long long first, long long n, int P, int W, int H,
+                                                  int gx, int n_quads, const GaussRec* __restrict__ rec, float* __restrict__ E,
+                                                  float* __restrict__ alpha, uint8_t* __restrict__ guards) {
+    const long long r = first + (long long)blockIdx.x;
+    if (r >= n) return;
+    const uint2 rq = req[r];
+    const int lane = threadIdx.x & 63;
+    const size_t o = (size_t)r * 64 + lane;
+    const QuadGeom t = quad_geom_of(rq.y < (uint32_t)n_quads ? (int)rq.y : -1, W, H, gx, n_quads);
+    if (t.tile < 0 || rq.x >= (uint32_t)P) {
+        E[o] = alpha[o] = __builtin_nanf("");
+        guards[o] = 0x80;
+        return;
+    }
+    const float4* r4 = reinterpret_cast<const float4*>(rec + rq.x);
+    const float4 q0 = r4[0], q1 = r4[1];
+    const float QCX = t.QX0 + 3.5f, QCY = t.QY0 + 3.5f;
+    const f32x2 uv = {t.pxf - QCX, t.pyf - QCY};
+    const PolyCoef pc = poly_coefs(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, QCX, QCY);
+    const PairEval e = eval_poly(pc.A35, pc.A12, pc.A0, pc.A4, pc.lim, uv);
+    E[o] = e.E;
+    alpha[o] = e.alpha;
+    guards[o] = (uint8_t)((e.below ? 1 : 0) | (e.seen ? 2 : 0));
+}
+
 }  // namespace
+
+void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* requests, long long n, float* E, float* alpha,
+                      uint8_t* guards, hipStream_t s) {
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    constexpr long long CHUNK = 1ll << 20;  // requests per launch: a whole frame's member pairs go through in a few launches
+    for (long long first = 0; first < n; first += CHUNK) {
+        const long long cnt = n - first < CHUNK ? n - first : CHUNK;
+        pair_eval_k<<<dim3((unsigned)cnt), dim3(64), 0, s>>>(reinterpret_cast<const uint2*>(requests), first, n, P, W, H, gx,
+                                                            gx * gy * 4, g.rec, E, alpha, guards);
+    }
+}
 
 void launch_blend_stats(int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                         const unsigned long long* qmask, unsigned long long* out, hipStream_t s) {

@@ -209,6 +209,10 @@ constexpr int HOST_STAMP_WORD = 33;
 // lane utilisation of the blend kernels counted from a forward's member masks / n_contrib (blend_stats.hip): out[GOI_BLEND_STATS_WORDS]
 void launch_blend_stats(int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                         const unsigned long long* qmask, unsigned long long* out, hipStream_t s);
+// one wave per request (Gaussian id, 4 tile + quadrant): E, alpha and the guard bits of the quadrant's 64 pixels through
+// poly_coefs / eval_poly (blend_stats.hip; tests only)
+void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* requests, long long n, float* E, float* alpha,
+                      uint8_t* guards, hipStream_t s);
 void launch_trace_fwd(const GoiRasterScene& sc, const float* img_sem, const GeomView& g, const ImageView& im,
                       const uint32_t* point_list, float* out_color, float* gau_sem, int* num_gsem, hipStream_t s);
 // launch order of the backward's quadrant waves (render_bwd.hip): im.qcost -> im.qorder

@@ -57,7 +57,7 @@ extern "C" {
  *    goi_raster_debug_reduce_row_floats, goi_raster_debug_reduce_workspace_bytes, goi_raster_debug_reduce_rows,
  *    goi_codebook_unique_rows_workspace_bytes, goi_codebook_unique_rows, goi_codebook_kmeans_workspace_bytes, goi_codebook_kmeans,
  *    goi_raster_photometric_workspace_bytes, goi_raster_photometric_forward, goi_raster_photometric_backward,
- *    goi_raster_debug_preprocess_backward
+ *    goi_raster_debug_preprocess_backward, goi_raster_debug_pair_eval, goi_raster_debug_backward_blend
  * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
@@ -700,6 +700,47 @@ int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source
                                          float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, const float* dL_ddepth,
                                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                                          void* workspace, void* stream);
+
+/* One (pixel, Gaussian) evaluation of the blend kernels, written out (tests only), asynchronously on `stream`.  Every blend
+ * kernel evaluates a pair through the same two device functions (csrc/blend_common.h: poly_coefs, eval_poly); this entry runs
+ * them for caller-chosen pairs of a frame whose forward filled geom_buffer (the records are read from it).
+ *   requests [n_requests][2] (DEVICE, 8-byte aligned): (Gaussian id, quadrant index 4 * tile + q; q = 0..3: the 8x8 pixel
+ *     quadrants of the 16x16 tile in row-major order, tiles row-major as everywhere).  One wave per request, one pixel per lane:
+ *     lane l is pixel (l & 7, l >> 3) of the quadrant, whether it lies inside the image or not.
+ *   E, alpha [n_requests][64]: opacity * exp(power) before the 0.99 clamp, and alpha = min(0.99, E);
+ *   guards [n_requests][64]: bit 0 "below" (the exponent passes the power <= tolerance guard), bit 1 "seen" (alpha >= 1/255); a pair
+ *     contributes where both are set.  A request that names no Gaussian (id >= P) or no quadrant gets NaN and 0x80.
+ * The records are the FIRST array of the geometry workspace, [P] x 12 floats (x, y, conic a, b | conic c, opacity, hx, hy | r, g, b,
+ * depth); only the first six are read here, so a test may also write records of its own into a zeroed workspace.
+ * Requests are processed 2^20 per launch. */
+int goi_raster_debug_pair_eval(int P, int W, int H, const void* geom_buffer, const uint32_t* requests, long long n_requests,
+                               float* E, float* alpha, uint8_t* guards, void* stream);
+
+/* The backward BLEND stage alone, on a real frame (tests only), asynchronously on `stream`: what goi_raster_backward3 /
+ * goi_raster_backward_semantics run before the row reduction -- the quadrant-order launch (or the memsets) and one blend kernel,
+ * through the product's launchers -- and copies of what it left.  From `scene`: P, S, W, H, bg, semantics.  R, the three
+ * workspaces, radii, out_alpha: as for goi_raster_backward of the same frame (R > 0).  The four upstream gradients may each be
+ * NULL (zero).  mode selects the kernel whatever goi_raster_set_option says:
+ *   0..3  render_bwd_rows_k: bit 0 set = exact-fp32 flush (else split-f16), bit 1 set = candidate testing (else member masks);
+ *   4..7  render_bwd_sem_k (rows of the padded semantic channels only), same two bits; needs dL_dout_semantic;
+ *   8     render_bwd_tile_k: the six per-id arrays of goi_raster_backward (zeroed, then accumulated with atomics).
+ * Modes 0..7 need `scratch` (goi_raster_backward_scratch_bytes(R, S), 256-byte aligned; rows the kernel does not write keep
+ * what the caller left there) and copy out  rows [4 R][row_floats] (row_floats = goi_raster_debug_reduce_row_floats(1, S), or
+ * (3, S) for modes 4..7; 16-byte aligned) and row_flags [4 R].  Row layout of modes 0..3:
+ *   [sem 0 .. 4 ceil(S/4)) | r g b depth | mean2D x y (NDC units) | conic a b c | opacity | pad]
+ * slot = 4 * (emit-order instance) + quadrant; a Gaussian's first instance is word 0 of its aux entry.
+ * Every mode copies out, where the pointer is not NULL:  aux [P][4] words;  qmask0 [4 T] and qmask [4 (R / 64 + 2)] 64-bit
+ * member words as the forward left them (round 0 of quadrant q of tile t: qmask0[4 t + q]; round r >= 1 of a tile whose list
+ * starts at x0: qmask[4 (x0 / 64 + r) + q]; bit j: list position 64 r + j contributed to some pixel of the quadrant);
+ * qcost [4 T];  qorder [8 ceil(4 T / 8)] when the quadrant order exists.
+ * Returns 1 when the quadrant order was launched (qorder written), 0 when not, < 0 on error (goi_raster_last_error). */
+int goi_raster_debug_backward_blend(const GoiRasterScene* scene, int R, int mode, const void* geom_buffer,
+                                    const void* binning_buffer, const void* image_buffer, const int* radii,
+                                    const float* out_alpha, const float* dL_dout_color, const float* dL_dout_semantic,
+                                    const float* dL_dout_depth, const float* dL_dout_alpha, void* scratch, float* rows,
+                                    uint8_t* row_flags, uint32_t* aux, unsigned long long* qmask0, unsigned long long* qmask,
+                                    uint32_t* qcost, uint32_t* qorder, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                    float* dL_dcolor, float* dL_dsemantic, float* dL_ddepth, void* stream);
 
 #ifdef __cplusplus
 }
