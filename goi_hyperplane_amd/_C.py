@@ -1037,12 +1037,13 @@ def _backward_impl(background, means3D, radii, colors, semantics, scales, rotati
                 binningBuffer = lazy_binning  # (a redone frame has a new buffer)
             R_scratch = _scratch_instances(R, R_layout)
             scratch = _backward_scratch(lib.goi_raster_backward_scratch_bytes(R_scratch or R_layout, S), dev)
-            r = lib.goi_raster_backward3(
+            # (no buffer pool on this path: every row is written, no mask is kept)
+            r = lib.goi_raster_backward4(
                 C.byref(sc), R_layout, R_scratch, 0, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(ten["radii"]),
                 _ptr(ten["alphas"]), _ptr(ten["g_c"]), _ptr(ten["g_s"]), _ptr(ten["g_d"]), _ptr(ten["g_a"]),
                 _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dsemantics),
                 _ptr(dL_ddepths), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
-                _ptr(dL_drotations), _ptr(scratch), None, _stream(dev))
+                _ptr(dL_drotations), _ptr(scratch), None, None, None, _stream(dev))
             if r < 0:
                 raise RuntimeError(_lib.last_error())
     return (dL_dmeans2D, dL_dcolors, dL_dsemantics, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,

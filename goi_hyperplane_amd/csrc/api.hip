@@ -457,6 +457,7 @@ size_t bwd_scratch_layout(int N, int S, char* base, BwdScratchView* v) {
     b.cap_big = reduce_cap_big(n / 4);
     carve(p, b.big_ctl, 8);
     carve(p, b.big_desc, b.cap_big);
+    carve(p, b.contrib, n / 4);  // (last: everything in front stays where it was)
     return (size_t)(p - base) + 256;
 }
 
@@ -490,6 +491,11 @@ size_t goi_raster_geom_bytes(int P) { return geom_layout(P, nullptr, nullptr) + 
 size_t goi_raster_image_bytes(int W, int H) { return image_layout(W, H, nullptr, nullptr) + 256; }
 size_t goi_raster_binning_bytes(int N) { return binning_layout(N, nullptr, nullptr) + 256; }
 size_t goi_raster_backward_scratch_bytes(int N, int S) { return bwd_scratch_layout(N, S, nullptr, nullptr) + 256; }
+size_t goi_raster_debug_backward_contrib_offset(int N, int S) {
+    BwdScratchView v;
+    bwd_scratch_layout(N, S, nullptr, &v);
+    return reinterpret_cast<size_t>(v.contrib);  // (laid out from base 0: the offset in a 256-byte aligned scratch)
+}
 
 int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
                        void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
@@ -727,6 +733,19 @@ int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instanc
                          const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                          float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                          float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, void* stream) {
+    return goi_raster_backward4(scene, R, scratch_instances, flags, geom_buffer, binning_buffer, image_buffer, radii, out_alpha,
+                                dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic, dL_dopacity,
+                                dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch,
+                                prev_radii, nullptr, nullptr, stream);
+}
+
+int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
+                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
+                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
+                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, const uint8_t* prev_mask,
+                         uint8_t* row_mask, void* stream) {
     refresh_options();
     if (validate(scene, true, false)) return -1;  // opacity lives in the forward's records
     const GoiRasterScene& sc = *scene;
@@ -749,6 +768,7 @@ int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instanc
     if (accumulate && (!rows_path || g_options.bwd_records != 1 || prev_radii || (sc.shs && !dL_dsh) || sc.debug))
         return fail("GOI_BACKWARD_ACCUMULATE needs the default backward (scratch given, bwd_variant 0 / 2, bwd_records 1), dL_dsh when "
                     "the colours are SH, prev_radii NULL and debug off");
+    if (accumulate && (prev_mask || row_mask)) return fail("GOI_BACKWARD_ACCUMULATE: prev_mask and row_mask must be NULL");
     if (rows_path) {
         // atomic-free path: (quadrant, Gaussian) partial rows + validity bytes, then a fixed-order sum
         BwdScratchView scr;
@@ -773,16 +793,23 @@ int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instanc
             // the per-Gaussian backward sums its Gaussians' rows itself; only the BIG Gaussians pass through reduce_big_k's records
             launch_reduce_big_only(sc, g, Rs, scr, s);
             launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                  dL_dscale, dL_drot, s, scr.rows, dL_dopacity, dL_dsemantic, prev_radii, scr.flags, Rs);
+                                  dL_dscale, dL_drot, s, scr.rows, dL_dopacity, dL_dsemantic, prev_radii, scr.flags, Rs, false, 0,
+                                  nullptr, prev_mask, row_mask);
         } else if (g_options.bwd_records) {
-            // the sums stay in the row scratch (one record per listed Gaussian); preprocess_bwd_k writes the per-id outputs
-            launch_reduce_rows(sc, g, Rs, scr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s, true);
+            // the sums stay in the row scratch (one record per listed Gaussian); preprocess_bwd_k writes the per-id outputs.
+            // bwd_skip_idle: the reduction publishes a contribution byte per listed Gaussian and stores no all-zero record;
+            // preprocess_bwd_k runs its chain only for the Gaussians that reached a pixel
+            uint8_t* contrib = g_options.bwd_skip_idle ? scr.contrib : nullptr;
+            launch_reduce_rows(sc, g, Rs, scr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s, true, contrib);
             launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                  dL_dscale, dL_drot, s, scr.rows, dL_dopacity, dL_dsemantic, prev_radii, nullptr, 0, accumulate);
+                                  dL_dscale, dL_drot, s, scr.rows, dL_dopacity, dL_dsemantic, prev_radii, nullptr, 0, accumulate, 0,
+                                  contrib, prev_mask, row_mask);
         } else {
+            // (every row is written: the previous mask is not consulted, this frame's is still produced)
             launch_reduce_rows(sc, g, Rs, scr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, s);
             launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                  dL_dscale, dL_drot, s);
+                                  dL_dscale, dL_drot, s, nullptr, nullptr, nullptr, nullptr, nullptr, 0, false, 0, nullptr, nullptr,
+                                  row_mask);
         }
     } else {
         // atomic path: the accumulated gradients start from zero
@@ -801,7 +828,8 @@ int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instanc
         if (check_stage(sc, s, "backward blend")) return -1;
         StageTimer t(GOI_STAGE_PREPROCESS_BWD, s);
         launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                              dL_dscale, dL_drot, s);
+                              dL_dscale, dL_drot, s, nullptr, nullptr, nullptr, nullptr, nullptr, 0, false, 0, nullptr, nullptr,
+                              row_mask);
     }
     if (check_stage(sc, s, "backward preprocess")) return -1;
     GOI_HIP(hipGetLastError());
@@ -1324,6 +1352,10 @@ int goi_raster_set_option(const char* name, int value) {
     else if (!strcmp(name, "bwd_records")) {
         if (value < 0 || value > 2) return fail("bwd_records must be 0, 1 or 2");
         g_options.bwd_records = value;
+    }
+    else if (!strcmp(name, "bwd_skip_idle")) {
+        if (value < 0 || value > 1) return fail("bwd_skip_idle must be 0 or 1");
+        g_options.bwd_skip_idle = value;
     }
     else if (!strcmp(name, "osh_path")) {
         if (value < 0 || value > 1) return fail("osh_path must be 0 or 1");

@@ -89,6 +89,10 @@ struct BwdScratchView {
     uint32_t* big_ctl;  // [8]: word 1 = HUGE Gaussians registered, word 2 = the other big ones (zeroed with the validity bytes)
     uint4* big_desc;    // [cap_big] (first instance, instances, -, Gaussian id): huge ones from the front, the others from the back
     size_t cap_big;
+    // [N] CONTRIBUTION bytes, indexed by a listed Gaussian's first emit-order instance (aux[g].x): 1 = the Gaussian owns at least
+    // one valid row.  Written by the record-mode row reduction for every listed Gaussian of a frame that is not truncated, read by
+    // preprocess_bwd_k, which runs its chain only for those.  The last region: the layout in front is unchanged.
+    uint8_t* contrib;
 };
 size_t bwd_scratch_layout(int N, int S, char* base, BwdScratchView* v);
 
@@ -136,7 +140,11 @@ struct Options {
                            // reduce_rows_k; 128-byte rows), 1 the per-Gaussian sums stay in the row scratch as records and
                            // preprocess_bwd_k writes every per-id output (default), 0 reduce_rows_k writes six per-id arrays
                            // (and zeros for the unlisted Gaussians) that preprocess_bwd_k reads back.  Same gradients, bit for bit.
-    int osh_path = 0;      // goi_semantic_osh_fit: 0 the register path where the shape allows it (D = 256, n_codes <= 320), 1 always
+    int bwd_skip_idle = 1; // record backward (bwd_records 1): 1 the row reduction publishes a contribution byte per listed Gaussian and
+                           // preprocess_bwd_k treats a visible Gaussian that reached no pixel like an invisible one (zeros, or nothing
+                           // where the row holds them; default), 0 every visible Gaussian goes through the chain.  Equal gradients
+                           // (the chain on a zero record could write -0.0 where the zero path writes +0.0).
+    int osh_path = 0;     // goi_semantic_osh_fit: 0 the register path where the shape allows it (D = 256, n_codes <= 320), 1 always
                            // the generic path (z re-formed from the LUT every epoch).  Same results, bit for bit.
 };
 // The switches an entry point works with are a per-THREAD snapshot taken when the call starts (refresh_options):
@@ -238,7 +246,8 @@ void launch_reduce_sem_rows(const GoiRasterScene& sc, const GeomView& g, int N, 
 // into one record per listed Gaussian, left in the row scratch over the Gaussian's first slot (the arrays may be NULL then)
 void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, float* dL_dmean2D,
                         float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, float* dL_ddepth,
-                        hipStream_t s, bool records = false);
+                        hipStream_t s, bool records = false,
+                        uint8_t* contrib = nullptr);  // (records only) BwdScratchView::contrib, or NULL: every record is stored, no byte
 void launch_render_bwd_tile(const GoiRasterScene& sc, const GeomView& g, const ImageView& im,
                             const uint32_t* point_list, const float* out_alpha, const float* dL_dpix,
                             const float* dL_dsem, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmean2D,
@@ -255,7 +264,9 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
                            const int* prev_radii = nullptr,  // prev_radii: BwdArgs (rows that already hold zeros)
                            const uint8_t* row_flags = nullptr, int N_cap = 0,  // row_flags: the kernel sums the rows itself (bwd_records 2)
                            bool accumulate = false,  // add to the outputs instead of writing them (record path only: BwdArgs::accumulate)
-                           int max_blocks = 0);  // > 0: cap on the persistent grid (the test entry; the product passes 0: its own choice)
+                           int max_blocks = 0,  // > 0: cap on the persistent grid (the test entry; the product passes 0: its own choice)
+                           const uint8_t* contrib = nullptr,  // (records only) BwdScratchView::contrib: idle visible Gaussians skip the chain
+                           const uint8_t* prev_mask = nullptr, uint8_t* row_mask = nullptr);  // BwdArgs (may be the same array)
 int launch_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
                            const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
                            hipStream_t s);

@@ -388,6 +388,14 @@ struct BwdArgs {
     // was invisible then and is invisible now already has zeros in every output row -- nothing is written for it (half of the
     // headline scene: 170 MB of zeros per step).  goi_raster_backward2, csrc/torch_binding.cpp: the gradient-buffer pool.
     const int* prev_radii;
+    // The same knowledge per ROW, which can also say "visible then, but the chain did not run" (an IDLE Gaussian, see RecArgs::contrib):
+    // prev_mask[id] == 0 -- the backward that last wrote these buffers left zeros in the row (and nothing has touched it since);
+    // it takes precedence over prev_radii.  row_mask (or NULL): this kernel writes 1 for every id whose row the chain wrote and 0
+    // for every other id < P, whatever it did about that row (zeros, or nothing where they were there already).  The two may be
+    // the SAME array: a thread reads the byte of an id before it writes it, and no other thread touches that byte.
+    // goi_raster_backward4; csrc/torch_binding.cpp keeps the mask with the pooled allocation.
+    const uint8_t* prev_mask;
+    uint8_t* row_mask;
     // ACCUMULATE (goi_raster_backward3, flags bit 0; the record path only): the outputs already hold the gradients of earlier
     // views of the same batch -- a visible Gaussian's rows are read, added to and written back, an invisible one's are left
     // alone.  The sum of K views then costs each view its visible rows once more instead of a dense [P, 75 + S] addition
@@ -414,6 +422,9 @@ struct RecArgs {
     const uint8_t* flags;           // validity bytes of the row slots
     const uint32_t* n_dev;          // the frame's counters from COUNTER_N on (instances, listed Gaussians: the BIG threshold)
     uint32_t N_cap;                 // slot capacity the scratch was laid out for
+    // SRC == 1, or NULL: the CONTRIBUTION bytes of the row reduction (reduce_rows.hip), contrib[aux[id].x] == 0 -- the listed Gaussian
+    // owns no valid row: its record is all +0 (and was not stored).  Such a Gaussian, and a visible one without tiles, is IDLE.
+    const uint8_t* contrib;
 };
 // Rows of the dL/dSH staging tile = visible Gaussians a workgroup takes through the chain at a time: 224 x (3 M + 1) floats =
 // 43.9 KB at M = 16, three workgroups per CU with the index lists (the kernel's 143 VGPRs allow three as well).
@@ -468,6 +479,12 @@ __global__ __launch_bounds__(256, GOI_PBWD_BLOCKS) void preprocess_bwd_k(const B
     // gradients, whichever block and lane a Gaussian lands on.
     // dL/dSH (192 B per Gaussian at degree 3) still leaves through an LDS tile (odd row stride: no bank conflicts) as
     // contiguous rows instead of 48 stores at a 192-byte lane stride.
+    // IDLE Gaussians (SRC == 1 with RecArgs::contrib): visible, but no pixel took anything from it -- it is listed and owns no valid
+    // row (contribution byte 0), or it has no tiles at all.  Its record is zero and so is everything the chain would form from it
+    // (69 % of the visible Gaussians of the headline view): the classification puts it with the INVISIBLE ids -- zeros where the
+    // row does not hold them already, otherwise nothing; nothing at all when accumulating; no SH row, no chain, no tile row.
+    // What the classification needs -- radii, tiles_touched, aux.x, the previous mask, all by id -- is requested for the NEXT
+    // segment while this one is worked on, and the contribution byte (through aux.x) first thing in its own trip.
     constexpr bool FROM_ROWS = SRC != 0;
     constexpr int BWD_TILE_ROWS = SRC == 2 ? BWD_TILE_ROWS_FUSED : BWD_TILE_ROWS_DEFAULT;
     extern __shared__ float s_dsh[];  // [BWD_TILE_ROWS][3 M + 1] when dL_dsh
@@ -488,18 +505,45 @@ __global__ __launch_bounds__(256, GOI_PBWD_BLOCKS) void preprocess_bwd_k(const B
     const int nseg = (args.P + 255) / 256;
     const bool truncated = counters[COUNTER_OVF] != 0;  // (a truncated frame is treated as if nothing were visible: all gradients zero)
     int npend = 0;  // (block-uniform)
+    const bool skip_idle = SRC == 1 && ra.contrib != nullptr;
+    struct SegIn {
+        int rad;           // radii[id]
+        uint32_t tt, ax;   // (skip_idle) tiles_touched[id], aux[id].x
+        uint32_t prev;     // 0: the row already holds zeros
+    };
+    auto load_seg = [&](int sg) {
+        SegIn v{0, 0u, 0u, 1u};
+        const int id = sg * 256 + (int)threadIdx.x;
+        if (sg < nseg && id < args.P) {
+            v.rad = radii[id];
+            if (skip_idle) {
+                v.tt = ra.tiles_touched[id];
+                v.ax = ra.aux[id].x;
+            }
+            if (args.prev_mask != nullptr) v.prev = args.prev_mask[id];
+            else if (args.prev_radii != nullptr) v.prev = args.prev_radii[id] != 0 ? 1u : 0u;
+        }
+        return v;
+    };
+    SegIn cur = load_seg(blockIdx.x);
     for (int seg = blockIdx.x; seg < nseg || npend > 0; seg += gridDim.x) {
     int nzero = 0;
     const int base = seg * 256;
+    // the contribution byte of a listed visible Gaussian (aux.x of any other id is not an instance), then the next segment's inputs
+    const bool vis_t = cur.rad > 0 && !truncated;  // (rad == 0 beyond P and beyond the last segment)
+    const bool listed_t = skip_idle && vis_t && cur.tt != 0u;
+    const uint8_t contrib_t = listed_t ? ra.contrib[cur.ax] : (uint8_t)0;
+    const SegIn nxt = load_seg(seg + (int)gridDim.x);
     if (seg < nseg) {
         const int gtid = base + threadIdx.x;
         const bool live = gtid < args.P;
-        const bool vis_t = live && radii[gtid] > 0 && !truncated;
-        // rows that already hold zeros (see BwdArgs::prev_radii) are not written again
-        const bool keep_t = live && !vis_t && args.prev_radii != nullptr && args.prev_radii[gtid] == 0;
-        const bool zero_t = live && !vis_t && !keep_t && !args.accumulate;
+        const bool work_t = skip_idle ? contrib_t != 0 : vis_t;  // the chain runs for it
+        // rows that already hold zeros (see BwdArgs::prev_radii, prev_mask) are not written again
+        const bool keep_t = live && !work_t && cur.prev == 0u;
+        const bool zero_t = live && !work_t && !keep_t && !args.accumulate;
+        if (args.row_mask != nullptr && live) args.row_mask[gtid] = work_t ? (uint8_t)1 : (uint8_t)0;
         const int wv = threadIdx.x >> 6;
-        const unsigned long long bv = __ballot(vis_t), bz = __ballot(zero_t);
+        const unsigned long long bv = __ballot(work_t), bz = __ballot(zero_t);
         if ((threadIdx.x & 63) == 0) {
             s_wcnt[0][wv] = __popcll(bv);
             s_wcnt[1][wv] = __popcll(bz);
@@ -513,7 +557,7 @@ __global__ __launch_bounds__(256, GOI_PBWD_BLOCKS) void preprocess_bwd_k(const B
         const int nv = s_wcnt[0][0] + s_wcnt[0][1] + s_wcnt[0][2] + s_wcnt[0][3];
         nzero = s_wcnt[1][0] + s_wcnt[1][1] + s_wcnt[1][2] + s_wcnt[1][3];
         const unsigned long long lt = (1ull << (threadIdx.x & 63)) - 1ull;
-        if (vis_t) s_vis[npend + ov + __popcll(bv & lt)] = (uint32_t)gtid;
+        if (work_t) s_vis[npend + ov + __popcll(bv & lt)] = (uint32_t)gtid;
         if (zero_t) s_zero[oz + __popcll(bz & lt)] = (uint16_t)threadIdx.x;
         npend += nv;
         __syncthreads();
@@ -1006,6 +1050,7 @@ __global__ __launch_bounds__(256, GOI_PBWD_BLOCKS) void preprocess_bwd_k(const B
     npend = rest;
     __syncthreads();
     }  // chunks of pending visible Gaussians
+    cur = nxt;
     }  // segments
 }
 
@@ -1118,9 +1163,12 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
                            const float* dL_dconic, float* dL_dcolor, const float* dL_ddepth, float* dL_dmean3D,
                            float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, hipStream_t s,
                            const float* record_rows, float* dL_dopacity, float* dL_dsemantic, const int* prev_radii,
-                           const uint8_t* row_flags, int N_cap, bool accumulate, int max_blocks) {
+                           const uint8_t* row_flags, int N_cap, bool accumulate, int max_blocks, const uint8_t* contrib,
+                           const uint8_t* prev_mask, uint8_t* row_mask) {
     BwdArgs a;
     a.prev_radii = prev_radii;
+    a.prev_mask = prev_mask;
+    a.row_mask = row_mask;
     a.accumulate = accumulate ? 1 : 0;
     a.P = sc.P; a.D = sc.D; a.M = sc.M; a.W = sc.W; a.H = sc.H;
     a.means3D = sc.means3D; a.shs = sc.shs; a.scales = sc.scales; a.rotations = sc.rotations;
@@ -1140,6 +1188,7 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
     ra.row_floats = bwd_row_floats(sc.S); ra.S = sc.S; ra.nch = 4 * ((sc.S + 3) / 4) + 4;
     ra.dL_dopacity = dL_dopacity; ra.dL_dsemantic = dL_dsemantic;
     ra.flags = row_flags; ra.n_dev = g.counters + COUNTER_N; ra.N_cap = (uint32_t)std::max(N_cap, 0);
+    ra.contrib = (record_rows != nullptr && !fused) ? contrib : nullptr;
     // persistent workgroups: every CU gets as many as fit (registers and the staging tile: BWD_BLOCKS_PER_CU), each walks
     // segments of 256 ids
     static const int n_cu = []() {

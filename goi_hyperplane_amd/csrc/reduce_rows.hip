@@ -32,6 +32,13 @@ namespace {
 // preprocess_bwd_k, which runs over the ids anyway, fetches the line through goff[] and writes every per-id output itself,
 // coalesced.  Measured on the headline view before it was built (timing builds): the zero phase 21 us, the scattered
 // stores 40 us of the kernel's 213; a dense 128-byte store instead 8 us.
+// CONTRIBUTION BYTES (`contrib`, optional; RECORD only).  Two thirds of the listed Gaussians of a scene with depth complexity sit
+// behind the saturation front in every tile they touch: they own slots but no valid row, their record is all +0 and every
+// gradient the per-Gaussian backward forms from it is zero.  The quarter wave has every validity word of its Gaussian in hand
+// anyway: it publishes contrib[first instance] = "owns at least one valid row" for EVERY listed Gaussian it (or reduce_big_k)
+// sums -- the region arrives uninitialised -- and does not store the all-zero record of one that owns none.  preprocess_bwd_k
+// reads the byte through aux[g].x and treats such a Gaussian like an invisible one.  contrib == NULL: every record is stored and
+// nothing is published, as before (the debug hooks; bwd_skip_idle 0).
 
 // BIG Gaussians.  A quarter wave sums ITS Gaussian's rows one trip after the other; a frame-filling blob or a long needle
 // of a reconstructed scene owns thousands of slots and ten thousand rows (clustered workload: 20 blobs x 6600 tiles, needles
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(256) void reduce_rows_k(int P, int S, int nch, uint
                                                      const uint32_t* __restrict__ tiles_touched,
                                                      float* rows, const uint8_t* __restrict__ flags, ReduceOut out,
                                                      uint32_t* __restrict__ big_ctl, uint4* __restrict__ big_desc,
-                                                     uint32_t cap_big) {
+                                                     uint32_t cap_big, uint8_t* __restrict__ contrib) {
     // N_cap: the slot capacity the scratch was laid out for; n_dev: the forward's instance count on the device (the
     // exact forward passes N_cap = num_rendered; the speculative one a capacity, and an overflowed frame stored only
     // the first N_cap instances)
@@ -192,8 +199,15 @@ __global__ __launch_bounds__(256) void reduce_rows_k(int P, int S, int nch, uint
         float sum[K];
 #pragma unroll
         for (int kk = 0; kk < K; kk++) sum[kk] = 0.f;
-        sum_instances<K, false, INFLIGHT>(rows, flags32, inst0, cnt, w_cur, quarter, e, sum, sum);  // (comp unused)
-        if (live && !big && (!RECORD || cnt > 0)) store_sums<K, RECORD>(sum, rows, inst0, cur.g, e, S, nch, out);
+        const bool any = sum_instances<K, false, INFLIGHT>(rows, flags32, inst0, cnt, w_cur, quarter, e, sum, sum);  // (comp unused)
+        if constexpr (RECORD) {
+            if (live && !big && cnt > 0) {  // (inst0 < off1 <= N: inside the region)
+                if (contrib && e == 0) contrib[inst0] = any ? (uint8_t)1 : (uint8_t)0;
+                if (any || !contrib) store_sums<K, RECORD>(sum, rows, inst0, cur.g, e, S, nch, out);
+            }
+        } else {
+            if (live && !big) store_sums<K, RECORD>(sum, rows, inst0, cur.g, e, S, nch, out);
+        }
         cur = nxt;
         nxt = nn;
         w_cur = w_nxt;
@@ -232,9 +246,11 @@ constexpr int BIG_PARTS = 64, MID_PARTS = 16;
 template <int K, bool RECORD>
 __global__ __launch_bounds__(16 * BIG_PARTS) void reduce_big_k(const uint32_t* __restrict__ big_ctl,
                                                               const uint4* __restrict__ big_desc, uint32_t cap_big, float* rows,
-                                                              const uint8_t* __restrict__ flags, int S, int nch, ReduceOut out) {
+                                                              const uint8_t* __restrict__ flags, int S, int nch, ReduceOut out,
+                                                              uint8_t* __restrict__ contrib) {
     constexpr int RF = 16 * K;
     __shared__ float s_part[BIG_PARTS][RF];
+    __shared__ uint8_t s_any[BIG_PARTS];  // part p found a valid row (the Gaussian's contribution byte is their OR)
     const int lane = threadIdx.x & 63, quarter = lane >> 4, e = lane & 15, part = threadIdx.x >> 4;
     const uint32_t* flags32 = reinterpret_cast<const uint32_t*>(flags);
     // PARTS quarter waves starting at quarter wave `first` sum the Gaussian of descriptor d (active: the group has one)
@@ -249,9 +265,10 @@ __global__ __launch_bounds__(16 * BIG_PARTS) void reduce_big_k(const uint32_t* _
         float sum[K], comp[K];
 #pragma unroll
         for (int kk = 0; kk < K; kk++) sum[kk] = comp[kk] = 0.f;
-        sum_instances<K, true>(rows, flags32, inst0, cnt, w0, quarter, e, sum, comp);
+        const bool any = sum_instances<K, true>(rows, flags32, inst0, cnt, w0, quarter, e, sum, comp);
 #pragma unroll
         for (int kk = 0; kk < K; kk++) s_part[part][K == 2 ? 2 * e + kk : e + 16 * kk] = sum[kk];
+        if (e == 0) s_any[part] = any ? (uint8_t)1 : (uint8_t)0;
         __syncthreads();
         if (p == 0 && active) {
             float tot[K], c[K];
@@ -266,6 +283,13 @@ __global__ __launch_bounds__(16 * BIG_PARTS) void reduce_big_k(const uint32_t* _
                     tot[kk] = t;
                 }
             store_sums<K, RECORD>(tot, rows, (size_t)d.x, d.w, e, S, nch, out);
+            if constexpr (RECORD) {
+                if (contrib && e == 0) {  // the true value (a big Gaussian's record is stored either way)
+                    uint8_t a = 0;
+                    for (int pp = 0; pp < parts; pp++) a |= s_any[first + pp];
+                    contrib[d.x] = a;
+                }
+            }
         }
         __syncthreads();
     };
@@ -299,33 +323,33 @@ constexpr size_t REDUCE_BIG_GRID = GOI_REDUCE_BIG_GRID;
 constexpr int REDUCE_LARGE_SCENE = GOI_REDUCE_LARGE_SCENE;  // Gaussians from which reduce_rows_k keeps 16 instead of 32 rows in flight
 template <int K, bool RECORD>
 static void launch_reduce_k(const GoiRasterScene& sc, const GeomView& g, int N, int nch, float* rows, const uint8_t* flags,
-                            const BwdScratchView& scr, const ReduceOut& out, hipStream_t s) {
+                            const BwdScratchView& scr, const ReduceOut& out, hipStream_t s, uint8_t* contrib = nullptr) {
     const dim3 grid((sc.P + 16 * REDUCE_GPQ - 1) / (16 * REDUCE_GPQ));
     const uint32_t* order = g.sort_vals[depth_sort_result_index()];
     if (sc.P >= REDUCE_LARGE_SCENE && GOI_REDUCE_INFLIGHT > 16)  // (one Gaussian per quarter wave there as well: 3 M 250 -> 227 us, 6 M 420 -> 377)
         reduce_rows_k<K, 1, RECORD, 16><<<dim3((sc.P + 15) / 16), dim3(256), 0, s>>>(sc.P, sc.S, nch, (uint32_t)N, g.counters + COUNTER_N,
                                                                                     order, g.offsets, g.tiles_touched, rows, flags, out,
-                                                                                    scr.big_ctl, scr.big_desc, (uint32_t)scr.cap_big);
+                                                                                    scr.big_ctl, scr.big_desc, (uint32_t)scr.cap_big, contrib);
     else
         reduce_rows_k<K, REDUCE_GPQ, RECORD><<<grid, dim3(256), 0, s>>>(sc.P, sc.S, nch, (uint32_t)N, g.counters + COUNTER_N, order,
                                                                         g.offsets, g.tiles_touched, rows, flags, out, scr.big_ctl,
-                                                                        scr.big_desc, (uint32_t)scr.cap_big);
+                                                                        scr.big_desc, (uint32_t)scr.cap_big, contrib);
     // the big Gaussians: fixed, small grids of persistent workgroups (their numbers are on the device; N == 0: no blend ran,
     // nothing cleared the counters and nothing can be registered)
     if (N > 0)
         reduce_big_k<K, RECORD><<<dim3((unsigned)std::min<size_t>(REDUCE_BIG_GRID, scr.cap_big)), dim3(16 * BIG_PARTS), 0, s>>>(
-            scr.big_ctl, scr.big_desc, (uint32_t)scr.cap_big, rows, flags, sc.S, nch, out);
+            scr.big_ctl, scr.big_desc, (uint32_t)scr.cap_big, rows, flags, sc.S, nch, out, contrib);
 }
 
 // records: the sums stay in the row scratch as per-Gaussian records (see reduce_rows_k); the six arrays are not written
 void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, float* dL_dmean2D,
                         float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, float* dL_ddepth,
-                        hipStream_t s, bool records) {
+                        hipStream_t s, bool records, uint8_t* contrib) {
     const int rf = bwd_row_floats(sc.S), nch = 4 * ((sc.S + 3) / 4) + 4;
     const ReduceOut out{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth};
 #define GOI_REDUCE(K)                                                                   \
     do {                                                                                \
-        if (records) launch_reduce_k<K, true>(sc, g, N, nch, scr.rows, scr.flags, scr, out, s);  \
+        if (records) launch_reduce_k<K, true>(sc, g, N, nch, scr.rows, scr.flags, scr, out, s, contrib);  \
         else launch_reduce_k<K, false>(sc, g, N, nch, scr.rows, scr.flags, scr, out, s);         \
     } while (0)
     if (rf == 32) GOI_REDUCE(2);
@@ -344,7 +368,7 @@ void launch_reduce_big_only(const GoiRasterScene& sc, const GeomView& g, int N, 
     find_big_k<<<dim3((sc.P + 255) / 256), dim3(256), 0, s>>>((uint32_t)N, g.counters + COUNTER_N, order, g.offsets, scr.big_ctl,
                                                              scr.big_desc, (uint32_t)scr.cap_big);
     reduce_big_k<2, true><<<dim3((unsigned)std::min<size_t>(REDUCE_BIG_GRID, scr.cap_big)), dim3(16 * BIG_PARTS), 0, s>>>(
-        scr.big_ctl, scr.big_desc, (uint32_t)scr.cap_big, scr.rows, scr.flags, sc.S, nch, out);
+        scr.big_ctl, scr.big_desc, (uint32_t)scr.cap_big, scr.rows, scr.flags, sc.S, nch, out, nullptr);
 }
 
 void launch_reduce_sem_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, int row_floats,

@@ -19,8 +19,9 @@ namespace goi {
 // how the rows are split over quarter waves (one component of one needle's dL/dscale moved by 2e-3 of the tensor's scale
 // between a 16- and a 64-part split: clustered workload, tools/diag_blown.py); the compensated sum is good to an ulp or two of
 // the result whatever the split.  Four additions instead of one, on the few hundred Gaussians that take this path.
+// Returns whether ANY of the quarter wave's instances had a valid row (uniform over the quarter wave: the contribution byte).
 template <int K, bool COMPENSATED = false, int INFLIGHT = GOI_REDUCE_INFLIGHT>
-__device__ __forceinline__ void sum_instances(const float* __restrict__ rows, const uint32_t* __restrict__ flags32,
+__device__ __forceinline__ bool sum_instances(const float* __restrict__ rows, const uint32_t* __restrict__ flags32,
                                               size_t inst0, uint32_t cnt, uint32_t w_first, int quarter, int e,
                                               float (&sum)[K], float (&comp)[K]) {
     constexpr int RF = 16 * K;
@@ -32,6 +33,7 @@ __device__ __forceinline__ void sum_instances(const float* __restrict__ rows, co
     // The instances are looked at 64 at a time: four validity words per lane, requested together (and the next 64 under this
     // block's rows), and a 16-instance chunk in which no quarter of the wave has a row is skipped on one ballot.
     uint32_t wq[4] = {w_first, 0u, 0u, 0u};
+    bool any = false;
     if (cmax > 16) {
 #pragma unroll
         for (int sblk = 1; sblk < 4; sblk++) wq[sblk] = load_flags(16u * sblk);
@@ -57,6 +59,7 @@ __device__ __forceinline__ void sum_instances(const float* __restrict__ rows, co
                 const unsigned long long bal = __ballot(((w >> (8 * q)) & 0xFFu) != 0);
                 m |= ((bal >> (16 * quarter)) & 0xFFFFull) << (16 * q);
             }
+            any |= m != 0;
             const float* chunk = rows + (inst0 + cc) * 4 * RF;
             // NF rows requested back to back, then added in mask order, bit 16q + i lowest first: quadrant-major (absent
             // slots add +0: the sums do not depend on NF).  Most Gaussians own a handful of rows -- 6 on average, half of
@@ -115,6 +118,7 @@ __device__ __forceinline__ void sum_instances(const float* __restrict__ rows, co
 #pragma unroll
         for (int sblk = 0; sblk < 4; sblk++) wq[sblk] = wn[sblk];
     }
+    return any;
 }
 
 }  // namespace goi

@@ -227,18 +227,20 @@ void* backward_scratch(size_t bytes, const c10::Device& dev, void* stream, const
     return it->second.data_ptr();
 }
 
-// ---- gradient-buffer pool (goi_raster_backward2: rows that already hold zeros are not written again) -------------------------
+// ---- gradient-buffer pool (goi_raster_backward4: rows that already hold zeros are not written again) -------------------------
 // The reference hands autograd eleven freshly zero-filled [P, ..] tensors per backward (rasterize_points.cu:252-262); on the
 // headline scene half of the Gaussians are invisible in any one view: 170 MB of zeros per step.  The binding keeps the ONE
-// allocation all outputs of a backward are views of, together with that frame's radii, and hands it out again once (a) nobody
+// allocation all outputs of a backward are views of, together with a byte per Gaussian the kernel writes (1: the chain of that
+// backward wrote the Gaussian's rows, 0: they hold zeros -- the Gaussian was invisible, or visible and reached no pixel, which the
+// frame's radii could not say), and hands it out again once (a) nobody
 // else holds it any more (the storage's reference count is back to the pool's own) and (b) nothing has written to it in place
 // (the version counter its views share is where the backward left it: an in-place collective, a gradient clip, zero_() all
-// bump it -- such a buffer is reused as if it were fresh).  The kernel then skips the rows of Gaussians that were invisible
-// then and are invisible now.  Keyed by device, stream and layout; a few buffers per key (a loop that keeps the gradients of
+// bump it -- such a buffer is reused as if it were fresh: the mask is not consulted, only rewritten).  The kernel then skips the
+// rows whose byte is 0 and that get zeros again, and updates the mask in place.  Keyed by device, stream and layout; a few buffers per key (a loop that keeps the gradients of
 // step k alive while step k + 1 runs alternates between two).  GOI_GRAD_POOL=0 / set_grad_pool(false) turns it off.
 struct PoolEntry {
     Tensor all;         // every output of one backward is a view of this
-    Tensor prev_radii;  // radii of the backward that last wrote it
+    Tensor mask;        // [P] bytes, written by the backward that last wrote it: 1 = the chain wrote that Gaussian's rows
     int64_t version;    // version counter of `all` when that backward returned
 };
 struct PoolKey {
@@ -316,7 +318,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     }
     void* stream = stream_of(dev);
     // a pooled buffer nobody else holds any more (see the pool's comment), or a fresh one
-    Tensor flat, prev_radii;
+    Tensor flat, mask;
+    bool mask_valid = false;  // the mask describes what `flat` holds
     const PoolKey key{(int)dev.index(), stream, total, P, sh_factored ? -M : M, S};
     const bool accumulate = accumulate_into.has_value() && accumulate_into->defined() && P != 0;
     if (accumulate) {
@@ -336,8 +339,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
             for (size_t i = 0; i < v.size(); i++) {
                 if (v[i].all.storage().use_count() != 1 || v[i].all.use_count() != 1) continue;  // still somebody's gradient
                 flat = v[i].all;
+                mask = v[i].mask;  // (rewritten by this backward either way)
                 if ((int64_t)flat._version() == v[i].version) {
-                    prev_radii = v[i].prev_radii;
+                    mask_valid = true;
                     g_pool_hits++;
                 } else {
                     g_pool_dirty++;  // written to in place since: every row is written again
@@ -375,22 +379,25 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
                                      pm, cp, tan_fovx, tan_fovy, false, debug);
         void* scratch = backward_scratch(goi_raster_backward_scratch_bytes(scratch_instances > 0 ? scratch_instances : R, S), dev,
                                          stream, means3D.options().dtype(torch::kByte));
-        const int r = goi_raster_backward3(
+        // the mask travels with the buffer it describes; read (a clean pooled buffer) and rewritten in place
+        const bool pooled = g_pool_on && !debug && !accumulate;
+        if (pooled && !mask.defined()) mask = torch::empty({(long long)P}, means3D.options().dtype(torch::kByte));
+        const int r = goi_raster_backward4(
             &sc, R, scratch_instances, accumulate ? GOI_BACKWARD_ACCUMULATE : 0, geomBuffer.data_ptr(), binningBuffer.numel() ? binningBuffer.data_ptr() : nullptr,
             imageBuffer.data_ptr(), rad.data_ptr<int>(), al.p, gc.p, gs.p, gd.p, ga.p, dL_dmeans2D.data_ptr<float>(),
             dL_dconic.data_ptr<float>(), dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
             dL_dsemantics.data_ptr<float>(), dL_ddepths.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
             dL_dcov3D.data_ptr<float>(), dL_dsh.defined() && dL_dsh.numel() ? dL_dsh.data_ptr<float>() : nullptr,
             dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(), scratch,
-            prev_radii.defined() ? prev_radii.data_ptr<int>() : nullptr, stream);
+            nullptr, pooled && mask_valid ? mask.data_ptr<uint8_t>() : nullptr, pooled ? mask.data_ptr<uint8_t>() : nullptr, stream);
         if (r < 0) raise_last();
-        // the buffer goes (back) into the pool with this frame's radii; it is handed out again only when every view the
+        // the buffer goes (back) into the pool with this frame's mask; it is handed out again only when every view the
         // caller got has been released and nothing has written to it in place
         std::lock_guard<std::mutex> lk(g_pool_mu);
-        if (g_pool_on && !debug && !accumulate) {  // (an accumulated buffer is the caller's: its zero rows are no longer this frame's)
+        if (pooled && g_pool_on) {  // (an accumulated buffer is the caller's: its zero rows are no longer this frame's)
             auto& v = g_pool[key];
             if (v.size() >= POOL_BUFFERS_PER_KEY) v.erase(v.begin());
-            v.push_back(PoolEntry{flat, rad, (int64_t)flat._version()});
+            v.push_back(PoolEntry{flat, mask, (int64_t)flat._version()});
         }
     }
     flat = Tensor();  // (the pool's reference is the only one besides the views returned below)

@@ -49,7 +49,10 @@
 extern "C" {
 #endif
 
-/* 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
+/* 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
+ *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
+ *    goi_raster_backward_scratch_bytes as ever)
+ * 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
  *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan,
  *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion,
  *    goi_raster_debug_sort_workspace_bytes, goi_raster_debug_sort_pairs, goi_raster_debug_scan_workspace_bytes,
@@ -62,7 +65,7 @@ extern "C" {
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
  * (3: + goi_raster_forward_reblend, goi_codebook_sim, goi_codebook_fused; 2: + the asynchronous forward; additions only) */
-#define GOI_RASTER_ABI_VERSION 6
+#define GOI_RASTER_ABI_VERSION 7
 
 typedef struct GoiRasterScene {
     int P;                       /* number of Gaussians */
@@ -249,6 +252,33 @@ int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instanc
                          const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                          float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                          float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, void* stream);
+
+/* goi_raster_backward3 with a per-ROW record of what a backward left in the eleven output arrays (ABI 7).  On the default path
+ * (row records, option bwd_skip_idle 1) the per-Gaussian chain runs only for a Gaussian that reached a pixel: the row reduction
+ * publishes one CONTRIBUTION byte per listed Gaussian ("owns at least one valid row") in the scratch, and a visible Gaussian whose
+ * byte is 0 -- it sits behind the saturation front in every tile it touches -- or that has no tiles is handled like an invisible
+ * one: its rows get zeros.  On a scene with depth complexity that is two thirds of the visible Gaussians.  "The row already holds
+ * zeros" can then no longer be told from a radii array, so:
+ *   row_mask  [P] bytes, written (or NULL): 1 -- this call's chain wrote the row of that Gaussian, 0 -- the row holds zeros now;
+ *   prev_mask [P] bytes, read (or NULL): the row_mask of the backward that LAST WROTE these very output buffers, nothing else
+ *             having written to them since: a row with prev_mask 0 that gets zeros again is not written.  Takes precedence over
+ *             prev_radii, which keeps its meaning.  prev_mask and row_mask may be the same array.
+ * Both NULL: goi_raster_backward3.  With GOI_BACKWARD_ACCUMULATE both must be NULL (an idle Gaussian then costs nothing at all).
+ * The gradients are those of bwd_skip_idle 0 under IEEE equality: the chain on an all-zero record could write -0.0 where the zero
+ * path writes +0.0; the blend-gradient arrays are bit-identical.  csrc/torch_binding.cpp keeps the mask with its pooled buffer. */
+int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
+                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
+                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
+                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, const uint8_t* prev_mask,
+                         uint8_t* row_mask, void* stream);
+
+/* Tests only: byte offset, in a 256-byte aligned scratch of goi_raster_backward_scratch_bytes(num_rendered, S), of the contribution
+ * bytes the default backward leaves there: [num_rendered] bytes indexed by a listed Gaussian's first emit-order instance (word 0 of
+ * its aux entry), 1 = the Gaussian owns at least one valid row.  Written for every listed Gaussian of a frame that is not truncated;
+ * every other byte keeps what the caller left there. */
+size_t goi_raster_debug_backward_contrib_offset(int num_rendered, int S);
 
 /* Feature-gradient-only backward: dL/dsemantics [P,S] from dL/d(semantic map) alone, bit-identical to
  * the dL_dsemantic of goi_raster_backward and about 3x cheaper.  For the reference's default training
@@ -467,6 +497,9 @@ int goi_raster_profile_collect(double* ms, int* calls);
  *                  arrays (dL_dconic, dL_ddepth, ... and zeros for the Gaussians that are not listed); same gradients, bit for bit;
  *                  2 EXPERIMENT (128-byte rows: S = 5 .. 20): the per-Gaussian pass sums its Gaussians' rows itself -- no record,
  *                  no reduce_rows_k; bit-identical, measured slower
+ *   "bwd_skip_idle" (bwd_records 1) 1 (default) a visible Gaussian that reached no pixel -- no valid row in any tile it touches, or
+ *                  no tiles -- skips the per-Gaussian chain and its rows get zeros (goi_raster_backward4); 0 every visible
+ *                  Gaussian goes through the chain.  Equal gradients (zeros may differ in sign)
  *   "osh_path"     goi_semantic_osh_fit: 0 (default) z in registers where the shape allows it (D = 256, n_codes <= 320),
  *                  1 always the generic path (z re-formed from the LUT every epoch); bit-identical (285 -> 437 us on the headline view: DESIGN.md 9.3)
  * Thread safety: the set is changed under a mutex; an entry point snapshots it when it starts. */
