@@ -45,6 +45,7 @@ UNITS = {
     "codebook_init.hip": [],
     "photometric.hip": [],
     "densify.hip": ["-ffp-contract=off"],  # the reference's elementwise torch ops, one rounding each
+    "display.hip": ["-ffp-contract=off"],  # the viewer's blend a*b + c*d is compared bit for bit: no FMA
 }
 
 

@@ -303,6 +303,9 @@ void launch_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, 
 void launch_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
                         hipStream_t s);
 void launch_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, hipStream_t s);
+void launch_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, long long HW,
+                          int style, int normalize, float ratio, float one_minus_ratio, float heat_thresh, const float* table,
+                          int n_colors, void* out, int out_dtype, uint32_t* stats, hipStream_t s);
 size_t uniq_workspace_bytes(int V, int D, uint32_t HW);
 uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW);  // [V] counts, then the flag word
 void launch_uniq_dedup(const float* const* maps, int V, int D, uint32_t HW, void* ws, hipStream_t s);

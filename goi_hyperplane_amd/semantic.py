@@ -11,6 +11,7 @@ checkpoints load unchanged:
     group_points             gui/main.py:1595-1665           (DBSCAN refinement of the selection: cluster.py)
     relevant_cameras         gui/main.py:407-478             (relevant-camera precompute: masks.py on the device)
     evaluate_cameras         gui/main.py:1957-2016           (eval_epoch's IoU / mPA / mP, utils/image_utils.py:59-102)
+    view_frame, video_frames gui/main.py:549-604, 1766-1801  (the displayed frame: display.py on the device)
     compute_similarity       gui/main.py:364-386             (inference decode)
     codebook_losses          train.py:142-163                (training losses)
 
@@ -693,6 +694,110 @@ def evaluate_cameras(cameras, gt_masks: torch.Tensor, pc, mlp: SemanticModel, lu
         total_mpa = total_mpa + m.mpa[v]
         total_mp = total_mp + m.mp[v]
     return SegEvaluation(m.iou, m.mpa, m.mp, total_iou / V, float(total_mpa / V), float(total_mp / V))
+
+
+# ---- the viewer's frame (gui/main.py:549-604 test_step, :387-398 set_clip_mask, :1766-1801 render_video) -----------------
+FRAME_MODES = ("image", "depth", "alpha")
+
+
+class _FrameDecoder:
+    """The fused decode with everything that does not depend on the view prepared once (weights, bias, the per-code score
+    table): decode(sem_chw, sim_out, mask_out) writes one view's similarity (background zeroed) and its uint8 background
+    mask into the caller's buffers.  One launch per view."""
+
+    def __init__(self, mlp, lut, score_fn, thresh, dev):
+        if mlp.num_layer != 1:
+            raise NotImplementedError("the fused decode covers the reference's configuration: one Linear(S -> tab_len)")
+        lin = mlp.layers[0]
+        self.n_codes, self.S = int(lin.weight.shape[0]), int(lin.weight.shape[1])
+        if lut.shape[0] != self.n_codes:
+            raise ValueError("shape mismatch between features, MLP and LUT")
+        self.w = lin.weight.detach().contiguous().float()
+        self.b = (lin.bias.detach() if lin.bias is not None else torch.zeros(self.n_codes, device=dev)).contiguous().float()
+        self.table = code_scores(lut, score_fn).to(dev)
+        self.thresh = float(thresh)
+
+    def decode(self, sem_chw, sim_out, mask_out):
+        if int(sem_chw.shape[0]) != self.S:
+            raise ValueError("shape mismatch between features, MLP and LUT")
+        sem = sem_chw.contiguous().float()
+        HW = int(sem[0].numel())
+        dev = sem.device
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        with torch.cuda.device(dev):
+            r = _lib.load().goi_semantic_decode(p(sem), self.S, HW, p(self.w), p(self.b), self.n_codes, p(self.table), self.thresh,
+                                                p(sim_out), None, p(mask_out), _stream(dev))
+        if r < 0:
+            raise RuntimeError(_lib.last_error())
+
+
+def _frame_args(mode, style, pc):
+    from . import display
+    if mode not in FRAME_MODES:
+        raise ValueError(f"mode must be one of {FRAME_MODES}, got {mode!r}")
+    if not pc.get_xyz.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    return display._style(style)
+
+
+@torch.no_grad()
+def video_frames(cameras, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float, bg_color: torch.Tensor,
+                 mode: str = "image", style="heat", overlay_ratio: float = 1.0, gaussian_mask=None,
+                 scaling_modifier: float = 1.0, dtype: torch.dtype = torch.uint8, heat_thresh: float = 0.7,
+                 colormap: torch.Tensor | None = None) -> torch.Tensor:
+    """The frames of render_video's loop (gui/main.py:1766-1801) for a camera set, [V, H, W, 3] on the device (uint8 as
+    the reference saves them, or float32): every camera is rendered with render_gui and decoded with the fused decode
+    into slot v of preallocated [V, ...] buffers, then ONE batched display.compose makes all the frames, each view with
+    its own minimum and maximum.  `mode` picks the render's "image", "depth" (min-max normalised per view, as
+    test_step's depth mode) or "alpha"; `style` is a display style (display.from_reference_flags maps the GUI's
+    switches).  Styles that need no similarity skip the decode.  All cameras must share one H x W.  Nothing is read back
+    to the host."""
+    from . import display
+    from .render import render_gui
+    code = _frame_args(mode, style, pc)
+    cams, H, W = _sweep_frame(cameras)
+    dev = pc.get_xyz.device
+    V, HW = len(cams), H * W
+    need_sim = code != display.NONE
+    base = torch.empty((V, 3 if mode == "image" else 1, H, W), dtype=torch.float32, device=dev)
+    sim = torch.empty((V, HW), dtype=torch.float32, device=dev) if need_sim else None
+    mask = torch.empty((V, HW), dtype=torch.uint8, device=dev) if need_sim else None
+    dec = _FrameDecoder(mlp, lut, score_fn, thresh, dev) if need_sim else None
+    for v, cam in enumerate(cams):
+        out = render_gui(cam, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask)
+        base[v].copy_(out[mode].reshape(base.shape[1:]))
+        if need_sim:
+            dec.decode(out["semantics"], sim[v], mask[v])
+    return display.compose(base, sim, mask, style=code, normalize=mode == "depth", overlay_ratio=overlay_ratio,
+                           heat_thresh=heat_thresh, colormap=colormap, dtype=dtype)
+
+
+@torch.no_grad()
+def view_frame(camera, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float, bg_color: torch.Tensor,
+               mode: str = "image", style="heat", overlay_ratio: float = 1.0, gaussian_mask=None,
+               scaling_modifier: float = 1.0, dtype: torch.dtype = torch.float32, heat_thresh: float = 0.7,
+               colormap: torch.Tensor | None = None, return_parts: bool = False):
+    """One displayed frame [H, W, 3] on the device: test_step with set_clip_mask (gui/main.py:549-604, :387-398) as
+    render_gui, the fused decode with its uint8 background mask, and display.compose on the render's own tensor (no copy
+    of the image).  `mode`, `style` and the rest as video_frames; float32 is what the viewer's texture takes.  Nothing is
+    read back to the host.  return_parts: also the dictionary {"base", "sim", "bg_mask"} the frame was composed from (sim
+    and bg_mask None for the styles that need no similarity)."""
+    from . import display
+    from .render import render_gui
+    code = _frame_args(mode, style, pc)
+    dev = pc.get_xyz.device
+    out = render_gui(camera, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask)
+    base = out[mode]
+    base = base.reshape((-1,) + tuple(base.shape[-2:]))
+    sim = mask = None
+    if code != display.NONE:
+        HW = int(base.shape[-2]) * int(base.shape[-1])
+        sim = torch.empty(HW, dtype=torch.float32, device=dev)
+        mask = torch.empty(HW, dtype=torch.uint8, device=dev)
+        _FrameDecoder(mlp, lut, score_fn, thresh, dev).decode(out["semantics"], sim, mask)
+    frame = display.compose(base, sim, mask, style=code, normalize=mode == "depth", overlay_ratio=overlay_ratio,
+                            heat_thresh=heat_thresh, colormap=colormap, dtype=dtype)
+    return (frame, {"base": base, "sim": sim, "bg_mask": mask}) if return_parts else frame
 
 
 # ---- code-book initialisation (train.py:78-86) -------------------------------------------------------------------------

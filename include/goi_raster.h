@@ -51,7 +51,8 @@ extern "C" {
 
 /* 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
- *    goi_raster_backward_scratch_bytes as ever)
+ *    goi_raster_backward_scratch_bytes as ever);
+ *    later additions: goi_semantic_frame_workspace_bytes, goi_semantic_frame_compose
  * 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
  *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan,
  *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion,
@@ -386,6 +387,44 @@ int goi_semantic_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, in
 int goi_semantic_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
                              void* stream);
 int goi_semantic_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, void* stream);
+
+/* ---- the viewer's frame (csrc/display.hip): the stage between a render with its decoded similarity and the displayed
+ * picture, which the reference runs on the host in numpy (gui/main.py:549-604 test_step, :387-398 set_clip_mask with
+ * utils/image_utils.py:129-178 cmap / clip_color, :1766-1801 render_video).
+ *
+ * goi_semantic_frame_compose: out [n_views][H][W][3] (GOI_FRAME_F32 or GOI_FRAME_U8, interleaved) from base [n_views]
+ *   [channels][H][W] fp32 (channels 1 or 3; 1 is repeated to three), sim [n_views][H][W] fp32 and bg_mask [n_views][H][W]
+ *   bytes (nonzero = background).  Every operation is one fp32 rounding, in this order:
+ *     normalize != 0: base = (base - min_v) / ((max_v - min_v) + 1e-20f), min / max over the whole view; then
+ *     base = clamp(base, 0, 1);
+ *     GOI_FRAME_NONE     out = base
+ *     GOI_FRAME_BINARY   out = sim > 0 ? 1 : 0                                   (base is not read)
+ *     GOI_FRAME_WHITEN   col = 1; opa = (bg ? 1 : 0) * r; om = 1 - opa
+ *     GOI_FRAME_HEAT     rel = clamp(((sim - t) - 0.05f) / (max_v(sim) - t), 0, 1); col = bg ? 1 : clamp(table[(long)(rel *
+ *                        (n_colors - 1))], 0, 1); opa = r; om = (float)(1.0 - overlay_ratio), the subtraction in double
+ *     GOI_FRAME_HEAT_FT  rel = clamp(sim + 0.2f, 0.1f, 0.9f); col as HEAT; opa = (bg ? 1 : 0) * r; om = 1 - opa
+ *     the three overlay styles: out = clamp(col * opa + base * om, 0, 1), never contracted to an FMA;
+ *     GOI_FRAME_U8: out = (uint8)(out * 255f), truncated.
+ *   r = (float)overlay_ratio, t = (float)heat_thresh.  sim is needed by BINARY, HEAT and HEAT_FT, bg_mask by WHITEN, HEAT
+ *   and HEAT_FT, table [n_colors][3] fp32 (2 <= n_colors <= GOI_FRAME_MAX_COLORS) by HEAT and HEAT_FT; the others may be
+ *   NULL.  The table index is clamped into the table and a NaN rel takes entry 0; the minima and maxima skip NaNs; the
+ *   sign of a zero in `out` is unspecified.  workspace: goi_semantic_frame_workspace_bytes(n_views) bytes of device
+ *   memory, 4-byte aligned, zeroed on `stream` by the call when it is used (normalize, or GOI_FRAME_HEAT).
+ *   At most two kernel launches whatever n_views is, asynchronous on `stream`: no allocation, copy or synchronisation.
+ *   16-byte aligned buffers with H * W a multiple of 4 take the vector path; anything else a scalar one with the same
+ *   result.  1 <= n_views <= 65535, H * W < 2^31.  Returns < 0 (goi_raster_last_error) for bad arguments. */
+#define GOI_FRAME_NONE 0
+#define GOI_FRAME_BINARY 1
+#define GOI_FRAME_WHITEN 2
+#define GOI_FRAME_HEAT 3
+#define GOI_FRAME_HEAT_FT 4
+#define GOI_FRAME_F32 0
+#define GOI_FRAME_U8 1
+#define GOI_FRAME_MAX_COLORS 1024 /* the table is staged in LDS: 12 KiB */
+size_t goi_semantic_frame_workspace_bytes(int n_views);
+int goi_semantic_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, int H, int W,
+                               int style, int normalize, double overlay_ratio, double heat_thresh, const float* table,
+                               int n_colors, void* out, int out_dtype, void* workspace, void* stream);
 
 /* ---- code-book initialisation (train.py:78-86; csrc/codebook_init.hip) ----------------------------------------------
  * goi_codebook_unique_rows: the rows of x.permute(1, 2, 0).reshape(-1, D).unique(dim=0) of each of n_views fp32 maps
