@@ -105,6 +105,25 @@ def _check_device(means3D):
     return means3D.device
 
 
+def check_selection(selection, P, dev=None):
+    """The per-Gaussian selection of rasterize_gaussians_selected: a contiguous torch.bool / torch.uint8 tensor of P elements on
+    the model's device.  It crosses into the library as a pointer to P bytes and is never copied or converted, so nothing here
+    repairs a tensor that does not fit: it is refused."""
+    if not isinstance(selection, torch.Tensor) or selection.dtype not in (torch.bool, torch.uint8):
+        got = selection.dtype if isinstance(selection, torch.Tensor) else type(selection).__name__
+        raise TypeError(f"selection must be a torch.bool or torch.uint8 tensor, got {got}")
+    if selection.numel() != P:
+        raise ValueError(f"selection has {selection.numel()} elements, the model {P} Gaussians")
+    if not selection.is_contiguous():
+        raise ValueError("selection must be contiguous (it is passed by pointer, never copied)")
+    if not selection.is_cuda:
+        raise RuntimeError("goi_hyperplane_amd: selection must live on a ROCm GPU (cuda device); there is no CPU fallback in "
+                           "this package")
+    if dev is not None and selection.device != dev:
+        raise ValueError(f"selection is on {selection.device}, expected {dev}")
+    return selection
+
+
 class _BinningAllocator:
     """The allocation callback handed to the library (reference: resizeFunctional,
     rasterize_points.cu:27-33): allocates the binning workspace as a uint8 torch tensor."""
@@ -729,12 +748,14 @@ def _ident(t):
 
 
 def _geom_key(dev, P, H, W, means3D, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, degree, campos, prefiltered,
-              colors, cov3D):
+              colors, cov3D, selection=None, selection_invert=False):
     # (precomputed colours / covariances are the caller's own tensors: their identity is meaningful; the SH coefficients and
     # the activated scales / rotations / opacities are rebuilt by the reference's model on every call and cannot be keyed)
+    # The selection decides which Gaussians the cached lists hold: its identity (None: no selection) and sense are part of the
+    # key -- a camera rendered under one selection is never reblended for another, or for none.
     return (dev.index, P, H, W, float(scale_modifier), float(tan_fovx), float(tan_fovy), int(degree), bool(prefiltered),
             _ident(means3D), _ident(viewmatrix), _ident(projmatrix), _ident(campos), _ident(colors), _ident(cov3D),
-            tuple(sorted(_lib.OPTIONS.items())))
+            tuple(sorted(_lib.OPTIONS.items())), _ident(selection), bool(selection_invert) and selection is not None)
 
 
 def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
@@ -742,16 +763,38 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
                         degree, campos, prefiltered, debug):
     """-> (num_rendered, color[3,H,W], semantic[S,H,W], depth[1,H,W], alpha[1,H,W], radii[P] i32,
     geomBuffer u8, binningBuffer u8, imgBuffer u8)"""
-    args = (background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-            projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug)
+    return _rasterize((background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                       viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                       debug), None, False)
+
+
+def rasterize_gaussians_selected(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
+                                 cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
+                                 degree, campos, prefiltered, debug, selection, selection_invert):
+    """rasterize_gaussians over a SELECTION of the Gaussians, rendered in place (include/goi_raster.h,
+    goi_raster_forward_selected; not in the reference's pybind module, whose callers index-select the operands first,
+    gui/gs_renderer.py:315-321).  selection: bool / uint8 [P] on the device (check_selection), or None = rasterize_gaussians;
+    selection_invert: render the Gaussians whose byte is 0 instead.  Same return tuple; radii stays [P] (0 for an unselected
+    Gaussian) and the workspaces serve the same backward calls."""
+    return _rasterize((background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                       viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                       debug), selection, bool(selection_invert))
+
+
+def _rasterize(args, selection, selection_invert):
+    (background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+     tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug) = args
     P = int(means3D.size(0)) if isinstance(means3D, torch.Tensor) and means3D.ndimension() == 2 else 0
+    if selection is not None:
+        check_selection(selection, P, means3D.device if isinstance(means3D, torch.Tensor) and means3D.is_cuda else None)
+    sel_kw = {} if selection is None else dict(selection=selection, selection_invert=selection_invert)
     if not (_GEOM_CACHE["max_bytes"] > 0 and getattr(_CALL, "geometry_frozen", False) and P > 0 and not debug
             and isinstance(semantics, torch.Tensor) and semantics.ndimension() == 2 and semantics.size(0) == P):
-        return _rasterize_gaussians_frame(*args)
+        return _rasterize_gaussians_frame(*args, **sel_kw)
     dev = _check_device(means3D)
     H, W = int(image_height), int(image_width)
     key = _geom_key(dev, P, H, W, means3D, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, degree, campos,
-                    prefiltered, colors, cov3D_precomp)
+                    prefiltered, colors, cov3D_precomp, selection, selection_invert)
     with _GEOM_LOCK:
         e = _GEOM_CACHE["entries"].get(key)
         if e is not None:
@@ -780,14 +823,14 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
                 e = None
     if e is not None:
         return _reblend(e, background, semantics, P, H, W, dev)
-    res = _rasterize_gaussians_frame(*args)
+    res = _rasterize_gaussians_frame(*args, **sel_kw)
     R, _c, _s, _d, _a, radii, geom, binning, img = res
     with _GEOM_LOCK:
         _GEOM_CACHE["misses"] += 1
         # The key identifies tensors by (address, version, shape): that is only sound while the tensors are ALIVE -- a freed
         # camera matrix or `xyz[mask]` temporary hands its address (version 0 again) to the next frame's tensors.  The entry
         # therefore holds strong references to every keyed tensor for as long as it lives (and accounts for their bytes).
-        keyed = tuple(t for t in (means3D, viewmatrix, projmatrix, campos, colors, cov3D_precomp)
+        keyed = tuple(t for t in (means3D, viewmatrix, projmatrix, campos, colors, cov3D_precomp, selection)
                       if isinstance(t, torch.Tensor) and t.numel() > 0)
         nbytes = (geom.numel() + img.numel() + radii.numel() * 4 + (binning.numel() if isinstance(binning, torch.Tensor) else 0)
                   + sum(t.numel() * t.element_size() for t in keyed))
@@ -833,10 +876,14 @@ def _reblend(e, background, semantics, P, H, W, dev):
 
 def _rasterize_gaussians_frame(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
                                cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                               degree, campos, prefiltered, debug):
+                               degree, campos, prefiltered, debug, selection=None, selection_invert=False):
     lib = _lib.load()
     dev = _check_device(means3D)
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    if selection is not None:
+        check_selection(selection, P, dev)
+        if P == 0:
+            selection = None
     if semantics is None or semantics.numel() == 0:
         if P > 0:
             raise RuntimeError("semantics [P,S] is required (the reference dereferences it unconditionally, "
@@ -856,18 +903,24 @@ def _rasterize_gaussians_frame(background, means3D, colors, semantics, opacity, 
                 _e(sh), int(degree), campos, bool(prefiltered), bool(debug))
         cap = _pick_capacity(dev, P, debug, prefiltered, _tiles(H, W))
         if cap is None:
-            res = ext.rasterize_gaussians(*args)
+            res = (ext.rasterize_gaussians(*args) if selection is None
+                   else ext.rasterize_gaussians_selected(*args, selection, bool(selection_invert)))
             _note_frame(res[6], P)
             if P > 0:
                 SPECULATION_STATS["exact_frames"] += 1
                 _note_count(dev, P, res[0], _tiles(H, W))
             return res
-        cut_key, z_in, z_out, n_prev = _depth_cut_for(dev, P, H, W, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                                                      scale_modifier)
+        # (a selected frame neither applies nor learns a depth cut: what a camera learnt belongs to the whole model's frame)
+        cut_key, z_in, z_out, n_prev = (None, None, None, 0) if selection is not None else _depth_cut_for(
+            dev, P, H, W, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier)
         if z_in is not None and n_prev > 0 and _FWD["capacity"] is None:
             cap = min(cap, max(_MIN_CAPACITY, int(_FWD["headroom"] * n_prev) + 4096))
-        ticket, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img = ext.rasterize_gaussians_async(
-            *args, cap, z_in, z_out)
+        if selection is not None:
+            ticket, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img = ext.rasterize_gaussians_async_selected(
+                *args, cap, selection, bool(selection_invert))
+        else:
+            ticket, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img = ext.rasterize_gaussians_async(
+                *args, cap, z_in, z_out)
         _note_frame(geom, P)
         SPECULATION_STATS["speculative_frames"] += 1
         refs = [weakref.ref(t) for t in (geom, img, radii, out_color, out_sem, out_depth, out_alpha)]
@@ -909,8 +962,8 @@ def _rasterize_gaussians_frame(background, means3D, colors, semantics, opacity, 
         cap = _pick_capacity(dev, P, debug, prefiltered, _tiles(H, W))
         if cap is not None:
             # speculative frame: everything is enqueued now, the count arrives through the ticket
-            cut_key, z_in, z_out, n_prev = _depth_cut_for(dev, P, H, W, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                                                          scale_modifier)
+            cut_key, z_in, z_out, n_prev = (None, None, None, 0) if selection is not None else _depth_cut_for(
+                dev, P, H, W, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier)
             if z_in is not None and n_prev > 0 and _FWD["capacity"] is None:
                 cap = min(cap, max(_MIN_CAPACITY, int(_FWD["headroom"] * n_prev) + 4096))
             step = 16 << 20
@@ -918,9 +971,14 @@ def _rasterize_gaussians_frame(background, means3D, colors, semantics, opacity, 
                                   device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
             outs = (out_color, out_sem, out_depth, out_alpha)
-            ticket = lib.goi_raster_forward_async_cut(C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap,
-                                                      *[_ptr(o) for o in outs], _ptr(radii), _ptr(z_in), _ptr(z_out),
-                                                      C.c_void_p(stream))
+            if selection is not None:
+                ticket = lib.goi_raster_forward_async_selected(C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap,
+                                                               *[_ptr(o) for o in outs], _ptr(radii), _ptr(selection),
+                                                               int(bool(selection_invert)), C.c_void_p(stream))
+            else:
+                ticket = lib.goi_raster_forward_async_cut(C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap,
+                                                          *[_ptr(o) for o in outs], _ptr(radii), _ptr(z_in), _ptr(z_out),
+                                                          C.c_void_p(stream))
             if ticket < 0:
                 raise RuntimeError(_lib.last_error())
             SPECULATION_STATS["speculative_frames"] += 1
@@ -940,8 +998,13 @@ def _rasterize_gaussians_frame(background, means3D, colors, semantics, opacity, 
                 SPECULATION_STATS["cut_frames"] += 1
             return n, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img
         alloc = _BinningAllocator(dev)
-        n = lib.goi_raster_forward(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color), _ptr(out_sem),
-                                   _ptr(out_depth), _ptr(out_alpha), _ptr(radii), _stream(dev))
+        if selection is not None:
+            n = lib.goi_raster_forward_selected(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color), _ptr(out_sem),
+                                                _ptr(out_depth), _ptr(out_alpha), _ptr(radii), _ptr(selection),
+                                                int(bool(selection_invert)), _stream(dev))
+        else:
+            n = lib.goi_raster_forward(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color), _ptr(out_sem),
+                                       _ptr(out_depth), _ptr(out_alpha), _ptr(radii), _stream(dev))
         if alloc.error is not None:
             raise alloc.error
         if n < 0:

@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgoi_raster.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 STAGES = ("preprocess", "depth_sort", "scan", "emit", "tile_sort", "ranges", "blend_fwd", "blend_bwd",
           "preprocess_bwd")
@@ -44,6 +44,10 @@ SYMBOLS = {
                            + [C.c_void_p] * 5 + [C.c_void_p]),
     "goi_raster_forward_async": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
                                  + [C.c_void_p] * 5 + [C.c_void_p]),
+    "goi_raster_forward_selected": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, ALLOC_FN, C.c_void_p]
+                                    + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "goi_raster_forward_async_selected": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+                                          + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
     "goi_raster_ticket_result": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "goi_raster_forward_async_cut": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
                                      + [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p]),

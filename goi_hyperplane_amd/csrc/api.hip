@@ -278,7 +278,8 @@ int enqueue_readback(const GeomView& g, int ticket, hipStream_t s, bool head_onl
 // ticket < 0: no read-back here (the speculative forward queues it behind the blend instead: nobody is waiting for it,
 // and a device-to-host copy in the middle of the frame costs the stream a ~10 us bubble)
 int enqueue_front(const GoiRasterScene& sc, GeomView& g, ImageView& im, int* radii, int ticket, const uint32_t** order_out,
-                  hipStream_t s, const float* zcut = nullptr, uint32_t* zlearn = nullptr) {
+                  hipStream_t s, const float* zcut = nullptr, uint32_t* zlearn = nullptr, const uint8_t* keep = nullptr,
+                  int keep_invert = 0) {
     const int P = sc.P;
     const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
     // one memset: the counters and, right behind them, the control words of the depth sort
@@ -290,7 +291,7 @@ int enqueue_front(const GoiRasterScene& sc, GeomView& g, ImageView& im, int* rad
                                                  reinterpret_cast<char*>(g.blk_coarse))), s));
     {
         StageTimer t(GOI_STAGE_PREPROCESS, s);
-        launch_preprocess_fwd(sc, g, radii, im.ranges, gx * gy, s, zcut, zlearn);  // also zeroes the tile ranges
+        launch_preprocess_fwd(sc, g, radii, im.ranges, gx * gy, s, zcut, zlearn, keep, keep_invert);  // also zeroes the tile ranges
     }
     if (check_stage(sc, s, "preprocess")) return -1;
     if (ticket >= 0 && enqueue_readback(g, ticket, s)) return -1;
@@ -369,11 +370,12 @@ int enqueue_back(const GoiRasterScene& sc, GeomView& g, ImageView& im, const Bin
 // and enqueues the back half while the GPU is still busy with the depth sort and the scan -- no idle gap on the device.
 // Returns num_rendered (>= 0) and the final point list through *plist.
 int geometry_and_binning(const GoiRasterScene& sc, GeomView& g, ImageView& im, goi_alloc_fn alloc, void* user,
-                         int* radii, const uint32_t** plist, hipStream_t s, unsigned long long** qmask = nullptr) {
+                         int* radii, const uint32_t** plist, hipStream_t s, unsigned long long** qmask = nullptr,
+                         const uint8_t* keep = nullptr, int keep_invert = 0) {
     const int ticket = ticket_acquire(0);
     if (ticket < 0) return -1;
     const uint32_t* order = nullptr;
-    if (enqueue_front(sc, g, im, radii, ticket, &order, s)) {
+    if (enqueue_front(sc, g, im, radii, ticket, &order, s, nullptr, nullptr, keep, keep_invert)) {
         ticket_release(ticket);
         return -1;
     }
@@ -497,9 +499,10 @@ size_t goi_raster_debug_backward_contrib_offset(int N, int S) {
     return reinterpret_cast<size_t>(v.contrib);  // (laid out from base 0: the offset in a 256-byte aligned scratch)
 }
 
-int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
-                       void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                       int* radii, void* stream) {
+// keep (or NULL) / invert: the per-Gaussian selection of the _selected entry points -- the plain ones pass NULL
+static int forward_exact(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
+                         void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                         int* radii, const uint8_t* keep, int invert, void* stream) {
     refresh_options();
     if (validate(scene, true)) return -1;
     const GoiRasterScene& sc = *scene;
@@ -519,7 +522,7 @@ int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* ima
     image_layout(sc.W, sc.H, static_cast<char*>(image_buffer), &im);
     const uint32_t* plist = nullptr;
     unsigned long long* qmask = nullptr;
-    const int N = geometry_and_binning(sc, g, im, binning_alloc, alloc_user, radii, &plist, s, &qmask);
+    const int N = geometry_and_binning(sc, g, im, binning_alloc, alloc_user, radii, &plist, s, &qmask, keep, invert);
     if (N < 0) return -1;
     {
         StageTimer t(GOI_STAGE_BLEND_FWD, s);
@@ -530,16 +533,48 @@ int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* ima
     return N;
 }
 
+int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
+                       void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                       int* radii, void* stream) {
+    return forward_exact(scene, geom_buffer, image_buffer, binning_alloc, alloc_user, out_color, out_semantic, out_depth,
+                         out_alpha, radii, nullptr, 0, stream);
+}
+
+int goi_raster_forward_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
+                                void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                                int* radii, const uint8_t* keep, int invert, void* stream) {
+    return forward_exact(scene, geom_buffer, image_buffer, binning_alloc, alloc_user, out_color, out_semantic, out_depth,
+                         out_alpha, radii, keep, invert, stream);
+}
+
+static int forward_speculative(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
+                               int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                               int* radii, const float* zcut_in, float* zcut_out, const uint8_t* keep, int invert, void* stream);
+
 int goi_raster_forward_async(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
                              int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
                              int* radii, void* stream) {
-    return goi_raster_forward_async_cut(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic,
-                                        out_depth, out_alpha, radii, nullptr, nullptr, stream);
+    return forward_speculative(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic, out_depth,
+                               out_alpha, radii, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int goi_raster_forward_async_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
+                                      int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                                      int* radii, const uint8_t* keep, int invert, void* stream) {
+    return forward_speculative(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic, out_depth,
+                               out_alpha, radii, nullptr, nullptr, keep, invert, stream);
 }
 
 int goi_raster_forward_async_cut(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
                                  int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
                                  int* radii, const float* zcut_in, float* zcut_out, void* stream) {
+    return forward_speculative(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic, out_depth,
+                               out_alpha, radii, zcut_in, zcut_out, nullptr, 0, stream);
+}
+
+static int forward_speculative(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
+                               int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                               int* radii, const float* zcut_in, float* zcut_out, const uint8_t* keep, int invert, void* stream) {
     refresh_options();
     if (validate(scene, true)) return -1;
     const GoiRasterScene& sc = *scene;
@@ -560,7 +595,7 @@ int goi_raster_forward_async_cut(const GoiRasterScene* scene, void* geom_buffer,
     const uint32_t* order = nullptr;
     const uint32_t* plist = nullptr;
     uint32_t* zlearn = reinterpret_cast<uint32_t*>(zcut_out);  // (positive floats: the kernels take their maximum as integers)
-    if (enqueue_front(sc, g, im, radii, /*ticket=*/-1, &order, s, zcut_in, zlearn) ||
+    if (enqueue_front(sc, g, im, radii, /*ticket=*/-1, &order, s, zcut_in, zlearn, keep, invert) ||
         enqueue_back(sc, g, im, bv, capacity, /*exact=*/false, order, radii, &plist, s)) {
         ticket_release(ticket);
         return -1;

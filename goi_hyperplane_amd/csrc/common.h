@@ -187,7 +187,8 @@ constexpr long long SORT_MAX_KEYS = 1ll << 30;
 
 // ---- stages ---------------------------------------------------------------------------------------
 void launch_preprocess_fwd(const GoiRasterScene& sc, const GeomView& g, int* radii, uint2* ranges, int n_tiles,
-                           hipStream_t s, const float* zcut = nullptr, uint32_t* zlearn = nullptr);
+                           hipStream_t s, const float* zcut = nullptr, uint32_t* zlearn = nullptr,
+                           const uint8_t* keep = nullptr, int keep_invert = 0);  // keep: [P] selection bytes (NULL: everything)
 // Listed Gaussians (tiles_touched > 0) compacted in id order into sort_keys[0] / sort_vals[0] (the depth sort's input),
 // counters[COUNTER_V / COUNTER_N], and -- ghist != NULL -- the four digit histograms of the compacted keys (the onesweep
 // sort's prologue).  pad: entries [V, P) get key 0xFFFFFFFF (a sort

@@ -71,6 +71,11 @@ struct PreArgs {
     // (cleared here, written by the forward blend)
     const float* zcut;
     uint32_t* zlearn;
+    // per-Gaussian SELECTION (goi_raster_forward_selected; read by preprocess_fwd_k<true> only): keep[id] is one byte per Gaussian,
+    // and Gaussian id is UNSELECTED when (keep[id] != 0) == (keep_invert != 0) -- keep_invert = 0 renders the Gaussians whose byte
+    // is set, keep_invert = 1 the others.  NULL: no selection (preprocess_fwd_k<false>).
+    const uint8_t* keep;
+    int keep_invert;
 };
 
 // The camera arrays are tiny, uniform device arrays: every thread reads them through the scalar
@@ -115,6 +120,11 @@ __device__ __forceinline__ V3 sh_to_rgb_sum(int D, const V3& dir, SHK_T SHK) {
 #ifndef GOI_PRE_MINBLOCKS
 #define GOI_PRE_MINBLOCKS 1
 #endif
+// SELECT: the frame renders a SELECTION of the Gaussians (PreArgs::keep).  An unselected Gaussian leaves phase A where one behind
+// the near plane does, before anything of it has been loaded -- its selection byte is all the kernel ever reads of it -- and is
+// from there on what a frustum-culled Gaussian is: radius 0, no tiles, key 0xFFFFFFFF, no record, no instance.  Nothing
+// downstream of this kernel knows about selections.  SELECT == false is the kernel as it was.
+template <bool SELECT>
 __global__ __launch_bounds__(256, GOI_PRE_MINBLOCKS) void preprocess_fwd_k(const PreArgs args, GaussRec* __restrict__ rec,
                                                         float* __restrict__ cov3D_out,
                                                         uint32_t* __restrict__ tiles_touched,
@@ -146,12 +156,18 @@ __global__ __launch_bounds__(256, GOI_PRE_MINBLOCKS) void preprocess_fwd_k(const
     uint32_t touched = 0, key = 0xFFFFFFFFu;
     uint8_t clamp_bits = 0;
 
-    const V3 p = {a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]};
+    // (a lane past P looks at the byte of Gaussian P - 1, as it redoes that Gaussian: in bounds, and if that one is unselected
+    // the lane leaves phase A with it)
+    bool unselected = false;
+    if constexpr (SELECT) unselected = (args.keep[idx] != 0) == (args.keep_invert != 0);
+    V3 p = {0.f, 0.f, 0.f};
+    if (!SELECT || !unselected) p = V3{a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]};
     const V3 p_view = xform_point_4x3(p, a.view);
     // ---- phase A: projection, covariance, conic, radius, 3-sigma rectangle: is the Gaussian rendered at all?
     bool vis = false;
     float pix = 0.f, piy = 0.f, con_a = 0.f, con_b = 0.f, con_c = 0.f, my_radius = 0.f;
     do {
+        if (SELECT && unselected) break;  // (not the caller's "prefiltered" promise broken: no trap)
         if (p_view.z <= 0.2f) {
             if (a.prefiltered) atomicOr(&counters[1], 1u);  // the reference traps here
             break;
@@ -1139,8 +1155,10 @@ __global__ __launch_bounds__(256) void mark_visible_k(int P, const float* __rest
 }  // namespace
 
 void launch_preprocess_fwd(const GoiRasterScene& sc, const GeomView& g, int* radii, uint2* ranges, int n_tiles,
-                           hipStream_t s, const float* zcut, uint32_t* zlearn) {
+                           hipStream_t s, const float* zcut, uint32_t* zlearn, const uint8_t* keep, int keep_invert) {
     PreArgs a;
+    a.keep = keep;
+    a.keep_invert = keep_invert;
     a.zcut = g_options.cull_variant >= 2 ? zcut : nullptr;  // (the cut lives in the ellipse tile masks)
     a.zlearn = zlearn;
     a.P = sc.P; a.D = sc.D; a.M = sc.M; a.W = sc.W; a.H = sc.H;
@@ -1155,8 +1173,13 @@ void launch_preprocess_fwd(const GoiRasterScene& sc, const GeomView& g, int* rad
     a.focal_x = sc.W / (2.0f * sc.tan_fovx);
     a.view_p = sc.viewmatrix; a.proj_p = sc.projmatrix; a.campos_p = sc.campos;
     static_assert(PRE_BLOCK == 256, "preprocess_fwd_k is written for 256-thread workgroups");
-    preprocess_fwd_k<<<dim3((sc.P + PRE_BLOCK - 1) / PRE_BLOCK), dim3(PRE_BLOCK), 0, s>>>(
-        a, g.rec, g.cov3D, g.tiles_touched, g.clamped, g.sort_keys[1], g.aux, g.blk_agg, g.blk_coarse, radii, g.counters, ranges, n_tiles);
+    const dim3 grid((sc.P + PRE_BLOCK - 1) / PRE_BLOCK);
+#define GOI_PRE(SELECT)                                                                                                          \
+    preprocess_fwd_k<SELECT><<<grid, dim3(PRE_BLOCK), 0, s>>>(a, g.rec, g.cov3D, g.tiles_touched, g.clamped, g.sort_keys[1], g.aux, \
+                                                              g.blk_agg, g.blk_coarse, radii, g.counters, ranges, n_tiles)
+    if (keep) GOI_PRE(true);
+    else GOI_PRE(false);
+#undef GOI_PRE
 }
 
 void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, float* dL_dmean2D,

@@ -150,10 +150,27 @@ Prepared prepare(GOI_FORWARD_ARGS, bool need_semantics) {
     return f;
 }
 
-std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_gaussians(GOI_FORWARD_ARGS) {
+// The per-Gaussian selection of the _selected operators (include/goi_raster.h, goi_raster_forward_selected): P bytes on the
+// frame's device, handed over by pointer -- never copied or converted.
+const uint8_t* selection_ptr(const Tensor& selection, const Prepared& f) {
+    TORCH_CHECK_TYPE(selection.scalar_type() == torch::kBool || selection.scalar_type() == torch::kByte,
+                     "selection must be torch.bool or torch.uint8, got ", selection.scalar_type());
+    TORCH_CHECK_VALUE(selection.numel() == f.P, "selection has ", selection.numel(), " elements, the model ", f.P, " Gaussians");
+    TORCH_CHECK_VALUE(selection.is_contiguous(), "selection must be contiguous (it is passed by pointer, never copied)");
+    TORCH_CHECK(selection.is_cuda(), "goi_hyperplane_amd: selection must live on a ROCm GPU (cuda device); there is no CPU "
+                                     "fallback in this package");
+    TORCH_CHECK(selection.device() == f.dev, "selection is on ", selection.device(), ", expected ", f.dev);
+    return f.P ? static_cast<const uint8_t*>(selection.data_ptr()) : nullptr;
+}
+
+using FrameTuple = std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+// selection (or NULL: every Gaussian) / invert: rasterize_gaussians_selected
+FrameTuple forward_frame(GOI_FORWARD_ARGS, const Tensor* selection, bool invert) {
     Prepared f = prepare(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                          viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                          prefiltered, debug, true);
+    const uint8_t* keep = selection ? selection_ptr(*selection, f) : nullptr;
     c10::hip::HIPGuard guard(f.dev.index());
     auto f32 = means3D.options().dtype(torch::kFloat32);
     auto bytes = means3D.options().dtype(torch::kByte);
@@ -163,21 +180,38 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> 
     Tensor geom = torch::empty({f.P > 0 ? (long long)goi_raster_geom_bytes(f.P) : 0}, bytes);
     Tensor img = torch::empty({f.P > 0 ? (long long)goi_raster_image_bytes(f.W, f.H) : 0}, bytes);
     Tensor binning = torch::empty({0}, bytes);
-    const int n = goi_raster_forward(&f.sc, f.P ? geom.data_ptr() : nullptr, f.P ? img.data_ptr() : nullptr, grow, &binning,
-                                     out_color.data_ptr<float>(), out_sem.data_ptr<float>(), out_depth.data_ptr<float>(),
-                                     out_alpha.data_ptr<float>(), f.P ? radii.data_ptr<int>() : nullptr, stream_of(f.dev));
+    const int n = goi_raster_forward_selected(&f.sc, f.P ? geom.data_ptr() : nullptr, f.P ? img.data_ptr() : nullptr, grow, &binning,
+                                              out_color.data_ptr<float>(), out_sem.data_ptr<float>(), out_depth.data_ptr<float>(),
+                                              out_alpha.data_ptr<float>(), f.P ? radii.data_ptr<int>() : nullptr, keep,
+                                              invert ? 1 : 0, stream_of(f.dev));
     if (n < 0) raise_last();
     return std::make_tuple(n, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img);
+}
+
+FrameTuple rasterize_gaussians(GOI_FORWARD_ARGS) {
+    return forward_frame(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                         debug, nullptr, false);
+}
+
+// rasterize_gaussians over a SELECTION of the Gaussians, in place: every tensor stays [P]-long (no counterpart in the reference,
+// which index-selects the operands first, gui/gs_renderer.py:315-321)
+FrameTuple rasterize_gaussians_selected(GOI_FORWARD_ARGS, const Tensor& selection, const bool invert) {
+    return forward_frame(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                         debug, &selection, invert);
 }
 
 // speculative forward: nothing waits; returns the read-back ticket instead of num_rendered (include/goi_raster.h)
 // zcut_in / zcut_out: the speculative depth cut-off of the tile lists (goi_raster_forward_async_cut): per-tile float32 arrays on
 // the device, either may be absent (None)
-std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_gaussians_async(
-    GOI_FORWARD_ARGS, const int capacity, const c10::optional<Tensor>& zcut_in, const c10::optional<Tensor>& zcut_out) {
+// selection (or NULL) / invert: rasterize_gaussians_async_selected -- a selected frame takes no depth cut
+FrameTuple forward_frame_async(GOI_FORWARD_ARGS, const int capacity, const c10::optional<Tensor>& zcut_in,
+                               const c10::optional<Tensor>& zcut_out, const Tensor* selection, bool invert) {
     Prepared f = prepare(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                          viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                          prefiltered, debug, true);
+    const uint8_t* keep = selection ? selection_ptr(*selection, f) : nullptr;
     c10::hip::HIPGuard guard(f.dev.index());
     auto f32 = means3D.options().dtype(torch::kFloat32);
     auto bytes = means3D.options().dtype(torch::kByte);
@@ -199,12 +233,29 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> 
         if (k == 0) zin = z->data_ptr<float>();
         else zout = z->data_ptr<float>();
     }
-    const int ticket = goi_raster_forward_async_cut(&f.sc, geom.data_ptr(), img.data_ptr(), binning.data_ptr(), capacity,
-                                                    out_color.data_ptr<float>(), out_sem.data_ptr<float>(),
-                                                    out_depth.data_ptr<float>(), out_alpha.data_ptr<float>(),
-                                                    radii.data_ptr<int>(), zin, zout, stream_of(f.dev));
+    const int ticket =
+        keep ? goi_raster_forward_async_selected(&f.sc, geom.data_ptr(), img.data_ptr(), binning.data_ptr(), capacity,
+                                                 out_color.data_ptr<float>(), out_sem.data_ptr<float>(),
+                                                 out_depth.data_ptr<float>(), out_alpha.data_ptr<float>(), radii.data_ptr<int>(),
+                                                 keep, invert ? 1 : 0, stream_of(f.dev))
+             : goi_raster_forward_async_cut(&f.sc, geom.data_ptr(), img.data_ptr(), binning.data_ptr(), capacity,
+                                            out_color.data_ptr<float>(), out_sem.data_ptr<float>(), out_depth.data_ptr<float>(),
+                                            out_alpha.data_ptr<float>(), radii.data_ptr<int>(), zin, zout, stream_of(f.dev));
     if (ticket < 0) raise_last();
     return std::make_tuple(ticket, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img);
+}
+
+FrameTuple rasterize_gaussians_async(GOI_FORWARD_ARGS, const int capacity, const c10::optional<Tensor>& zcut_in,
+                                     const c10::optional<Tensor>& zcut_out) {
+    return forward_frame_async(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                               viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                               prefiltered, debug, capacity, zcut_in, zcut_out, nullptr, false);
+}
+
+FrameTuple rasterize_gaussians_async_selected(GOI_FORWARD_ARGS, const int capacity, const Tensor& selection, const bool invert) {
+    return forward_frame_async(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                               viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                               prefiltered, debug, capacity, c10::nullopt, c10::nullopt, &selection, invert);
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------
@@ -507,6 +558,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("image_height"), pybind11::arg("image_width"), pybind11::arg("sh"), pybind11::arg("degree"),
           pybind11::arg("campos"), pybind11::arg("prefiltered"), pybind11::arg("debug"), pybind11::arg("capacity"),
           pybind11::arg("zcut_in") = pybind11::none(), pybind11::arg("zcut_out") = pybind11::none());
+    m.def("rasterize_gaussians_selected", &rasterize_gaussians_selected);
+    m.def("rasterize_gaussians_async_selected", &rasterize_gaussians_async_selected);
     m.def("backward_ex", &backward_ex);
     m.def("backward_semantics", &backward_semantics);
     m.def("release_scratch", &release_scratch);

@@ -14,10 +14,13 @@ Differences, all behind the same surface:
     default training configuration) the feature-gradient-only kernel runs, with the SH coefficients frozen dL/dSH
     is not formed (see set_backward_mode);
   * the number of semantic channels S is read from `semantics.shape[1]` at run time (the reference
-    compiles SEM_CHANNELS = 10 in, cuda_rasterizer/config.h:18).
+    compiles SEM_CHANNELS = 10 in, cuda_rasterizer/config.h:18);
+  * GaussianRasterizer.forward takes two keyword-only extensions, `selection` / `selection_invert`: a per-Gaussian
+    selection the rasterizer itself honours (rasterize_gaussians_selected).
 """
 from __future__ import annotations
 
+import inspect
 import os
 
 from typing import NamedTuple
@@ -169,11 +172,14 @@ def take_sh_factor():
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, selection=None, selection_invert=False):
         args = _forward_args(raster_settings, means3D, colors_precomp, semantics, opacities, scales, rotations,
                              cov3Ds_precomp, sh)
+        fn = _C.rasterize_gaussians
+        if selection is not None:  # the frame of a selection, in place: everything the backward reads stays [P]-long
+            fn, args = _C.rasterize_gaussians_selected, args + (selection, bool(selection_invert))
         (num_rendered, color, semant, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer) = _call_with_snapshot(
-            _C.rasterize_gaussians, args, raster_settings.debug, "snapshot_fw.dump", "forward")
+            fn, args, raster_settings.debug, "snapshot_fw.dump", "forward")
         ctx.raster_settings = raster_settings
         ctx.num_rendered = num_rendered  # an int, or the LazyCount of a speculative frame (never forced here)
         _LAST_FORWARD["num_rendered"] = num_rendered
@@ -185,6 +191,12 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_out_sem, grad_out_radii, grad_depth, grad_alpha):
+        # (+ the selection and its sense: not differentiable.  The backward itself knows nothing of a selection: an unselected
+        # Gaussian has radius 0 and no instance in the frame's workspaces, and gets the zero rows of any culled one.)
+        return _RasterizeGaussians._backward(ctx, grad_out_color, grad_out_sem, grad_out_radii, grad_depth, grad_alpha) + (None, None)
+
+    @staticmethod
+    def _backward(ctx, grad_out_color, grad_out_sem, grad_out_radii, grad_depth, grad_alpha):
         rs = ctx.raster_settings
         (colors_precomp, semantics, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer, alpha) = ctx.saved_tensors
@@ -253,6 +265,15 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
+    return rasterize_gaussians_selected(means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations,
+                                        cov3Ds_precomp, raster_settings, None, False)
+
+
+def rasterize_gaussians_selected(means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp,
+                                 raster_settings, selection, selection_invert=False):
+    """rasterize_gaussians over a per-Gaussian selection (bool / uint8 [P] on the device, passed by pointer; None: everything),
+    rendered in place: same five outputs, radii [P] with 0 for an unselected Gaussian, [P]-long gradients whose unselected rows
+    are zero.  selection_invert renders the complement without forming it."""
     # can a backward follow this frame?  (inside Function.forward grad mode is always off, so it is decided here.)  A frame
     # rendered only for its image takes the exact forward by default, see _C._CALL
     # (means2D is the caller's gradient SINK -- the reference's harness makes it require a gradient on every call -- so it
@@ -266,8 +287,11 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, semantics, opaciti
     _C._CALL.geometry_frozen = not any(isinstance(t, torch.Tensor) and t.requires_grad
                                        for t in (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
     try:
+        if selection is None:
+            return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations,
+                                             cov3Ds_precomp, raster_settings)
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations,
-                                         cov3Ds_precomp, raster_settings)
+                                         cov3Ds_precomp, raster_settings, selection, bool(selection_invert))
     finally:
         _C._CALL.inference = False
         _C._CALL.geometry_frozen = False
@@ -343,12 +367,22 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, semantics=None, scales=None,
-                rotations=None, cov3D_precomp=None):
+                rotations=None, cov3D_precomp=None, *, selection=None, selection_invert=False):
+        """The reference's call, plus two keyword-only extensions: `selection`, a contiguous torch.bool / torch.uint8 tensor
+        of P elements on the model's device -- only the Gaussians whose element is non-zero (`selection_invert=True`: zero) are
+        rendered, in place: nothing is gathered, the tensor is passed by pointer, radii and every gradient stay P-long."""
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        if selection is not None:
+            _C.check_selection(selection, int(means3D.shape[0]), means3D.device if means3D.is_cuda else None)
         shs, colors_precomp, semantics, scales, rotations, cov3D_precomp = _absent_to_empty(
             shs, colors_precomp, semantics, scales, rotations, cov3D_precomp)
-        return rasterize_gaussians(means3D, means2D, shs, colors_precomp, semantics, opacities, scales, rotations,
-                                   cov3D_precomp, self.raster_settings)
+        return rasterize_gaussians_selected(means3D, means2D, shs, colors_precomp, semantics, opacities, scales, rotations,
+                                            cov3D_precomp, self.raster_settings, selection, selection_invert)
+
+    # inspect.signature(forward) keeps reporting the reference's parameter list (diff_gaussian_rasterization/__init__.py:278-279,
+    # the drop-in surface): the two keyword-only parameters are this package's own and are documented above.
+    forward.__signature__ = inspect.Signature(
+        [p for p in inspect.signature(forward).parameters.values() if p.kind is not inspect.Parameter.KEYWORD_ONLY])
 
     def trace(self, means3D, means2D, opacities, shs=None, colors_precomp=None, img_sem=None, scales=None,
               rotations=None, cov3D_precomp=None):

@@ -198,8 +198,16 @@ def _screenspace_placeholder(xyz):
     return z.expand(xyz.shape[0], 3).detach().requires_grad_(True)
 
 
-def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, gaussian_mask=None):
-    """gaussian_renderer.render; `gaussian_mask` adds gui/gs_renderer.py:315-321's index-select."""
+def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, gaussian_mask=None,
+           in_place=False, mask_invert=False):
+    """gaussian_renderer.render; `gaussian_mask` adds gui/gs_renderer.py:315-321's index-select.
+
+    in_place=True hands `gaussian_mask` (bool / uint8 [P], contiguous, on the device) to the rasterizer as a SELECTION instead:
+    nothing is gathered, nothing synchronises, and `radii`, `visibility_filter` and `viewspace_points` are P-long (an
+    unselected Gaussian has radius 0 and zero gradient rows) -- the same four maps bit for bit.  mask_invert=True renders the
+    complement without forming ~gaussian_mask.  in_place with no mask is the plain render."""
+    if mask_invert and gaussian_mask is not None and not in_place:
+        gaussian_mask = gaussian_mask == 0  # (bool or uint8)
     screenspace_points = _screenspace_placeholder(pc.get_xyz)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
@@ -228,14 +236,17 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         colors_precomp = override_color
     semantics = pc.get_semantics
 
-    if gaussian_mask is not None:
+    selection = {}
+    if gaussian_mask is not None and in_place:
+        selection = dict(selection=gaussian_mask, selection_invert=bool(mask_invert))
+    elif gaussian_mask is not None:
         sel = lambda t: None if t is None else t[gaussian_mask]  # noqa: E731
         semantics, means3D, scales, rotations, opacity, shs = map(sel, (semantics, means3D, scales, rotations, opacity, shs))
         cov3D_precomp, colors_precomp, means2D = sel(cov3D_precomp), sel(colors_precomp), sel(means2D)
 
     rendered_image, rendered_sem, radii, depth, alpha = rasterizer(
         means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, semantics=semantics,
-        opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+        opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **selection)
     return RenderResult({"render": rendered_image, "semantics": rendered_sem, "depth": depth, "alpha": alpha,
                          "viewspace_points": screenspace_points, "radii": radii})
 
@@ -284,12 +295,12 @@ def render_views(cameras, pc, pipe, bg_color, loss_fn=None, streams=2, **render_
 
 
 def render_gui(viewpoint_camera, pc, bg_color, scaling_modifier=1.0, override_color=None, compute_cov3D_python=False,
-               convert_SHs_python=False, gaussian_mask=None):
+               convert_SHs_python=False, gaussian_mask=None, in_place=False, mask_invert=False):
     """gui/gs_renderer.py:231-348 (Renderer.render): same rasterizer call as render(), optional
     `gaussian_mask` index-select of every per-Gaussian tensor (:315-321), image clamped to [0,1] (:336),
-    result keyed "image" instead of "render"."""
+    result keyed "image" instead of "render".  in_place / mask_invert: as for render()."""
     pipe = PipelineParams(convert_SHs_python=convert_SHs_python, compute_cov3D_python=compute_cov3D_python)
-    out = render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, gaussian_mask)
+    out = render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, gaussian_mask, in_place, mask_invert)
     return {"image": out["render"].clamp(0, 1), "semantics": out["semantics"], "depth": out["depth"],
             "alpha": out["alpha"], "viewspace_points": out["viewspace_points"],
             "visibility_filter": out["visibility_filter"], "radii": out["radii"]}

@@ -524,7 +524,8 @@ def select_gaussians(pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh
 @torch.no_grad()
 def group_points(pc, selected: torch.Tensor, viewpoint_camera, bg_color: torch.Tensor, mlp: SemanticModel, lut: torch.Tensor,
                  score_fn, res_mask: torch.Tensor, eps: float = 0.35, min_samples: int = 600, keep_ratio: float = 0.7,
-                 thresh: float = 0.5, scaling_modifier: float = 1.0, gaussian_mask: torch.Tensor | None = None) -> torch.Tensor:
+                 thresh: float = 0.5, scaling_modifier: float = 1.0, gaussian_mask: torch.Tensor | None = None,
+                 in_place: bool = False, mask_invert: bool = False) -> torch.Tensor:
     """The cluster refinement of the retrieved Gaussians (gui/main.py:1595-1665, group_points) on the device.
 
     `selected` (bool [P], e.g. select_gaussians' result) picks the Gaussians whose positions pc.get_xyz are clustered with
@@ -541,7 +542,8 @@ def group_points(pc, selected: torch.Tensor, viewpoint_camera, bg_color: torch.T
     left as it was found and the caller applies the result (gui/main.py:1664 stores it as rel_gs_index).  The ratios are
     accumulated on the device: host synchronisations are the index gather of `selected` and dbscan's one read of the
     cluster count, none per cluster.  With rasterizer.set_geometry_cache on, the K renders of one camera share the
-    geometry: renders 2..K are blend-only."""
+    geometry: renders 2..K are blend-only.  in_place / mask_invert: how gaussian_mask is applied (render.render): handed to
+    the rasterizer as a selection instead of index-selecting the model for every cluster's render -- the same result."""
     from . import cluster
     from .render import render_gui
 
@@ -565,7 +567,8 @@ def group_points(pc, selected: torch.Tensor, viewpoint_camera, bg_color: torch.T
             member = torch.zeros(P, dtype=torch.bool, device=dev)
             member.index_put_((sel_idx,), labels == k)
             pc.set_semantic_masks(member)
-            out = render_gui(viewpoint_camera, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask)
+            out = render_gui(viewpoint_camera, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask, in_place=in_place,
+                             mask_invert=mask_invert)
             sem = compute_similarity(out["semantics"], mlp, lut, score_fn, thresh).reshape(-1) > 0
             n_sem = sem.sum()
             ratio = (sem & res).sum().float() / n_sem.float()
@@ -744,14 +747,15 @@ def _frame_args(mode, style, pc):
 def video_frames(cameras, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float, bg_color: torch.Tensor,
                  mode: str = "image", style="heat", overlay_ratio: float = 1.0, gaussian_mask=None,
                  scaling_modifier: float = 1.0, dtype: torch.dtype = torch.uint8, heat_thresh: float = 0.7,
-                 colormap: torch.Tensor | None = None) -> torch.Tensor:
+                 colormap: torch.Tensor | None = None, in_place: bool = False, mask_invert: bool = False) -> torch.Tensor:
     """The frames of render_video's loop (gui/main.py:1766-1801) for a camera set, [V, H, W, 3] on the device (uint8 as
     the reference saves them, or float32): every camera is rendered with render_gui and decoded with the fused decode
     into slot v of preallocated [V, ...] buffers, then ONE batched display.compose makes all the frames, each view with
     its own minimum and maximum.  `mode` picks the render's "image", "depth" (min-max normalised per view, as
     test_step's depth mode) or "alpha"; `style` is a display style (display.from_reference_flags maps the GUI's
     switches).  Styles that need no similarity skip the decode.  All cameras must share one H x W.  Nothing is read back
-    to the host."""
+    to the host -- with a gaussian_mask only when in_place=True hands it to the rasterizer as a selection (render.render;
+    mask_invert: its complement, the viewer's del mode): the default index-select synchronises once per frame."""
     from . import display
     from .render import render_gui
     code = _frame_args(mode, style, pc)
@@ -764,7 +768,8 @@ def video_frames(cameras, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, t
     mask = torch.empty((V, HW), dtype=torch.uint8, device=dev) if need_sim else None
     dec = _FrameDecoder(mlp, lut, score_fn, thresh, dev) if need_sim else None
     for v, cam in enumerate(cams):
-        out = render_gui(cam, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask)
+        out = render_gui(cam, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask, in_place=in_place,
+                         mask_invert=mask_invert)
         base[v].copy_(out[mode].reshape(base.shape[1:]))
         if need_sim:
             dec.decode(out["semantics"], sim[v], mask[v])
@@ -776,17 +781,19 @@ def video_frames(cameras, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, t
 def view_frame(camera, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float, bg_color: torch.Tensor,
                mode: str = "image", style="heat", overlay_ratio: float = 1.0, gaussian_mask=None,
                scaling_modifier: float = 1.0, dtype: torch.dtype = torch.float32, heat_thresh: float = 0.7,
-               colormap: torch.Tensor | None = None, return_parts: bool = False):
+               colormap: torch.Tensor | None = None, return_parts: bool = False, in_place: bool = False,
+               mask_invert: bool = False):
     """One displayed frame [H, W, 3] on the device: test_step with set_clip_mask (gui/main.py:549-604, :387-398) as
     render_gui, the fused decode with its uint8 background mask, and display.compose on the render's own tensor (no copy
     of the image).  `mode`, `style` and the rest as video_frames; float32 is what the viewer's texture takes.  Nothing is
-    read back to the host.  return_parts: also the dictionary {"base", "sim", "bg_mask"} the frame was composed from (sim
-    and bg_mask None for the styles that need no similarity)."""
+    read back to the host (with a gaussian_mask: when in_place=True, see video_frames).  return_parts: also the dictionary
+    {"base", "sim", "bg_mask"} the frame was composed from (sim and bg_mask None for the styles that need no similarity)."""
     from . import display
     from .render import render_gui
     code = _frame_args(mode, style, pc)
     dev = pc.get_xyz.device
-    out = render_gui(camera, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask)
+    out = render_gui(camera, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask, in_place=in_place,
+                     mask_invert=mask_invert)
     base = out[mode]
     base = base.reshape((-1,) + tuple(base.shape[-2:]))
     sim = mask = None

@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-/* 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
+/* 8: + goi_raster_forward_selected, goi_raster_forward_async_selected (a per-Gaussian selection the forward itself honours)
+ * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
  *    goi_raster_backward_scratch_bytes as ever);
  *    later additions: goi_semantic_frame_workspace_bytes, goi_semantic_frame_compose
@@ -66,7 +67,7 @@ extern "C" {
  *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
  * (3: + goi_raster_forward_reblend, goi_codebook_sim, goi_codebook_fused; 2: + the asynchronous forward; additions only) */
-#define GOI_RASTER_ABI_VERSION 7
+#define GOI_RASTER_ABI_VERSION 8
 
 typedef struct GoiRasterScene {
     int P;                       /* number of Gaussians */
@@ -182,6 +183,30 @@ const uint32_t* goi_raster_truncated_flag(const void* geom_buffer, int P);
 int goi_raster_forward_redo(const GoiRasterScene* scene, int num_rendered, void* geom_buffer, void* image_buffer,
                             void* binning_buffer, float* out_color, float* out_semantic, float* out_depth,
                             float* out_alpha, const int* radii, void* stream);
+
+/* ---- A SELECTION of the Gaussians, rendered in place (ABI 8) ----------------------------------------------------------------
+ * (the reference's viewer index-selects every per-Gaussian tensor by a boolean mask before it calls the rasterizer,
+ * gui/gs_renderer.py:315-321: a host synchronisation, a second copy of the selected set, and outputs of the subset's length)
+ *
+ * goi_raster_forward_selected / goi_raster_forward_async_selected are goi_raster_forward / goi_raster_forward_async with
+ *   keep   : [P] device bytes, one per Gaussian (never written; a torch.bool or torch.uint8 tensor as it is), or NULL;
+ *   invert : 0 -- Gaussian i is rendered iff keep[i] != 0;  non-zero -- iff keep[i] == 0 (the complement, without forming it).
+ * The frame is the frame of the selected Gaussians alone, bit for bit what the plain entry points produce for the
+ * index-selected arrays (outputs, num_rendered, and -- scattered to their ids -- radii and every gradient).  An unselected
+ * Gaussian is dropped by the first kernel before anything of it but its selection byte is read, exactly where a Gaussian
+ * behind the near plane is dropped: radii[i] = 0, no tile, no instance, zero gradient rows; it does not trip the
+ * `prefiltered` check.  All arrays stay [P]-long and are indexed by the caller's own ids.
+ * keep == NULL is the plain call.  Everything that reads the geometry workspace -- goi_raster_forward_redo, _reblend, every
+ * goi_raster_backward*, goi_raster_backward_semantics -- works behind a selected forward unchanged and takes no selection
+ * (a reblend shows the selection of the frame that filled the workspaces).  There is no selected _async_cut, trace or
+ * mark_visible. */
+int goi_raster_forward_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer,
+                                goi_alloc_fn binning_alloc, void* alloc_user,
+                                float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                                int* radii, const uint8_t* keep, int invert, void* stream);
+int goi_raster_forward_async_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
+                                      int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                                      int* radii, const uint8_t* keep, int invert, void* stream);
 
 /* The blend of a frame whose geometry and tile lists are already in workspaces filled by an earlier goi_raster_forward /
  * _async / _redo of the SAME camera over the SAME Gaussian geometry (positions, covariances, opacities, colours): only the
