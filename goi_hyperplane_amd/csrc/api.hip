@@ -478,6 +478,57 @@ size_t binning_layout(int N, char* base, BinView* v) {
     return (size_t)(p - base) + 256;
 }
 
+namespace {
+
+// What a finished forward left in the caller's opaque workspaces: the geometry state, the image state and the binning state of
+// the R instances the forward returned, with the final (tile-sorted) point list.  The image view stays zero where image is
+// NULL, the binning view and the list where binning is NULL (only a frame with R == 0 may come without one: callers check).
+struct FrameViews {
+    GeomView g;
+    ImageView im;
+    BinView bv;
+    const uint32_t* plist;
+};
+FrameViews frame_views(int P, int W, int H, int R, const void* geom, const void* image, const void* binning) {
+    FrameViews f{};
+    // (the views are the forward's, hence writable.  Through a const workspace an entry writes only what the frame keeps for
+    // that very entry: im.qorder, the member masks of a reblend.)
+    geom_layout(P, static_cast<char*>(const_cast<void*>(geom)), &f.g);
+    if (image) image_layout(W, H, static_cast<char*>(const_cast<void*>(image)), &f.im);
+    if (binning) {
+        binning_layout(R, static_cast<char*>(const_cast<void*>(binning)), &f.bv);
+        f.plist = f.bv.vals[tile_sort_result_index(W, H, R)];
+    }
+    return f;
+}
+
+// Starts a row backward on a scratch laid out for `cap` instances: the validity bytes of the slots this frame can use and
+// big_ctl are cleared by extra workgroups of the quadrant-order launch (count on the device: 4 x num_rendered bytes, not
+// 4 x capacity) -- or by memsets where that launch does not exist.  Returns 1 (the quadrant order is used), 0 or -1 (error).
+int start_row_backward(const GoiRasterScene& sc, const FrameViews& f, const BwdScratchView& scr, int cap, hipStream_t s) {
+    if (launch_quad_order(sc, f.im, s, scr.flags, f.g.counters + COUNTER_N, (uint32_t)cap, scr.big_ctl)) return 1;
+    GOI_HIP(hipMemsetAsync(scr.flags, 0, round_up_256((size_t)cap * 4), s));  // (the layout ends with 256 spare bytes)
+    GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
+    return 0;
+}
+
+// the per-tile backward blend accumulates with atomics: its six arrays (P Gaussians, S channels) start from zero
+int zero_blend_grads(const BlendGrads& b, size_t P, int S, hipStream_t s) {
+    GOI_HIP(hipMemsetAsync(b.dL_dmean2D, 0, 3 * P * sizeof(float), s));
+    GOI_HIP(hipMemsetAsync(b.dL_dconic, 0, 4 * P * sizeof(float), s));
+    GOI_HIP(hipMemsetAsync(b.dL_dopacity, 0, P * sizeof(float), s));
+    GOI_HIP(hipMemsetAsync(b.dL_dcolor, 0, 3 * P * sizeof(float), s));
+    GOI_HIP(hipMemsetAsync(b.dL_dsemantic, 0, (size_t)S * P * sizeof(float), s));
+    GOI_HIP(hipMemsetAsync(b.dL_ddepth, 0, P * sizeof(float), s));
+    return 0;
+}
+
+// the form of the row blend kernels the process-wide switches ask for (launch_render_bwd_rows / _sem)
+bool option_exact_flush() { return (g_options.bwd_variant & 15) == 2; }
+bool option_walk_masks() { return g_options.bwd_masks != 0; }
+
+}  // namespace
+
 }  // namespace goi
 
 using namespace goi;
@@ -555,7 +606,7 @@ int goi_raster_forward_async(const GoiRasterScene* scene, void* geom_buffer, voi
                              int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
                              int* radii, void* stream) {
     return forward_speculative(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic, out_depth,
-                               out_alpha, radii, nullptr, nullptr, nullptr, 0, stream);
+                               out_alpha, radii, /*zcut_in=*/nullptr, /*zcut_out=*/nullptr, /*keep=*/nullptr, /*invert=*/0, stream);
 }
 
 int goi_raster_forward_async_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
@@ -701,23 +752,18 @@ int goi_raster_forward_reblend(const GoiRasterScene* scene, int R, const void* g
         return fail("workspace pointer is NULL");
     if (!out_color || !out_semantic || !out_depth || !out_alpha) return fail("output pointer is NULL");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    GeomView g;
-    ImageView im_old, im;
-    BinView bv;
-    geom_layout(sc.P, static_cast<char*>(const_cast<void*>(geom_buffer)), &g);
-    image_layout(sc.W, sc.H, static_cast<char*>(const_cast<void*>(cached_image_buffer)), &im_old);
+    const FrameViews f = frame_views(sc.P, sc.W, sc.H, R, geom_buffer, cached_image_buffer, binning_buffer);
+    ImageView im;
     image_layout(sc.W, sc.H, static_cast<char*>(image_buffer), &im);
-    binning_layout(R, static_cast<char*>(const_cast<void*>(binning_buffer)), &bv);
     const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
     // the new frame gets its own image state (n_contrib is written by the blend and read by ITS backward); the tile ranges
     // are the cached frame's
-    GOI_HIP(hipMemcpyAsync(im.ranges, im_old.ranges, sizeof(uint2) * (size_t)gx * gy, hipMemcpyDeviceToDevice, s));
-    const uint32_t* plist = bv.vals[tile_sort_result_index(sc.W, sc.H, R)];
+    GOI_HIP(hipMemcpyAsync(im.ranges, f.im.ranges, sizeof(uint2) * (size_t)gx * gy, hipMemcpyDeviceToDevice, s));
     {
         // (the member masks of rounds >= 1 go into the CACHED binning workspace: they depend on geometry and tile lists only,
         // so every reblend of this camera writes the words that are already there)
         StageTimer t(GOI_STAGE_BLEND_FWD, s);
-        launch_render_fwd(sc, g, im, plist, out_color, out_semantic, out_depth, out_alpha, s, bv.qmask);
+        launch_render_fwd(sc, f.g, im, f.plist, out_color, out_semantic, out_depth, out_alpha, s, f.bv.qmask);
     }
     GOI_HIP(hipGetLastError());
     return 0;
@@ -750,30 +796,6 @@ int goi_raster_trace(const GoiRasterScene* scene, const float* img_sem, void* ge
     return N;
 }
 
-int goi_raster_backward(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,
-                        const void* image_buffer, const int* radii, const float* out_alpha, const float* dL_dout_color,
-                        const float* dL_dout_semantic, const float* dL_dout_depth, const float* dL_dout_alpha,
-                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
-                        float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                        float* dL_drot, void* scratch, void* stream) {
-    return goi_raster_backward2(scene, R, geom_buffer, binning_buffer, image_buffer, radii, out_alpha, dL_dout_color,
-                                dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
-                                dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch, nullptr,
-                                stream);
-}
-
-int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
-                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
-                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
-                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, void* stream) {
-    return goi_raster_backward4(scene, R, scratch_instances, flags, geom_buffer, binning_buffer, image_buffer, radii, out_alpha,
-                                dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic, dL_dopacity,
-                                dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch,
-                                prev_radii, nullptr, nullptr, stream);
-}
-
 int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
                          const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
                          const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
@@ -788,13 +810,14 @@ int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instanc
     const size_t P = (size_t)sc.P;
     if (P == 0) return 0;
     if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail("workspace pointer is NULL");
-    GeomView g;
-    ImageView im;
-    BinView bv;
-    geom_layout(sc.P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
-    image_layout(sc.W, sc.H, const_cast<char*>(static_cast<const char*>(image_buffer)), &im);
-    const int fin = tile_sort_result_index(sc.W, sc.H, R);
-    if (R > 0) binning_layout(R, const_cast<char*>(static_cast<const char*>(binning_buffer)), &bv);
+    const FrameViews f = frame_views(sc.P, sc.W, sc.H, R, geom_buffer, image_buffer, binning_buffer);
+    const PixelGrads dpix{dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha};
+    const BlendGrads blend{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth};
+    // what every branch below hands to the per-Gaussian backward; a branch adds its own source of the blend gradients
+    PreprocessBwdArgs pa;
+    pa.blend = blend;
+    pa.out = GaussGrads{dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
+    pa.row_mask = row_mask;
     const bool rows_path = scratch != nullptr && (g_options.bwd_variant & 15) != 1;
     if (scratch_instances < 0 || scratch_instances > R) return fail("scratch_instances must be in 0..R (0: the scratch is laid out for R)");
     // Rs: instances the ROW SCRATCH holds rows for (the binning workspace keeps R); every slot index is below 4 x num_rendered <= 4 Rs
@@ -811,64 +834,63 @@ int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instanc
         {
             StageTimer t(GOI_STAGE_BLEND_BWD, s);
             if (R > 0) {
-                // the validity bytes of the slots this frame can use are cleared by extra workgroups of the quadrant-order
-                // launch (count on the device: 4 x num_rendered bytes, not 4 x capacity) -- or by a memset where that
-                // launch does not exist
-                if (!launch_quad_order(sc, im, s, scr.flags, g.counters + COUNTER_N, (uint32_t)Rs, scr.big_ctl)) {
-                    GOI_HIP(hipMemsetAsync(scr.flags, 0, round_up_256((size_t)Rs * 4), s));  // (the layout ends with 256 spare bytes)
-                    GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
-                }
-                launch_render_bwd_rows(sc, g, im, bv.vals[fin], radii, out_alpha, dL_dout_color, dL_dout_semantic,
-                                       dL_dout_depth, dL_dout_alpha, scr, s, bv.qmask);
+                if (start_row_backward(sc, f, scr, Rs, s) < 0) return -1;
+                launch_render_bwd_rows(sc, f.g, f.im, f.plist, radii, out_alpha, dpix, scr, option_exact_flush(),
+                                       option_walk_masks(), s, f.bv.qmask);
             }
         }
         if (check_stage(sc, s, "backward blend")) return -1;
         StageTimer t(GOI_STAGE_PREPROCESS_BWD, s);
+        if (g_options.bwd_records) {  // the blend gradients stay in the row scratch; the kernel skips rows that hold zeros already
+            pa.rows = scr.rows;
+            pa.prev_radii = prev_radii;
+            pa.prev_mask = prev_mask;
+        }
         if (g_options.bwd_records == 2 && bwd_row_floats(sc.S) == 32 && R > 0 && !accumulate) {
             // the per-Gaussian backward sums its Gaussians' rows itself; only the BIG Gaussians pass through reduce_big_k's records
-            launch_reduce_big_only(sc, g, Rs, scr, s);
-            launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                  dL_dscale, dL_drot, s, scr.rows, dL_dopacity, dL_dsemantic, prev_radii, scr.flags, Rs, false, 0,
-                                  nullptr, prev_mask, row_mask);
+            launch_reduce_big_only(sc, f.g, Rs, scr, s);
+            pa.flags = scr.flags;
+            pa.n_cap = Rs;
         } else if (g_options.bwd_records) {
             // the sums stay in the row scratch (one record per listed Gaussian); preprocess_bwd_k writes the per-id outputs.
             // bwd_skip_idle: the reduction publishes a contribution byte per listed Gaussian and stores no all-zero record;
             // preprocess_bwd_k runs its chain only for the Gaussians that reached a pixel
             uint8_t* contrib = g_options.bwd_skip_idle ? scr.contrib : nullptr;
-            launch_reduce_rows(sc, g, Rs, scr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s, true, contrib);
-            launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                  dL_dscale, dL_drot, s, scr.rows, dL_dopacity, dL_dsemantic, prev_radii, nullptr, 0, accumulate, 0,
-                                  contrib, prev_mask, row_mask);
+            launch_reduce_rows(sc, f.g, Rs, scr, BlendGrads{}, s, true, contrib);
+            pa.contrib = contrib;
+            pa.accumulate = accumulate;
         } else {
             // (every row is written: the previous mask is not consulted, this frame's is still produced)
-            launch_reduce_rows(sc, g, Rs, scr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, s);
-            launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                  dL_dscale, dL_drot, s, nullptr, nullptr, nullptr, nullptr, nullptr, 0, false, 0, nullptr, nullptr,
-                                  row_mask);
+            launch_reduce_rows(sc, f.g, Rs, scr, blend, s);
         }
+        launch_preprocess_bwd(sc, f.g, radii, pa, s);
     } else {
-        // atomic path: the accumulated gradients start from zero
-        GOI_HIP(hipMemsetAsync(dL_dmean2D, 0, 3 * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dconic, 0, 4 * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dopacity, 0, P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dcolor, 0, 3 * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dsemantic, 0, (size_t)sc.S * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_ddepth, 0, P * sizeof(float), s));
+        // atomic path
+        if (zero_blend_grads(blend, P, sc.S, s) < 0) return -1;
         if (R > 0) {
             StageTimer t(GOI_STAGE_BLEND_BWD, s);
-            launch_render_bwd_tile(sc, g, im, bv.vals[fin], out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth,
-                                   dL_dout_alpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic,
-                                   dL_ddepth, s);
+            launch_render_bwd_tile(sc, f.g, f.im, f.plist, out_alpha, dpix, blend, s);
         }
         if (check_stage(sc, s, "backward blend")) return -1;
         StageTimer t(GOI_STAGE_PREPROCESS_BWD, s);
-        launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh,
-                              dL_dscale, dL_drot, s, nullptr, nullptr, nullptr, nullptr, nullptr, 0, false, 0, nullptr, nullptr,
-                              row_mask);
+        launch_preprocess_bwd(sc, f.g, radii, pa, s);
     }
     if (check_stage(sc, s, "backward preprocess")) return -1;
     GOI_HIP(hipGetLastError());
     return 0;
+}
+
+// The older entries: the same backward without the arguments that came later.
+int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
+                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
+                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
+                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, void* stream) {
+    return goi_raster_backward4(scene, R, scratch_instances, flags, geom_buffer, binning_buffer, image_buffer, radii, out_alpha,
+                                dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic, dL_dopacity,
+                                dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch,
+                                prev_radii, /*prev_mask=*/nullptr, /*row_mask=*/nullptr, stream);
 }
 
 int goi_raster_backward2(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,
@@ -877,10 +899,22 @@ int goi_raster_backward2(const GoiRasterScene* scene, int R, const void* geom_bu
                          float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
                          float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
                          float* dL_drot, void* scratch, const int* prev_radii, void* stream) {
-    return goi_raster_backward3(scene, R, 0, 0, geom_buffer, binning_buffer, image_buffer, radii, out_alpha, dL_dout_color,
-                                dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
-                                dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch, prev_radii,
-                                stream);
+    return goi_raster_backward4(scene, R, /*scratch_instances=*/0, /*flags=*/0, geom_buffer, binning_buffer, image_buffer, radii,
+                                out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic,
+                                dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                                scratch, prev_radii, /*prev_mask=*/nullptr, /*row_mask=*/nullptr, stream);
+}
+
+int goi_raster_backward(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,
+                        const void* image_buffer, const int* radii, const float* out_alpha, const float* dL_dout_color,
+                        const float* dL_dout_semantic, const float* dL_dout_depth, const float* dL_dout_alpha,
+                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
+                        float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                        float* dL_drot, void* scratch, void* stream) {
+    return goi_raster_backward4(scene, R, /*scratch_instances=*/0, /*flags=*/0, geom_buffer, binning_buffer, image_buffer, radii,
+                                out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic,
+                                dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                                scratch, /*prev_radii=*/nullptr, /*prev_mask=*/nullptr, /*row_mask=*/nullptr, stream);
 }
 
 int goi_raster_backward_semantics(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,
@@ -894,30 +928,21 @@ int goi_raster_backward_semantics(const GoiRasterScene* scene, int R, const void
     if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail("workspace pointer is NULL");
     if (!scratch) return fail("goi_raster_backward_semantics needs the scratch of goi_raster_backward_scratch_bytes");
     if (!dL_dout_semantic || !dL_dsemantic || !out_alpha || !radii) return fail("a required pointer is NULL");
-    GeomView g;
-    ImageView im;
-    BinView bv;
-    geom_layout(sc.P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
-    image_layout(sc.W, sc.H, const_cast<char*>(static_cast<const char*>(image_buffer)), &im);
-    const int fin = tile_sort_result_index(sc.W, sc.H, R);
-    if (R > 0) binning_layout(R, const_cast<char*>(static_cast<const char*>(binning_buffer)), &bv);
+    const FrameViews f = frame_views(sc.P, sc.W, sc.H, R, geom_buffer, image_buffer, binning_buffer);
     BwdScratchView scr;  // same allocation as the full backward; rows are narrower here
     bwd_scratch_layout(R, sc.S, static_cast<char*>(scratch), &scr);
     const int row_floats = bwd_sem_row_floats(sc.S);
     {
         StageTimer t(GOI_STAGE_BLEND_BWD, s);
         if (R > 0) {
-            if (!launch_quad_order(sc, im, s, scr.flags, g.counters + COUNTER_N, (uint32_t)R, scr.big_ctl)) {
-                GOI_HIP(hipMemsetAsync(scr.flags, 0, round_up_256((size_t)R * 4), s));  // (the layout ends with 256 spare bytes)
-                GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
-            }
-            launch_render_bwd_sem(sc, g, im, bv.vals[fin], radii, out_alpha, dL_dout_semantic, scr.rows, scr.flags,
-                                  row_floats, s, bv.qmask);
+            if (start_row_backward(sc, f, scr, R, s) < 0) return -1;
+            launch_render_bwd_sem(sc, f.g, f.im, f.plist, radii, out_alpha, dL_dout_semantic, scr.rows, scr.flags, row_floats,
+                                  option_exact_flush(), option_walk_masks(), s, f.bv.qmask);
         }
     }
     if (check_stage(sc, s, "backward blend (semantics)")) return -1;
     StageTimer t(GOI_STAGE_PREPROCESS_BWD, s);
-    launch_reduce_sem_rows(sc, g, R, scr, row_floats, dL_dsemantic, s);
+    launch_reduce_sem_rows(sc, f.g, R, scr, row_floats, dL_dsemantic, s);
     GOI_HIP(hipGetLastError());
     return 0;
 }
@@ -1346,9 +1371,7 @@ int goi_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, double
 
 const uint32_t* goi_raster_truncated_flag(const void* geom_buffer, int P) {
     if (!geom_buffer || P <= 0) return nullptr;
-    GeomView g;
-    geom_layout(P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
-    return g.counters + COUNTER_OVF;
+    return frame_views(P, 0, 0, 0, geom_buffer, nullptr, nullptr).g.counters + COUNTER_OVF;
 }
 
 int goi_adam_step_guarded(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
@@ -1454,13 +1477,8 @@ int goi_raster_blend_stats(int P, int W, int H, int R, const void* geom_buffer, 
     if (!geom_buffer || !image_buffer || !counters || (R > 0 && !binning_buffer)) return fail("workspace pointer is NULL");
     GOI_HIP(hipMemsetAsync(counters, 0, GOI_BLEND_STATS_WORDS * sizeof(unsigned long long), s));
     if (R == 0) return 0;
-    GeomView g;
-    ImageView im;
-    BinView bv;
-    geom_layout(P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
-    image_layout(W, H, const_cast<char*>(static_cast<const char*>(image_buffer)), &im);
-    binning_layout(R, const_cast<char*>(static_cast<const char*>(binning_buffer)), &bv);
-    launch_blend_stats(W, H, g, im, bv.vals[tile_sort_result_index(W, H, R)], bv.qmask, counters, s);
+    const FrameViews f = frame_views(P, W, H, R, geom_buffer, image_buffer, binning_buffer);
+    launch_blend_stats(W, H, f.g, f.im, f.plist, f.bv.qmask, counters, s);
     GOI_HIP(hipGetLastError());
     return 0;
 }
@@ -1471,10 +1489,9 @@ int goi_raster_debug_views(int P, int W, int H, int R, const void* geom_buffer, 
                            void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (P <= 0) return 0;
-    GeomView g;
-    ImageView im;
-    geom_layout(P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
-    image_layout(W, H, const_cast<char*>(static_cast<const char*>(image_buffer)), &im);
+    const FrameViews f = frame_views(P, W, H, R, geom_buffer, image_buffer, binning_buffer);
+    const GeomView& g = f.g;
+    const ImageView& im = f.im;
     const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
     // strided copies out of the 48-byte records
     const char* rec = reinterpret_cast<const char*>(g.rec);
@@ -1492,12 +1509,8 @@ int goi_raster_debug_views(int P, int W, int H, int R, const void* geom_buffer, 
     if (ranges) GOI_HIP(hipMemcpyAsync(ranges, im.ranges, sizeof(uint2) * gx * gy, hipMemcpyDeviceToDevice, s));
     if (n_contrib)
         GOI_HIP(hipMemcpyAsync(n_contrib, im.n_contrib, sizeof(uint32_t) * (size_t)W * H, hipMemcpyDeviceToDevice, s));
-    if (point_list && R > 0) {
-        BinView bv;
-        binning_layout(R, const_cast<char*>(static_cast<const char*>(binning_buffer)), &bv);
-        const int fin = tile_sort_result_index(W, H, R);
-        GOI_HIP(hipMemcpyAsync(point_list, bv.vals[fin], sizeof(uint32_t) * (size_t)R, hipMemcpyDeviceToDevice, s));
-    }
+    if (point_list && R > 0)
+        GOI_HIP(hipMemcpyAsync(point_list, f.plist, sizeof(uint32_t) * (size_t)R, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -1585,7 +1598,7 @@ int goi_raster_debug_reduce_row_floats(int mode, int S) {
 
 size_t goi_raster_debug_reduce_workspace_bytes(long long n_cap) {
     if (n_cap < 0 || n_cap > INT_MAX) return 0;
-    return debug_reduce_layout(n_cap, nullptr, nullptr, nullptr) + 256;
+    return debug_reduce_layout(n_cap, /*base=*/nullptr, /*counters=*/nullptr, /*v=*/nullptr) + 256;  // (sizes only)
 }
 
 int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const uint32_t* frame, const uint32_t* order,
@@ -1621,9 +1634,9 @@ int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const 
     GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
     const int N = (int)n_cap;
     if (mode == 0)
-        launch_reduce_rows(sc, g, N, scr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, s, false);
+        launch_reduce_rows(sc, g, N, scr, BlendGrads{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth}, s);
     else if (mode == 1)
-        launch_reduce_rows(sc, g, N, scr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s, true);
+        launch_reduce_rows(sc, g, N, scr, BlendGrads{}, s, true);
     else if (mode == 2)
         launch_reduce_big_only(sc, g, N, scr, s);
     else
@@ -1690,9 +1703,17 @@ int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source
     GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_N, frame + 0, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_V, frame + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_OVF, frame + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    launch_preprocess_bwd(sc, g, radii, dL_dmean2D, dL_dconic, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                          dL_drot, s, source != 0 ? rows : nullptr, dL_dopacity, dL_dsemantic, prev_radii,
-                          source == 2 ? row_flags : nullptr, (int)n_cap, accumulate, max_blocks);
+    PreprocessBwdArgs pa;
+    pa.blend = BlendGrads{dL_dmean2D, const_cast<float*>(dL_dconic), dL_dopacity, dL_dcolor, dL_dsemantic,
+                          const_cast<float*>(dL_ddepth)};  // (dL_dconic and dL_ddepth are only ever read)
+    pa.out = GaussGrads{dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
+    pa.rows = source != 0 ? rows : nullptr;
+    pa.flags = source == 2 ? row_flags : nullptr;
+    pa.n_cap = (int)n_cap;
+    pa.prev_radii = prev_radii;
+    pa.accumulate = accumulate;
+    pa.max_blocks = max_blocks;
+    launch_preprocess_bwd(sc, g, radii, pa, s);
     GOI_HIP(hipGetLastError());
     return 0;
 }
@@ -1708,8 +1729,7 @@ int goi_raster_debug_pair_eval(int P, int W, int H, const void* geom_buffer, con
     if (reinterpret_cast<uintptr_t>(requests) & 7u) return fail(fn + ": requests must be 8-byte aligned");
     if ((reinterpret_cast<uintptr_t>(E) & 3u) || (reinterpret_cast<uintptr_t>(alpha) & 3u))
         return fail(fn + ": E and alpha must be 4-byte aligned");
-    GeomView g;
-    geom_layout(P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
+    const GeomView g = frame_views(P, W, H, 0, geom_buffer, nullptr, nullptr).g;
     launch_pair_eval(P, W, H, g, requests, n_requests, E, alpha, guards, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
     return 0;
@@ -1754,57 +1774,41 @@ int goi_raster_debug_backward_blend(const GoiRasterScene* scene, int R, int mode
         (qmask && (reinterpret_cast<uintptr_t>(qmask) & 7u)))
         return fail(fn + ": aux must be 16-byte aligned, qmask0 and qmask 8-byte aligned");
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    GeomView g;
-    ImageView im;
-    BinView bv;
-    geom_layout(sc.P, const_cast<char*>(static_cast<const char*>(geom_buffer)), &g);
-    image_layout(sc.W, sc.H, const_cast<char*>(static_cast<const char*>(image_buffer)), &im);
-    binning_layout(R, const_cast<char*>(static_cast<const char*>(binning_buffer)), &bv);
-    const int fin = tile_sort_result_index(sc.W, sc.H, R);
+    const FrameViews f = frame_views(sc.P, sc.W, sc.H, R, geom_buffer, image_buffer, binning_buffer);
+    const PixelGrads dpix{dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha};
     const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
     const size_t n_quads = (size_t)gx * gy * 4;
-    bool ordered = false;
+    int ordered = 0;
     if (tile) {
-        const size_t P = (size_t)sc.P;
-        GOI_HIP(hipMemsetAsync(dL_dmean2D, 0, 3 * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dconic, 0, 4 * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dopacity, 0, P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dcolor, 0, 3 * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_dsemantic, 0, (size_t)sc.S * P * sizeof(float), s));
-        GOI_HIP(hipMemsetAsync(dL_ddepth, 0, P * sizeof(float), s));
-        launch_render_bwd_tile(sc, g, im, bv.vals[fin], out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha,
-                               dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, s);
+        const BlendGrads blend{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth};
+        if (zero_blend_grads(blend, (size_t)sc.P, sc.S, s) < 0) return -1;
+        launch_render_bwd_tile(sc, f.g, f.im, f.plist, out_alpha, dpix, blend, s);
     } else {
-        // the form of the kernel is the mode's, whatever the process-wide switches say (this thread's snapshot only)
-        g_options.bwd_variant = (mode & 1) ? 2 : 0;
-        g_options.bwd_masks = (mode & 2) ? 0 : 1;
+        // the form of the kernel is the mode's, whatever the process-wide switches say
+        const bool exact_flush = (mode & 1) != 0, walk_masks = (mode & 2) == 0;
         BwdScratchView scr;
         bwd_scratch_layout(R, sc.S, static_cast<char*>(scratch), &scr);
-        ordered = launch_quad_order(sc, im, s, scr.flags, g.counters + COUNTER_N, (uint32_t)R, scr.big_ctl);
-        if (!ordered) {
-            GOI_HIP(hipMemsetAsync(scr.flags, 0, round_up_256((size_t)R * 4), s));
-            GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
-        }
+        ordered = start_row_backward(sc, f, scr, R, s);
+        if (ordered < 0) return -1;
         const int row_floats = sem ? bwd_sem_row_floats(sc.S) : bwd_row_floats(sc.S);
         if (sem)
-            launch_render_bwd_sem(sc, g, im, bv.vals[fin], radii, out_alpha, dL_dout_semantic, scr.rows, scr.flags, row_floats, s,
-                                  bv.qmask);
+            launch_render_bwd_sem(sc, f.g, f.im, f.plist, radii, out_alpha, dL_dout_semantic, scr.rows, scr.flags, row_floats,
+                                  exact_flush, walk_masks, s, f.bv.qmask);
         else
-            launch_render_bwd_rows(sc, g, im, bv.vals[fin], radii, out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth,
-                                   dL_dout_alpha, scr, s, bv.qmask);
+            launch_render_bwd_rows(sc, f.g, f.im, f.plist, radii, out_alpha, dpix, scr, exact_flush, walk_masks, s, f.bv.qmask);
         GOI_HIP(hipGetLastError());
         GOI_HIP(hipMemcpyAsync(rows, scr.rows, (size_t)R * 4 * row_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
         GOI_HIP(hipMemcpyAsync(row_flags, scr.flags, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
     }
     GOI_HIP(hipGetLastError());
-    if (aux) GOI_HIP(hipMemcpyAsync(aux, g.aux, (size_t)sc.P * sizeof(uint4), hipMemcpyDeviceToDevice, s));
-    if (qmask0) GOI_HIP(hipMemcpyAsync(qmask0, im.qmask0, n_quads * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    if (aux) GOI_HIP(hipMemcpyAsync(aux, f.g.aux, (size_t)sc.P * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+    if (qmask0) GOI_HIP(hipMemcpyAsync(qmask0, f.im.qmask0, n_quads * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
     if (qmask)
-        GOI_HIP(hipMemcpyAsync(qmask, bv.qmask, 4 * ((size_t)R / 64 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
-    if (qcost) GOI_HIP(hipMemcpyAsync(qcost, im.qcost, n_quads * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        GOI_HIP(hipMemcpyAsync(qmask, f.bv.qmask, 4 * ((size_t)R / 64 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    if (qcost) GOI_HIP(hipMemcpyAsync(qcost, f.im.qcost, n_quads * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     if (qorder && ordered)
-        GOI_HIP(hipMemcpyAsync(qorder, im.qorder, 8 * ((n_quads + 7) / 8) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    return ordered ? 1 : 0;
+        GOI_HIP(hipMemcpyAsync(qorder, f.im.qorder, 8 * ((n_quads + 7) / 8) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    return ordered;
 }
 
 }  // extern "C"

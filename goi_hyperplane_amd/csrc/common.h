@@ -224,6 +224,21 @@ void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* re
                       uint8_t* guards, hipStream_t s);
 void launch_trace_fwd(const GoiRasterScene& sc, const float* img_sem, const GeomView& g, const ImageView& im,
                       const uint32_t* point_list, float* out_color, float* gau_sem, int* num_gsem, hipStream_t s);
+// ---- the backward's three gradient sets ---------------------------------------------------------
+// upstream gradients of the rendered images: [3,H,W], [S,H,W], [H,W], [H,W]
+struct PixelGrads {
+    const float *color, *semantic, *depth, *alpha;
+};
+// the blend gradients per Gaussian id: [P,3] (.z = 0), [P,2,2], [P], [P,3], [P,S], [P].  Passed to reduce_rows_k / reduce_big_k
+// by value: the member order is the kernel argument's layout.
+struct BlendGrads {
+    float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dsemantic, *dL_ddepth;
+};
+// what the per-Gaussian backward writes: [P,3], [P,6], [P,M,3] (or NULL: factored SH), [P,3], [P,4]
+struct GaussGrads {
+    float *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
+};
+
 // launch order of the backward's quadrant waves (render_bwd.hip): im.qcost -> im.qorder
 bool quad_order_enabled(int W, int H);
 // clear_flags != NULL: extra workgroups of the same launch zero the first 4 * min(*n_dev, cap) validity bytes of the backward
@@ -231,43 +246,53 @@ bool quad_order_enabled(int W, int H);
 // order is not used (quad_order_enabled).
 bool launch_quad_order(const GoiRasterScene& sc, const ImageView& im, hipStream_t s, uint8_t* clear_flags = nullptr,
                        const uint32_t* n_dev = nullptr, uint32_t cap = 0, uint32_t* clear_ctl = nullptr);
-// atomic-free backward blend: partial rows + flags into the scratch (render_bwd.hip)
-void launch_render_bwd_rows(const GoiRasterScene& sc, const GeomView& g, const ImageView& im,
-                            const uint32_t* point_list, const int* radii, const float* out_alpha, const float* dL_dpix,
-                            const float* dL_dsem, const float* dL_ddepth, const float* dL_dalpha,
-                            const BwdScratchView& scr, hipStream_t s, const unsigned long long* qmask = nullptr);
+// atomic-free backward blend: partial rows + flags into the scratch (render_bwd.hip).  The form of the kernel, here and in
+// launch_render_bwd_sem, is the caller's choice (the product: Options::bwd_variant == 2 and Options::bwd_masks):
+//   exact_flush: the exact-fp32 flush instead of the split-f16 MFMA flush;
+//   walk_masks : walk the MEMBER masks the forward blend left instead of testing every candidate (qmask == NULL: no masks
+//                of the rounds >= 1 to walk, candidates are tested whatever this says).
+void launch_render_bwd_rows(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
+                            const int* radii, const float* out_alpha, const PixelGrads& dpix, const BwdScratchView& scr,
+                            bool exact_flush, bool walk_masks, hipStream_t s, const unsigned long long* qmask = nullptr);
 // feature-gradient-only backward blend (render_bwd_sem.hip) and its row reduction: dL/dsemantics only
 void launch_render_bwd_sem(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                            const int* radii, const float* out_alpha, const float* dL_dsem, float* rows, uint8_t* flags,
-                           int row_floats, hipStream_t s, const unsigned long long* qmask = nullptr);
+                           int row_floats, bool exact_flush, bool walk_masks, hipStream_t s,
+                           const unsigned long long* qmask = nullptr);
 void launch_reduce_big_only(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, hipStream_t s);
 void launch_reduce_sem_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, int row_floats,
                             float* dL_dsemantic, hipStream_t s);
 // sums every Gaussian's partial rows (fixed order) into the six blend-gradient arrays (writes all P rows) -- or, `records`,
-// into one record per listed Gaussian, left in the row scratch over the Gaussian's first slot (the arrays may be NULL then)
-void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, float* dL_dmean2D,
-                        float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, float* dL_ddepth,
+// into one record per listed Gaussian, left in the row scratch over the Gaussian's first slot (`out` may be empty then)
+void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, const BlendGrads& out,
                         hipStream_t s, bool records = false,
                         uint8_t* contrib = nullptr);  // (records only) BwdScratchView::contrib, or NULL: every record is stored, no byte
-void launch_render_bwd_tile(const GoiRasterScene& sc, const GeomView& g, const ImageView& im,
-                            const uint32_t* point_list, const float* out_alpha, const float* dL_dpix,
-                            const float* dL_dsem, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmean2D,
-                            float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
-                            float* dL_ddepths, hipStream_t s);
+void launch_render_bwd_tile(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
+                            const float* out_alpha, const PixelGrads& dpix, const BlendGrads& out, hipStream_t s);
 void launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* campos, const float* gcol,
                                float* dL_dsh, hipStream_t s);
-// record_rows != NULL: the blend gradients are the per-Gaussian records reduce_rows left in the row scratch, and the kernel
-// writes dL_dmean2D, dL_dcolor, dL_dopacity and dL_dsemantic itself (dL_dconic / dL_ddepth are then neither read nor written)
-void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, float* dL_dmean2D,
-                           const float* dL_dconic, float* dL_dcolor, const float* dL_ddepth, float* dL_dmean3D,
-                           float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, hipStream_t s,
-                           const float* record_rows = nullptr, float* dL_dopacity = nullptr, float* dL_dsemantic = nullptr,
-                           const int* prev_radii = nullptr,  // prev_radii: BwdArgs (rows that already hold zeros)
-                           const uint8_t* row_flags = nullptr, int N_cap = 0,  // row_flags: the kernel sums the rows itself (bwd_records 2)
-                           bool accumulate = false,  // add to the outputs instead of writing them (record path only: BwdArgs::accumulate)
-                           int max_blocks = 0,  // > 0: cap on the persistent grid (the test entry; the product passes 0: its own choice)
-                           const uint8_t* contrib = nullptr,  // (records only) BwdScratchView::contrib: idle visible Gaussians skip the chain
-                           const uint8_t* prev_mask = nullptr, uint8_t* row_mask = nullptr);  // BwdArgs (may be the same array)
+// What launch_preprocess_bwd works on besides the scene and the forward's geometry state.  Value-initialised: a caller names
+// what it uses.
+struct PreprocessBwdArgs {
+    // The blend gradients.  Without `rows` all six arrays are inputs (dL_dmean2D and dL_dcolor are also written).  With `rows`
+    // the kernel writes dL_dmean2D, dL_dcolor, dL_dopacity and dL_dsemantic itself; dL_dconic / dL_ddepth are then neither read
+    // nor written.
+    BlendGrads blend{};
+    GaussGrads out{};
+    // Where the blend gradients come from:
+    const float* rows = nullptr;     // NULL: the six arrays; otherwise the row scratch with the records reduce_rows left in it ...
+    const uint8_t* flags = nullptr;  // ... or, with its validity bytes given, the rows themselves: the kernel sums them (bwd_records 2)
+    int n_cap = 0;                   // (with flags) instances the row scratch was laid out for
+    const uint8_t* contrib = nullptr;  // (records only) BwdScratchView::contrib: idle visible Gaussians skip the chain
+    // What the output buffers already hold (BwdArgs in preprocess.hip):
+    const int* prev_radii = nullptr;     // rows that already hold zeros
+    const uint8_t* prev_mask = nullptr;  // the same per row ...
+    uint8_t* row_mask = nullptr;         // ... and what this call leaves (may be the same array)
+    bool accumulate = false;  // add to the outputs instead of writing them (record path only: BwdArgs::accumulate)
+    int max_blocks = 0;       // > 0: cap on the persistent grid (the test entry; the product passes 0: its own choice)
+};
+void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, const PreprocessBwdArgs& args,
+                           hipStream_t s);
 int launch_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
                            const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
                            hipStream_t s);

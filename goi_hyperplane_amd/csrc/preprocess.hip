@@ -1182,17 +1182,15 @@ void launch_preprocess_fwd(const GoiRasterScene& sc, const GeomView& g, int* rad
 #undef GOI_PRE
 }
 
-void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, float* dL_dmean2D,
-                           const float* dL_dconic, float* dL_dcolor, const float* dL_ddepth, float* dL_dmean3D,
-                           float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, hipStream_t s,
-                           const float* record_rows, float* dL_dopacity, float* dL_dsemantic, const int* prev_radii,
-                           const uint8_t* row_flags, int N_cap, bool accumulate, int max_blocks, const uint8_t* contrib,
-                           const uint8_t* prev_mask, uint8_t* row_mask) {
+void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, const PreprocessBwdArgs& args,
+                           hipStream_t s) {
+    const BlendGrads& bl = args.blend;
+    const GaussGrads& out = args.out;
     BwdArgs a;
-    a.prev_radii = prev_radii;
-    a.prev_mask = prev_mask;
-    a.row_mask = row_mask;
-    a.accumulate = accumulate ? 1 : 0;
+    a.prev_radii = args.prev_radii;
+    a.prev_mask = args.prev_mask;
+    a.row_mask = args.row_mask;
+    a.accumulate = args.accumulate ? 1 : 0;
     a.P = sc.P; a.D = sc.D; a.M = sc.M; a.W = sc.W; a.H = sc.H;
     a.means3D = sc.means3D; a.shs = sc.shs; a.scales = sc.scales; a.rotations = sc.rotations;
     a.cov3D = sc.cov3D_precomp ? sc.cov3D_precomp : g.cov3D;
@@ -1200,18 +1198,18 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
     a.focal_y = sc.H / (2.0f * sc.tan_fovy);
     a.focal_x = sc.W / (2.0f * sc.tan_fovx);
     a.view_p = sc.viewmatrix; a.proj_p = sc.projmatrix; a.campos_p = sc.campos;
-    const bool with_sh = sc.shs && sc.M > 0 && dL_dsh;  // dL_dsh == NULL with SH colours: factored mode
-    // record_rows: the blend gradients are the records reduce_rows_k<.., RECORD> left in the row scratch -- or, with row_flags
+    const bool with_sh = sc.shs && sc.M > 0 && out.dL_dsh;  // dL_dsh == NULL with SH colours: factored mode
+    // args.rows: the blend gradients are the records reduce_rows_k<.., RECORD> left in the row scratch -- or, with args.flags
     // (bwd_records 2), the rows themselves: the kernel sums them (128-byte rows only: the caller checks)
-    const bool fused = record_rows != nullptr && row_flags != nullptr;
+    const bool fused = args.rows != nullptr && args.flags != nullptr;
     const int tile_rows = fused ? BWD_TILE_ROWS_FUSED : BWD_TILE_ROWS_DEFAULT;
     const size_t lds = with_sh ? (size_t)tile_rows * (3 * sc.M + 1) * sizeof(float) : 0;  // 43.9 KB at M = 16 (40.8 fused)
     RecArgs ra;
-    ra.rows = record_rows; ra.aux = g.aux; ra.tiles_touched = g.tiles_touched;
+    ra.rows = args.rows; ra.aux = g.aux; ra.tiles_touched = g.tiles_touched;
     ra.row_floats = bwd_row_floats(sc.S); ra.S = sc.S; ra.nch = 4 * ((sc.S + 3) / 4) + 4;
-    ra.dL_dopacity = dL_dopacity; ra.dL_dsemantic = dL_dsemantic;
-    ra.flags = row_flags; ra.n_dev = g.counters + COUNTER_N; ra.N_cap = (uint32_t)std::max(N_cap, 0);
-    ra.contrib = (record_rows != nullptr && !fused) ? contrib : nullptr;
+    ra.dL_dopacity = bl.dL_dopacity; ra.dL_dsemantic = bl.dL_dsemantic;
+    ra.flags = args.flags; ra.n_dev = g.counters + COUNTER_N; ra.N_cap = (uint32_t)std::max(args.n_cap, 0);
+    ra.contrib = (args.rows != nullptr && !fused) ? args.contrib : nullptr;
     // persistent workgroups: every CU gets as many as fit (registers and the staging tile: BWD_BLOCKS_PER_CU), each walks
     // segments of 256 ids
     static const int n_cu = []() {
@@ -1221,17 +1219,17 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
     }();
     // max_blocks > 0 (goi_raster_debug_preprocess_backward only): fewer persistent workgroups, each walking more segments
     int blocks = std::min((sc.P + 255) / 256, n_cu * BWD_BLOCKS_PER_CU);
-    if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+    if (args.max_blocks > 0) blocks = std::min(blocks, args.max_blocks);
     const dim3 grid((unsigned)blocks);
-#define GOI_PBWD(DSH, SRC, LDS)                                                                                             \
-    preprocess_bwd_k<DSH, SRC><<<grid, dim3(256), LDS, s>>>(a, radii, g.counters, g.clamped, dL_dmean2D, dL_dconic, dL_dcolor, \
-                                                            dL_ddepth, ra, dL_dmean3D, dL_dcov3D, DSH ? dL_dsh : nullptr,      \
-                                                            dL_dscale, dL_drot)
+#define GOI_PBWD(DSH, SRC, LDS)                                                                                           \
+    preprocess_bwd_k<DSH, SRC><<<grid, dim3(256), LDS, s>>>(a, radii, g.counters, g.clamped, bl.dL_dmean2D, bl.dL_dconic,     \
+                                                            bl.dL_dcolor, bl.dL_ddepth, ra, out.dL_dmean3D, out.dL_dcov3D,   \
+                                                            DSH ? out.dL_dsh : nullptr, out.dL_dscale, out.dL_drot)
     if (with_sh && fused) GOI_PBWD(true, 2, lds);
-    else if (with_sh && record_rows) GOI_PBWD(true, 1, lds);
+    else if (with_sh && args.rows) GOI_PBWD(true, 1, lds);
     else if (with_sh) GOI_PBWD(true, 0, lds);
     else if (fused) GOI_PBWD(false, 2, 0);
-    else if (record_rows) GOI_PBWD(false, 1, 0);
+    else if (args.rows) GOI_PBWD(false, 1, 0);
     else GOI_PBWD(false, 0, 0);
 #undef GOI_PBWD
 }

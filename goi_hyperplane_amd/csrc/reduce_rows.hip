@@ -60,15 +60,11 @@ namespace {
 constexpr uint32_t BIG_INST = REDUCE_BIG_INST;  // (common.h: the scratch layout sizes the descriptor list from it)
 constexpr uint32_t HUGE_INST = REDUCE_HUGE_INST;
 
-struct ReduceOut {
-    float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dsemantic, *dL_ddepth;
-};
-
 // What a Gaussian's summed row turns into: its RECORD (back into the row scratch, over the first slot it owns), or the six
 // per-id arrays.  Lane e of the quarter wave holds elements 2e, 2e+1 (K == 2) or e, e + 16, .. of the row.
 template <int K, bool RECORD>
 __device__ __forceinline__ void store_sums(const float (&sum)[K], float* rows, size_t inst0, uint32_t g, int e, int S, int nch,
-                                           const ReduceOut& o) {
+                                           const BlendGrads& o) {
     constexpr int RF = 16 * K;
     if constexpr (RECORD) {
         float* dst = rows + inst0 * 4 * RF;  // (the row elements this lane summed, back where it read them)
@@ -113,7 +109,7 @@ __global__ __launch_bounds__(256) void reduce_rows_k(int P, int S, int nch, uint
                                                      const uint32_t* __restrict__ order,
                                                      const uint32_t* __restrict__ offsets,
                                                      const uint32_t* __restrict__ tiles_touched,
-                                                     float* rows, const uint8_t* __restrict__ flags, ReduceOut out,
+                                                     float* rows, const uint8_t* __restrict__ flags, BlendGrads out,
                                                      uint32_t* __restrict__ big_ctl, uint4* __restrict__ big_desc,
                                                      uint32_t cap_big, uint8_t* __restrict__ contrib) {
     // N_cap: the slot capacity the scratch was laid out for; n_dev: the forward's instance count on the device (the
@@ -246,7 +242,7 @@ constexpr int BIG_PARTS = 64, MID_PARTS = 16;
 template <int K, bool RECORD>
 __global__ __launch_bounds__(16 * BIG_PARTS) void reduce_big_k(const uint32_t* __restrict__ big_ctl,
                                                               const uint4* __restrict__ big_desc, uint32_t cap_big, float* rows,
-                                                              const uint8_t* __restrict__ flags, int S, int nch, ReduceOut out,
+                                                              const uint8_t* __restrict__ flags, int S, int nch, BlendGrads out,
                                                               uint8_t* __restrict__ contrib) {
     constexpr int RF = 16 * K;
     __shared__ float s_part[BIG_PARTS][RF];
@@ -323,7 +319,7 @@ constexpr size_t REDUCE_BIG_GRID = GOI_REDUCE_BIG_GRID;
 constexpr int REDUCE_LARGE_SCENE = GOI_REDUCE_LARGE_SCENE;  // Gaussians from which reduce_rows_k keeps 16 instead of 32 rows in flight
 template <int K, bool RECORD>
 static void launch_reduce_k(const GoiRasterScene& sc, const GeomView& g, int N, int nch, float* rows, const uint8_t* flags,
-                            const BwdScratchView& scr, const ReduceOut& out, hipStream_t s, uint8_t* contrib = nullptr) {
+                            const BwdScratchView& scr, const BlendGrads& out, hipStream_t s, uint8_t* contrib = nullptr) {
     const dim3 grid((sc.P + 16 * REDUCE_GPQ - 1) / (16 * REDUCE_GPQ));
     const uint32_t* order = g.sort_vals[depth_sort_result_index()];
     if (sc.P >= REDUCE_LARGE_SCENE && GOI_REDUCE_INFLIGHT > 16)  // (one Gaussian per quarter wave there as well: 3 M 250 -> 227 us, 6 M 420 -> 377)
@@ -342,11 +338,9 @@ static void launch_reduce_k(const GoiRasterScene& sc, const GeomView& g, int N, 
 }
 
 // records: the sums stay in the row scratch as per-Gaussian records (see reduce_rows_k); the six arrays are not written
-void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, float* dL_dmean2D,
-                        float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, float* dL_ddepth,
+void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, const BlendGrads& out,
                         hipStream_t s, bool records, uint8_t* contrib) {
     const int rf = bwd_row_floats(sc.S), nch = 4 * ((sc.S + 3) / 4) + 4;
-    const ReduceOut out{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth};
 #define GOI_REDUCE(K)                                                                   \
     do {                                                                                \
         if (records) launch_reduce_k<K, true>(sc, g, N, nch, scr.rows, scr.flags, scr, out, s, contrib);  \
@@ -363,7 +357,7 @@ void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, cons
 void launch_reduce_big_only(const GoiRasterScene& sc, const GeomView& g, int N, const BwdScratchView& scr, hipStream_t s) {
     if (N <= 0) return;
     const int nch = 4 * ((sc.S + 3) / 4) + 4;
-    const ReduceOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const BlendGrads out{};
     const uint32_t* order = g.sort_vals[depth_sort_result_index()];
     find_big_k<<<dim3((sc.P + 255) / 256), dim3(256), 0, s>>>((uint32_t)N, g.counters + COUNTER_N, order, g.offsets, scr.big_ctl,
                                                              scr.big_desc, (uint32_t)scr.cap_big);
@@ -375,7 +369,8 @@ void launch_reduce_sem_rows(const GoiRasterScene& sc, const GeomView& g, int N, 
                             float* dL_dsemantic, hipStream_t s) {
     // rows hold semantic channels only: with nch = row_floats + 4 every element index is a semantic one
     const int nch = row_floats + 4;
-    const ReduceOut out{nullptr, nullptr, nullptr, nullptr, dL_dsemantic, nullptr};
+    BlendGrads out{};
+    out.dL_dsemantic = dL_dsemantic;
     if (row_floats == 16) launch_reduce_k<1, false>(sc, g, N, nch, scr.rows, scr.flags, scr, out, s);
     else launch_reduce_k<2, false>(sc, g, N, nch, scr.rows, scr.flags, scr, out, s);
 }

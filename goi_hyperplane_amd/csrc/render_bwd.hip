@@ -704,18 +704,17 @@ __global__ __launch_bounds__(QO_THREADS) void quad_order_k(const uint32_t* __res
 
 template <int S4>
 void launch_bwd_rows_s4(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
-                        const int* radii, const float* out_alpha, const float* dL_dpix, const float* dL_dsem,
-                        const float* dL_ddepth, const float* dL_dalpha, const BwdScratchView& scr, hipStream_t s,
-                        const unsigned long long* qmask) {
+                        const int* radii, const float* out_alpha, const PixelGrads& dpix, const BwdScratchView& scr,
+                        bool exact_flush, bool walk_masks, hipStream_t s, const unsigned long long* qmask) {
     const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
     const int n_quads = gx * gy * 4;
 #define GOI_LAUNCH_ROWS(F16, MASKS)                                                                                    \
     render_bwd_rows_k<S4, F16, MASKS><<<dim3(quad_grid(n_quads)), dim3(64), 0, s>>>(                                     \
         im.ranges, point_list, sc.W, sc.H, gx, gy, n_quads, sc.S, g.rec, sc.semantics, radii, g.aux, sc.bg, out_alpha, \
-        im.n_contrib, dL_dpix, dL_dsem, dL_ddepth, dL_dalpha, scr.rows, scr.flags, bwd_row_floats(sc.S),                 \
+        im.n_contrib, dpix.color, dpix.semantic, dpix.depth, dpix.alpha, scr.rows, scr.flags, bwd_row_floats(sc.S),    \
         g.counters, quad_order_enabled(sc.W, sc.H) ? im.qorder : nullptr, im.qmask0, qmask, im.qcost)
-    const bool masks = qmask != nullptr && g_options.bwd_masks != 0;
-    if ((g_options.bwd_variant & 15) == 2) {  // exact-fp32 flush
+    const bool masks = qmask != nullptr && walk_masks;
+    if (exact_flush) {
         if (masks) GOI_LAUNCH_ROWS(false, true);
         else GOI_LAUNCH_ROWS(false, false);
     } else {  // split-f16 flush
@@ -744,12 +743,10 @@ bool launch_quad_order(const GoiRasterScene& sc, const ImageView& im, hipStream_
     return true;
 }
 
-void launch_render_bwd_rows(const GoiRasterScene& sc, const GeomView& g, const ImageView& im,
-                            const uint32_t* point_list, const int* radii, const float* out_alpha, const float* dL_dpix,
-                            const float* dL_dsem, const float* dL_ddepth, const float* dL_dalpha,
-                            const BwdScratchView& scr, hipStream_t s, const unsigned long long* qmask) {
-#define GOI_CALL(N) \
-    launch_bwd_rows_s4<N>(sc, g, im, point_list, radii, out_alpha, dL_dpix, dL_dsem, dL_ddepth, dL_dalpha, scr, s, qmask)
+void launch_render_bwd_rows(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
+                            const int* radii, const float* out_alpha, const PixelGrads& dpix, const BwdScratchView& scr,
+                            bool exact_flush, bool walk_masks, hipStream_t s, const unsigned long long* qmask) {
+#define GOI_CALL(N) launch_bwd_rows_s4<N>(sc, g, im, point_list, radii, out_alpha, dpix, scr, exact_flush, walk_masks, s, qmask)
     GOI_DISPATCH_S4(sc.S, GOI_CALL)
 #undef GOI_CALL
 }

@@ -264,15 +264,15 @@ __global__ __launch_bounds__(64) void render_bwd_sem_k(
 template <int S4>
 void launch_bwd_sem_s4(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                        const int* radii, const float* out_alpha, const float* dL_dsem, float* rows, uint8_t* flags,
-                       int row_floats, hipStream_t s, const unsigned long long* qmask) {
+                       int row_floats, bool exact_flush, bool walk_masks, hipStream_t s, const unsigned long long* qmask) {
     const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
     const int n_quads = gx * gy * 4;
 #define GOI_LAUNCH_SEM(SP, MK)                                                                                         \
     render_bwd_sem_k<S4, SP, MK><<<dim3(quad_grid(n_quads)), dim3(64), 0, s>>>(                                          \
         im.ranges, point_list, sc.W, sc.H, gx, gy, n_quads, sc.S, g.rec, radii, g.aux, out_alpha, im.n_contrib, dL_dsem, \
         rows, flags, row_floats, g.counters, quad_order_enabled(sc.W, sc.H) ? im.qorder : nullptr, im.qmask0, qmask, im.qcost)
-    const bool masks = qmask != nullptr && g_options.bwd_masks != 0;
-    if ((g_options.bwd_variant & 15) == 2) {  // exact-fp32 flush, as in the full backward
+    const bool masks = qmask != nullptr && walk_masks;
+    if (exact_flush) {  // as in the full backward
         if (masks) GOI_LAUNCH_SEM(false, true);
         else GOI_LAUNCH_SEM(false, false);
     } else {
@@ -287,8 +287,10 @@ void launch_bwd_sem_s4(const GoiRasterScene& sc, const GeomView& g, const ImageV
 // rows: [4N][row_floats] with row_floats = 16 * ceil(4*ceil(S/4) / 16); flags [4N] zeroed by the caller
 void launch_render_bwd_sem(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                            const int* radii, const float* out_alpha, const float* dL_dsem, float* rows, uint8_t* flags,
-                           int row_floats, hipStream_t s, const unsigned long long* qmask) {
-#define GOI_CALL(N) launch_bwd_sem_s4<N>(sc, g, im, point_list, radii, out_alpha, dL_dsem, rows, flags, row_floats, s, qmask)
+                           int row_floats, bool exact_flush, bool walk_masks, hipStream_t s, const unsigned long long* qmask) {
+#define GOI_CALL(N)                                                                                                        \
+    launch_bwd_sem_s4<N>(sc, g, im, point_list, radii, out_alpha, dL_dsem, rows, flags, row_floats, exact_flush, walk_masks, s, \
+                         qmask)
     GOI_DISPATCH_S4(sc.S, GOI_CALL)
 #undef GOI_CALL
 }

@@ -326,25 +326,19 @@ __global__ __launch_bounds__(256) void render_bwd_tile_k(
 
 template <int S4>
 void launch_bwd_tile_s4(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
-                   const float* out_alpha, const float* dL_dpix, const float* dL_dsem, const float* dL_ddepth,
-                   const float* dL_dalpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                   float* dL_dsemantic, float* dL_ddepths, hipStream_t s) {
+                        const float* out_alpha, const PixelGrads& dpix, const BlendGrads& out, hipStream_t s) {
     const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
     render_bwd_tile_k<S4><<<dim3(gx * gy), dim3(256), 0, s>>>(im.ranges, point_list, sc.W, sc.H, gx, sc.S, g.rec, sc.semantics,
-                                                       sc.bg, out_alpha, im.n_contrib, dL_dpix, dL_dsem, dL_ddepth,
-                                                       dL_dalpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
-                                                       dL_dsemantic, dL_ddepths, g.counters);
+                                                       sc.bg, out_alpha, im.n_contrib, dpix.color, dpix.semantic, dpix.depth,
+                                                       dpix.alpha, out.dL_dmean2D, out.dL_dconic, out.dL_dopacity,
+                                                       out.dL_dcolor, out.dL_dsemantic, out.dL_ddepth, g.counters);
 }
 
 }  // namespace
 
 void launch_render_bwd_tile(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
-                       const float* out_alpha, const float* dL_dpix, const float* dL_dsem, const float* dL_ddepth,
-                       const float* dL_dalpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                       float* dL_dcolor, float* dL_dsemantic, float* dL_ddepths, hipStream_t s) {
-#define GOI_CALL(N)                                                                                              \
-    launch_bwd_tile_s4<N>(sc, g, im, point_list, out_alpha, dL_dpix, dL_dsem, dL_ddepth, dL_dalpha, dL_dmean2D, dL_dconic, \
-                     dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepths, s)
+                            const float* out_alpha, const PixelGrads& dpix, const BlendGrads& out, hipStream_t s) {
+#define GOI_CALL(N) launch_bwd_tile_s4<N>(sc, g, im, point_list, out_alpha, dpix, out, s)
     GOI_DISPATCH_S4(sc.S, GOI_CALL)
 #undef GOI_CALL
 }
