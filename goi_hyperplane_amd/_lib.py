@@ -105,6 +105,12 @@ SYMBOLS = {
     "goi_semantic_frame_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p]),
+    "goi_semantic_pca_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "goi_semantic_pca_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p]),
+    "goi_semantic_pca_solve": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "goi_semantic_pca_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_double,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "goi_codebook_unique_rows_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "goi_codebook_unique_rows": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_longlong), C.POINTER(C.c_uint), ALLOC_FN,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -332,6 +332,13 @@ void launch_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views
 void launch_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, long long HW,
                           int style, int normalize, float ratio, float one_minus_ratio, float heat_thresh, const float* table,
                           int n_colors, void* out, int out_dtype, uint32_t* stats, hipStream_t s);
+size_t pca_fit_workspace_bytes(int S);
+size_t pca_stats_bytes(int n_views);
+void launch_pca_accumulate(const float* x, int layout, int S, long long n, const uint8_t* mask, int first, void* workspace,
+                           hipStream_t s);
+void launch_pca_solve(int S, void* workspace, float* basis, hipStream_t s);
+void launch_pca_apply(const float* x, int in_layout, int S, long long n, int n_views, const float* basis, int normalize,
+                      float two_k, float* out, int out_layout, uint32_t* stats, hipStream_t s);
 size_t uniq_workspace_bytes(int V, int D, uint32_t HW);
 uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW);  // [V] counts, then the flag word
 void launch_uniq_dedup(const float* const* maps, int V, int D, uint32_t HW, void* ws, hipStream_t s);

@@ -700,7 +700,7 @@ def evaluate_cameras(cameras, gt_masks: torch.Tensor, pc, mlp: SemanticModel, lu
 
 
 # ---- the viewer's frame (gui/main.py:549-604 test_step, :387-398 set_clip_mask, :1766-1801 render_video) -----------------
-FRAME_MODES = ("image", "depth", "alpha")
+FRAME_MODES = ("image", "depth", "alpha", "semantics")
 
 
 class _FrameDecoder:
@@ -734,10 +734,20 @@ class _FrameDecoder:
             raise RuntimeError(_lib.last_error())
 
 
-def _frame_args(mode, style, pc):
-    from . import display
+def _alpha_mask(out, pca_mask_alpha):
+    """The samples a frame's own PCA fit uses: alpha > pca_mask_alpha (None: every pixel)."""
+    return None if pca_mask_alpha is None else out["alpha"].reshape(-1) > float(pca_mask_alpha)
+
+
+def _frame_args(mode, style, pc, basis=None, pca_normalize="sigma"):
+    from . import display, pca
     if mode not in FRAME_MODES:
         raise ValueError(f"mode must be one of {FRAME_MODES}, got {mode!r}")
+    if mode == "semantics":
+        if pca_normalize not in pca.NORMALIZATIONS:
+            raise ValueError(f"pca_normalize must be one of {sorted(pca.NORMALIZATIONS)}, got {pca_normalize!r}")
+        if basis is not None and not isinstance(basis, pca.PcaBasis):
+            raise TypeError(f"basis must be a pca.PcaBasis, got {type(basis).__name__}")
     if not pc.get_xyz.is_cuda:
         raise RuntimeError(_NO_CPU)
     return display._style(style)
@@ -747,7 +757,8 @@ def _frame_args(mode, style, pc):
 def video_frames(cameras, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float, bg_color: torch.Tensor,
                  mode: str = "image", style="heat", overlay_ratio: float = 1.0, gaussian_mask=None,
                  scaling_modifier: float = 1.0, dtype: torch.dtype = torch.uint8, heat_thresh: float = 0.7,
-                 colormap: torch.Tensor | None = None, in_place: bool = False, mask_invert: bool = False) -> torch.Tensor:
+                 colormap: torch.Tensor | None = None, in_place: bool = False, mask_invert: bool = False, basis=None,
+                 pca_normalize: str = "sigma", pca_mask_alpha: float | None = None) -> torch.Tensor:
     """The frames of render_video's loop (gui/main.py:1766-1801) for a camera set, [V, H, W, 3] on the device (uint8 as
     the reference saves them, or float32): every camera is rendered with render_gui and decoded with the fused decode
     into slot v of preallocated [V, ...] buffers, then ONE batched display.compose makes all the frames, each view with
@@ -755,22 +766,43 @@ def video_frames(cameras, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, t
     test_step's depth mode) or "alpha"; `style` is a display style (display.from_reference_flags maps the GUI's
     switches).  Styles that need no similarity skip the decode.  All cameras must share one H x W.  Nothing is read back
     to the host -- with a gaussian_mask only when in_place=True hands it to the rasterizer as a selection (render.render;
-    mask_invert: its complement, the viewer's del mode): the default index-select synchronises once per frame."""
+    mask_invert: its complement, the viewer's del mode): the default index-select synchronises once per frame.
+
+    mode "semantics" shows the rendered feature map through a PCA basis (pca.py), normalised by `pca_normalize` ("sigma",
+    "minmax" or "raw").  With basis=None ONE basis is fitted for the whole camera set, so the colours do not flicker: a
+    first sweep renders every view and accumulates its features (those with alpha > pca_mask_alpha, if given) into the
+    fit's workspace, keeping no map; the basis is solved on the device and every view is rendered AGAIN to be projected.
+    That is two renders per view with flat memory.  Passing a basis (pca.fit_gaussians(pc), say) renders once.
+    pca_mask_alpha only selects what a fit made HERE uses: it is ignored when a basis is passed.  In the other modes
+    basis, pca_normalize and pca_mask_alpha are neither used nor checked."""
     from . import display
     from .render import render_gui
-    code = _frame_args(mode, style, pc)
+    code = _frame_args(mode, style, pc, basis, pca_normalize)
     cams, H, W = _sweep_frame(cameras)
     dev = pc.get_xyz.device
     V, HW = len(cams), H * W
     need_sim = code != display.NONE
-    base = torch.empty((V, 3 if mode == "image" else 1, H, W), dtype=torch.float32, device=dev)
+    semantics = mode == "semantics"
+    if semantics:
+        from . import pca
+        if basis is None:
+            fit = pca.Fit(int(pc.get_semantics.shape[1]), dev)
+            for cam in cams:
+                out = render_gui(cam, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask, in_place=in_place,
+                                 mask_invert=mask_invert)
+                fit.add(out["semantics"], "planar", _alpha_mask(out, pca_mask_alpha))
+            basis = fit.solve()
+    base = torch.empty((V, 3 if mode in ("image", "semantics") else 1, H, W), dtype=torch.float32, device=dev)
     sim = torch.empty((V, HW), dtype=torch.float32, device=dev) if need_sim else None
     mask = torch.empty((V, HW), dtype=torch.uint8, device=dev) if need_sim else None
     dec = _FrameDecoder(mlp, lut, score_fn, thresh, dev) if need_sim else None
     for v, cam in enumerate(cams):
         out = render_gui(cam, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask, in_place=in_place,
                          mask_invert=mask_invert)
-        base[v].copy_(out[mode].reshape(base.shape[1:]))
+        if semantics:
+            pca.transform(out["semantics"], basis, normalize=pca_normalize, out=base[v])
+        else:
+            base[v].copy_(out[mode].reshape(base.shape[1:]))
         if need_sim:
             dec.decode(out["semantics"], sim[v], mask[v])
     return display.compose(base, sim, mask, style=code, normalize=mode == "depth", overlay_ratio=overlay_ratio,
@@ -782,19 +814,30 @@ def view_frame(camera, pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thre
                mode: str = "image", style="heat", overlay_ratio: float = 1.0, gaussian_mask=None,
                scaling_modifier: float = 1.0, dtype: torch.dtype = torch.float32, heat_thresh: float = 0.7,
                colormap: torch.Tensor | None = None, return_parts: bool = False, in_place: bool = False,
-               mask_invert: bool = False):
+               mask_invert: bool = False, basis=None, pca_normalize: str = "sigma", pca_mask_alpha: float | None = None):
     """One displayed frame [H, W, 3] on the device: test_step with set_clip_mask (gui/main.py:549-604, :387-398) as
     render_gui, the fused decode with its uint8 background mask, and display.compose on the render's own tensor (no copy
     of the image).  `mode`, `style` and the rest as video_frames; float32 is what the viewer's texture takes.  Nothing is
     read back to the host (with a gaussian_mask: when in_place=True, see video_frames).  return_parts: also the dictionary
-    {"base", "sim", "bg_mask"} the frame was composed from (sim and bg_mask None for the styles that need no similarity)."""
+    {"base", "sim", "bg_mask"} the frame was composed from (sim and bg_mask None for the styles that need no similarity).
+    mode "semantics": the base is pca.transform(out["semantics"], basis, normalize=pca_normalize); with basis=None the
+    basis is fitted on this frame alone (on its pixels with alpha > pca_mask_alpha, if given, so that an empty background
+    does not own the first component) -- fit one basis for an orbit and pass it to keep the colours from flickering.
+    pca_mask_alpha is ignored when a basis is passed; in the other modes the three PCA arguments are neither used nor
+    checked."""
     from . import display
     from .render import render_gui
-    code = _frame_args(mode, style, pc)
+    code = _frame_args(mode, style, pc, basis, pca_normalize)
     dev = pc.get_xyz.device
     out = render_gui(camera, pc, bg_color, scaling_modifier, gaussian_mask=gaussian_mask, in_place=in_place,
                      mask_invert=mask_invert)
-    base = out[mode]
+    if mode == "semantics":
+        from . import pca
+        if basis is None:
+            basis = pca.fit(out["semantics"], "planar", _alpha_mask(out, pca_mask_alpha))
+        base = pca.transform(out["semantics"], basis, normalize=pca_normalize)
+    else:
+        base = out[mode]
     base = base.reshape((-1,) + tuple(base.shape[-2:]))
     sim = mask = None
     if code != display.NONE:

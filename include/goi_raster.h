@@ -49,7 +49,9 @@
 extern "C" {
 #endif
 
-/* 8: + goi_raster_forward_selected, goi_raster_forward_async_selected (a per-Gaussian selection the forward itself honours)
+/* 8: + goi_raster_forward_selected, goi_raster_forward_async_selected (a per-Gaussian selection the forward itself honours);
+ *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
+ *    goi_semantic_pca_apply
  * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
  *    goi_raster_backward_scratch_bytes as ever);
@@ -450,6 +452,61 @@ size_t goi_semantic_frame_workspace_bytes(int n_views);
 int goi_semantic_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, int H, int W,
                                int style, int normalize, double overlay_ratio, double heat_thresh, const float* table,
                                int n_colors, void* out, int out_dtype, void* workspace, void* stream);
+
+/* ---- a PCA picture of the semantic features (csrc/pca.hip): three principal components of the S-dimensional feature
+ * field as a colour, which the reference computes on the host (gui/main_edit.py:1841-1870 visual_latent with
+ * utils/visual_latent.py:32-40: the rendered map copied to the host and sklearn's PCA(n_components=3).fit_transform).
+ * Samples come in one of two layouts, GOI_PCA_PLANAR [S][n] (a rendered map, read in place) or GOI_PCA_ROWS [n][S] (the
+ * Gaussians' own features); 3 <= S <= 32, 1 <= n < 2^31.
+ *
+ * goi_semantic_pca_accumulate: adds the count, the per-channel sums and the S x S second moments of x's samples to
+ *   `workspace` (goi_semantic_pca_workspace_bytes(S, 0) bytes of device memory, 256-byte aligned).  mask: NULL, or n
+ *   bytes, nonzero = use the sample; a sample that is not used is never read into the sums (it may hold a NaN).
+ *   first != 0 starts a fit: it fixes the pivot c (the channel means of the used samples among 2048 samples, in chunks of
+ *   32 spread evenly over the whole set, so a map whose first rows are empty background still gets its foreground's mean; of all of
+ *   these when none is used; 0 where that is not finite) and overwrites the workspace; first == 0 adds to it, which
+ *   is how a camera set is fitted.  The sums are of (x - c) and (x - c)(x - c)^T, so features far from zero lose
+ *   nothing; fp32 inside a wave (the Gram update is v_mfma_f32_16x16x4_f32, an exact fmaf chain), fp64 across waves,
+ *   workgroups and calls, in a fixed order: no float atomics, the result is bit-reproducible.
+ * goi_semantic_pca_solve: the basis of what was accumulated, GOI_PCA_BASIS_FLOATS(S) fp32 at `basis`:
+ *     mean[S]; components[3][S]; explained_variance[3]; total_variance; count
+ *   in fp64: mean = c + sum / n, covariance with divisor n - 1 (the pivot cancels exactly), cyclic Jacobi with a fixed
+ *   maximum of 16 sweeps, the three largest eigenpairs in descending order, the entry of largest magnitude of each
+ *   component positive (sklearn >= 1.5: svd_flip(u_based_decision=False)), negative eigenvalues clipped to 0:
+ *   sklearn.decomposition.PCA(3)'s mean_, components_, explained_variance_.  total_variance is the trace of the
+ *   covariance.  count is rounded to fp32 (exact below 2^24).  Fewer than two used samples: components and variances
+ *   are 0, the mean is that of what there was, nothing is NaN.  Non-finite input gives a non-finite basis, never a hang.
+ * goi_semantic_pca_apply: q_k = sum_c (x_c - mean_c) * component_k[c], c ascending, every operation one fp32 rounding
+ *   (no FMA), for each sample of n_views views x [n_views][S][n] or [n_views][n][S]; out [n_views][3][n]
+ *   (GOI_PCA_PLANAR: a `base` of goi_semantic_frame_compose) or [n_views][n][3] (GOI_PCA_ROWS: a colors_precomp).
+ *     GOI_PCA_RAW     out = q                                                     (PCA.fit_transform / transform)
+ *     GOI_PCA_SIGMA   out = clamp(0.5f + q / ((2 k) * max(sqrtf(explained_variance_k), FLT_MIN)), 0, 1), k = (float)k_sigma;
+ *                     a NaN q gives 0.  The scale is the basis's, so colours are stable from frame to frame; k is a
+ *                     display choice (2.0: +-2 sigma span the range)
+ *     GOI_PCA_MINMAX  out = (q - min) / ((max - min) + 1e-20f), min / max per view and component, NaNs skipped
+ *   q is computed by the same code in every mode, layout and path.  workspace: needed by GOI_PCA_MINMAX only,
+ *   goi_semantic_pca_workspace_bytes(0, n_views) bytes, 4-byte aligned, zeroed by the call with one hipMemsetAsync on
+ *   `stream`.  At most two kernel launches (plus that memset for GOI_PCA_MINMAX) whatever n_views is.  Planar input with n % 4 == 0 and x, out on 16-byte boundaries takes 16-byte
+ *   loads and stores; anything else one sample per thread, with the same bits.  0 <= n_views <= 65535 (0: nothing is
+ *   done, 0 is returned).
+ * goi_semantic_pca_workspace_bytes(S, n_views): the bytes a fit of S channels needs (S > 0) plus those a MINMAX apply of
+ *   n_views views needs (n_views > 0); 0 for arguments out of range.
+ * All three are asynchronous on `stream`: no allocation, copy or synchronisation.  They return < 0
+ * (goi_raster_last_error) for bad arguments. */
+#define GOI_PCA_PLANAR 0
+#define GOI_PCA_ROWS 1
+#define GOI_PCA_RAW 0
+#define GOI_PCA_SIGMA 1
+#define GOI_PCA_MINMAX 2
+#define GOI_PCA_MIN_DIM 3
+#define GOI_PCA_MAX_DIM 32
+#define GOI_PCA_BASIS_FLOATS(S) (4 * (S) + 5)
+size_t goi_semantic_pca_workspace_bytes(int S, int n_views);
+int goi_semantic_pca_accumulate(const float* x, int layout, int S, long long n, const uint8_t* mask, int first, void* workspace,
+                                void* stream);
+int goi_semantic_pca_solve(int S, void* workspace, float* basis, void* stream);
+int goi_semantic_pca_apply(const float* x, int in_layout, int S, long long n, int n_views, const float* basis, int normalize,
+                           double k_sigma, float* out, int out_layout, void* workspace, void* stream);
 
 /* ---- code-book initialisation (train.py:78-86; csrc/codebook_init.hip) ----------------------------------------------
  * goi_codebook_unique_rows: the rows of x.permute(1, 2, 0).reshape(-1, D).unique(dim=0) of each of n_views fp32 maps
