@@ -124,6 +124,14 @@ def check_selection(selection, P, dev=None):
     return selection
 
 
+def _binning_tensor(dev, nbytes):
+    """A binning workspace of at least `nbytes` (goi_raster_binning_bytes(instances), or what the library's allocation
+    callback asks for).  num_rendered changes with every view; rounding the size up to 16 MiB steps lets the caching
+    allocator hand back the same block instead of growing a new one (a fresh hipMalloc inside a training step)."""
+    step = 16 << 20
+    return torch.empty((int(nbytes) + step - 1) // step * step, dtype=torch.uint8, device=dev)
+
+
 class _BinningAllocator:
     """The allocation callback handed to the library (reference: resizeFunctional,
     rasterize_points.cu:27-33): allocates the binning workspace as a uint8 torch tensor."""
@@ -136,10 +144,7 @@ class _BinningAllocator:
 
     def _alloc(self, _user, nbytes):
         try:
-            # num_rendered changes with every view; rounding the request up to 16 MiB steps lets the caching allocator
-            # hand back the same block instead of growing a new one (a fresh hipMalloc inside a training step)
-            step = 16 << 20
-            self.tensor = torch.empty((int(nbytes) + step - 1) // step * step, dtype=torch.uint8, device=self.dev)
+            self.tensor = _binning_tensor(self.dev, nbytes)
             return self.tensor.data_ptr()
         except Exception as ex:  # never let an exception cross the C boundary
             self.error = ex
@@ -347,19 +352,25 @@ class LazyCount:
     __slots__ = ("dev", "ticket", "capacity", "layout", "binning", "overflowed", "redone", "_n", "_redo", "_stream",
                  "_error", "P", "tiles", "_hold", "cut_key", "cam_key", "cut_failed", "_full_args", "__weakref__")
 
-    def __init__(self, dev, ticket, capacity, binning, stream, redo, P, workspaces=None):
+    def __init__(self, dev, ticket, capacity, frame, stream, background, semantics, P, tiles, cam_key=None, cut_key=None,
+                 full_args=None):
+        """frame: what the launch returned behind the ticket (color, semantic, depth, alpha, radii, geom, binning, img).
+        tiles: the image size, part of what the capacity policy compares.  cam_key: this frame's camera in the depth-cut
+        registry (its count is reported back there); cut_key: the same iff the frame's lists were built with the camera's learnt
+        cut, full_args: the operator's arguments then -- what rendering the frame AGAIN without a cut needs."""
+        color, sem, depth, alpha, radii, geom, binning, img = frame
         self.dev, self.ticket, self.capacity, self.layout, self.binning = dev, ticket, capacity, capacity, binning
-        self.overflowed = self.redone = False
-        self._n, self._redo, self._stream, self._error, self.P = None, redo, stream, None, P
-        self.tiles = 0  # (set by the caller: the image size is part of what the capacity policy compares)
-        self.cam_key = None      # key of this frame's camera in the depth-cut registry (its count is reported back there)
-        self.cut_key = None      # ... set iff the frame's lists were built with the camera's learnt depth cut
-        self.cut_failed = False  # ... and the cut turned out too tight for this frame
-        self._full_args = None   # the operator's arguments: what rendering the frame AGAIN without a cut needs
+        self.overflowed = self.redone = self.cut_failed = False  # (cut_failed: the cut turned out too tight for this frame)
+        self._n, self._stream, self._error, self.P, self.tiles = None, stream, None, P, tiles
+        self.cam_key, self.cut_key, self._full_args = cam_key, cut_key, full_args
+        # what a redo needs: workspaces and outputs (weakly: dead outputs have no consumer left to repair for) and the two
+        # inputs the back half of the frame reads, the background and the semantic rows (strongly: they may be temporaries
+        # of the caller, e.g. pc.get_semantics under a mask).  The scene struct is built only if a redo happens.
+        self._redo = (background, semantics, [weakref.ref(t) for t in (geom, img, radii, color, sem, depth, alpha)])
         # The frame's workspaces (geometry / image state, radii) are needed for a redo but belong to nobody once the
         # operator has returned under no_grad: the newest few pending frames of a device keep them alive (a caller who
         # reads the count does so right after the forward), older ones let go (a pending frame must not pin memory).
-        self._hold = workspaces
+        self._hold = (geom, img, radii)
         pend = _spec_state(dev)["pending"]
         pend.append(self)
         if len(pend) > _KEEP_WORKSPACES:
@@ -400,7 +411,7 @@ class LazyCount:
             self._error = RuntimeError(_lib.last_error())
             raise self._error
         self._n = int(n.value)
-        _note_count(self.dev, self.P, self._n, getattr(self, "tiles", 0), cut=self.cut_key is not None)
+        _note_count(self.dev, self.P, self._n, self.tiles, cut=self.cut_key is not None)
         if self.cam_key is not None:
             ce = _DEPTH_CUTS["entries"].get(self.cam_key)
             if ce is not None:
@@ -461,24 +472,33 @@ class LazyCount:
         self._redo = self._hold = None
         return True
 
+    def _live_frame(self, trouble):
+        """-> (geom, img, radii, outputs) for rendering the frame again, or None: every output has been released, nobody can
+        consume the frame, nothing to repair"""
+        live = [r() for r in self._redo[2]]
+        if all(t is None for t in live[3:7]):
+            return None
+        if any(t is None for t in live):
+            raise RasterOverflowError(f"{trouble}: its workspaces have already been released (the count was read too late -- "
+                                      f"the last {_KEEP_WORKSPACES} frames of a device keep theirs)")
+        return live[0], live[1], live[2], live[3:7]
+
+    def _on_frame_stream(self):
+        """context: the frame's device and stream current (what is allocated for the frame again belongs to that stream)"""
+        return torch.cuda.stream(torch.cuda.ExternalStream(self._stream, device=self.dev))
+
     def _redo_frame(self):
         lib = _lib.load()
-        make_scene, refs = self._redo
-        live = [r() for r in refs]
-        if all(t is None for t in live[3:7]):
-            return  # every output has been released: nobody can consume the truncated frame, nothing to repair
-        if any(t is None for t in live):
-            raise RasterOverflowError(
-                f"a speculative forward overflowed its binning capacity (num_rendered = {self._n} > {self.capacity}) and "
-                "cannot be redone: its workspaces have already been released (the count was read too late -- the last "
-                f"{_KEEP_WORKSPACES} frames of a device keep theirs)")
-        sc, _keep = make_scene()
-        geom, img, radii, outs = live[0], live[1], live[2], live[3:7]
-        stream = torch.cuda.ExternalStream(self._stream, device=self.dev)
-        with torch.cuda.device(self.dev), torch.cuda.stream(stream):
-            step = 16 << 20
-            need = int(lib.goi_raster_binning_bytes(self._n))
-            binning = torch.empty((need + step - 1) // step * step, dtype=torch.uint8, device=self.dev)
+        frame = self._live_frame(f"a speculative forward overflowed its binning capacity (num_rendered = {self._n} > "
+                                 f"{self.capacity}) and cannot be redone")
+        if frame is None:
+            return
+        geom, img, radii, outs = frame
+        with torch.cuda.device(self.dev), self._on_frame_stream():
+            # only what the back half of a frame reads (include/goi_raster.h, goi_raster_forward_redo)
+            sc, _keep = _prepared_scene(self.dev, self.P, outs[1].size(0), outs[0].size(1), outs[0].size(2),
+                                        background=self._redo[0], semantics=self._redo[1])
+            binning = _binning_tensor(self.dev, lib.goi_raster_binning_bytes(self._n))
             r = lib.goi_raster_forward_redo(C.byref(sc), self._n, _ptr(geom), _ptr(img), _ptr(binning),
                                             *[_ptr(o) for o in outs], _ptr(radii), C.c_void_p(self._stream))
         if r < 0:
@@ -487,44 +507,22 @@ class LazyCount:
         SPECULATION_STATS["redone"] += 1
 
     def _render_again_uncut(self):
-        """The frame once more, whole and exact (goi_raster_forward), into the same outputs and workspaces."""
-        lib = _lib.load()
+        """The frame once more, whole and exact (_launch_exact: goi_raster_forward_selected without a selection, which is
+        goi_raster_forward), into the same outputs and workspaces."""
+        trouble = "a frame's depth cut-off was too tight and the frame cannot be rendered again"
         if self._full_args is None or self._redo is None:
-            raise RasterOverflowError("a frame's depth cut-off was too tight and the frame cannot be rendered again: its inputs "
-                                      f"have been released (the count was read too late -- the last {_KEEP_WORKSPACES} frames of "
-                                      "a device keep theirs)")
-        _mk, refs = self._redo
-        live = [r() for r in refs]
-        if all(t is None for t in live[3:7]):
+            raise RasterOverflowError(f"{trouble}: its inputs have been released (the count was read too late -- the last "
+                                      f"{_KEEP_WORKSPACES} frames of a device keep theirs)")
+        frame = self._live_frame(trouble)
+        if frame is None:
             return
-        if any(t is None for t in live):
-            raise RasterOverflowError("a frame's depth cut-off was too tight and the frame cannot be rendered again: its "
-                                      "workspaces have already been released")
-        geom, img, radii, outs = live[0], live[1], live[2], live[3:7]
-        (background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-         projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug) = self._full_args
-        dev = self.dev
-        stream = torch.cuda.ExternalStream(self._stream, device=dev)
-        with torch.cuda.device(dev), torch.cuda.stream(stream):
-            ten = dict(bg=_prep(background, "background", dev), means3D=_prep(means3D, "means3D", dev), sh=_prep(sh, "sh", dev),
-                       colors=_prep(colors, "colors_precomp", dev), semantics=_prep(semantics, "semantics", dev),
-                       opacity=_prep(opacity, "opacities", dev), scales=_prep(scales, "scales", dev),
-                       rotations=_prep(rotations, "rotations", dev), cov3D=_prep(cov3D_precomp, "cov3D_precomp", dev),
-                       viewmatrix=_prep(viewmatrix, "viewmatrix", dev), projmatrix=_prep(projmatrix, "projmatrix", dev),
-                       campos=_prep(campos, "campos", dev))
-            sc = _scene(self.P, int(semantics.size(1)), int(H), int(W), ten["bg"], ten["means3D"], ten["sh"], ten["colors"],
-                        ten["semantics"], ten["opacity"], ten["scales"], ten["rotations"], scale_modifier, ten["cov3D"],
-                        ten["viewmatrix"], ten["projmatrix"], tan_fovx, tan_fovy, degree, ten["campos"], prefiltered, False)
-            alloc = _BinningAllocator(dev)
-            n = lib.goi_raster_forward(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, *[_ptr(o) for o in outs], _ptr(radii),
-                                       C.c_void_p(self._stream))
-        if alloc.error is not None:
-            raise alloc.error
-        if n < 0:
-            raise RuntimeError(_lib.last_error())
-        self.binning, self.layout, self.redone, self._n = alloc.tensor, int(n), True, int(n)
+        fa = self._full_args
+        with torch.cuda.device(self.dev), self._on_frame_stream():
+            res = _launch_exact(fa, self.dev, self.P, int(fa.semantics.size(1)), None, False, into=frame + (self._stream,))
+        n, binning = res[0], res[7]
+        self.binning, self.layout, self.redone, self._n = binning, n, True, n
         SPECULATION_STATS["redone"] += 1
-        _note_count(dev, self.P, int(n), getattr(self, "tiles", 0))
+        _note_count(self.dev, self.P, n, self.tiles)
 
     def resolve(self) -> int:
         """Waits for the count; an overflowed frame is redone in place (exact outputs from here on)."""
@@ -708,6 +706,21 @@ def _scene(P, S, H, W, bg, means3D, sh, colors, semantics, opacity, scales, rota
         int(bool(debug)))
 
 
+def _prepared_scene(dev, P, S, image_height, image_width, background=None, means3D=None, colors=None, semantics=None,
+                    opacity=None, scales=None, rotations=None, scale_modifier=1.0, cov3D_precomp=None, viewmatrix=None,
+                    projmatrix=None, tan_fovx=0.0, tan_fovy=0.0, sh=None, degree=0, campos=None, prefiltered=False, debug=False):
+    """-> (the scene struct over the checked, contiguous operands (_prep; None / empty: absent), those operands: the struct
+    holds raw pointers into them, so they must live for as long as it is used).  The keywords are the operator's argument
+    names: _prepared_scene(dev, P, S, **frame_args._asdict()) is a forward's scene."""
+    keep = [_prep(t, name, dev) for t, name in (
+        (background, "background"), (means3D, "means3D"), (sh, "sh"), (colors, "colors_precomp"), (semantics, "semantics"),
+        (opacity, "opacities"), (scales, "scales"), (rotations, "rotations"), (cov3D_precomp, "cov3D_precomp"),
+        (viewmatrix, "viewmatrix"), (projmatrix, "projmatrix"), (campos, "campos"))]
+    bg, m3, shs, col, sem, opa, sca, rot, cov, view, proj, cam = keep
+    return _scene(P, S, image_height, image_width, bg, m3, shs, col, sem, opa, sca, rot, scale_modifier, cov, view, proj,
+                  tan_fovx, tan_fovy, degree, cam, prefiltered, debug), keep
+
+
 # ---- opt-in geometry cache (DESIGN.md 7c) ---------------------------------------------------------------------------
 # The reference's semantic stage trains ONLY the semantic features (arguments/__init__.py:85-90): positions, covariances,
 # opacities and SH colours are frozen, so for a camera that was rendered before, everything in front of the blend
@@ -747,15 +760,32 @@ def _ident(t):
     return None if (t is None or not isinstance(t, torch.Tensor) or t.numel() == 0) else (t.data_ptr(), t._version, tuple(t.shape))
 
 
-def _geom_key(dev, P, H, W, means3D, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, degree, campos, prefiltered,
-              colors, cov3D, selection=None, selection_invert=False):
+def _geom_key(dev, P, fa, selection=None, selection_invert=False):
     # (precomputed colours / covariances are the caller's own tensors: their identity is meaningful; the SH coefficients and
     # the activated scales / rotations / opacities are rebuilt by the reference's model on every call and cannot be keyed)
     # The selection decides which Gaussians the cached lists hold: its identity (None: no selection) and sense are part of the
     # key -- a camera rendered under one selection is never reblended for another, or for none.
-    return (dev.index, P, H, W, float(scale_modifier), float(tan_fovx), float(tan_fovy), int(degree), bool(prefiltered),
-            _ident(means3D), _ident(viewmatrix), _ident(projmatrix), _ident(campos), _ident(colors), _ident(cov3D),
+    return (dev.index, P, int(fa.image_height), int(fa.image_width), float(fa.scale_modifier), float(fa.tan_fovx),
+            float(fa.tan_fovy), int(fa.degree), bool(fa.prefiltered), _ident(fa.means3D), _ident(fa.viewmatrix),
+            _ident(fa.projmatrix), _ident(fa.campos), _ident(fa.colors), _ident(fa.cov3D_precomp),
             tuple(sorted(_lib.OPTIONS.items())), _ident(selection), bool(selection_invert) and selection is not None)
+
+
+# The operator's twenty arguments (ext.cpp:15-20, rasterize_points.cu:35-57) as ONE object.  The public functions keep the
+# reference's positional signature and pack it once; the geometry cache, the frame driver, its launchers and the LazyCount of
+# a cut frame pass that object on.  (rasterize_gaussians_trace puts img_sem where the semantic rows are.)
+_FrameArgs = collections.namedtuple("_FrameArgs", (
+    "background", "means3D", "colors", "semantics", "opacity", "scales", "rotations", "scale_modifier", "cov3D_precomp",
+    "viewmatrix", "projmatrix", "tan_fovx", "tan_fovy", "image_height", "image_width", "sh", "degree", "campos", "prefiltered",
+    "debug"))
+
+
+def _ext_args(fa):
+    """The operator's arguments as the compiled binding takes them: an empty tensor for an absent one, plain scalars."""
+    return (fa.background, fa.means3D, _e(fa.colors), _e(fa.semantics), _e(fa.opacity), _e(fa.scales), _e(fa.rotations),
+            float(fa.scale_modifier), _e(fa.cov3D_precomp), fa.viewmatrix, fa.projmatrix, float(fa.tan_fovx),
+            float(fa.tan_fovy), int(fa.image_height), int(fa.image_width), _e(fa.sh), int(fa.degree), fa.campos,
+            bool(fa.prefiltered), bool(fa.debug))
 
 
 def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
@@ -763,9 +793,9 @@ def rasterize_gaussians(background, means3D, colors, semantics, opacity, scales,
                         degree, campos, prefiltered, debug):
     """-> (num_rendered, color[3,H,W], semantic[S,H,W], depth[1,H,W], alpha[1,H,W], radii[P] i32,
     geomBuffer u8, binningBuffer u8, imgBuffer u8)"""
-    return _rasterize((background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                       viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-                       debug), None, False)
+    return _rasterize(_FrameArgs(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
+                                 cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
+                                 degree, campos, prefiltered, debug), None, False)
 
 
 def rasterize_gaussians_selected(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
@@ -776,25 +806,21 @@ def rasterize_gaussians_selected(background, means3D, colors, semantics, opacity
     gui/gs_renderer.py:315-321).  selection: bool / uint8 [P] on the device (check_selection), or None = rasterize_gaussians;
     selection_invert: render the Gaussians whose byte is 0 instead.  Same return tuple; radii stays [P] (0 for an unselected
     Gaussian) and the workspaces serve the same backward calls."""
-    return _rasterize((background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                       viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-                       debug), selection, bool(selection_invert))
+    return _rasterize(_FrameArgs(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
+                                 cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
+                                 degree, campos, prefiltered, debug), selection, bool(selection_invert))
 
 
-def _rasterize(args, selection, selection_invert):
-    (background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
-     tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug) = args
+def _rasterize(fa, selection, selection_invert):
+    means3D, semantics = fa.means3D, fa.semantics
     P = int(means3D.size(0)) if isinstance(means3D, torch.Tensor) and means3D.ndimension() == 2 else 0
-    if selection is not None:
+    if selection is not None:  # (the one check of a frame's selection: the cache keys it, the frame driver relies on it)
         check_selection(selection, P, means3D.device if isinstance(means3D, torch.Tensor) and means3D.is_cuda else None)
-    sel_kw = {} if selection is None else dict(selection=selection, selection_invert=selection_invert)
-    if not (_GEOM_CACHE["max_bytes"] > 0 and getattr(_CALL, "geometry_frozen", False) and P > 0 and not debug
+    if not (_GEOM_CACHE["max_bytes"] > 0 and getattr(_CALL, "geometry_frozen", False) and P > 0 and not fa.debug
             and isinstance(semantics, torch.Tensor) and semantics.ndimension() == 2 and semantics.size(0) == P):
-        return _rasterize_gaussians_frame(*args, **sel_kw)
+        return _rasterize_gaussians_frame(fa, selection, selection_invert)
     dev = _check_device(means3D)
-    H, W = int(image_height), int(image_width)
-    key = _geom_key(dev, P, H, W, means3D, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, degree, campos,
-                    prefiltered, colors, cov3D_precomp, selection, selection_invert)
+    key = _geom_key(dev, P, fa, selection, selection_invert)
     with _GEOM_LOCK:
         e = _GEOM_CACHE["entries"].get(key)
         if e is not None:
@@ -822,15 +848,15 @@ def _rasterize(args, selection, selection_invert):
                     del _GEOM_CACHE["entries"][key]
                 e = None
     if e is not None:
-        return _reblend(e, background, semantics, P, H, W, dev)
-    res = _rasterize_gaussians_frame(*args, **sel_kw)
+        return _reblend(e, fa.background, semantics, P, int(fa.image_height), int(fa.image_width), dev)
+    res = _rasterize_gaussians_frame(fa, selection, selection_invert)
     R, _c, _s, _d, _a, radii, geom, binning, img = res
     with _GEOM_LOCK:
         _GEOM_CACHE["misses"] += 1
         # The key identifies tensors by (address, version, shape): that is only sound while the tensors are ALIVE -- a freed
         # camera matrix or `xyz[mask]` temporary hands its address (version 0 again) to the next frame's tensors.  The entry
         # therefore holds strong references to every keyed tensor for as long as it lives (and accounts for their bytes).
-        keyed = tuple(t for t in (means3D, viewmatrix, projmatrix, campos, colors, cov3D_precomp, selection)
+        keyed = tuple(t for t in (means3D, fa.viewmatrix, fa.projmatrix, fa.campos, fa.colors, fa.cov3D_precomp, selection)
                       if isinstance(t, torch.Tensor) and t.numel() > 0)
         nbytes = (geom.numel() + img.numel() + radii.numel() * 4 + (binning.numel() if isinstance(binning, torch.Tensor) else 0)
                   + sum(t.numel() * t.element_size() for t in keyed))
@@ -852,38 +878,30 @@ def _reblend(e, background, semantics, P, H, W, dev):
     R = e["R"]
     layout, bin_override = _layout_of(R)
     binning = bin_override if bin_override is not None else e["binning"]
-    f32 = dict(dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         cur = torch.cuda.current_stream(dev)
         if e["stream"] != cur:
             cur.wait_stream(e["stream"])  # the frame that filled the workspaces ran on another stream
-        out_color = torch.empty((3, H, W), **f32)
-        out_sem = torch.empty((S, H, W), **f32)
-        out_depth = torch.empty((1, H, W), **f32)
-        out_alpha = torch.empty((1, H, W), **f32)
+        outs = _new_outputs(dev, S, H, W)
         img = torch.empty_like(e["img"])
-        bg_c, sem_c = _prep(background, "background", dev), _prep(semantics, "semantics", dev)
-        sc = _scene(P, S, H, W, bg_c, None, None, None, sem_c, None, None, None, 1.0, None, None, None, 0.0, 0.0, 0, None,
-                    False, False)
+        sc, _keep = _prepared_scene(dev, P, S, H, W, background=background, semantics=semantics)
         r = lib.goi_raster_forward_reblend(C.byref(sc), int(layout), _ptr(e["geom"]), _ptr(binning), _ptr(e["img"]), _ptr(img),
-                                           _ptr(out_color), _ptr(out_sem), _ptr(out_depth), _ptr(out_alpha), _stream(dev))
+                                           *[_ptr(o) for o in outs], _stream(dev))
     if r < 0:
         raise RuntimeError(_lib.last_error())
     _note_frame(e["geom"], P)
     SPECULATION_STATS["cached_frames"] += 1
-    return R, out_color, out_sem, out_depth, out_alpha, e["radii"], e["geom"], binning, img
+    return (R,) + outs + (e["radii"], e["geom"], binning, img)
 
 
-def _rasterize_gaussians_frame(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
-                               cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                               degree, campos, prefiltered, debug, selection=None, selection_invert=False):
-    lib = _lib.load()
-    dev = _check_device(means3D)
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    if selection is not None:
-        check_selection(selection, P, dev)
-        if P == 0:
-            selection = None
+def _rasterize_gaussians_frame(fa, selection=None, selection_invert=False):
+    """One frame, whole: the bookkeeping of the exact and of the speculative forward, each step once, over the two launchers
+    below -- the only place where the two bindings differ.  The selection has been checked (_rasterize)."""
+    dev = _check_device(fa.means3D)
+    P, H, W = int(fa.means3D.size(0)), int(fa.image_height), int(fa.image_width)
+    semantics = fa.semantics
+    if P == 0:
+        selection = None
     if semantics is None or semantics.numel() == 0:
         if P > 0:
             raise RuntimeError("semantics [P,S] is required (the reference dereferences it unconditionally, "
@@ -895,124 +913,96 @@ def _rasterize_gaussians_frame(background, means3D, colors, semantics, opacity, 
         S = int(semantics.size(1))
     if not (1 <= S <= 32):
         raise RuntimeError(f"unsupported number of semantic channels S={S} (1..32)")
-    ext = _ext()
-    if ext is not None:
-        poll_counts(dev)
-        args = (background, means3D, _e(colors), _e(semantics), _e(opacity), _e(scales), _e(rotations),
-                float(scale_modifier), _e(cov3D_precomp), viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), H, W,
-                _e(sh), int(degree), campos, bool(prefiltered), bool(debug))
-        cap = _pick_capacity(dev, P, debug, prefiltered, _tiles(H, W))
-        if cap is None:
-            res = (ext.rasterize_gaussians(*args) if selection is None
-                   else ext.rasterize_gaussians_selected(*args, selection, bool(selection_invert)))
-            _note_frame(res[6], P)
-            if P > 0:
-                SPECULATION_STATS["exact_frames"] += 1
-                _note_count(dev, P, res[0], _tiles(H, W))
-            return res
-        # (a selected frame neither applies nor learns a depth cut: what a camera learnt belongs to the whole model's frame)
-        cut_key, z_in, z_out, n_prev = (None, None, None, 0) if selection is not None else _depth_cut_for(
-            dev, P, H, W, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier)
-        if z_in is not None and n_prev > 0 and _FWD["capacity"] is None:
-            cap = min(cap, max(_MIN_CAPACITY, int(_FWD["headroom"] * n_prev) + 4096))
-        if selection is not None:
-            ticket, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img = ext.rasterize_gaussians_async_selected(
-                *args, cap, selection, bool(selection_invert))
-        else:
-            ticket, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img = ext.rasterize_gaussians_async(
-                *args, cap, z_in, z_out)
-        _note_frame(geom, P)
-        SPECULATION_STATS["speculative_frames"] += 1
-        refs = [weakref.ref(t) for t in (geom, img, radii, out_color, out_sem, out_depth, out_alpha)]
-
-        def make_scene(bg=background, sem=semantics):  # only what a redo reads (include/goi_raster.h)
-            bg_c, sem_c = bg.contiguous(), sem.contiguous()
-            return _scene(P, S, H, W, bg_c, None, None, None, sem_c, None, None, None, 1.0, None, None, None, 0.0, 0.0, 0,
-                          None, False, False), (bg_c, sem_c)
-        n = LazyCount(dev, ticket, cap, binning, torch.cuda.current_stream(dev).cuda_stream, (make_scene, refs), P,
-                      workspaces=(geom, img, radii))
-        n.tiles = _tiles(H, W)
-        n.cam_key = cut_key
-        if z_in is not None:
-            n.cut_key = cut_key
-            n._full_args = (background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                            viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug)
-            SPECULATION_STATS["cut_frames"] += 1
-        return n, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img
-    f32 = dict(dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        out_color = torch.empty((3, H, W), **f32)
-        out_sem = torch.empty((S, H, W), **f32)
-        out_depth = torch.empty((1, H, W), **f32)
-        out_alpha = torch.empty((1, H, W), **f32)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        ten = dict(bg=_prep(background, "background", dev), means3D=_prep(means3D, "means3D", dev),
-                   sh=_prep(sh, "sh", dev), colors=_prep(colors, "colors_precomp", dev),
-                   semantics=_prep(semantics, "semantics", dev), opacity=_prep(opacity, "opacities", dev),
-                   scales=_prep(scales, "scales", dev), rotations=_prep(rotations, "rotations", dev),
-                   cov3D=_prep(cov3D_precomp, "cov3D_precomp", dev), viewmatrix=_prep(viewmatrix, "viewmatrix", dev),
-                   projmatrix=_prep(projmatrix, "projmatrix", dev), campos=_prep(campos, "campos", dev))
-        geom = torch.empty(lib.goi_raster_geom_bytes(P) if P > 0 else 0, dtype=torch.uint8, device=dev)
-        img = torch.empty(lib.goi_raster_image_bytes(W, H) if P > 0 else 0, dtype=torch.uint8, device=dev)
-        _note_frame(geom, P)
-        sc = _scene(P, S, H, W, ten["bg"], ten["means3D"], ten["sh"], ten["colors"], ten["semantics"], ten["opacity"],
-                    ten["scales"], ten["rotations"], scale_modifier, ten["cov3D"], ten["viewmatrix"],
-                    ten["projmatrix"], tan_fovx, tan_fovy, degree, ten["campos"], prefiltered, debug)
-        poll_counts(dev)
-        cap = _pick_capacity(dev, P, debug, prefiltered, _tiles(H, W))
-        if cap is not None:
-            # speculative frame: everything is enqueued now, the count arrives through the ticket
-            cut_key, z_in, z_out, n_prev = (None, None, None, 0) if selection is not None else _depth_cut_for(
-                dev, P, H, W, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier)
-            if z_in is not None and n_prev > 0 and _FWD["capacity"] is None:
-                cap = min(cap, max(_MIN_CAPACITY, int(_FWD["headroom"] * n_prev) + 4096))
-            step = 16 << 20
-            binning = torch.empty((int(lib.goi_raster_binning_bytes(cap)) + step - 1) // step * step, dtype=torch.uint8,
-                                  device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            outs = (out_color, out_sem, out_depth, out_alpha)
-            if selection is not None:
-                ticket = lib.goi_raster_forward_async_selected(C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap,
-                                                               *[_ptr(o) for o in outs], _ptr(radii), _ptr(selection),
-                                                               int(bool(selection_invert)), C.c_void_p(stream))
-            else:
-                ticket = lib.goi_raster_forward_async_cut(C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap,
-                                                          *[_ptr(o) for o in outs], _ptr(radii), _ptr(z_in), _ptr(z_out),
-                                                          C.c_void_p(stream))
-            if ticket < 0:
-                raise RuntimeError(_lib.last_error())
-            SPECULATION_STATS["speculative_frames"] += 1
-            # what a redo needs: workspaces and outputs (weakly: dead outputs have no consumer left to repair for) and the
-            # two inputs the back half of the frame reads, the semantic rows and the background (strongly: they may be
-            # temporaries of the caller, e.g. pc.get_semantics under a mask)
-            refs = [weakref.ref(t) for t in (geom, img, radii) + outs]
-            keep = (ten["semantics"], ten["bg"])
-            n = LazyCount(dev, ticket, cap, binning, stream, (lambda: (sc, keep), refs), P, workspaces=(geom, img, radii))
-            n.tiles = _tiles(H, W)
-            n.cam_key = cut_key
-            if z_in is not None:
-                n.cut_key = cut_key
-                n._full_args = (background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier,
-                                cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered,
-                                debug)
-                SPECULATION_STATS["cut_frames"] += 1
-            return n, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img
-        alloc = _BinningAllocator(dev)
-        if selection is not None:
-            n = lib.goi_raster_forward_selected(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color), _ptr(out_sem),
-                                                _ptr(out_depth), _ptr(out_alpha), _ptr(radii), _ptr(selection),
-                                                int(bool(selection_invert)), _stream(dev))
-        else:
-            n = lib.goi_raster_forward(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color), _ptr(out_sem),
-                                       _ptr(out_depth), _ptr(out_alpha), _ptr(radii), _stream(dev))
-        if alloc.error is not None:
-            raise alloc.error
-        if n < 0:
-            raise RuntimeError(_lib.last_error())
+    tiles = _tiles(H, W)
+    poll_counts(dev)
+    cap = _pick_capacity(dev, P, fa.debug, fa.prefiltered, tiles)
+    if cap is None:
+        res = _launch_exact(fa, dev, P, S, selection, bool(selection_invert))
+        _note_frame(res[6], P)
         if P > 0:
             SPECULATION_STATS["exact_frames"] += 1
-            _note_count(dev, P, n, _tiles(H, W))
-    return n, out_color, out_sem, out_depth, out_alpha, radii, geom, alloc.tensor, img
+            _note_count(dev, P, res[0], tiles)
+        return res
+    # speculative frame: everything is enqueued now, the count arrives through the ticket
+    # (a selected frame neither applies nor learns a depth cut: what a camera learnt belongs to the whole model's frame)
+    cut_key, z_in, z_out, n_prev = (None, None, None, 0) if selection is not None else _depth_cut_for(
+        dev, P, H, W, fa.viewmatrix, fa.projmatrix, fa.campos, fa.tan_fovx, fa.tan_fovy, fa.scale_modifier)
+    if z_in is not None and n_prev > 0 and _FWD["capacity"] is None:
+        cap = min(cap, max(_MIN_CAPACITY, int(_FWD["headroom"] * n_prev) + 4096))
+    res = _launch_async(fa, dev, P, S, cap, z_in, z_out, selection, bool(selection_invert))
+    _note_frame(res[6], P)
+    SPECULATION_STATS["speculative_frames"] += 1
+    cut = z_in is not None  # the frame's lists were built with its camera's learnt cut
+    if cut:
+        SPECULATION_STATS["cut_frames"] += 1
+    n = LazyCount(dev, res[0], cap, res[1:], torch.cuda.current_stream(dev).cuda_stream, fa.background, semantics, P, tiles,
+                  cam_key=cut_key, cut_key=cut_key if cut else None, full_args=fa if cut else None)
+    return (n,) + res[1:]
+
+
+def _new_outputs(dev, S, H, W):
+    """-> (color, semantic, depth, alpha), for the library to fill"""
+    f32 = dict(dtype=torch.float32, device=dev)
+    return (torch.empty((3, H, W), **f32), torch.empty((S, H, W), **f32), torch.empty((1, H, W), **f32),
+            torch.empty((1, H, W), **f32))
+
+
+def _new_workspaces(dev, P, H, W):
+    """-> (geom, img, radii) of a frame, for the library to fill"""
+    lib = _lib.load()
+    return (torch.empty(lib.goi_raster_geom_bytes(P) if P > 0 else 0, dtype=torch.uint8, device=dev),
+            torch.empty(lib.goi_raster_image_bytes(W, H) if P > 0 else 0, dtype=torch.uint8, device=dev),
+            torch.empty((P,), dtype=torch.int32, device=dev))
+
+
+def _launch_exact(fa, dev, P, S, selection, invert, into=None):
+    """The exact, synchronous forward -> the operator's nine-tuple, num_rendered first.  into = (geom, img, radii, outputs,
+    stream) of an earlier launch: the frame AGAIN into those tensors and on that stream, by the C entry under either binding.
+    (The caller has also made that stream current, for the binning workspace allocated here; the pointer is handed over all the
+    same: what current_stream() reports inside an ExternalStream context is not the frame's stream.)"""
+    ext = _ext() if into is None else None
+    if ext is not None:
+        return (ext.rasterize_gaussians(*_ext_args(fa)) if selection is None
+                else ext.rasterize_gaussians_selected(*_ext_args(fa), selection, invert))
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        H, W = int(fa.image_height), int(fa.image_width)
+        geom, img, radii, outs, stream = into or (*_new_workspaces(dev, P, H, W), _new_outputs(dev, S, H, W),
+                                                  torch.cuda.current_stream(dev).cuda_stream)
+        sc, _keep = _prepared_scene(dev, P, S, **fa._asdict())
+        alloc = _BinningAllocator(dev)
+        # (without a selection this is goi_raster_forward: keep == NULL is the plain call, include/goi_raster.h)
+        n = lib.goi_raster_forward_selected(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, *[_ptr(o) for o in outs],
+                                            _ptr(radii), _ptr(selection), int(invert), C.c_void_p(stream))
+    if alloc.error is not None:
+        raise alloc.error
+    if n < 0:
+        raise RuntimeError(_lib.last_error())
+    return (n,) + tuple(outs) + (radii, geom, alloc.tensor, img)
+
+
+def _launch_async(fa, dev, P, S, cap, z_in, z_out, selection, invert):
+    """The speculative forward, enqueued whole against a binning workspace of `cap` instances -> the same nine-tuple with the
+    TICKET of the count's read-back first.  z_in / z_out: the camera's depth cut to apply / to learn (None: absent; a selected
+    frame has neither)."""
+    ext = _ext()
+    if ext is not None:
+        return (ext.rasterize_gaussians_async(*_ext_args(fa), cap, z_in, z_out) if selection is None
+                else ext.rasterize_gaussians_async_selected(*_ext_args(fa), cap, selection, invert))
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        H, W = int(fa.image_height), int(fa.image_width)
+        geom, img, radii, outs = (*_new_workspaces(dev, P, H, W), _new_outputs(dev, S, H, W))
+        sc, _keep = _prepared_scene(dev, P, S, **fa._asdict())
+        binning = _binning_tensor(dev, lib.goi_raster_binning_bytes(cap))
+        frame = (C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap, *[_ptr(o) for o in outs], _ptr(radii))
+        if selection is not None:
+            ticket = lib.goi_raster_forward_async_selected(*frame, _ptr(selection), int(invert), _stream(dev))
+        else:
+            ticket = lib.goi_raster_forward_async_cut(*frame, _ptr(z_in), _ptr(z_out), _stream(dev))
+    if ticket < 0:
+        raise RuntimeError(_lib.last_error())
+    return (ticket,) + outs + (radii, geom, binning, img)
 
 
 def _backward_impl(background, means3D, radii, colors, semantics, scales, rotations, scale_modifier,
@@ -1083,18 +1073,13 @@ def _backward_impl(background, means3D, radii, colors, semantics, scales, rotati
         dL_dconic = torch.empty((P, 2, 2), **f32)
         dL_dcov3D = torch.empty((P, 6), **f32)
         if P != 0:
-            ten = dict(bg=_prep(background, "background", dev), means3D=_prep(means3D, "means3D", dev),
-                       sh=_prep(sh, "sh", dev), colors=_prep(colors, "colors_precomp", dev),
-                       semantics=_prep(semantics, "semantics", dev), scales=_prep(scales, "scales", dev),
-                       rotations=_prep(rotations, "rotations", dev), cov3D=_prep(cov3D_precomp, "cov3D_precomp", dev),
-                       viewmatrix=_prep(viewmatrix, "viewmatrix", dev), projmatrix=_prep(projmatrix, "projmatrix", dev),
-                       campos=_prep(campos, "campos", dev), radii=_prep(radii, "radii", dev, torch.int32),
-                       alphas=_prep(alphas, "alphas", dev), g_c=_prep(dL_dout_color, "dL_dout_color", dev),
-                       g_s=_prep(dL_dout_semantic, "dL_dout_semantic", dev),
-                       g_d=_prep(dL_dout_depth, "dL_dout_depth", dev), g_a=_prep(dL_dout_alpha, "dL_dout_alpha", dev))
-            sc = _scene(P, S, H, W, ten["bg"], ten["means3D"], ten["sh"], ten["colors"], ten["semantics"], None,
-                        ten["scales"], ten["rotations"], scale_modifier, ten["cov3D"], ten["viewmatrix"],
-                        ten["projmatrix"], tan_fovx, tan_fovy, degree, ten["campos"], False, debug)
+            sc, _keep = _prepared_scene(dev, P, S, H, W, background=background, means3D=means3D, sh=sh, colors=colors,
+                                        semantics=semantics, scales=scales, rotations=rotations, scale_modifier=scale_modifier,
+                                        cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix,
+                                        tan_fovx=tan_fovx, tan_fovy=tan_fovy, degree=degree, campos=campos, debug=debug)
+            radii_c, alphas_c = _prep(radii, "radii", dev, torch.int32), _prep(alphas, "alphas", dev)
+            ups = [_prep(g, name, dev) for g, name in ((dL_dout_color, "dL_dout_color"), (dL_dout_semantic, "dL_dout_semantic"),
+                                                       (dL_dout_depth, "dL_dout_depth"), (dL_dout_alpha, "dL_dout_alpha"))]
             R_layout, lazy_binning = _layout_of(R)
             if lazy_binning is not None:
                 binningBuffer = lazy_binning  # (a redone frame has a new buffer)
@@ -1102,8 +1087,8 @@ def _backward_impl(background, means3D, radii, colors, semantics, scales, rotati
             scratch = _backward_scratch(lib.goi_raster_backward_scratch_bytes(R_scratch or R_layout, S), dev)
             # (no buffer pool on this path: every row is written, no mask is kept)
             r = lib.goi_raster_backward4(
-                C.byref(sc), R_layout, R_scratch, 0, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(ten["radii"]),
-                _ptr(ten["alphas"]), _ptr(ten["g_c"]), _ptr(ten["g_s"]), _ptr(ten["g_d"]), _ptr(ten["g_a"]),
+                C.byref(sc), R_layout, R_scratch, 0, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(radii_c),
+                _ptr(alphas_c), *[_ptr(g) for g in ups],
                 _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dsemantics),
                 _ptr(dL_ddepths), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
                 _ptr(dL_drotations), _ptr(scratch), None, None, None, _stream(dev))
@@ -1181,23 +1166,21 @@ def rasterize_gaussians_backward_semantics(background, means3D, radii, semantics
     with torch.cuda.device(dev):
         dL_dsemantics = torch.empty((P, S), dtype=torch.float32, device=dev)
         if P != 0:
-            ten = dict(bg=_prep(background, "background", dev), means3D=_prep(means3D, "means3D", dev),
-                       semantics=_prep(semantics, "semantics", dev), viewmatrix=_prep(viewmatrix, "viewmatrix", dev),
-                       projmatrix=_prep(projmatrix, "projmatrix", dev), campos=_prep(campos, "campos", dev),
-                       radii=_prep(radii, "radii", dev, torch.int32), alphas=_prep(alphas, "alphas", dev),
-                       g_s=_prep(dL_dout_semantic, "dL_dout_semantic", dev))
             # the geometry inputs are not read by this path (everything it needs is in the forward's
             # workspaces); the scene only has to pass validation
-            sc = _scene(P, S, H, W, ten["bg"], ten["means3D"], None, ten["means3D"], ten["semantics"], None,
-                        None, None, 1.0, ten["means3D"], ten["viewmatrix"], ten["projmatrix"], tan_fovx, tan_fovy,
-                        sh_degree, ten["campos"], False, debug)
+            sc, _keep = _prepared_scene(dev, P, S, H, W, background=background, means3D=means3D, colors=means3D,
+                                        semantics=semantics, cov3D_precomp=means3D, viewmatrix=viewmatrix,
+                                        projmatrix=projmatrix, tan_fovx=tan_fovx, tan_fovy=tan_fovy, degree=sh_degree,
+                                        campos=campos, debug=debug)
+            radii_c, alphas_c = _prep(radii, "radii", dev, torch.int32), _prep(alphas, "alphas", dev)
+            g_s = _prep(dL_dout_semantic, "dL_dout_semantic", dev)
             R_layout, lazy_binning = _layout_of(R)
             if lazy_binning is not None:
                 binningBuffer = lazy_binning
             scratch = _backward_scratch(lib.goi_raster_backward_scratch_bytes(R_layout, S), dev)
             r = lib.goi_raster_backward_semantics(C.byref(sc), R_layout, _ptr(geomBuffer), _ptr(binningBuffer),
-                                                  _ptr(imageBuffer), _ptr(ten["radii"]), _ptr(ten["alphas"]),
-                                                  _ptr(ten["g_s"]), _ptr(dL_dsemantics), _ptr(scratch), _stream(dev))
+                                                  _ptr(imageBuffer), _ptr(radii_c), _ptr(alphas_c), _ptr(g_s),
+                                                  _ptr(dL_dsemantics), _ptr(scratch), _stream(dev))
             if r < 0:
                 raise RuntimeError(_lib.last_error())
     return dL_dsemantics
@@ -1212,43 +1195,31 @@ def rasterize_gaussians_trace(background, means3D, colors, img_sem, opacity, sca
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
     if img_sem is None or img_sem.numel() == 0:
         raise RuntimeError("img_sem [S,H,W] is required")
+    fa = _FrameArgs(background, means3D, colors, img_sem, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                    projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug)
     ext = _ext()
     if ext is not None:
-        res = ext.rasterize_gaussians_trace(background, means3D, _e(colors), img_sem, _e(opacity), _e(scales),
-                                            _e(rotations), float(scale_modifier), _e(cov3D_precomp), viewmatrix,
-                                            projmatrix, float(tan_fovx), float(tan_fovy), H, W, _e(sh), int(degree),
-                                            campos, bool(prefiltered), bool(debug))
-        if P > 0:
-            _note_count(dev, P, res[0], _tiles(H, W))
-        return res
-    S = int(img_sem.size(0))
-    f32 = dict(dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        out_color = torch.empty((3, H, W), **f32)
-        gau_sem = torch.zeros((P, S), **f32)
-        num_gsem = torch.zeros((P,), dtype=torch.int32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        ten = dict(bg=_prep(background, "background", dev), means3D=_prep(means3D, "means3D", dev),
-                   sh=_prep(sh, "sh", dev), colors=_prep(colors, "colors_precomp", dev),
-                   img=_prep(img_sem, "img_sem", dev), opacity=_prep(opacity, "opacities", dev),
-                   scales=_prep(scales, "scales", dev), rotations=_prep(rotations, "rotations", dev),
-                   cov3D=_prep(cov3D_precomp, "cov3D_precomp", dev), viewmatrix=_prep(viewmatrix, "viewmatrix", dev),
-                   projmatrix=_prep(projmatrix, "projmatrix", dev), campos=_prep(campos, "campos", dev))
-        geom = torch.empty(lib.goi_raster_geom_bytes(P) if P > 0 else 0, dtype=torch.uint8, device=dev)
-        img = torch.empty(lib.goi_raster_image_bytes(W, H) if P > 0 else 0, dtype=torch.uint8, device=dev)
-        alloc = _BinningAllocator(dev)
-        sc = _scene(P, S, H, W, ten["bg"], ten["means3D"], ten["sh"], ten["colors"], None, ten["opacity"],
-                    ten["scales"], ten["rotations"], scale_modifier, ten["cov3D"], ten["viewmatrix"],
-                    ten["projmatrix"], tan_fovx, tan_fovy, degree, ten["campos"], prefiltered, debug)
-        n = lib.goi_raster_trace(C.byref(sc), _ptr(ten["img"]), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color),
-                                 _ptr(gau_sem), _ptr(num_gsem), _ptr(radii), _stream(dev))
+        res = ext.rasterize_gaussians_trace(*_ext_args(fa))
+    else:
+        S = int(img_sem.size(0))
+        with torch.cuda.device(dev):
+            out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+            gau_sem = torch.zeros((P, S), dtype=torch.float32, device=dev)
+            num_gsem = torch.zeros((P,), dtype=torch.int32, device=dev)
+            geom, img, radii = _new_workspaces(dev, P, H, W)
+            sc, _keep = _prepared_scene(dev, P, S, **fa._replace(semantics=None)._asdict())  # (no semantic rows: a trace)
+            img_c = _prep(img_sem, "img_sem", dev)
+            alloc = _BinningAllocator(dev)
+            n = lib.goi_raster_trace(C.byref(sc), _ptr(img_c), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color),
+                                     _ptr(gau_sem), _ptr(num_gsem), _ptr(radii), _stream(dev))
         if alloc.error is not None:
             raise alloc.error
         if n < 0:
             raise RuntimeError(_lib.last_error())
-        if P > 0:
-            _note_count(dev, P, n, _tiles(H, W))
-    return n, out_color, gau_sem, num_gsem, geom, alloc.tensor, img
+        res = (n, out_color, gau_sem, num_gsem, geom, alloc.tensor, img)
+    if P > 0:
+        _note_count(dev, P, res[0], _tiles(H, W))
+    return res
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

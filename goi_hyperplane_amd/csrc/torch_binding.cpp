@@ -31,11 +31,15 @@ namespace {
 
 using torch::Tensor;
 
+// num_rendered changes with every view: binning workspaces in 16 MiB steps let the caching allocator hand back the same block
+long long binning_size(size_t bytes) {
+    const long long step = 16ll << 20;
+    return ((long long)bytes + step - 1) / step * step;
+}
+
 void* grow(void* user, size_t bytes) {  // reference: resizeFunctional, rasterize_points.cu:27-33
     auto* t = static_cast<Tensor*>(user);
-    // num_rendered changes with every view: 16 MiB steps let the caching allocator hand back the same block
-    const long long step = 16ll << 20;
-    t->resize_({((long long)bytes + step - 1) / step * step});
+    t->resize_({binning_size(bytes)});
     return t->data_ptr();
 }
 
@@ -63,6 +67,8 @@ c10::Device check_device(const Tensor& means3D) {
                                    "fallback in this package");
     return means3D.device();
 }
+
+void* ptr(const Tensor& t) { return t.numel() ? t.data_ptr() : nullptr; }  // (an empty tensor: NULL)
 
 void* stream_of(const c10::Device& dev) { return c10::hip::getCurrentHIPStream(dev.index()).stream(); }
 
@@ -118,6 +124,10 @@ GoiRasterScene scene_of(int P, int degree, const Tensor& sh, int S, int W, int H
         const Tensor &cov3D_precomp, const Tensor &viewmatrix, const Tensor &projmatrix, const float tan_fovx,         \
         const float tan_fovy, const int image_height, const int image_width, const Tensor &sh, const int degree,       \
         const Tensor &campos, const bool prefiltered, const bool debug
+// ... and the same twenty, handed on
+#define GOI_FORWARD_PASS                                                                                               \
+    background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,     \
+        projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug
 
 struct Prepared {
     c10::Device dev;
@@ -165,41 +175,49 @@ const uint8_t* selection_ptr(const Tensor& selection, const Prepared& f) {
 
 using FrameTuple = std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
+// What the library fills for one frame: the outputs, radii and the geometry / image workspaces (empty for P == 0), allocated
+// like `like` on the frame's device, plus the binning workspace (`binning_bytes`; 0: grown by the library through `grow`).
+// maps = false: the colour map only (a trace has no other).
+struct Frame {
+    c10::hip::HIPGuard guard;
+    Tensor color, sem, depth, alpha, radii, geom, img, binning;
+    Frame(const Prepared& f, const Tensor& like, size_t binning_bytes = 0, bool maps = true) : guard(f.dev.index()) {
+        auto f32 = like.options().dtype(torch::kFloat32);
+        auto bytes = like.options().dtype(torch::kByte);
+        color = torch::empty({3, f.H, f.W}, f32);
+        if (maps) {
+            sem = torch::empty({f.S, f.H, f.W}, f32);
+            depth = torch::empty({1, f.H, f.W}, f32);
+            alpha = torch::empty({1, f.H, f.W}, f32);
+        }
+        radii = torch::empty({f.P}, like.options().dtype(torch::kInt32));
+        geom = torch::empty({f.P > 0 ? (long long)goi_raster_geom_bytes(f.P) : 0}, bytes);
+        img = torch::empty({f.P > 0 ? (long long)goi_raster_image_bytes(f.W, f.H) : 0}, bytes);
+        binning = torch::empty({binning_bytes ? binning_size(binning_bytes) : 0}, bytes);
+    }
+    FrameTuple result(int first) const { return std::make_tuple(first, color, sem, depth, alpha, radii, geom, binning, img); }
+};
+
 // selection (or NULL: every Gaussian) / invert: rasterize_gaussians_selected
 FrameTuple forward_frame(GOI_FORWARD_ARGS, const Tensor* selection, bool invert) {
-    Prepared f = prepare(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                         prefiltered, debug, true);
+    Prepared f = prepare(GOI_FORWARD_PASS, true);
     const uint8_t* keep = selection ? selection_ptr(*selection, f) : nullptr;
-    c10::hip::HIPGuard guard(f.dev.index());
-    auto f32 = means3D.options().dtype(torch::kFloat32);
-    auto bytes = means3D.options().dtype(torch::kByte);
-    Tensor out_color = torch::empty({3, f.H, f.W}, f32), out_sem = torch::empty({f.S, f.H, f.W}, f32);
-    Tensor out_depth = torch::empty({1, f.H, f.W}, f32), out_alpha = torch::empty({1, f.H, f.W}, f32);
-    Tensor radii = torch::empty({f.P}, means3D.options().dtype(torch::kInt32));
-    Tensor geom = torch::empty({f.P > 0 ? (long long)goi_raster_geom_bytes(f.P) : 0}, bytes);
-    Tensor img = torch::empty({f.P > 0 ? (long long)goi_raster_image_bytes(f.W, f.H) : 0}, bytes);
-    Tensor binning = torch::empty({0}, bytes);
-    const int n = goi_raster_forward_selected(&f.sc, f.P ? geom.data_ptr() : nullptr, f.P ? img.data_ptr() : nullptr, grow, &binning,
-                                              out_color.data_ptr<float>(), out_sem.data_ptr<float>(), out_depth.data_ptr<float>(),
-                                              out_alpha.data_ptr<float>(), f.P ? radii.data_ptr<int>() : nullptr, keep,
-                                              invert ? 1 : 0, stream_of(f.dev));
+    Frame o(f, means3D);
+    const int n = goi_raster_forward_selected(&f.sc, ptr(o.geom), ptr(o.img), grow, &o.binning, o.color.data_ptr<float>(),
+                                              o.sem.data_ptr<float>(), o.depth.data_ptr<float>(), o.alpha.data_ptr<float>(),
+                                              static_cast<int*>(ptr(o.radii)), keep, invert ? 1 : 0, stream_of(f.dev));
     if (n < 0) raise_last();
-    return std::make_tuple(n, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img);
+    return o.result(n);
 }
 
 FrameTuple rasterize_gaussians(GOI_FORWARD_ARGS) {
-    return forward_frame(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-                         debug, nullptr, false);
+    return forward_frame(GOI_FORWARD_PASS, nullptr, false);
 }
 
 // rasterize_gaussians over a SELECTION of the Gaussians, in place: every tensor stays [P]-long (no counterpart in the reference,
 // which index-selects the operands first, gui/gs_renderer.py:315-321)
 FrameTuple rasterize_gaussians_selected(GOI_FORWARD_ARGS, const Tensor& selection, const bool invert) {
-    return forward_frame(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-                         debug, &selection, invert);
+    return forward_frame(GOI_FORWARD_PASS, &selection, invert);
 }
 
 // speculative forward: nothing waits; returns the read-back ticket instead of num_rendered (include/goi_raster.h)
@@ -208,20 +226,9 @@ FrameTuple rasterize_gaussians_selected(GOI_FORWARD_ARGS, const Tensor& selectio
 // selection (or NULL) / invert: rasterize_gaussians_async_selected -- a selected frame takes no depth cut
 FrameTuple forward_frame_async(GOI_FORWARD_ARGS, const int capacity, const c10::optional<Tensor>& zcut_in,
                                const c10::optional<Tensor>& zcut_out, const Tensor* selection, bool invert) {
-    Prepared f = prepare(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                         prefiltered, debug, true);
+    Prepared f = prepare(GOI_FORWARD_PASS, true);
     const uint8_t* keep = selection ? selection_ptr(*selection, f) : nullptr;
-    c10::hip::HIPGuard guard(f.dev.index());
-    auto f32 = means3D.options().dtype(torch::kFloat32);
-    auto bytes = means3D.options().dtype(torch::kByte);
-    Tensor out_color = torch::empty({3, f.H, f.W}, f32), out_sem = torch::empty({f.S, f.H, f.W}, f32);
-    Tensor out_depth = torch::empty({1, f.H, f.W}, f32), out_alpha = torch::empty({1, f.H, f.W}, f32);
-    Tensor radii = torch::empty({f.P}, means3D.options().dtype(torch::kInt32));
-    Tensor geom = torch::empty({(long long)goi_raster_geom_bytes(f.P)}, bytes);
-    Tensor img = torch::empty({(long long)goi_raster_image_bytes(f.W, f.H)}, bytes);
-    const long long step = 16ll << 20;
-    Tensor binning = torch::empty({((long long)goi_raster_binning_bytes(capacity) + step - 1) / step * step}, bytes);
+    Frame o(f, means3D, goi_raster_binning_bytes(capacity));
     const long long tiles = ((long long)(f.W + 15) / 16) * ((f.H + 15) / 16);
     const float* zin = nullptr;
     float* zout = nullptr;
@@ -233,29 +240,24 @@ FrameTuple forward_frame_async(GOI_FORWARD_ARGS, const int capacity, const c10::
         if (k == 0) zin = z->data_ptr<float>();
         else zout = z->data_ptr<float>();
     }
+    float *color = o.color.data_ptr<float>(), *sem = o.sem.data_ptr<float>(), *depth = o.depth.data_ptr<float>();
+    float* alpha = o.alpha.data_ptr<float>();
     const int ticket =
-        keep ? goi_raster_forward_async_selected(&f.sc, geom.data_ptr(), img.data_ptr(), binning.data_ptr(), capacity,
-                                                 out_color.data_ptr<float>(), out_sem.data_ptr<float>(),
-                                                 out_depth.data_ptr<float>(), out_alpha.data_ptr<float>(), radii.data_ptr<int>(),
-                                                 keep, invert ? 1 : 0, stream_of(f.dev))
-             : goi_raster_forward_async_cut(&f.sc, geom.data_ptr(), img.data_ptr(), binning.data_ptr(), capacity,
-                                            out_color.data_ptr<float>(), out_sem.data_ptr<float>(), out_depth.data_ptr<float>(),
-                                            out_alpha.data_ptr<float>(), radii.data_ptr<int>(), zin, zout, stream_of(f.dev));
+        keep ? goi_raster_forward_async_selected(&f.sc, o.geom.data_ptr(), o.img.data_ptr(), o.binning.data_ptr(), capacity, color,
+                                                 sem, depth, alpha, o.radii.data_ptr<int>(), keep, invert ? 1 : 0, stream_of(f.dev))
+             : goi_raster_forward_async_cut(&f.sc, o.geom.data_ptr(), o.img.data_ptr(), o.binning.data_ptr(), capacity, color,
+                                            sem, depth, alpha, o.radii.data_ptr<int>(), zin, zout, stream_of(f.dev));
     if (ticket < 0) raise_last();
-    return std::make_tuple(ticket, out_color, out_sem, out_depth, out_alpha, radii, geom, binning, img);
+    return o.result(ticket);
 }
 
 FrameTuple rasterize_gaussians_async(GOI_FORWARD_ARGS, const int capacity, const c10::optional<Tensor>& zcut_in,
                                      const c10::optional<Tensor>& zcut_out) {
-    return forward_frame_async(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                               viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                               prefiltered, debug, capacity, zcut_in, zcut_out, nullptr, false);
+    return forward_frame_async(GOI_FORWARD_PASS, capacity, zcut_in, zcut_out, nullptr, false);
 }
 
 FrameTuple rasterize_gaussians_async_selected(GOI_FORWARD_ARGS, const int capacity, const Tensor& selection, const bool invert) {
-    return forward_frame_async(background, means3D, colors, semantics, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                               viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                               prefiltered, debug, capacity, c10::nullopt, c10::nullopt, &selection, invert);
+    return forward_frame_async(GOI_FORWARD_PASS, capacity, c10::nullopt, c10::nullopt, &selection, invert);
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------
@@ -434,7 +436,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
         const bool pooled = g_pool_on && !debug && !accumulate;
         if (pooled && !mask.defined()) mask = torch::empty({(long long)P}, means3D.options().dtype(torch::kByte));
         const int r = goi_raster_backward4(
-            &sc, R, scratch_instances, accumulate ? GOI_BACKWARD_ACCUMULATE : 0, geomBuffer.data_ptr(), binningBuffer.numel() ? binningBuffer.data_ptr() : nullptr,
+            &sc, R, scratch_instances, accumulate ? GOI_BACKWARD_ACCUMULATE : 0, geomBuffer.data_ptr(), ptr(binningBuffer),
             imageBuffer.data_ptr(), rad.data_ptr<int>(), al.p, gc.p, gs.p, gd.p, ga.p, dL_dmeans2D.data_ptr<float>(),
             dL_dconic.data_ptr<float>(), dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
             dL_dsemantics.data_ptr<float>(), dL_ddepths.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
@@ -491,10 +493,9 @@ Tensor backward_semantics(const Tensor& background, const Tensor& means3D, const
         void* stream = stream_of(dev);
         void* scratch = backward_scratch(goi_raster_backward_scratch_bytes(R, S), dev, stream,
                                          means3D.options().dtype(torch::kByte));
-        if (goi_raster_backward_semantics(&sc, R, geomBuffer.data_ptr(),
-                                          binningBuffer.numel() ? binningBuffer.data_ptr() : nullptr,
-                                          imageBuffer.data_ptr(), rad.data_ptr<int>(), al.p, gs.p,
-                                          dL_dsemantics.data_ptr<float>(), scratch, stream) < 0)
+        if (goi_raster_backward_semantics(&sc, R, geomBuffer.data_ptr(), ptr(binningBuffer), imageBuffer.data_ptr(),
+                                          rad.data_ptr<int>(), al.p, gs.p, dL_dsemantics.data_ptr<float>(), scratch,
+                                          stream) < 0)
             raise_last();
     }
     return dL_dsemantics;
@@ -511,23 +512,15 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_gaussi
     Prepared f = prepare(background, means3D, colors, img_sem, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                          viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                          prefiltered, debug, false);
-    c10::hip::HIPGuard guard(f.dev.index());
+    Frame o(f, means3D, 0, false);
     Arg img_in = arg(img_sem, "img_sem", f.dev);
-    auto f32 = means3D.options().dtype(torch::kFloat32);
-    auto bytes = means3D.options().dtype(torch::kByte);
-    Tensor out_color = torch::empty({3, f.H, f.W}, f32);
-    Tensor gau_sem = torch::zeros({f.P, f.S}, f32);
+    Tensor gau_sem = torch::zeros({f.P, f.S}, means3D.options().dtype(torch::kFloat32));
     Tensor num_gsem = torch::zeros({f.P}, means3D.options().dtype(torch::kInt32));
-    Tensor radii = torch::empty({f.P}, means3D.options().dtype(torch::kInt32));
-    Tensor geom = torch::empty({f.P > 0 ? (long long)goi_raster_geom_bytes(f.P) : 0}, bytes);
-    Tensor img = torch::empty({f.P > 0 ? (long long)goi_raster_image_bytes(f.W, f.H) : 0}, bytes);
-    Tensor binning = torch::empty({0}, bytes);
-    const int n = goi_raster_trace(&f.sc, img_in.p, f.P ? geom.data_ptr() : nullptr, f.P ? img.data_ptr() : nullptr, grow,
-                                   &binning, out_color.data_ptr<float>(), f.P ? gau_sem.data_ptr<float>() : nullptr,
-                                   f.P ? num_gsem.data_ptr<int>() : nullptr, f.P ? radii.data_ptr<int>() : nullptr,
-                                   stream_of(f.dev));
+    const int n = goi_raster_trace(&f.sc, img_in.p, ptr(o.geom), ptr(o.img), grow, &o.binning, o.color.data_ptr<float>(),
+                                   f.P ? gau_sem.data_ptr<float>() : nullptr, f.P ? num_gsem.data_ptr<int>() : nullptr,
+                                   static_cast<int*>(ptr(o.radii)), stream_of(f.dev));
     if (n < 0) raise_last();
-    return std::make_tuple(n, out_color, gau_sem, num_gsem, geom, binning, img);
+    return std::make_tuple(n, o.color, gau_sem, num_gsem, o.geom, o.binning, o.img);
 }
 
 Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tensor& projmatrix) {
