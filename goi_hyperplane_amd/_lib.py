@@ -146,6 +146,17 @@ SYMBOLS = {
     "goi_raster_debug_backward_blend": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int] + [C.c_void_p] * 24),
 }
 
+# the goi_field_* family (csrc/field.hip: density grid and iso-surface), bound by load() like the table above
+FIELD_SYMBOLS = {
+    "goi_field_density_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_double]),
+    "goi_field_density": (C.c_int, [C.c_longlong] + [C.c_void_p] * 5 + [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_double] + [C.c_void_p] * 9),
+    "goi_field_iso_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "goi_field_iso_count": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "goi_field_iso_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 4
+                           + [C.c_longlong, C.c_longlong] + [C.c_void_p] * 4),
+}
+
 _lib = None
 
 
@@ -163,7 +174,7 @@ def load():
         # the system copy and the two runtimes would not see each other's devices and allocations).
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(FIELD_SYMBOLS.items()):
             fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -47,6 +47,7 @@ UNITS = {
     "densify.hip": ["-ffp-contract=off"],  # the reference's elementwise torch ops, one rounding each
     "display.hip": ["-ffp-contract=off"],  # the viewer's blend a*b + c*d is compared bit for bit: no FMA
     "pca.hip": ["-ffp-contract=off"],  # the projection and its normalisations are one rounding per operation
+    "field.hip": ["-ffp-contract=off"],  # the iso-surface's vertices are one rounding per operation (the density loop names its FMAs)
 }
 
 

@@ -339,6 +339,17 @@ void launch_pca_accumulate(const float* x, int layout, int S, long long n, const
 void launch_pca_solve(int S, void* workspace, float* basis, hipStream_t s);
 void launch_pca_apply(const float* x, int in_layout, int S, long long n, int n_views, const float* basis, int normalize,
                       float two_k, float* out, int out_layout, uint32_t* stats, hipStream_t s);
+size_t field_density_workspace_bytes(long long P, int num_blocks, double relax_ratio);
+void launch_field_density(long long P, const float* xyz, const float* opacity, const float* scaling, const float* rotation,
+                          const uint8_t* selection, int selection_invert, float min_opacity, const float* attributes,
+                          const float* bounds, int R, int num_blocks, double relax_ratio, const float* coords,
+                          const float* block_lo, const float* block_hi, float* occ, float* attr_out, float* frame, int* status,
+                          void* workspace, hipStream_t s);
+size_t field_iso_workspace_bytes(long long N);
+void launch_field_iso_count(const float* grid, int X, int Y, int Z, float thresh, void* workspace, int* counts, hipStream_t s);
+void launch_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z, float thresh, const float* cx,
+                           const float* cy, const float* cz, const void* workspace, long long V, long long F, float* vertices,
+                           int* faces, float* colors, hipStream_t s);
 size_t uniq_workspace_bytes(int V, int D, uint32_t HW);
 uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW);  // [V] counts, then the flag word
 void launch_uniq_dedup(const float* const* maps, int V, int D, uint32_t HW, void* ws, hipStream_t s);

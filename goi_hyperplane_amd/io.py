@@ -8,6 +8,9 @@ that scenes, code books and checkpoints move in both directions:
   * LUT.pt                 train.py:189 (torch.save of the [tab_len, ape_dim] Parameter)
   * chkpnt<iter>.pth       train.py:202 + scene/gaussian_model.py:54-90: ((13-tuple), iteration)
   * k-means code-book init train.py:36-56
+  * mesh.ply               what field.extract_mesh gives (the reference's "save mesh" button, gui/main.py:607-617): binary
+                           little-endian PLY, `vertex` (float x y z, optionally uchar red green blue) and `face`
+                           (list uchar int vertex_indices)
 
 The reference reads and writes PLY through the `plyfile` package; this module speaks the format
 directly with numpy (header grammar of the PLY 1.0 spec: ascii / binary_little_endian /
@@ -157,6 +160,91 @@ def activate(raw: dict) -> dict:
     return {"means3D": t["xyz"], "scales": torch.exp(t["scaling"]),
             "rotations": torch.nn.functional.normalize(t["rotation"]), "opacities": torch.sigmoid(t["opacity"]),
             "shs": torch.cat((t["features_dc"], t["features_rest"]), dim=1), "semantics": t["semantics"]}
+
+
+# ---- mesh ----------------------------------------------------------------------------------------
+def save_mesh_ply(path, vertices, faces, colors=None) -> None:
+    """A triangle mesh as binary little-endian PLY: element vertex (float x y z, and uchar red green blue when colors [V, 3]
+    in [0, 1] are given: round(255 c)), element face (list uchar int vertex_indices).  Zero vertices or faces are fine."""
+    v = np.ascontiguousarray(_np(vertices), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(_np(faces), dtype="<i4").reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"save_mesh_ply: face indices outside 0 .. {v.shape[0] - 1}")
+    vt = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        c = np.asarray(_np(colors), dtype=np.float64).reshape(-1, 3)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f"save_mesh_ply: {c.shape[0]} colours for {v.shape[0]} vertices")
+        vt += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vrec = np.empty(v.shape[0], dtype=vt)
+    vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        c8 = np.rint(np.clip(np.nan_to_num(c), 0.0, 1.0) * 255.0).astype(np.uint8)
+        vrec["red"], vrec["green"], vrec["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
+    frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    frec["n"] = 3
+    frec["i"] = f
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+    header += "property float x\nproperty float y\nproperty float z\n"
+    if colors is not None:
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def read_mesh_ply(path):
+    """-> (vertices float32 [V, 3], faces int32 [F, 3], colors uint8 [V, 3] or None) of a file save_mesh_ply wrote (binary
+    little-endian, scalar vertex properties, triangles as `list uchar int`)."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PLY header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property" and elements:
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: read_mesh_ply reads binary_little_endian files, not {fmt}")
+        vertices = faces = colors = None
+        for name, count, props in elements:
+            if name == "vertex":
+                if any(p[0] == "list" for p in props):
+                    raise ValueError(f"{path}: list properties are not supported in the vertex element")
+                dt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in props])
+                rec = np.frombuffer(fh.read(count * dt.itemsize), dtype=dt, count=count)
+                vertices = np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float32).reshape(-1, 3)
+                if all(n in rec.dtype.names for n in ("red", "green", "blue")):
+                    colors = np.stack([rec["red"], rec["green"], rec["blue"]], axis=1).astype(np.uint8).reshape(-1, 3)
+            elif name == "face":
+                if len(props) != 1 or props[0][0] != "list":
+                    raise ValueError(f"{path}: the face element must be one list property")
+                dt = np.dtype([("n", "<" + _PLY_TYPES[props[0][1]]), ("i", "<" + _PLY_TYPES[props[0][2]], (3,))])
+                rec = np.frombuffer(fh.read(count * dt.itemsize), dtype=dt, count=count)
+                if count and not np.all(rec["n"] == 3):
+                    raise ValueError(f"{path}: only triangles are supported")
+                faces = rec["i"].astype(np.int32).reshape(-1, 3)
+            else:
+                raise ValueError(f"{path}: unexpected element {name}")
+        if vertices is None or faces is None:
+            raise ValueError(f"{path}: a mesh needs a vertex and a face element")
+        return vertices, faces, colors
 
 
 # ---- code book -----------------------------------------------------------------------------------

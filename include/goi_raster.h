@@ -51,7 +51,8 @@ extern "C" {
 
 /* 8: + goi_raster_forward_selected, goi_raster_forward_async_selected (a per-Gaussian selection the forward itself honours);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
- *    goi_semantic_pca_apply
+ *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
+ *    goi_field_iso_count, goi_field_iso_emit
  * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
  *    goi_raster_backward_scratch_bytes as ever);
@@ -895,6 +896,59 @@ int goi_raster_debug_backward_blend(const GoiRasterScene* scene, int R, int mode
                                     uint8_t* row_flags, uint32_t* aux, unsigned long long* qmask0, unsigned long long* qmask,
                                     uint32_t* qcost, uint32_t* qorder, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
                                     float* dL_dcolor, float* dL_dsemantic, float* dL_ddepth, void* stream);
+
+/* ---- a mesh from the Gaussians (csrc/field.hip) ---------------------------------------------------------
+ * goi_field_density: DreamGaussian's extract_fields(resolution, num_blocks, relax_ratio), which the reference's viewers
+ * presuppose (gui/main.py:607-617 calls extract_mesh; gui/gs_renderer.py:66-85 keeps only gaussian_3d_coeff).  Asynchronous on
+ * `stream`, nothing read back, no float atomics: the same bits every run.
+ *   kept        opacity[i] > (float)min_opacity, selected (selection NULL: all; otherwise (selection[i] != 0) != selection_invert),
+ *               and a finite centre.  The model is read in place.
+ *   frame       out, 4 floats: center = (min + max) / 2 of the kept centres, scale = (float)(1.8 / max extent); bounds != NULL
+ *               (device, 4 floats: center, scale) replaces it.  Nothing kept: (0, 0, 0, 1); no extent: scale 1.
+ *   inputs      xyz [P][3], opacity [P] (activated), scaling [P][3] (activated), rotation [P][4] (raw: normalised here),
+ *               attributes [P][3] or NULL.  Centre and scales are multiplied by scale; covariance (R S)(R S)^T as
+ *               build_scaling_rotation / strip_symmetric and its inverse by gaussian_3d_coeff's formulas (1 / (det + 1e-24)), in
+ *               fp64 once per Gaussian; the weight as gaussian_3d_coeff writes it in fp32 (power > 0: 0).
+ *   grid        coords [resolution] = torch.linspace(-1, 1, resolution) (read, never recomputed); block_lo / block_hi [num_blocks]:
+ *               the point bounds of block b, coords[b split] and coords[(b + 1) split - 1], widened by (2 / num_blocks) relax_ratio
+ *               in fp32; split = resolution / num_blocks.  A Gaussian joins block (bx, by, bz) iff lo < centre < hi strictly on every
+ *               axis.  occ [R][R][R] (x, y, z) = sum opacity w over the block's members; attr_out [3][R][R][R] = sum opacity w a
+ *               (attributes != NULL).
+ *   limits      0 <= P < 2^30, GOI_FIELD_MIN_SPLIT <= split <= GOI_FIELD_MAX_SPLIT, resolution <= GOI_FIELD_MAX_RESOLUTION,
+ *               resolution % num_blocks == 0, 0 <= relax_ratio <= GOI_FIELD_MAX_RELAX.  Anything else: -1.
+ *   status      out, one word: 0, or bit 1 when the sort's look-back timed out (the grids are then garbage: a caller that reads
+ *               anything back must look at it first, as field.extract_mesh does).
+ *   workspace   goi_field_density_workspace_bytes(P, resolution, num_blocks, relax_ratio) bytes (0: bad arguments), 256-byte aligned.
+ * GOI_FIELD_BATCH: members a block collects in LDS before its threads add them to their points (the sum does not depend on it).
+ *
+ * goi_field_iso_count / goi_field_iso_emit: marching tetrahedra on the Kuhn split of every cube of a [X][Y][Z] fp32 grid.  A point
+ * is inside iff value > (float)thresh.  A grid point owns seven edges (slots +x +y +z +xy +xz +yz +xyz); a vertex exists on an
+ * owned edge whose end points differ, at p_a + t (p_b - p_a), t = (thresh - v_a) / (v_b - v_a), a the owner, every operation one
+ * fp32 rounding; its colour is (A_a + t (A_b - A_a)) / thresh (attr [3][X][Y][Z] or NULL).  cx / cy / cz: the coordinates of the
+ * grid lines per axis, or NULL for the index itself.  Vertices are ordered by (owner, slot), faces by (cube, tetrahedron, triangle),
+ * normals point from inside to outside, the surface is open where it meets the grid's boundary.
+ *   count: fills the workspace and writes counts[0] = vertices, counts[1] = faces (device): the caller reads them back, sizes
+ *          vertices [V][3], faces [F][3] (int32), colors [V][3] and calls emit with the same grid, thresh and workspace.
+ *   workspace: goi_field_iso_workspace_bytes(X, Y, Z) bytes (0: bad dimensions), 256-byte aligned.  1 <= X, Y, Z and X Y Z <= GOI_FIELD_MAX_GRID_POINTS = 2^26 (a
+ *          point owns at most 7 crossings and a cube has at most 12 triangles, so both counts stay below 2^31 and their sum, which
+ *          one 32-bit scan forms, below 2^32). */
+#define GOI_FIELD_BATCH 128
+#define GOI_FIELD_MIN_SPLIT 4
+#define GOI_FIELD_MAX_SPLIT 16
+#define GOI_FIELD_MAX_RESOLUTION 256
+#define GOI_FIELD_MAX_RELAX 4.0
+#define GOI_FIELD_MAX_GRID_POINTS (1ll << 26)
+size_t goi_field_density_workspace_bytes(long long P, int resolution, int num_blocks, double relax_ratio);
+int goi_field_density(long long P, const float* xyz, const float* opacity, const float* scaling, const float* rotation,
+                      const uint8_t* selection, int selection_invert, double min_opacity, const float* attributes,
+                      const float* bounds, int resolution, int num_blocks, double relax_ratio, const float* coords,
+                      const float* block_lo, const float* block_hi, float* occ, float* attr_out, float* frame, int* status,
+                      void* workspace, void* stream);
+size_t goi_field_iso_workspace_bytes(int X, int Y, int Z);
+int goi_field_iso_count(const float* grid, int X, int Y, int Z, double thresh, void* workspace, int* counts, void* stream);
+int goi_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z, double thresh, const float* cx, const float* cy,
+                       const float* cz, const void* workspace, long long n_vertices, long long n_faces, float* vertices, int* faces,
+                       float* colors, void* stream);
 
 #ifdef __cplusplus
 }
