@@ -1195,6 +1195,9 @@ def rasterize_gaussians_trace(background, means3D, colors, img_sem, opacity, sca
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
     if img_sem is None or img_sem.numel() == 0:
         raise RuntimeError("img_sem [S,H,W] is required")
+    # (the kernel reads S * H * W floats of it: a smaller image would be read out of bounds)
+    if img_sem.ndimension() != 3 or int(img_sem.size(1)) != H or int(img_sem.size(2)) != W or not 1 <= int(img_sem.size(0)) <= 32:
+        raise RuntimeError("img_sem must have dimensions (S, image_height, image_width)")
     fa = _FrameArgs(background, means3D, colors, img_sem, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                     projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug)
     ext = _ext()

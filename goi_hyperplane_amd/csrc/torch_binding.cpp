@@ -509,6 +509,10 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_gaussi
     const int image_width, const Tensor& sh, const int degree, const Tensor& campos, const bool prefiltered,
     const bool debug) {
     TORCH_CHECK(img_sem.defined() && img_sem.numel() > 0, "img_sem [S,H,W] is required");
+    // (the kernel reads S * H * W floats of it: a smaller image would be read out of bounds)
+    TORCH_CHECK(img_sem.ndimension() == 3 && img_sem.size(1) == image_height && img_sem.size(2) == image_width &&
+                    img_sem.size(0) >= 1 && img_sem.size(0) <= 32,
+                "img_sem must have dimensions (S, image_height, image_width)");
     Prepared f = prepare(background, means3D, colors, img_sem, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                          viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                          prefiltered, debug, false);

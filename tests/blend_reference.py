@@ -662,12 +662,15 @@ def forward_reference(fr: Frame, qd: Quads, alpha, hit) -> dict:
     return dict(acc=acc[inv], mag=mag[inv], T=T[inv], k=k_depth[inv], stop=stop[inv], last_hit=last_hit[inv])
 
 
-def check_forward(fr: Frame, qd: Quads, fw: dict, maps: dict, gate: dict) -> dict:
+def check_forward(fr: Frame, qd: Quads, fw: dict, maps: dict, gate: dict, *, colour_only: bool = False) -> dict:
     """n_contrib against the stop rule in float64 -- the last contributor is a hit, the product after it is not below 1e-4, the
     stopper's product is below it, each within (k + 2) 2^-23 relative (k: the pixel's contributors; two roundings per factor of
     the fp32 product chain) -- and out_alpha and the four maps against the float64 composite within the element's magnitude
     companion times the gate (16 x the yardstick's maximum: features for the semantic map, colour / depth for the others).
-    maps: color [3,HW], sem [S,HW], depth [HW], alpha [HW].  Returns the largest normalised errors."""
+    maps: color [3,HW], sem [S,HW], depth [HW], alpha [HW], all four -- or, with colour_only (a trace has no other map), `color`
+    alone.  Returns the largest normalised errors."""
+    want_keys = {"color"} if colour_only else {"color", "sem", "depth", "alpha"}
+    assert set(maps) == want_keys, f"maps must hold exactly {sorted(want_keys)}, got {sorted(maps)}"
     ins = qd.inside
     nc = qd.nc
     assert (fw["last_hit"] | (nc == 0))[ins].all(), "a pixel's last contributor is not a pair that passes the guards"
@@ -691,12 +694,14 @@ def check_forward(fr: Frame, qd: Quads, fw: dict, maps: dict, gate: dict) -> dic
 
     gf, gc = 16 * gate["features"][2], 16 * gate["colour_depth"][2]
     acc, mag, T = fw["acc"][ins], fw["mag"][ins], fw["T"][ins]
-    for ch in range(fr.S):
+    for ch in range(0 if colour_only else fr.S):
         cmp("sem", np.asarray(maps["sem"]).reshape(fr.S, -1)[ch, pix], acc[:, ch], mag[:, ch], gf)
     for ch in range(3):
         cmp("color", np.asarray(maps["color"]).reshape(3, -1)[ch, pix], acc[:, n + ch] + T * bg[ch], mag[:, n + ch] + T * abs(bg[ch]), gc)
-    cmp("depth", np.asarray(maps["depth"]).reshape(-1)[pix], acc[:, n + 3], mag[:, n + 3], gc)
-    cmp("alpha", np.asarray(maps["alpha"]).reshape(-1)[pix], 1 - T, np.ones_like(T), gc)
+    if not colour_only:
+        cmp("depth", np.asarray(maps["depth"]).reshape(-1)[pix], acc[:, n + 3], mag[:, n + 3], gc)
+    if not colour_only:
+        cmp("alpha", np.asarray(maps["alpha"]).reshape(-1)[pix], 1 - T, np.ones_like(T), gc)
     return out
 
 

@@ -1,0 +1,177 @@
+"""markVisible (csrc/preprocess.hip: mark_visible_k) at its threshold: view depth > 0.2f, the depth formed as gmath.h's
+xform_point_4x3 forms it -- m[2] x + m[6] y + m[10] z + m[14], left to right, one rounding per operation (the file is built without
+contraction).
+
+100 000 points lie within 1e-6 of the near plane, spread over the frustum and far beyond it sideways.  The camera is
+make_camera(yaw=0.3, pitch=-0.1, distance=0.2): the distance is NOT make_camera's default of 5.  At distance 5, m[14] = 5 and a
+depth near 0.2 is 5 + s with s near -4.8, an exact difference on the grid of s's last bit, 2^-21 = 4.8e-7: the fp32 depth could
+then never be 0.2f nor either neighbouring float (1.5e-8 apart).  At distance 0.2, m[14] is fp32(0.2) itself and the three
+products nearly cancel: the fp32 depth takes every float around 0.2f -- 0.2f exactly (must be False) and both neighbours among
+them -- and which side a point falls on depends on the order of the four operations.  The kernel must agree
+  * with a numpy float32 restatement in that order, on every point;
+  * with oracle.mark_visible, on every point;
+  * with the float64 decision wherever the float64 depth is further from the threshold than gamma(4) x (the sum of the four terms'
+    magnitudes): every term goes through at most four roundings, its product and three additions.  (The threshold the kernel
+    compares with is 0.2f = 0.2 + 2.98e-9; the float64 decision uses that number.)
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+import torch
+
+from goi_hyperplane_amd.scene import make_camera
+from tests import preprocess_reference as PR
+from tests import trace_reference as TR
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+NEAR = np.float32(0.2)
+N_SLAB = 100_000
+
+
+@pytest.fixture(autouse=True)
+def _restore():
+    from goi_hyperplane_amd import _C
+    _C.set_binding("compiled")  # fails loudly if lib/_goi_C.so has not been built
+    yield
+    _C.poll_counts(wait=True)
+    _C.set_binding("compiled")
+
+
+def camera():
+    # (distance 0.2, not the default 5: see the module docstring)
+    return make_camera(64, 48, yaw=0.3, pitch=-0.1, distance=0.2)
+
+
+def depth64(points, view):
+    """(float64 view depth of fp32 points under the fp32 matrix, the sum of the four terms' magnitudes)."""
+    m = np.asarray(view, np.float64).reshape(16)
+    p = np.asarray(points, np.float64)
+    terms = np.stack([m[2] * p[:, 0], m[6] * p[:, 1], m[10] * p[:, 2], np.full(len(p), m[14])], 1)
+    return terms.sum(1), np.abs(terms).sum(1)
+
+
+def depth32(points, view):
+    """The kernel's depth: fp32, left to right, no contraction (gmath.h:55-58)."""
+    m = np.asarray(view, np.float32).reshape(16)
+    p = np.asarray(points, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        z = ((m[2] * p[:, 0] + m[6] * p[:, 1]) + m[10] * p[:, 2]) + m[14]
+    assert z.dtype == np.float32
+    return z
+
+
+def slab_points(cam, n=N_SLAB, seed=20):
+    """n fp32 points whose float64 view depth lies within 1e-6 of 0.2: a third inside the frustum, the others up to 3 units
+    (30 half-widths of the frustum at that depth) to the side."""
+    rng = np.random.default_rng(seed)
+    V = np.asarray(cam.world_view_transform, np.float64)  # row vectors: p_view = [p, 1] V
+    inv = np.linalg.inv(V)
+    out = []
+    while sum(len(x) for x in out) < n:
+        k = 2 * n
+        half = np.where(rng.uniform(size=k) < 1 / 3, 0.2 * cam.tanfovx, 3.0)
+        pv = np.stack([rng.uniform(-1, 1, k) * half, rng.uniform(-1, 1, k) * half, 0.2 + rng.uniform(-0.8e-6, 0.8e-6, k), np.ones(k)], 1)
+        pts = (pv @ inv)[:, :3].astype(np.float32)
+        z, _ = depth64(pts, cam.world_view_transform)
+        out.append(pts[np.abs(z - 0.2) < 1e-6])
+    return np.ascontiguousarray(np.concatenate(out)[:n])
+
+
+@pytest.fixture(scope="module")
+def slab():
+    cam = camera()
+    pts = slab_points(cam)
+    view = np.asarray(cam.world_view_transform, np.float32)
+    z32 = depth32(pts, view)
+    z64, mag = depth64(pts, view)
+    # the input conditions
+    assert view.reshape(16)[14] == NEAR and all(view.reshape(16)[i] != 0 for i in (2, 6, 10))
+    assert len(pts) == N_SLAB and (np.abs(z64 - 0.2) < 1e-6).all()
+    below, above = np.nextafter(NEAR, np.float32(0)), np.nextafter(NEAR, np.float32(1))
+    n_at, n_below, n_above = int((z32 == NEAR).sum()), int((z32 == below).sum()), int((z32 == above).sum())
+    assert min(n_at, n_below, n_above) > 0, (n_at, n_below, n_above)
+    inside = (np.abs(pts.astype(np.float64) @ np.asarray(view, np.float64)[:3, :2] + np.asarray(view, np.float64)[3, :2])
+              <= 0.2 * np.array([cam.tanfovx, cam.tanfovy])).all(axis=1)
+    assert 0.05 < inside.mean() < 0.6
+    t = float(NEAR)
+    clear = np.abs(z64 - t) > TR.gamma(4) * mag
+    flips = int(((z32 > NEAR) != (z64 > t)).sum())
+    assert clear.sum() > N_SLAB // 2 and (~clear).sum() > 100 and flips > 0, (int(clear.sum()), flips)
+    assert ((z32 > NEAR) == (z64 > t))[clear].all(), "the restatement itself leaves the derived band"
+    print(dict(at_threshold=n_at, one_below=n_below, one_above=n_above, clear=int(clear.sum()), fp32_differs_from_fp64=flips))
+    return dict(cam=cam, pts=pts, view=view, z32=z32, z64=z64, clear=clear)
+
+
+def _mark(pts, cam, proj=None):
+    from goi_hyperplane_amd import _C
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(DEV)  # noqa: E731
+    p = pts if torch.is_tensor(pts) else t(pts)
+    out = _C.mark_visible(p, t(cam.world_view_transform), t(cam.full_proj_transform) if proj is None else proj)
+    assert out.dtype == torch.bool and tuple(out.shape) == (p.shape[0],)
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("binding", ["compiled", "ctypes"])
+def test_points_at_the_near_plane(slab, oracle_mod, binding):
+    from goi_hyperplane_amd import _C
+    _C.set_binding(binding)
+    cam, pts = slab["cam"], slab["pts"]
+    for P in (N_SLAB, 1, 255, 256, 257):
+        got = _mark(pts[:P], cam)
+        want = slab["z32"][:P] > NEAR
+        assert np.array_equal(got, want), (f"P = {P}: {int((got != want).sum())} points differ from the float32 restatement, first "
+                                           f"{int(np.flatnonzero(got != want)[0])}")
+        assert np.array_equal(got, oracle_mod.mark_visible(pts[:P], cam.world_view_transform, cam.full_proj_transform))
+    got = _mark(pts, cam)
+    assert not got[slab["z32"] == NEAR].any(), "a point at depth 0.2f exactly is visible"
+    assert got[slab["z32"] == np.nextafter(NEAR, np.float32(1))].all() and not got[slab["z32"] == np.nextafter(NEAR, np.float32(0))].any()
+    c = slab["clear"]
+    assert np.array_equal(got[c], (slab["z64"] > float(NEAR))[c]), "the kernel leaves the float64 decision outside the derived band"
+
+
+def test_special_values_strides_and_the_unused_matrix(slab, oracle_mod):
+    from goi_hyperplane_amd import _C
+    cam, pts, view = slab["cam"], slab["pts"][:1000], slab["view"]
+    m = view.reshape(16)
+    inf, nan = np.float32(np.inf), np.float32(np.nan)
+    s = np.sign(m[2])
+    special = np.array([[nan, 0, 0], [0, nan, 0], [0, 0, nan], [s * inf, 0, 0], [-s * inf, 0, 0], [0, 0, 1], [0, 0, -1]], np.float32)
+    z = depth32(special, view)
+    assert np.isnan(z[:3]).all() and z[3] == inf and z[4] == -inf
+    got = _mark(special, cam)
+    assert np.array_equal(got[:5], [False, False, False, True, False]), got
+    # (the oracle, like the reference's `if (p_view.z <= 0.2f) return false`, calls a NaN depth visible; the product's `z > 0.2f`
+    # does not: the two are compared on the other rows)
+    assert np.array_equal(got, z > NEAR)
+    assert np.array_equal(got[3:], oracle_mod.mark_visible(special, cam.world_view_transform, cam.full_proj_transform)[3:])
+    want = slab["z32"][:1000] > NEAR
+    wide = torch.full((2000, 5), float("nan"), device=DEV)
+    wide[::2, 1:4] = torch.from_numpy(pts).to(DEV)
+    strided = wide[::2, 1:4]
+    assert not strided.is_contiguous()
+    garbage = torch.full((4, 4), float("nan"), device=DEV)
+    for name in ("compiled", "ctypes"):
+        _C.set_binding(name)
+        assert np.array_equal(_mark(strided, cam), want), f"{name}: a strided means3D"
+        assert np.array_equal(_mark(pts, cam, proj=garbage), want), f"{name}: projmatrix is not read"
+
+
+def test_visibility_and_the_forward_agree_on_the_camera_inside_scene():
+    """radii > 0 implies visible; not visible implies radii == 0."""
+    from goi_hyperplane_amd import _C
+    inp = PR.make_inputs(3000, "inside")
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(DEV)  # noqa: E731
+    E = torch.Tensor([])
+    view, proj = t(inp["viewmatrix"]), t(inp["projmatrix"])
+    res = _C.rasterize_gaussians(torch.zeros(3, device=DEV), t(inp["means3D"]), E, t(inp["semantics"]), t(inp["opacities"]),
+                                 t(inp["scales"]), t(inp["rotations"]), 1.0, E, view, proj, inp["tan_fovx"], inp["tan_fovy"], inp["H"],
+                                 inp["W"], t(inp["shs"]), inp["sh_degree"], t(inp["campos"]), False, False)
+    radii = res[5].cpu().numpy()
+    for name in ("compiled", "ctypes"):
+        _C.set_binding(name)
+        vis = _C.mark_visible(t(inp["means3D"]), view, proj).cpu().numpy()
+        assert np.array_equal(vis, depth32(inp["means3D"], inp["viewmatrix"]) > NEAR)
+        assert (~vis).sum() > 100 and (radii > 0).sum() > 100 and (vis & (radii == 0)).sum() > 0
+        assert vis[radii > 0].all() and not radii[~vis].any()
