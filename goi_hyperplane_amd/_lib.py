@@ -157,6 +157,23 @@ FIELD_SYMBOLS = {
                            + [C.c_longlong, C.c_longlong] + [C.c_void_p] * 4),
 }
 
+# the goi_mesh_* family (csrc/mesh.hip: components, clean-up, vertex clustering, normals)
+_LL, _P = C.c_longlong, C.c_void_p
+MESH_SYMBOLS = {
+    "goi_mesh_components_workspace_bytes": (C.c_size_t, [_LL, _LL]),
+    "goi_mesh_components": (C.c_int, [_LL, _LL] + [_P] * 6),
+    "goi_mesh_clean_workspace_bytes": (C.c_size_t, [_LL, _LL]),
+    "goi_mesh_clean_plan": (C.c_int, [_LL, _LL, _P, _P, _LL, C.c_double, _P, _P, _P]),
+    "goi_mesh_clean_emit": (C.c_int, [_LL, _LL] + [_P] * 4 + [_LL, _LL] + [_P] * 6),
+    "goi_mesh_decimate_workspace_bytes": (C.c_size_t, [_LL, _LL]),
+    "goi_mesh_decimate_members": (C.c_int, [_LL, _LL] + [_P] * 4),
+    "goi_mesh_decimate_probe": (C.c_int, [_LL, _LL, _P, _P, C.c_int, _P, _P, _P]),
+    "goi_mesh_decimate_plan": (C.c_int, [_LL, _LL, _P, _P, C.c_int, _P, _P, _P]),
+    "goi_mesh_decimate_emit": (C.c_int, [_LL, _LL, _P, _P, C.c_int, C.c_int, _P, _LL, _LL] + [_P] * 5),
+    "goi_mesh_normals_workspace_bytes": (C.c_size_t, [_LL, _LL]),
+    "goi_mesh_normals": (C.c_int, [_LL, _LL] + [_P] * 6),
+}
+
 _lib = None
 
 
@@ -174,7 +191,7 @@ def load():
         # the system copy and the two runtimes would not see each other's devices and allocations).
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(FIELD_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(FIELD_SYMBOLS.items()) + list(MESH_SYMBOLS.items()):
             fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

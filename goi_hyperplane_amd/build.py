@@ -48,6 +48,7 @@ UNITS = {
     "display.hip": ["-ffp-contract=off"],  # the viewer's blend a*b + c*d is compared bit for bit: no FMA
     "pca.hip": ["-ffp-contract=off"],  # the projection and its normalisations are one rounding per operation
     "field.hip": ["-ffp-contract=off"],  # the iso-surface's vertices are one rounding per operation (the density loop names its FMAs)
+    "mesh.hip": ["-ffp-contract=off"],  # null faces, cells, means and normals are compared bit for bit: one rounding per operation
 }
 
 

@@ -350,6 +350,28 @@ void launch_field_iso_count(const float* grid, int X, int Y, int Z, float thresh
 void launch_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z, float thresh, const float* cx,
                            const float* cy, const float* cz, const void* workspace, long long V, long long F, float* vertices,
                            int* faces, float* colors, hipStream_t s);
+// mesh clean-up (mesh.hip); V, F >= 0, the sizes checked by api.hip
+size_t mesh_components_workspace_bytes(long long V, long long F);
+void launch_mesh_components(long long V, long long F, const int* faces, int* vertex_label, int* face_label, int* status,
+                            void* workspace, hipStream_t s);
+size_t mesh_clean_workspace_bytes(long long V, long long F);
+void launch_mesh_clean_plan(long long V, long long F, const float* vertices, const int* faces, long long min_faces,
+                            double min_diag2, void* workspace, int* counts, hipStream_t s);
+void launch_mesh_clean_emit(long long V, long long F, const float* vertices, const int* faces, const float* colors,
+                            const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
+                            float* out_colors, int* vertex_index, int* face_index, hipStream_t s);
+size_t mesh_decimate_workspace_bytes(long long V, long long F);
+void launch_mesh_decimate_members(long long V, long long F, const float* vertices, const int* faces, void* workspace, hipStream_t s);
+void launch_mesh_decimate_probe(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
+                                int* count, hipStream_t s);
+int launch_mesh_decimate_plan(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
+                              int* counts, hipStream_t s);
+void launch_mesh_decimate_emit(long long V, long long F, const float* vertices, const float* colors, int divisions, int sorted_in,
+                               const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
+                               float* out_colors, int* cluster, hipStream_t s);
+size_t mesh_normals_workspace_bytes(long long V, long long F);
+void launch_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
+                         void* workspace, hipStream_t s);
 size_t uniq_workspace_bytes(int V, int D, uint32_t HW);
 uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW);  // [V] counts, then the flag word
 void launch_uniq_dedup(const float* const* maps, int V, int D, uint32_t HW, void* ws, hipStream_t s);

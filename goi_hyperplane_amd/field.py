@@ -24,8 +24,8 @@ Semantics of density_grid (tests/field_reference.py restates them in float64):
 Everything runs on the current stream.  density_grid reads nothing back; isosurface reads its two counts back once to size
 its outputs.  No float atomics: results are bit-identical from run to run.  There is no CPU fallback.
 
-Not here: the reference's follow-ups clean_mesh / decimate_mesh (pymeshlab), UV unwrapping and the nvdiffrast texture bake
-of mode='geo+tex'.
+Not here: the reference's follow-ups clean_mesh / decimate_mesh and the normals of Mesh.auto_normal (mesh.py has them:
+mesh.extract chains them behind extract_mesh), UV unwrapping and the nvdiffrast texture bake of mode='geo+tex'.
 """
 from __future__ import annotations
 

@@ -163,14 +163,20 @@ def activate(raw: dict) -> dict:
 
 
 # ---- mesh ----------------------------------------------------------------------------------------
-def save_mesh_ply(path, vertices, faces, colors=None) -> None:
-    """A triangle mesh as binary little-endian PLY: element vertex (float x y z, and uchar red green blue when colors [V, 3]
-    in [0, 1] are given: round(255 c)), element face (list uchar int vertex_indices).  Zero vertices or faces are fine."""
+def save_mesh_ply(path, vertices, faces, colors=None, normals=None) -> None:
+    """A triangle mesh as binary little-endian PLY: element vertex (float x y z, float nx ny nz when normals [V, 3] are given
+    (mesh.vertex_normals), and uchar red green blue when colors [V, 3] in [0, 1] are given: round(255 c)), element face (list
+    uchar int vertex_indices).  Zero vertices or faces are fine."""
     v = np.ascontiguousarray(_np(vertices), dtype="<f4").reshape(-1, 3)
     f = np.ascontiguousarray(_np(faces), dtype="<i4").reshape(-1, 3)
     if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
         raise ValueError(f"save_mesh_ply: face indices outside 0 .. {v.shape[0] - 1}")
     vt = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        n = np.ascontiguousarray(_np(normals), dtype="<f4").reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"save_mesh_ply: {n.shape[0]} normals for {v.shape[0]} vertices")
+        vt += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if colors is not None:
         c = np.asarray(_np(colors), dtype=np.float64).reshape(-1, 3)
         if c.shape[0] != v.shape[0]:
@@ -178,6 +184,8 @@ def save_mesh_ply(path, vertices, faces, colors=None) -> None:
         vt += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     vrec = np.empty(v.shape[0], dtype=vt)
     vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if colors is not None:
         c8 = np.rint(np.clip(np.nan_to_num(c), 0.0, 1.0) * 255.0).astype(np.uint8)
         vrec["red"], vrec["green"], vrec["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
@@ -189,6 +197,8 @@ def save_mesh_ply(path, vertices, faces, colors=None) -> None:
         os.makedirs(d, exist_ok=True)
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
     header += "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
     if colors is not None:
         header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
@@ -198,9 +208,10 @@ def save_mesh_ply(path, vertices, faces, colors=None) -> None:
         fh.write(frec.tobytes())
 
 
-def read_mesh_ply(path):
+def read_mesh_ply(path, with_normals=False):
     """-> (vertices float32 [V, 3], faces int32 [F, 3], colors uint8 [V, 3] or None) of a file save_mesh_ply wrote (binary
-    little-endian, scalar vertex properties, triangles as `list uchar int`)."""
+    little-endian, scalar vertex properties, triangles as `list uchar int`).  with_normals: a fourth item, the file's nx ny nz as
+    float32 [V, 3] or None."""
     with open(path, "rb") as fh:
         if fh.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -222,7 +233,7 @@ def read_mesh_ply(path):
                 break
         if fmt != "binary_little_endian":
             raise ValueError(f"{path}: read_mesh_ply reads binary_little_endian files, not {fmt}")
-        vertices = faces = colors = None
+        vertices = faces = colors = normals = None
         for name, count, props in elements:
             if name == "vertex":
                 if any(p[0] == "list" for p in props):
@@ -232,6 +243,8 @@ def read_mesh_ply(path):
                 vertices = np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float32).reshape(-1, 3)
                 if all(n in rec.dtype.names for n in ("red", "green", "blue")):
                     colors = np.stack([rec["red"], rec["green"], rec["blue"]], axis=1).astype(np.uint8).reshape(-1, 3)
+                if all(n in rec.dtype.names for n in ("nx", "ny", "nz")):
+                    normals = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=1).astype(np.float32).reshape(-1, 3)
             elif name == "face":
                 if len(props) != 1 or props[0][0] != "list":
                     raise ValueError(f"{path}: the face element must be one list property")
@@ -244,7 +257,7 @@ def read_mesh_ply(path):
                 raise ValueError(f"{path}: unexpected element {name}")
         if vertices is None or faces is None:
             raise ValueError(f"{path}: a mesh needs a vertex and a face element")
-        return vertices, faces, colors
+        return (vertices, faces, colors, normals) if with_normals else (vertices, faces, colors)
 
 
 # ---- code book -----------------------------------------------------------------------------------

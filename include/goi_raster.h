@@ -52,7 +52,10 @@ extern "C" {
 /* 8: + goi_raster_forward_selected, goi_raster_forward_async_selected (a per-Gaussian selection the forward itself honours);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
- *    goi_field_iso_count, goi_field_iso_emit
+ *    goi_field_iso_count, goi_field_iso_emit; goi_mesh_components_workspace_bytes, goi_mesh_components,
+ *    goi_mesh_clean_workspace_bytes, goi_mesh_clean_plan, goi_mesh_clean_emit, goi_mesh_decimate_workspace_bytes,
+ *    goi_mesh_decimate_members, goi_mesh_decimate_probe, goi_mesh_decimate_plan, goi_mesh_decimate_emit,
+ *    goi_mesh_normals_workspace_bytes, goi_mesh_normals
  * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
  *    goi_raster_backward_scratch_bytes as ever);
@@ -949,6 +952,57 @@ int goi_field_iso_count(const float* grid, int X, int Y, int Z, double thresh, v
 int goi_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z, double thresh, const float* cx, const float* cy,
                        const float* cz, const void* workspace, long long n_vertices, long long n_faces, float* vertices, int* faces,
                        float* colors, void* stream);
+
+/* ---- Mesh clean-up (csrc/mesh.hip) -----------------------------------------------------------------------
+ * A mesh is vertices [V][3] fp32 and faces [F][3] int32, both on the device; 0 <= V, F and V, 3 F < 2^30.  Every entry point
+ * runs on `stream`, returns 0 (or -1: goi_raster_last_error) and never reads the device back; workspaces are the matching
+ * *_workspace_bytes(V, F) bytes (0: bad sizes), 256-byte aligned.  Integer outputs are exact, float outputs have one fixed
+ * summation order and no float atomics: two calls give the same bits.  All float arithmetic is one fp32 rounding per operation.
+ * `status` words are device words holding GOI_MESH_STATUS_* bits: a caller that reads results back looks at them first.
+ *
+ * goi_mesh_components: two vertices are connected when a face names both.  vertex_label [V] = the smallest vertex index of the
+ *   vertex's component, -1 for a vertex no face names; face_label [F] = the label of the face's first vertex.
+ * goi_mesh_clean_plan / _emit: in this order, drops null faces (a repeated index, a non-finite vertex, or the cross product
+ *   (v1 - v0) x (v2 - v0) exactly zero), duplicate faces (the same set of three indices; the lowest face stays), components
+ *   with fewer than min_faces faces or with d2 < min_diag2 * d2 of the mesh (d2: the fp64 sum, x y z, of the squares of the fp32
+ *   extents of the box of the vertices still referenced), and unreferenced vertices.  plan writes counts[0] = vertices,
+ *   counts[1] = faces, counts[2] = status; the caller reads them back, sizes the outputs and calls emit with the same mesh and
+ *   workspace.  Survivors keep their order; vertex_index / face_index give their original indices; colors [V][3] or NULL.
+ * goi_mesh_decimate_*: vertex clustering on a divisions^3 grid over the box of the members (finite vertices a face names):
+ *   lo = the per-axis minimum, cell = (largest extent) / divisions, q = min(floor((v - lo) / cell), divisions - 1), key =
+ *   (qx n + qy) n + qz; no extent: cell 0.  members: once per mesh.  probe: *count = faces whose three vertices are members in
+ *   three distinct cells.  plan: sorts, maps the faces through the cells, drops those without three distinct cells and duplicates,
+ *   writes counts as clean_plan does and returns (0 or 1) the value emit wants as sorted_in.  emit: vertices (and colours) = the
+ *   mean of a cell's members, summed in fp64 in ascending vertex index, divided by the count and rounded once; only cells a
+ *   surviving face names, by ascending key; cluster [V] = the output vertex of every input vertex or -1.  1 <= divisions <= 1024.
+ * goi_mesh_normals: Mesh.auto_normal -- every face adds its un-normalised cross product to its three corners; here each vertex
+ *   sums its corners in ascending (face, corner) order; a sum with dot <= 1e-20 becomes (0, 0, 1); divided by
+ *   sqrt(max(dot, 1e-20)). */
+#define GOI_MESH_STATUS_SORT 2   /* a look-back of a sort timed out on a wedged device: the results are garbage */
+#define GOI_MESH_STATUS_UNION 4  /* a union-find walk ran out of its bound (cannot happen: parents only decrease) */
+#define GOI_MESH_STATUS_RANGE 8  /* a face names an index outside [0, V): it was treated as absent */
+#define GOI_MESH_MAX_DIVISIONS 1024
+size_t goi_mesh_components_workspace_bytes(long long V, long long F);
+int goi_mesh_components(long long V, long long F, const int* faces, int* vertex_label, int* face_label, int* status,
+                        void* workspace, void* stream);
+size_t goi_mesh_clean_workspace_bytes(long long V, long long F);
+int goi_mesh_clean_plan(long long V, long long F, const float* vertices, const int* faces, long long min_faces, double min_diag2,
+                        void* workspace, int* counts, void* stream);
+int goi_mesh_clean_emit(long long V, long long F, const float* vertices, const int* faces, const float* colors,
+                        const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
+                        float* out_colors, int* vertex_index, int* face_index, void* stream);
+size_t goi_mesh_decimate_workspace_bytes(long long V, long long F);
+int goi_mesh_decimate_members(long long V, long long F, const float* vertices, const int* faces, void* workspace, void* stream);
+int goi_mesh_decimate_probe(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
+                            int* count, void* stream);
+int goi_mesh_decimate_plan(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
+                           int* counts, void* stream);
+int goi_mesh_decimate_emit(long long V, long long F, const float* vertices, const float* colors, int divisions, int sorted_in,
+                           const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
+                           float* out_colors, int* cluster, void* stream);
+size_t goi_mesh_normals_workspace_bytes(long long V, long long F);
+int goi_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
+                     void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
