@@ -174,6 +174,20 @@ MESH_SYMBOLS = {
     "goi_mesh_normals": (C.c_int, [_LL, _LL] + [_P] * 6),
 }
 
+# the goi_texture_* family (csrc/texture.hip: rasterize, resolve, grid put, accumulate, fill)
+_I = C.c_int
+TEXTURE_SYMBOLS = {
+    "goi_texture_rasterize_workspace_bytes": (C.c_size_t, [_LL, _I, _I]),
+    "goi_texture_rasterize": (C.c_int, [_LL, _LL, _P, _P, _I, _I] + [_P] * 6),
+    "goi_texture_resolve": (C.c_int, [_LL, _LL, _LL, _I, _I] + [_P] * 13),
+    "goi_texture_grid_put_workspace_bytes": (C.c_size_t, [_LL, _I, _I, _I]),
+    "goi_texture_grid_put": (C.c_int, [_LL, _I, _I, _I, _I] + [_P] * 12),
+    "goi_texture_accumulate": (C.c_int, [_LL, _I] + [_P] * 5),
+    "goi_texture_normalize": (C.c_int, [_LL, _I] + [_P] * 5),
+    "goi_texture_fill_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "goi_texture_fill": (C.c_int, [_I, _I, _I, _I] + [_P] * 6),
+}
+
 _lib = None
 
 
@@ -191,7 +205,8 @@ def load():
         # the system copy and the two runtimes would not see each other's devices and allocations).
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(FIELD_SYMBOLS.items()) + list(MESH_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(FIELD_SYMBOLS.items()) + list(MESH_SYMBOLS.items()) + \
+                list(TEXTURE_SYMBOLS.items()):
             fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

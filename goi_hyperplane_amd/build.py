@@ -49,6 +49,7 @@ UNITS = {
     "pca.hip": ["-ffp-contract=off"],  # the projection and its normalisations are one rounding per operation
     "field.hip": ["-ffp-contract=off"],  # the iso-surface's vertices are one rounding per operation (the density loop names its FMAs)
     "mesh.hip": ["-ffp-contract=off"],  # null faces, cells, means and normals are compared bit for bit: one rounding per operation
+    "texture.hip": ["-ffp-contract=off"],  # barycentrics, splat weights and upsampling are compared bit for bit: no FMA
 }
 
 

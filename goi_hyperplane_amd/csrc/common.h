@@ -372,6 +372,22 @@ void launch_mesh_decimate_emit(long long V, long long F, const float* vertices, 
 size_t mesh_normals_workspace_bytes(long long V, long long F);
 void launch_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
                          void* workspace, hipStream_t s);
+// texture bake (texture.hip); the sizes checked by api.hip
+size_t texture_rasterize_workspace_bytes(long long F, int H, int W);
+void launch_texture_rasterize(long long V, long long F, const float* v_clip, const int* faces, int H, int W, int* tri, float* bary,
+                              float* zw, int* status, void* workspace, hipStream_t s);
+void launch_texture_resolve(long long n_vt, long long n_vn, long long F, int H, int W, const int* tri, const float* bary,
+                            const float* vt, const int* ft, const float* vn, const int* faces, const float* pose_rot,
+                            const float* image, float* coords, float* values, unsigned char* valid, int* status, hipStream_t s);
+size_t texture_grid_put_workspace_bytes(long long N, int C, int H, int W);
+void launch_texture_grid_put(long long N, int C, int H, int W, int min_resolution, const float* coords, const float* values,
+                             const unsigned char* valid, float* result, float* count, float* acc, float* acc_count, float* norm_out,
+                             unsigned char* norm_mask, int* status, void* workspace, hipStream_t s);
+void launch_texture_accumulate(long long T, int C, float* albedo, float* cnt, const float* cur, const float* cur_cnt, hipStream_t s);
+void launch_texture_normalize(long long T, int C, const float* albedo, const float* cnt, float* out, unsigned char* mask, hipStream_t s);
+size_t texture_fill_workspace_bytes(int h, int w);
+void launch_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
+                         void* workspace, hipStream_t s);
 size_t uniq_workspace_bytes(int V, int D, uint32_t HW);
 uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW);  // [V] counts, then the flag word
 void launch_uniq_dedup(const float* const* maps, int V, int D, uint32_t HW, void* ws, hipStream_t s);

@@ -11,6 +11,8 @@ that scenes, code books and checkpoints move in both directions:
   * mesh.ply               what field.extract_mesh gives (the reference's "save mesh" button, gui/main.py:607-617): binary
                            little-endian PLY, `vertex` (float x y z, optionally uchar red green blue) and `face`
                            (list uchar int vertex_indices)
+  * mesh.obj               what texture.bake gives (the button's mode 'geo+tex', gui/mesh.py:576-622 write_obj): .obj + .mtl +
+                           _albedo.png
 
 The reference reads and writes PLY through the `plyfile` package; this module speaks the format
 directly with numpy (header grammar of the PLY 1.0 spec: ascii / binary_little_endian /
@@ -258,6 +260,94 @@ def read_mesh_ply(path, with_normals=False):
         if vertices is None or faces is None:
             raise ValueError(f"{path}: a mesh needs a vertex and a face element")
         return (vertices, faces, colors, normals) if with_normals else (vertices, faces, colors)
+
+
+def _write_png_rgb(path, rgb) -> None:
+    """uint8 [h, w, 3] as an 8-bit RGB PNG (filter 0 on every row), with zlib and struct alone."""
+    import struct
+    import zlib
+    h, w, _ = rgb.shape
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), rgb.reshape(h, 3 * w)], axis=1)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+                 + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def save_mesh_obj(path, textured_mesh) -> None:
+    """write_obj (gui/mesh.py:576-622) for a texture.TexturedMesh: `path` (.obj) with `mtllib`, the `v` lines, `vt u 1-v` (1 - v
+    in float32), `vn`, `usemtl defaultMat` and `f a/b/c` one-based (vertex / vt / normal indices: faces / ft / faces); the .mtl
+    next to it with the reference's lines; <name>_albedo.png = (albedo * 255).astype(uint8) as RGB (albedo clipped to [0, 1]
+    first), written with zlib and struct: no image package.  Numbers are printed as Python prints a float32 (the shortest text
+    that reads back to the same value).  The reference's .glb writer is not here: pygltflib is not available."""
+    if not path.endswith(".obj"):
+        raise ValueError(f"save_mesh_obj: {path!r} must end in .obj")
+    m = textured_mesh
+    v = np.ascontiguousarray(_np(m.vertices), dtype=np.float32).reshape(-1, 3)
+    vt = np.ascontiguousarray(_np(m.vt), dtype=np.float32).reshape(-1, 2)
+    vn = np.ascontiguousarray(_np(m.normals), dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(_np(m.faces), dtype=np.int64).reshape(-1, 3)
+    ft = np.ascontiguousarray(_np(m.ft), dtype=np.int64).reshape(-1, 3)
+    if ft.shape != f.shape or vn.shape != v.shape:
+        raise ValueError("save_mesh_obj: faces / ft and vertices / normals must have matching shapes")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0] or ft.min() < 0 or ft.max() >= vt.shape[0]):
+        raise ValueError("save_mesh_obj: an index outside its array")
+    albedo = np.asarray(_np(m.albedo), dtype=np.float32)
+    if albedo.ndim != 3 or albedo.shape[2] != 3:
+        raise ValueError("save_mesh_obj: albedo must be [h, w, 3]")
+    mtl_path, albedo_path = path[:-4] + ".mtl", path[:-4] + "_albedo.png"
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    one = np.float32(1)
+    lines = [f"mtllib {os.path.basename(mtl_path)} \n"]
+    lines += [f"v {p[0]} {p[1]} {p[2]} \n" for p in v]
+    lines += [f"vt {p[0]} {one - p[1]} \n" for p in vt]
+    lines += [f"vn {p[0]} {p[1]} {p[2]} \n" for p in vn]
+    lines.append("usemtl defaultMat \n")
+    lines += [f"f {a[0] + 1}/{b[0] + 1}/{a[0] + 1} {a[1] + 1}/{b[1] + 1}/{a[1] + 1} {a[2] + 1}/{b[2] + 1}/{a[2] + 1} \n"
+              for a, b in zip(f.tolist(), ft.tolist())]
+    with open(path, "w") as fp:
+        fp.writelines(lines)
+    with open(mtl_path, "w") as fp:
+        fp.write("newmtl defaultMat \nKa 1 1 1 \nKd 1 1 1 \nKs 0 0 0 \nTr 1 \nillum 1 \nNs 0 \n"
+                 f"map_Kd {os.path.basename(albedo_path)} \n")
+    _write_png_rgb(albedo_path, (np.clip(np.nan_to_num(albedo), 0.0, 1.0) * 255).astype(np.uint8))
+
+
+def read_mesh_obj(path) -> dict:
+    """A file save_mesh_obj wrote -> {"vertices" float32 [V, 3], "vt" float32 [Nt, 2] AS PRINTED (u, 1 - v), "normals" float32
+    [Nn, 3], "faces", "ft", "fn" int32 [F, 3] zero-based, "mtllib", "usemtl", "mtl": the .mtl file's lines as {key: text}}."""
+    rows = {"v": [], "vt": [], "vn": []}
+    tri, names = [], {"mtllib": None, "usemtl": None}
+    with open(path) as fp:
+        for line in fp:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] in rows:
+                rows[tok[0]].append([float(t) for t in tok[1:]])
+            elif tok[0] == "f":
+                if len(tok) != 4:
+                    raise ValueError(f"{path}: only triangles are supported")
+                tri.append([[int(i) - 1 for i in t.split("/")] for t in tok[1:]])
+            elif tok[0] in names:
+                names[tok[0]] = tok[1]
+    t = np.asarray(tri, dtype=np.int32).reshape(-1, 3, 3)
+    out = {"vertices": np.asarray(rows["v"], dtype=np.float32).reshape(-1, 3), "vt": np.asarray(rows["vt"], dtype=np.float32).reshape(-1, 2),
+           "normals": np.asarray(rows["vn"], dtype=np.float32).reshape(-1, 3), "faces": t[:, :, 0], "ft": t[:, :, 1], "fn": t[:, :, 2]}
+    out.update(names)
+    out["mtl"] = {}
+    if names["mtllib"]:
+        with open(os.path.join(os.path.dirname(path), names["mtllib"])) as fp:
+            for line in fp:
+                tok = line.split()
+                if tok:
+                    out["mtl"][tok[0]] = " ".join(tok[1:])
+    return out
 
 
 # ---- code book -----------------------------------------------------------------------------------

@@ -24,7 +24,8 @@ in ascending vertex index, divided by the count, rounded to float32; colours lik
 Vertex clustering does not preserve manifoldness: two sheets that pass through one cell are welded, and on the torus of the
 tests at 16 divisions ten edges come out used three times.  Not here: quadric edge collapse (meshing_decimation_quadric_edge_
 collapse, which is what decimate_mesh runs by default), isotropic remeshing, non-manifold repair (clean_mesh's
-meshing_repair_non_manifold_*), UV unwrapping and the texture bake of mode='geo+tex'.
+meshing_repair_non_manifold_*).  UV unwrapping and the texture bake of mode='geo+tex' are texture.py's:
+texture.bake(pc, mesh.extract(pc, ...), bg_color) -> io.save_mesh_obj.
 """
 from __future__ import annotations
 

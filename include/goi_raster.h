@@ -55,7 +55,9 @@ extern "C" {
  *    goi_field_iso_count, goi_field_iso_emit; goi_mesh_components_workspace_bytes, goi_mesh_components,
  *    goi_mesh_clean_workspace_bytes, goi_mesh_clean_plan, goi_mesh_clean_emit, goi_mesh_decimate_workspace_bytes,
  *    goi_mesh_decimate_members, goi_mesh_decimate_probe, goi_mesh_decimate_plan, goi_mesh_decimate_emit,
- *    goi_mesh_normals_workspace_bytes, goi_mesh_normals
+ *    goi_mesh_normals_workspace_bytes, goi_mesh_normals; goi_texture_rasterize_workspace_bytes, goi_texture_rasterize,
+ *    goi_texture_resolve, goi_texture_grid_put_workspace_bytes, goi_texture_grid_put, goi_texture_accumulate,
+ *    goi_texture_normalize, goi_texture_fill_workspace_bytes, goi_texture_fill
  * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
  *    goi_raster_backward_scratch_bytes as ever);
@@ -1002,6 +1004,54 @@ int goi_mesh_decimate_emit(long long V, long long F, const float* vertices, cons
                            float* out_colors, int* cluster, void* stream);
 size_t goi_mesh_normals_workspace_bytes(long long V, long long F);
 int goi_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
+                     void* workspace, void* stream);
+
+/* ---- Texture bake (csrc/texture.hip) ----------------------------------------------------------------------
+ * What gui/main.py:614-752 (save_model, mode 'geo+tex') does with nvdiffrast, grid_put.py, scipy and sklearn.  Every pointer is
+ * a device pointer; every entry point runs on `stream`, returns 0 (or -1: goi_raster_last_error) and never reads the device
+ * back; workspaces are the matching *_workspace_bytes bytes (0: bad sizes), 256-byte aligned.  No float atomics: two calls
+ * give the same bits.  All float arithmetic is one fp32 rounding per operation, in the order DESIGN.md 4.22 writes down.
+ * `status` words are device words holding GOI_TEXTURE_STATUS_* bits.
+ *
+ * goi_texture_rasterize: v_clip [V][4] clip-space positions, faces [F][3].  Screen position = ((x / w + 1) size - 1) / 2 (pixel
+ *   centres at integers, the Gaussian rasterizer's mapping), snapped to 1/256 pixel (round half to even); coverage by 64-bit
+ *   integer edge functions with a top-left rule; no culling; a face with a w <= 0, a position beyond 2^20 pixels or no area draws
+ *   nothing.  Depth = z / w interpolated with the perspective-correct barycentrics; the nearest wins, equal bits go to the lower
+ *   face.  tri [H][W] = face + 1 or 0, bary [H][W][2] = the weights of vertices 0 and 1, zw [H][W]; 0 where empty.
+ * goi_texture_resolve: per pixel of a rasterization, uv (vt [n_vt][2] through ft [F][3]) and normal (vn [n_vn][3] through
+ *   faces [F][3]) interpolated as (u a0 + v a1) + ((1 - u) - v) a2; n / sqrt(max(n.n, 1e-20)); viewcos = (n @ pose_rot)[2],
+ *   pose_rot [3][3]; valid [HW] = tri > 0 and viewcos > 0.5; coords [HW][2] = clamp(uv, 0, 1)[[1, 0]] * 2 - 1 (0 where tri = 0);
+ *   values [HW][3] = image [3][H][W] transposed.
+ * goi_texture_grid_put: mipmap_linear_grid_put_2d(H, W, coords [N][2], values [N][C], min_resolution, return_count = True)
+ *   without its early exit; valid [N] or NULL; 1 <= C <= GOI_TEXTURE_MAX_CHANNELS; N < 2^28.  Every texel sums its taps in
+ *   ascending (tap 00 01 10 11, sample) order.  result [H][W][C], count [H][W].  acc / acc_count (both or neither): the view is
+ *   also accumulated into them as goi_texture_accumulate does; norm_out / norm_mask (both or neither, and only with acc): what
+ *   goi_texture_normalize gives for acc / acc_count after that, written by the same kernel.
+ * goi_texture_accumulate: where cnt < 0.1: albedo += cur, cnt += cur_cnt (T texels).  goi_texture_normalize: mask = cnt > 0,
+ *   out = albedo / cnt where mask, albedo elsewhere.
+ * goi_texture_fill: a texel outside mask [h][w] with a mask texel within L1 distance `radius` (<= GOI_TEXTURE_MAX_RADIUS) takes
+ *   albedo [h][w][C] of its nearest mask texel: the smallest (dx^2 + dy^2, row, column); nearest [h][w] = that texel's flat
+ *   index, -1 elsewhere; out = albedo elsewhere.  h, w < 2^21. */
+#define GOI_TEXTURE_STATUS_SORT 2   /* a look-back of a sort timed out on a wedged device: the results are garbage */
+#define GOI_TEXTURE_STATUS_RANGE 8  /* an index outside its array: the face (or pixel) was treated as absent */
+#define GOI_TEXTURE_MAX_CHANNELS 4
+#define GOI_TEXTURE_MAX_RADIUS 127
+#define GOI_TEXTURE_MAX_SIZE 16384
+size_t goi_texture_rasterize_workspace_bytes(long long F, int H, int W);
+int goi_texture_rasterize(long long V, long long F, const float* v_clip, const int* faces, int H, int W, int* tri, float* bary,
+                          float* zw, int* status, void* workspace, void* stream);
+int goi_texture_resolve(long long n_vt, long long n_vn, long long F, int H, int W, const int* tri, const float* bary,
+                        const float* vt, const int* ft, const float* vn, const int* faces, const float* pose_rot,
+                        const float* image, float* coords, float* values, unsigned char* valid, int* status, void* stream);
+size_t goi_texture_grid_put_workspace_bytes(long long N, int C, int H, int W);
+int goi_texture_grid_put(long long N, int C, int H, int W, int min_resolution, const float* coords, const float* values,
+                         const unsigned char* valid, float* result, float* count, float* acc, float* acc_count, float* norm_out,
+                         unsigned char* norm_mask, int* status, void* workspace, void* stream);
+int goi_texture_accumulate(long long T, int C, float* albedo, float* cnt, const float* cur, const float* cur_cnt, void* stream);
+int goi_texture_normalize(long long T, int C, const float* albedo, const float* cnt, float* out, unsigned char* mask,
+                          void* stream);
+size_t goi_texture_fill_workspace_bytes(int h, int w);
+int goi_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
                      void* workspace, void* stream);
 
 #ifdef __cplusplus
