@@ -17,7 +17,7 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import ALLOC_FN, GoiRasterScene
+from ._lib import GoiRasterScene
 
 
 # ---- which binding crosses into libgoi_raster.so ----------------------------------------------------------------------
@@ -74,10 +74,8 @@ def _e(t):
 
 
 def _ptr(t):
-    """Device pointer of a tensor, or None for the reference's 'empty tensor means absent'."""
-    if t is None or t.numel() == 0:
-        return None
-    return C.c_void_p(t.data_ptr())
+    """_lib.ptr with the reference's 'empty tensor means absent': None for an empty tensor too."""
+    return None if t is None or t.numel() == 0 else _lib.ptr(t)
 
 
 def _prep(t, name, dev, dtype=torch.float32):
@@ -89,10 +87,6 @@ def _prep(t, name, dev, dtype=torch.float32):
     if t.device != dev:
         raise ValueError(f"{name} is on {t.device}, expected {dev}")
     return t.contiguous()
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check_device(means3D):
@@ -132,23 +126,12 @@ def _binning_tensor(dev, nbytes):
     return torch.empty((int(nbytes) + step - 1) // step * step, dtype=torch.uint8, device=dev)
 
 
-class _BinningAllocator:
+class _BinningAllocator(_lib.TensorAlloc):
     """The allocation callback handed to the library (reference: resizeFunctional,
     rasterize_points.cu:27-33): allocates the binning workspace as a uint8 torch tensor."""
 
     def __init__(self, dev):
-        self.dev = dev
-        self.tensor = torch.empty(0, dtype=torch.uint8, device=dev)
-        self.error = None
-        self.cb = ALLOC_FN(self._alloc)
-
-    def _alloc(self, _user, nbytes):
-        try:
-            self.tensor = _binning_tensor(self.dev, nbytes)
-            return self.tensor.data_ptr()
-        except Exception as ex:  # never let an exception cross the C boundary
-            self.error = ex
-            return None
+        super().__init__(lambda nbytes: _binning_tensor(dev, nbytes), torch.empty(0, dtype=torch.uint8, device=dev))
 
 
 _SCRATCH = {}
@@ -501,8 +484,7 @@ class LazyCount:
             binning = _binning_tensor(self.dev, lib.goi_raster_binning_bytes(self._n))
             r = lib.goi_raster_forward_redo(C.byref(sc), self._n, _ptr(geom), _ptr(img), _ptr(binning),
                                             *[_ptr(o) for o in outs], _ptr(radii), C.c_void_p(self._stream))
-        if r < 0:
-            raise RuntimeError(_lib.last_error())
+        _lib.check(r)
         self.binning, self.layout, self.redone = binning, self._n, True
         SPECULATION_STATS["redone"] += 1
 
@@ -559,7 +541,7 @@ class LazyCount:
 def _flag_view(geom, P):
     if geom is None or P <= 0 or geom.numel() == 0:
         return None
-    ptr = _lib.load().goi_raster_truncated_flag(C.c_void_p(geom.data_ptr()), P)
+    ptr = _lib.load().goi_raster_truncated_flag(_lib.ptr(geom), P)
     if not ptr:
         return None
     off = int(ptr) - int(geom.data_ptr())
@@ -886,9 +868,8 @@ def _reblend(e, background, semantics, P, H, W, dev):
         img = torch.empty_like(e["img"])
         sc, _keep = _prepared_scene(dev, P, S, H, W, background=background, semantics=semantics)
         r = lib.goi_raster_forward_reblend(C.byref(sc), int(layout), _ptr(e["geom"]), _ptr(binning), _ptr(e["img"]), _ptr(img),
-                                           *[_ptr(o) for o in outs], _stream(dev))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+                                           *[_ptr(o) for o in outs], _lib.stream(dev))
+    _lib.check(r)
     _note_frame(e["geom"], P)
     SPECULATION_STATS["cached_frames"] += 1
     return (R,) + outs + (e["radii"], e["geom"], binning, img)
@@ -976,8 +957,7 @@ def _launch_exact(fa, dev, P, S, selection, invert, into=None):
                                             _ptr(radii), _ptr(selection), int(invert), C.c_void_p(stream))
     if alloc.error is not None:
         raise alloc.error
-    if n < 0:
-        raise RuntimeError(_lib.last_error())
+    _lib.check(n)
     return (n,) + tuple(outs) + (radii, geom, alloc.tensor, img)
 
 
@@ -997,11 +977,10 @@ def _launch_async(fa, dev, P, S, cap, z_in, z_out, selection, invert):
         binning = _binning_tensor(dev, lib.goi_raster_binning_bytes(cap))
         frame = (C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap, *[_ptr(o) for o in outs], _ptr(radii))
         if selection is not None:
-            ticket = lib.goi_raster_forward_async_selected(*frame, _ptr(selection), int(invert), _stream(dev))
+            ticket = lib.goi_raster_forward_async_selected(*frame, _ptr(selection), int(invert), _lib.stream(dev))
         else:
-            ticket = lib.goi_raster_forward_async_cut(*frame, _ptr(z_in), _ptr(z_out), _stream(dev))
-    if ticket < 0:
-        raise RuntimeError(_lib.last_error())
+            ticket = lib.goi_raster_forward_async_cut(*frame, _ptr(z_in), _ptr(z_out), _lib.stream(dev))
+    _lib.check(ticket)
     return (ticket,) + outs + (radii, geom, binning, img)
 
 
@@ -1091,9 +1070,8 @@ def _backward_impl(background, means3D, radii, colors, semantics, scales, rotati
                 _ptr(alphas_c), *[_ptr(g) for g in ups],
                 _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dsemantics),
                 _ptr(dL_ddepths), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
-                _ptr(dL_drotations), _ptr(scratch), None, None, None, _stream(dev))
-            if r < 0:
-                raise RuntimeError(_lib.last_error())
+                _ptr(dL_drotations), _ptr(scratch), None, None, None, _lib.stream(dev))
+            _lib.check(r)
     return (dL_dmeans2D, dL_dcolors, dL_dsemantics, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
             dL_drotations)
 
@@ -1137,8 +1115,8 @@ def sh_grad_from_views(means3D, campos, gcol, degree, M):
         out = torch.empty((P, int(M), 3), dtype=torch.float32, device=dev)
         if P and V:
             m, c, g = _prep(means3D, "means3D", dev), _prep(campos, "campos", dev), _prep(gcol, "gcol", dev)
-            if lib.goi_raster_sh_grad_from_views(P, int(degree), int(M), V, _ptr(m), _ptr(c), _ptr(g), _ptr(out), _stream(dev)) < 0:
-                raise RuntimeError(_lib.last_error())
+            _lib.check(lib.goi_raster_sh_grad_from_views(P, int(degree), int(M), V, _ptr(m), _ptr(c), _ptr(g), _ptr(out),
+                                                         _lib.stream(dev)))
         elif P:
             out.zero_()
     return out
@@ -1178,11 +1156,9 @@ def rasterize_gaussians_backward_semantics(background, means3D, radii, semantics
             if lazy_binning is not None:
                 binningBuffer = lazy_binning
             scratch = _backward_scratch(lib.goi_raster_backward_scratch_bytes(R_layout, S), dev)
-            r = lib.goi_raster_backward_semantics(C.byref(sc), R_layout, _ptr(geomBuffer), _ptr(binningBuffer),
-                                                  _ptr(imageBuffer), _ptr(radii_c), _ptr(alphas_c), _ptr(g_s),
-                                                  _ptr(dL_dsemantics), _ptr(scratch), _stream(dev))
-            if r < 0:
-                raise RuntimeError(_lib.last_error())
+            _lib.check(lib.goi_raster_backward_semantics(C.byref(sc), R_layout, _ptr(geomBuffer), _ptr(binningBuffer),
+                                                         _ptr(imageBuffer), _ptr(radii_c), _ptr(alphas_c), _ptr(g_s),
+                                                         _ptr(dL_dsemantics), _ptr(scratch), _lib.stream(dev)))
     return dL_dsemantics
 
 
@@ -1214,11 +1190,10 @@ def rasterize_gaussians_trace(background, means3D, colors, img_sem, opacity, sca
             img_c = _prep(img_sem, "img_sem", dev)
             alloc = _BinningAllocator(dev)
             n = lib.goi_raster_trace(C.byref(sc), _ptr(img_c), _ptr(geom), _ptr(img), alloc.cb, None, _ptr(out_color),
-                                     _ptr(gau_sem), _ptr(num_gsem), _ptr(radii), _stream(dev))
+                                     _ptr(gau_sem), _ptr(num_gsem), _ptr(radii), _lib.stream(dev))
         if alloc.error is not None:
             raise alloc.error
-        if n < 0:
-            raise RuntimeError(_lib.last_error())
+        _lib.check(n)
         res = (n, out_color, gau_sem, num_gsem, geom, alloc.tensor, img)
     if P > 0:
         _note_count(dev, P, res[0], _tiles(H, W))
@@ -1239,9 +1214,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
             m = _prep(means3D, "means3D", dev)
             v = _prep(viewmatrix, "viewmatrix", dev)
             p = _prep(projmatrix, "projmatrix", dev)
-            if lib.goi_raster_mark_visible(P, _ptr(m), _ptr(v), _ptr(p), C.c_void_p(present.data_ptr()),
-                                           _stream(dev)) < 0:
-                raise RuntimeError(_lib.last_error())
+            _lib.check(lib.goi_raster_mark_visible(P, _ptr(m), _ptr(v), _ptr(p), _lib.ptr(present), _lib.stream(dev)))
     return present
 
 
@@ -1262,9 +1235,8 @@ def blend_stats(P, W, H, R, geomBuffer, binningBuffer, imgBuffer) -> dict:
         binningBuffer = lazy_binning
     with torch.cuda.device(dev):
         out = torch.zeros(16, dtype=torch.int64, device=dev)
-        if lib.goi_raster_blend_stats(P, W, H, R, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), _ptr(out),
-                                      _stream(dev)) < 0:
-            raise RuntimeError(_lib.last_error())
+        _lib.check(lib.goi_raster_blend_stats(P, W, H, R, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), _ptr(out),
+                                              _lib.stream(dev)))
         v = [int(x) for x in out.cpu().tolist()]
     d = dict(zip(BLEND_STATS_FIELDS, v))
     live = float(d["live_lanes"])
@@ -1297,9 +1269,8 @@ def debug_views(P, W, H, R, geomBuffer, binningBuffer, imgBuffer):
         r = lib.goi_raster_debug_views(P, W, H, R, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer),
                                        *[_ptr(out[k]) for k in ("depths", "means2D", "conic_opacity", "rgb",
                                                                 "tiles_touched", "point_list", "ranges", "n_contrib")],
-                                       _stream(dev))
-        if r < 0:
-            raise RuntimeError(_lib.last_error())
+                                       _lib.stream(dev))
+        _lib.check(r)
         torch.cuda.synchronize(dev)
     out["point_list"] = out["point_list"][:n_true]  # (the workspace of a speculative frame holds `capacity` slots)
     return out

@@ -146,7 +146,8 @@ SYMBOLS = {
     "goi_raster_debug_backward_blend": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int] + [C.c_void_p] * 24),
 }
 
-# the goi_field_* family (csrc/field.hip: density grid and iso-surface), bound by load() like the table above
+_LL, _P, _I = C.c_longlong, C.c_void_p, C.c_int
+# the goi_field_* family (csrc/field.hip: density grid and iso-surface)
 FIELD_SYMBOLS = {
     "goi_field_density_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_double]),
     "goi_field_density": (C.c_int, [C.c_longlong] + [C.c_void_p] * 5 + [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -156,9 +157,7 @@ FIELD_SYMBOLS = {
     "goi_field_iso_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 4
                            + [C.c_longlong, C.c_longlong] + [C.c_void_p] * 4),
 }
-
 # the goi_mesh_* family (csrc/mesh.hip: components, clean-up, vertex clustering, normals)
-_LL, _P = C.c_longlong, C.c_void_p
 MESH_SYMBOLS = {
     "goi_mesh_components_workspace_bytes": (C.c_size_t, [_LL, _LL]),
     "goi_mesh_components": (C.c_int, [_LL, _LL] + [_P] * 6),
@@ -173,9 +172,7 @@ MESH_SYMBOLS = {
     "goi_mesh_normals_workspace_bytes": (C.c_size_t, [_LL, _LL]),
     "goi_mesh_normals": (C.c_int, [_LL, _LL] + [_P] * 6),
 }
-
 # the goi_texture_* family (csrc/texture.hip: rasterize, resolve, grid put, accumulate, fill)
-_I = C.c_int
 TEXTURE_SYMBOLS = {
     "goi_texture_rasterize_workspace_bytes": (C.c_size_t, [_LL, _I, _I]),
     "goi_texture_rasterize": (C.c_int, [_LL, _LL, _P, _P, _I, _I] + [_P] * 6),
@@ -187,6 +184,7 @@ TEXTURE_SYMBOLS = {
     "goi_texture_fill_workspace_bytes": (C.c_size_t, [_I, _I]),
     "goi_texture_fill": (C.c_int, [_I, _I, _I, _I] + [_P] * 6),
 }
+SYMBOL_TABLES = (SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS)  # what load() binds
 
 _lib = None
 
@@ -205,11 +203,11 @@ def load():
         # the system copy and the two runtimes would not see each other's devices and allocations).
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(FIELD_SYMBOLS.items()) + list(MESH_SYMBOLS.items()) + \
-                list(TEXTURE_SYMBOLS.items()):
-            fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-            fn.restype = res
-            fn.argtypes = args
+        for table in SYMBOL_TABLES:
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
+                fn.restype = res
+                fn.argtypes = args
         got = lib.goi_raster_abi_version()
         if got != ABI_VERSION:
             raise ImportError(f"libgoi_raster.so ABI {got} != expected {ABI_VERSION}; rebuild")
@@ -225,6 +223,46 @@ def load():
 
 def last_error() -> str:
     return load().goi_raster_last_error().decode("utf-8", "replace")
+
+
+# ---- what every module's calls into the library share --------------------------------------------------------------------
+def check(r, exc=RuntimeError):
+    """The return value of a library call: raises `exc` with the library's message when it is negative."""
+    if r < 0:
+        raise exc(last_error())
+    return r
+
+
+def ptr(t):
+    """Device pointer of a tensor (an empty one included: the C entries go by counts), None for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def workspace(nbytes, dev):
+    import torch
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+
+
+class TensorAlloc:
+    """An allocation callback to hand to the library (`.cb`): `make(nbytes)` returns the tensor, which is kept in `.tensor`;
+    an exception it raises is kept in `.error` for the caller to re-raise, because none may cross the C boundary."""
+
+    def __init__(self, make, tensor=None):
+        self.make, self.tensor, self.error = make, tensor, None
+        self.cb = ALLOC_FN(self._alloc)
+
+    def _alloc(self, _user, nbytes):
+        try:
+            self.tensor = self.make(int(nbytes))
+            return self.tensor.data_ptr()
+        except Exception as ex:  # noqa: BLE001
+            self.error = ex
+            return None
 
 
 class GoiAdamGroup(C.Structure):
@@ -248,8 +286,7 @@ OPTIONS = {}  # the switches set through set_option / GOI_OPTIONS in this proces
 
 
 def set_option(name: str, value: int) -> None:
-    if load().goi_raster_set_option(name.encode(), int(value)) < 0:
-        raise RuntimeError(last_error())
+    check(load().goi_raster_set_option(name.encode(), int(value)))
     OPTIONS[name] = int(value)
 
 
@@ -267,6 +304,5 @@ def profile_collect() -> dict:
     n = len(STAGES)
     ms = (C.c_double * n)()
     calls = (C.c_int * n)()
-    if load().goi_raster_profile_collect(ms, calls) < 0:
-        raise RuntimeError(last_error())
+    check(load().goi_raster_profile_collect(ms, calls))
     return {STAGES[i]: (ms[i], calls[i]) for i in range(n)}

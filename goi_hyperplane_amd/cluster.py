@@ -11,8 +11,6 @@ There is no CPU path: a CPU tensor is an error, and a numpy array is copied to t
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -69,12 +67,10 @@ def dbscan(points: torch.Tensor, eps: float, min_samples: int, return_core: bool
     core = torch.empty(n, dtype=torch.uint8, device=dev) if return_core else None
     result = torch.empty(2, dtype=torch.int32, device=dev)
     ws = torch.empty(max(int(lib.goi_semantic_dbscan_workspace_bytes(n)), 1), dtype=torch.uint8, device=dev)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    p = _lib.ptr
     with torch.cuda.device(dev):
-        r = lib.goi_semantic_dbscan(n, p(pts), float(eps), int(min_samples), p(labels), p(core), p(result), p(ws),
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if r < 0:
-        raise ValueError(_lib.last_error())
+        _lib.check(lib.goi_semantic_dbscan(n, p(pts), float(eps), int(min_samples), p(labels), p(core), p(result), p(ws),
+                                           _lib.stream(dev)), ValueError)
     n_clusters, flags = (int(v) for v in result.cpu())  # the one synchronisation
     if flags:
         raise _flag_error(flags, pts)

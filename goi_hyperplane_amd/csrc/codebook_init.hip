@@ -31,6 +31,7 @@
 //     km_dead_k         dead centres in index order take x[perm_{it+1}[0 .. ndead)]; ndead > N is the reference's
 //                       shape-mismatch RuntimeError and is recorded in status[p] (first iteration + 1)
 #include "common.h"
+#include "wave_util.h"
 
 namespace goi {
 
@@ -51,7 +52,7 @@ inline size_t div_up_sz(size_t a, size_t b) { return (a + b - 1) / b; }
 __device__ __forceinline__ uint32_t order_key(float f) {
     uint32_t u = __float_as_uint(f);
     if ((u << 1) == 0u) u = 0u;  // -0 -> +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ord_enc_bits(u);
 }
 
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
@@ -246,12 +247,6 @@ __device__ __forceinline__ bool km_better(float va, int ia, float vb, int ib) { 
     const bool na = va != va, nb = vb != vb;
     if (na || nb) return na && (!nb || ia < ib);
     return va > vb || (va == vb && ia < ib);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // x [rows][D] /= its norm, one wave per row

@@ -42,6 +42,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "wave_util.h"
 
 namespace goi {
 
@@ -52,15 +53,8 @@ constexpr int DB_AXIS_BITS = 21;
 constexpr int DB_AXIS_CELLS = 1 << DB_AXIS_BITS;
 constexpr uint32_t CELL_CLIQUE = 1u, CELL_DENSE = 2u, CELL_CORE = 4u;  // cell_info bits
 // once one of these is raised the labels are void: the searches stop (clamped or NaN cells could be huge and quadratic)
+constexpr uint32_t DB_UNION = DBSCAN_FLAG_UNION;  // find_root (wave_util.h) raises it when its walk overruns: never reached
 constexpr uint32_t DB_ABORT = DBSCAN_FLAG_NONFINITE | DBSCAN_FLAG_RANGE | DBSCAN_FLAG_GRID;
-
-__device__ __forceinline__ uint32_t ord_enc(float f) {  // order-preserving float -> uint32
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_dec(uint32_t e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e);
-}
 
 __device__ __forceinline__ float d2_form(float xi, float yi, float zi, float xj, float yj, float zj) {
     const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
@@ -128,40 +122,6 @@ __device__ __forceinline__ void for_window(uint64_t k, const uint64_t* __restric
             for (uint32_t d = lower_bound(ckey, nc, pack_key(x0, (uint32_t)y, (uint32_t)z)); d < nc && ckey[d] <= k1; d++)
                 if (f(d)) return;
         }
-}
-
-__device__ __forceinline__ uint32_t load_parent(const uint32_t* parent, uint32_t x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // past the non-coherent L1
-}
-// root of x; parents only decrease, so the walk ends within nc steps (the bound is a guard, never reached)
-__device__ __forceinline__ uint32_t find_root(const uint32_t* parent, uint32_t x, uint32_t nc, uint32_t* flags) {
-    for (uint32_t it = 0; it <= nc; it++) {
-        const uint32_t p = load_parent(parent, x);
-        if (p == x) return x;
-        x = p;
-    }
-    atomicOr(flags, (uint32_t)DBSCAN_FLAG_UNION);
-    return x;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u(uint32_t v) {
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-// true when every active lane of the wave carries the same key (then one lane can speak for the wave)
-__device__ __forceinline__ bool wave_same(bool active, uint32_t key) {
-    const unsigned long long m = __ballot(active);
-    if (!m) return false;
-    const uint32_t lead = (uint32_t)__shfl((int)key, __builtin_ctzll(m));
-    return __all(!active || key == lead);
 }
 
 // enc[0..2] = min, enc[3..5] = max over the finite coordinates (ordered encodings; initialised to ~0 / 0 by the launcher)
@@ -353,7 +313,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_k(int n, const uint32_t* 
     for_window(ckey[c], ckey, nc, [&](uint32_t d) {
         if (d <= c || !(info[d] & CELL_CORE)) return false;
         if (box_box_d2(bc, load_box(cbox, d)) > eps2) return false;
-        if (find_root(parent, c, nc, flags) == find_root(parent, d, nc, flags)) return false;
+        if (find_root(parent, c, nc, flags, DB_UNION) == find_root(parent, d, nc, flags, DB_UNION)) return false;
         const uint32_t d0 = cstart[d], d1 = cstart[d + 1];
         bool hit = false;
         for (uint32_t a0 = c0; a0 < c1 && !hit; a0 += 64) {
@@ -373,7 +333,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_k(int n, const uint32_t* 
         if (hit && lane == 0) {
             // hook the larger root under the smaller; a failed CAS means that root was hooked meanwhile (bounded: <= nc unions)
             for (uint32_t it = 0;; it++) {
-                uint32_t ra = find_root(parent, c, nc, flags), rb = find_root(parent, d, nc, flags);
+                uint32_t ra = find_root(parent, c, nc, flags, DB_UNION), rb = find_root(parent, d, nc, flags, DB_UNION);
                 if (ra == rb) break;
                 if (ra > rb) {
                     const uint32_t t = ra;
@@ -382,7 +342,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_union_k(int n, const uint32_t* 
                 }
                 if (atomicCAS(parent + rb, rb, ra) == rb) break;
                 if (it >= nc) {
-                    atomicOr(flags, (uint32_t)DBSCAN_FLAG_UNION);
+                    atomicOr(flags, DB_UNION);
                     break;
                 }
             }
@@ -398,7 +358,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_flatten_k(int n, const uint32_t
     const uint32_t c = blockIdx.x * DB_THREADS + threadIdx.x;
     const uint32_t nc = *ncell;
     if (c >= nc || !(info[c] & CELL_CORE)) return;
-    parent[c] = find_root(parent, c, nc, flags);
+    parent[c] = find_root(parent, c, nc, flags, DB_UNION);
 }
 
 // cmin[root] = smallest input index of a core point in the component
@@ -411,7 +371,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_cmin_k(int n, const float4* __r
     const uint32_t r = active ? parent[scell[i]] : 0u;
     const uint32_t id = active ? __float_as_uint(spt[i].w) : ~0u;
     if (wave_same(active, r)) {
-        const uint32_t m = wave_min_u(id);
+        const uint32_t m = wave_min(id);
         const unsigned long long act = __ballot(active);
         if ((threadIdx.x & 63) == __builtin_ctzll(act)) atomicMin(&cmin[r], m);
     } else if (active) {

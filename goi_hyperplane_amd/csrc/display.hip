@@ -31,6 +31,7 @@
 //
 // Neither allocates, copies or synchronises: both are asynchronous on the caller's stream.
 #include "common.h"
+#include "wave_util.h"
 
 namespace goi {
 
@@ -41,15 +42,8 @@ constexpr int FRAME_WAVES = FRAME_THREADS / 64;
 constexpr int STATS_MAX_BLOCKS = 256;     // per view (one per CU): they all hit the view's three words
 constexpr int COMPOSE_MAX_BLOCKS = 2048;  // per launch, spread over the views
 
-// Order-preserving key of a float: a < b  <=>  key(a) < key(b) as unsigned (-0 < +0).  The buffer holds the key of the
-// maximum and the COMPLEMENT of the key of the minimum, so both are atomicMax and the all-zero buffer is the identity.
-__device__ __forceinline__ uint32_t float_key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// The stats buffer holds the ordered key (ord_enc, wave_util.h) of the maximum and the COMPLEMENT of the key of the minimum,
+// so both are atomicMax and the all-zero buffer is the identity.
 
 struct MinMax {
     float mn, mx;
@@ -80,15 +74,6 @@ __device__ __forceinline__ MinMax span_minmax(const float* __restrict__ p, long 
     return r;
 }
 
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // blockIdx.y = view.  base == nullptr or sim == nullptr skips that statistic.  stats [V][3]: ~key(min base), key(max base),
 // key(max sim).
 __global__ void __launch_bounds__(FRAME_THREADS) frame_stats_k(const float* __restrict__ base, long long base_len,
@@ -112,7 +97,7 @@ __global__ void __launch_bounds__(FRAME_THREADS) frame_stats_k(const float* __re
     if (threadIdx.x < 3) {
         float v = part[0][threadIdx.x];
         for (int w = 1; w < FRAME_WAVES; ++w) v = threadIdx.x == 0 ? fminf(v, part[w][0]) : fmaxf(v, part[w][threadIdx.x]);
-        const uint32_t key = threadIdx.x == 0 ? ~float_key(v) : float_key(v);
+        const uint32_t key = threadIdx.x == 0 ? ~ord_enc(v) : ord_enc(v);
         if ((threadIdx.x < 2) ? base != nullptr : sim != nullptr) atomicMax(stats + (size_t)view * 3 + threadIdx.x, key);
     }
 }
@@ -233,11 +218,11 @@ __global__ void __launch_bounds__(FRAME_THREADS) frame_compose_k(const FramePara
     const long long HW = p.HW;
     ViewConsts vc{0.0f, 1.0f, 1.0f};
     if (USE_BASE && p.normalize) {
-        const float mn = key_float(~p.stats[(size_t)view * 3]), mx = key_float(p.stats[(size_t)view * 3 + 1]);
+        const float mn = ord_dec(~p.stats[(size_t)view * 3]), mx = ord_dec(p.stats[(size_t)view * 3 + 1]);
         vc.mn = mn;
         vc.den = (mx - mn) + 1e-20f;
     }
-    if (STYLE == GOI_FRAME_HEAT) vc.hden = key_float(p.stats[(size_t)view * 3 + 2]) - p.thresh;
+    if (STYLE == GOI_FRAME_HEAT) vc.hden = ord_dec(p.stats[(size_t)view * 3 + 2]) - p.thresh;
     const float* b0 = p.base + (size_t)view * p.channels * HW;
     const float* b1 = p.channels == 3 ? b0 + HW : b0;
     const float* b2 = p.channels == 3 ? b0 + 2 * HW : b0;

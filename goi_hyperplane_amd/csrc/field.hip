@@ -29,6 +29,7 @@
 // s (-1)^m (positive: its normal points away from m); two inside vertices a < b against c < d give the quad
 // (ac, ad, bd, bc) with orientation s sign(a b c d) (positive: towards c d).
 #include "common.h"
+#include "wave_util.h"
 
 #include <math.h>
 
@@ -39,12 +40,6 @@ constexpr int FIELD_THREADS = 256;
 constexpr int FIELD_BATCH = GOI_FIELD_BATCH;
 constexpr int FIELD_CAP = FIELD_BATCH + FIELD_THREADS;  // a chunk of candidates always fits behind a list below FIELD_BATCH
 constexpr uint32_t ENC_NONE = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint32_t enc_f32(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e); }
 
 __device__ __forceinline__ bool field_keep(long long i, const float* xyz, const float* opacity, const uint8_t* sel, int sel_invert,
                                            float min_opacity, float& x, float& y, float& z) {
@@ -82,8 +77,8 @@ __global__ void __launch_bounds__(FIELD_THREADS) field_bounds_k(long long P, con
     if ((threadIdx.x & 63) == 0 && wave_any) {
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-            atomicMin(enc + a, enc_f32(mn[a]));
-            atomicMax(enc + 3 + a, enc_f32(mx[a]));
+            atomicMin(enc + a, ord_enc(mn[a]));
+            atomicMax(enc + 3 + a, ord_enc(mx[a]));
         }
     }
 }
@@ -102,7 +97,7 @@ __global__ void field_frame_k(const uint32_t* __restrict__ enc, const float* __r
     }
     float ext = 0.f;
     for (int a = 0; a < 3; a++) {
-        const float mn = dec_f32(enc[a]), mx = dec_f32(enc[3 + a]);
+        const float mn = ord_dec(enc[a]), mx = ord_dec(enc[3 + a]);
         frame[a] = (mn + mx) / 2.f;
         ext = fmaxf(ext, mx - mn);
     }

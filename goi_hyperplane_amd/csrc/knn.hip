@@ -24,6 +24,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "wave_util.h"
 
 namespace goi {
 
@@ -33,23 +34,6 @@ constexpr int KNN_BOX = 256;
 // box bounds and point distances round differently; shrink the bound so rounding can never prune a
 // box that holds a (by <= 1 ulp) nearer neighbour
 constexpr float SLACK = 0.999999f;
-
-__device__ __forceinline__ uint32_t ord_enc(float f) {  // order-preserving float -> uint32
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_dec(uint32_t e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e);
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 
 // enc[0..2] = min, enc[3..5] = max (ordered-integer encoding; initialised to ~0 / 0 by the launcher)
 __global__ __launch_bounds__(256) void knn_bounds_k(int P, const float* __restrict__ pts, uint32_t* __restrict__ enc) {

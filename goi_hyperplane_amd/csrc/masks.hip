@@ -18,6 +18,7 @@
 //
 // None of them allocates, copies or synchronises: every launch is asynchronous on the caller's stream.
 #include "common.h"
+#include "wave_util.h"
 
 namespace goi {
 
@@ -130,11 +131,6 @@ __global__ void __launch_bounds__(MASK_THREADS) mask_unpack_k(const uint64_t* __
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ void __launch_bounds__(MASK_THREADS) mask_confusion_k(const uint64_t* __restrict__ pred, const uint64_t* __restrict__ gt,
                                                                 int H, int Wwords, uint64_t tail, long long* __restrict__ out) {
     __shared__ unsigned long long part[MASK_WAVES][4];
@@ -151,10 +147,10 @@ __global__ void __launch_bounds__(MASK_THREADS) mask_confusion_k(const uint64_t*
         fn += __popcll(~a & b);
         tn += __popcll(~a & ~b & valid);
     }
-    tp = wave_sum_u64(tp);
-    fp = wave_sum_u64(fp);
-    fn = wave_sum_u64(fn);
-    tn = wave_sum_u64(tn);
+    tp = wave_sum(tp);
+    fp = wave_sum(fp);
+    fn = wave_sum(fn);
+    tn = wave_sum(tn);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         part[wave][0] = tp;

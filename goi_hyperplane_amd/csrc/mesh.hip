@@ -21,6 +21,7 @@
 //   normals      a stable sort of (vertex, 3 face + corner); one lane per vertex finds its run by binary search and adds the
 //                faces' cross products in ascending (face, corner) order.
 #include "common.h"
+#include "wave_util.h"
 
 #include <math.h>
 
@@ -29,15 +30,6 @@ namespace {
 
 constexpr int MESH_THREADS = 256;
 constexpr uint32_t ENC_NONE = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint32_t enc_f32(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(uint32_t e) {
-    const uint32_t m = (uint32_t)((int32_t)e >> 31);  // all ones for an encoded non-negative value: clear its top bit; else ~e
-    return __uint_as_float(e ^ (~m | 0x80000000u));
-}
 
 unsigned blocks_for(long long n) { return (unsigned)((n + MESH_THREADS - 1) / MESH_THREADS); }
 __device__ __forceinline__ long long gid() { return (long long)blockIdx.x * MESH_THREADS + threadIdx.x; }
@@ -51,31 +43,11 @@ __device__ __forceinline__ bool load_face(const int* __restrict__ faces, long lo
     return a < V && b < V && c < V;  // (a negative index is a huge unsigned one)
 }
 
-// true when every active lane of the wave carries the same key (then one lane can speak for the wave)
-__device__ __forceinline__ bool wave_same(bool active, uint32_t key) {
-    const unsigned long long m = __ballot(active);
-    if (!m) return false;
-    const uint32_t lead = (uint32_t)__shfl((int)key, __builtin_ctzll(m));
-    return __all(!active || key == lead);
-}
-
-// ---- union-find ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t load_parent(const uint32_t* parent, uint32_t x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // past the non-coherent L1
-}
-// root of x; parents only decrease, so the walk ends within V steps (the bound is a guard, never reached)
-__device__ __forceinline__ uint32_t find_root(const uint32_t* parent, uint32_t x, uint32_t V, uint32_t* status) {
-    for (uint32_t it = 0; it <= V; it++) {
-        const uint32_t p = load_parent(parent, x);
-        if (p == x) return x;
-        x = p;
-    }
-    atomicOr(status, (uint32_t)GOI_MESH_STATUS_UNION);
-    return x;
-}
+// ---- union-find (find_root: wave_util.h) -----------------------------------------------------------------------------------
+constexpr uint32_t MESH_UNION = GOI_MESH_STATUS_UNION;
 __device__ __forceinline__ void unite(uint32_t* parent, uint32_t a, uint32_t b, uint32_t V, uint32_t* status) {
     for (uint32_t it = 0;; it++) {
-        uint32_t ra = find_root(parent, a, V, status), rb = find_root(parent, b, V, status);
+        uint32_t ra = find_root(parent, a, V, status, MESH_UNION), rb = find_root(parent, b, V, status, MESH_UNION);
         if (ra == rb) return;
         if (ra > rb) {
             const uint32_t t = ra;
@@ -86,7 +58,7 @@ __device__ __forceinline__ void unite(uint32_t* parent, uint32_t a, uint32_t b, 
         a = ra;  // both are ancestors still: start the next walk from them
         b = rb;
         if (it >= V) {
-            atomicOr(status, (uint32_t)GOI_MESH_STATUS_UNION);
+            atomicOr(status, MESH_UNION);
             return;
         }
     }
@@ -122,7 +94,7 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_flatten_k(uint32_t V, const
                                                               uint32_t* __restrict__ status) {
     const long long v = gid();
     if (v >= V) return;
-    label[v] = named[v] ? (int)find_root(parent, (uint32_t)v, V, status) : -1;
+    label[v] = named[v] ? (int)find_root(parent, (uint32_t)v, V, status, MESH_UNION) : -1;
 }
 
 __global__ void __launch_bounds__(MESH_THREADS) mesh_face_label_k(long long F, uint32_t V, const int* __restrict__ faces,
@@ -275,7 +247,7 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_comp_box_k(uint32_t V, cons
     const bool same = wave_same(r >= 0, (uint32_t)r);  // the usual case: the wave's vertices are of one component
     if (r >= 0 && !same)
         for (int d = 0; d < 3; d++) {
-            const uint32_t e = enc_f32(p[d]);
+            const uint32_t e = ord_enc(p[d]);
             atomicMin(cbox + 6 * (size_t)r + d, e);
             atomicMax(cbox + 6 * (size_t)r + 3 + d, e);
         }
@@ -287,11 +259,11 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_comp_box_k(uint32_t V, cons
             mx = fmaxf(mx, __shfl_xor(mx, o));
         }
         if ((threadIdx.x & 63) == 0 && mn <= mx) {
-            atomicMin(mbox + d, enc_f32(mn));
-            atomicMax(mbox + 3 + d, enc_f32(mx));
+            atomicMin(mbox + d, ord_enc(mn));
+            atomicMax(mbox + 3 + d, ord_enc(mx));
             if (same) {
-                atomicMin(cbox + 6 * (size_t)lead + d, enc_f32(mn));
-                atomicMax(cbox + 6 * (size_t)lead + 3 + d, enc_f32(mx));
+                atomicMin(cbox + 6 * (size_t)lead + d, ord_enc(mn));
+                atomicMax(cbox + 6 * (size_t)lead + 3 + d, ord_enc(mx));
             }
         }
     }
@@ -300,7 +272,7 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_comp_box_k(uint32_t V, cons
 __device__ __forceinline__ double box_d2(const uint32_t* __restrict__ box) {
     double d2 = 0.0;
     for (int d = 0; d < 3; d++) {
-        const float e = dec_f32(box[3 + d]) - dec_f32(box[d]);
+        const float e = ord_dec(box[3 + d]) - ord_dec(box[d]);
         d2 += (double)e * (double)e;
     }
     return d2;
@@ -460,8 +432,8 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_member_k(uint32_t V, const 
             mx = fmaxf(mx, __shfl_xor(mx, o));
         }
         if ((threadIdx.x & 63) == 0 && mn <= mx) {
-            atomicMin(box + d, enc_f32(mn));
-            atomicMax(box + 3 + d, enc_f32(mx));
+            atomicMin(box + d, ord_enc(mn));
+            atomicMax(box + 3 + d, ord_enc(mx));
         }
     }
 }
@@ -474,8 +446,8 @@ __device__ __forceinline__ Cells load_cells(const uint32_t* __restrict__ box, in
     float e = 0.f;
     const bool none = box[0] == ENC_NONE;
     for (int d = 0; d < 3; d++) {
-        c.lo[d] = none ? 0.f : dec_f32(box[d]);
-        e = fmaxf(e, none ? 0.f : dec_f32(box[3 + d]) - c.lo[d]);
+        c.lo[d] = none ? 0.f : ord_dec(box[d]);
+        e = fmaxf(e, none ? 0.f : ord_dec(box[3 + d]) - c.lo[d]);
     }
     c.flat = !(e > 0.f);
     c.cell = e / (float)n;
@@ -499,7 +471,7 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_probe_k(long long F, uint32
         const uint32_t ka = cell_key(c, n, vert, a), kb = cell_key(c, n, vert, b), kd = cell_key(c, n, vert, d);
         mine += (ka != kb && kb != kd && ka != kd) ? 1u : 0u;
     }
-    for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
 }
 __global__ void __launch_bounds__(MESH_THREADS) mesh_cell_key_k(uint32_t V, const float* __restrict__ vert,

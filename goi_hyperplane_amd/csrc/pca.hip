@@ -31,6 +31,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "wave_util.h"
 
 namespace goi {
 
@@ -419,15 +420,8 @@ __global__ void __launch_bounds__(64) pca_solve_k(const float* __restrict__ pivo
 }
 
 // ---------------------------------------------------------------------------------------------------------- apply
-// Order-preserving key of a float (display.hip): the buffer holds the key of the maximum and the COMPLEMENT of the key of
-// the minimum, so both are atomicMax and the all-zero buffer is the identity.
-__device__ __forceinline__ uint32_t float_key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// As in display.hip, the stats buffer holds the ordered key (ord_enc, wave_util.h) of the maximum and the COMPLEMENT of the key
+// of the minimum, so both are atomicMax and the all-zero buffer is the identity.
 
 struct ApplyParams {
     const float* x;      // [V][S][n] or [V][n][S]
@@ -482,8 +476,8 @@ __global__ void __launch_bounds__(APPLY_THREADS) pca_apply_k(const ApplyParams p
     if (PASS == 1 && p.mode == GOI_PCA_MINMAX) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float mn = key_float(~p.stats[((size_t)view * 3 + k) * 2]);
-            const float mx = key_float(p.stats[((size_t)view * 3 + k) * 2 + 1]);
+            const float mn = ord_dec(~p.stats[((size_t)view * 3 + k) * 2]);
+            const float mx = ord_dec(p.stats[((size_t)view * 3 + k) * 2 + 1]);
             nm.a[k] = mn;
             nm.b[k] = (mx - mn) + 1e-20f;
         }
@@ -578,7 +572,7 @@ __global__ void __launch_bounds__(APPLY_THREADS) pca_apply_k(const ApplyParams p
             for (int w = 1; w < APPLY_WAVES; ++w) v = is_min ? fminf(v, wpart[w][threadIdx.x]) : fmaxf(v, wpart[w][threadIdx.x]);
             // an infinity of the wrong sign means no finite-or-not value was seen at all: leave the identity
             if (is_min ? v != INFINITY : v != -INFINITY)
-                atomicMax(p.stats + (size_t)view * 6 + threadIdx.x, is_min ? ~float_key(v) : float_key(v));
+                atomicMax(p.stats + (size_t)view * 6 + threadIdx.x, is_min ? ~ord_enc(v) : ord_enc(v));
         }
     }
 }

@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "wave_util.h"
 
 namespace goi {
 
@@ -49,12 +50,6 @@ struct PhotoMaps {  // the partial maps of one call, [N][C][H][W] each; NULL whe
     float* xx;
     float* xy;
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <int R>
 __global__ void __launch_bounds__(PH_THREADS) photo_fwd_k(const float* __restrict__ x, const float* __restrict__ y, int H, int W,
@@ -157,8 +152,7 @@ __global__ void __launch_bounds__(PH_THREADS) photo_fwd_k(const float* __restric
 
 // Block-wide fp64 sum in a fixed tree order; every thread gets the result.
 __device__ __forceinline__ double block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     const int tid = threadIdx.x;
     __syncthreads();
     if (tid % WAVE == 0) lds[tid / WAVE] = v;

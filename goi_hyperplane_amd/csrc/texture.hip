@@ -20,6 +20,7 @@
 //   fill         tex_fill_columns_k: per texel the nearest mask texel above / below within the radius; tex_fill_nearest_k:
 //                the minimum over the 2 R + 1 columns of (dx^2 + dy^2, row, column), the L1 test carried along.
 #include "common.h"
+#include "wave_util.h"
 
 #include <math.h>
 
@@ -37,11 +38,6 @@ constexpr uint8_t TEX_FAR = 255;
 unsigned tblocks(long long n) { return (unsigned)((n + TEX_THREADS - 1) / TEX_THREADS); }
 __device__ __forceinline__ long long tgid() { return (long long)blockIdx.x * TEX_THREADS + threadIdx.x; }
 int tbits_for(uint32_t limit) { return limit == 0 ? 1 : 32 - __builtin_clz(limit); }
-
-__device__ __forceinline__ uint32_t tex_enc_f32(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // ---- rasterize -------------------------------------------------------------------------------------------------------------
 struct TriSetup {
@@ -124,7 +120,7 @@ __device__ __forceinline__ void tex_draw(const TriSetup& t, uint32_t f, int px, 
     float u, v, zw;
     tex_shade(t, e, u, v, zw);
     if (!(zw == zw)) return;  // a depth that is not a number draws nothing
-    atomicMin(zbuf + (size_t)py * W + px, ((unsigned long long)tex_enc_f32(zw) << 32) | f);
+    atomicMin(zbuf + (size_t)py * W + px, ((unsigned long long)ord_enc(zw) << 32) | f);
 }
 
 __global__ void __launch_bounds__(TEX_THREADS) tex_raster_wave_k(long long F, uint32_t V, const float* __restrict__ vclip,

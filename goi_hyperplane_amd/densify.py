@@ -35,12 +35,11 @@ only; there is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import nn
 
 from . import _lib
+from ._lib import check, ptr, stream, workspace
 
 _NO_CPU = "goi_hyperplane_amd.densify: tensors must live on a ROCm GPU; there is no CPU fallback"
 
@@ -51,14 +50,6 @@ _ATTR = dict(PARAMS)
 STATS = ("xyz_gradient_accum", "denom", "max_radii2D")
 _PARAM, _MOMENT, _XYZ, _SCALING, _ZERO = 0, 1, 2, 3, 4  # GOI_DENSIFY_* of include/goi_raster.h
 _ROW = {"_xyz": (3,), "_opacity": (1,), "_scaling": (3,), "_rotation": (4,)}  # the row shapes the kernels read
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check(t, what, fn, dev=None):
@@ -144,11 +135,11 @@ def _moments(opt, group, p, fn, name):
     return st, mv
 
 
-def _workspace(lib, P, dev, fn):
+def _plan_workspace(lib, P, dev, fn):
     nbytes = int(lib.goi_raster_densify_workspace_bytes(P))
     if nbytes == 0:
         raise ValueError(f"{fn}: P = {P} is out of range (P < 2^30)")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return workspace(nbytes, dev)
 
 
 def _row_len(t):
@@ -192,10 +183,8 @@ def _rebuild(g, fn, lib, P, P_new, params, opt, groups, moments, stats, stats_ze
     if P_new > 0 and rows:
         arr = (_lib.GoiDensifyRows * len(rows))(*rows)
         with torch.cuda.device(dev):
-            r = lib.goi_raster_densify_apply(P, arr, len(rows), _p(params["_rotation"]), _p(params["_scaling"]), _p(z), n_split,
-                                             kept_children, _p(ws), _stream(dev))
-        if r < 0:
-            raise ValueError(_lib.last_error())
+            check(lib.goi_raster_densify_apply(P, arr, len(rows), ptr(params["_rotation"]), ptr(params["_scaling"]), ptr(z), n_split,
+                                               kept_children, ptr(ws), stream(dev)), ValueError)
     for name, attr in PARAMS:
         old, t, group = params[attr], new[attr], groups.get(name)
         if group is None:
@@ -225,17 +214,15 @@ def densify_and_prune(g, max_grad, min_opacity, extent, max_screen_size, generat
     opt, groups = _groups(g, fn)
     moments = {name: _moments(opt, groups.get(name), params[attr], fn, name) for name, attr in PARAMS}
     lib = _lib.load()
-    ws = _workspace(lib, P, dev, fn)
+    ws = _plan_workspace(lib, P, dev, fn)
     counts = torch.empty(4, dtype=torch.int32, device=dev)
     screen = bool(max_screen_size)
     with torch.cuda.device(dev):
         # thresholds formed in Python double arithmetic, as the reference forms them
-        r = lib.goi_raster_densify_plan(P, _p(stats["xyz_gradient_accum"]), _p(stats["denom"]), _p(params["_scaling"]),
-                                        _p(params["_opacity"]), float(max_grad), float(g.percent_dense * extent),
-                                        float(min_opacity), 1 if screen else 0, float(max_screen_size) if screen else 0.0,
-                                        float(0.1 * extent), _p(counts), _p(ws), _stream(dev))
-    if r < 0:
-        raise ValueError(_lib.last_error())
+        check(lib.goi_raster_densify_plan(P, ptr(stats["xyz_gradient_accum"]), ptr(stats["denom"]), ptr(params["_scaling"]),
+                                          ptr(params["_opacity"]), float(max_grad), float(g.percent_dense * extent),
+                                          float(min_opacity), 1 if screen else 0, float(max_screen_size) if screen else 0.0,
+                                          float(0.1 * extent), ptr(counts), ptr(ws), stream(dev)), ValueError)
     kept, clones, children, n_split = (int(c) for c in counts.tolist())  # the one host synchronisation
     z = _draw_z(n_split, dev, generator)
     _rebuild(g, fn, lib, P, kept + clones + 2 * children, params, opt, groups, moments, stats, True, ws, dev, z, n_split,
@@ -259,12 +246,10 @@ def prune_points(g, mask) -> None:
         raise ValueError(f"{fn}: mask is on {mask.device}, expected {dev}")
     mask = mask.contiguous()
     lib = _lib.load()
-    ws = _workspace(lib, P, dev, fn)
+    ws = _plan_workspace(lib, P, dev, fn)
     counts = torch.empty(4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        r = lib.goi_raster_densify_prune_plan(P, _p(mask), _p(counts), _p(ws), _stream(dev))
-    if r < 0:
-        raise ValueError(_lib.last_error())
+        check(lib.goi_raster_densify_prune_plan(P, ptr(mask), ptr(counts), ptr(ws), stream(dev)), ValueError)
     kept = int(counts[0].item())  # the one host synchronisation
     _rebuild(g, fn, lib, P, kept, params, opt, groups, moments, stats, False, ws, dev)
 
@@ -302,9 +287,8 @@ def add_densification_stats(g, viewspace_point_tensor, update_filter) -> None:
     filt = update_filter.contiguous()
     lib = _lib.load()
     with torch.cuda.device(dev):
-        r = lib.goi_raster_densify_stats(P, _p(grad), int(grad.stride(0)), _p(filt), _p(accum), _p(denom), _stream(dev))
-    if r < 0:
-        raise ValueError(_lib.last_error())
+        check(lib.goi_raster_densify_stats(P, ptr(grad), int(grad.stride(0)), ptr(filt), ptr(accum), ptr(denom), stream(dev)),
+              ValueError)
 
 
 @torch.no_grad()

@@ -31,11 +31,10 @@ stream: at most two kernel launches whatever the number of views, and nothing is
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 # GOI_FRAME_* of include/goi_raster.h
 NONE, BINARY, WHITEN, HEAT, HEAT_FT = 0, 1, 2, 3, 4
@@ -81,10 +80,6 @@ def _style(style) -> int:
     if isinstance(style, bool) or not isinstance(style, int) or not NONE <= style <= HEAT_FT:
         raise ValueError(f"compose: unknown style {style!r}; expected display.NONE .. display.HEAT_FT or a name")
     return style
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def compose(base: torch.Tensor, sim: torch.Tensor | None = None, bg_mask: torch.Tensor | None = None, *, style,
@@ -171,10 +166,7 @@ def compose(base: torch.Tensor, sim: torch.Tensor | None = None, bg_mask: torch.
     need_ws = (normalize and code != BINARY) or code == HEAT
     ws = torch.empty((V, 3), dtype=torch.int32, device=dev) if need_ws else None
     with torch.cuda.device(dev):
-        r = lib.goi_semantic_frame_compose(_ptr(src), Cc, _ptr(s), _ptr(m), V, H, W, code, 1 if normalize else 0, ratio, thresh,
-                                           _ptr(table), 0 if table is None else int(table.shape[0]), _ptr(out),
-                                           _U8 if dtype == torch.uint8 else _F32, _ptr(ws),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+        check(lib.goi_semantic_frame_compose(ptr(src), Cc, ptr(s), ptr(m), V, H, W, code, 1 if normalize else 0, ratio, thresh,
+                                             ptr(table), 0 if table is None else int(table.shape[0]), ptr(out),
+                                             _U8 if dtype == torch.uint8 else _F32, ptr(ws), stream(dev)))
     return out

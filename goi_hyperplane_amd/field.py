@@ -29,12 +29,12 @@ mesh.extract chains them behind extract_mesh), UV unwrapping and the nvdiffrast 
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import namedtuple
 
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream, workspace
 
 # GOI_FIELD_* of include/goi_raster.h
 BATCH = 128  # members a block stages in LDS before its threads consume them
@@ -50,14 +50,6 @@ sort's look-back timed out on a wedged device and the grids are garbage.  densit
 raise for it: check `status` where you read the grids back (extract_mesh does, and raises)."""
 IsoSurface = namedtuple("IsoSurface", "vertices faces colors")
 Mesh = namedtuple("Mesh", "vertices faces colors center scale")
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def check_grid(resolution, num_blocks, relax_ratio) -> int:
@@ -163,13 +155,11 @@ def density_grid(xyz, opacity, scaling, rotation, resolution=128, num_blocks=16,
     att = attributes.detach().contiguous() if attributes is not None else None
     ws = None
     if P > 0:
-        ws = torch.empty(int(lib.goi_field_density_workspace_bytes(P, R, nb, float(relax_ratio))), dtype=torch.uint8, device=dev)
+        ws = workspace(lib.goi_field_density_workspace_bytes(P, R, nb, float(relax_ratio)), dev)
     with torch.cuda.device(dev):
-        r = lib.goi_field_density(P, _ptr(src[0]), _ptr(src[1]), _ptr(src[2]), _ptr(src[3]), _ptr(sel), 1 if selection_invert else 0,
-                                  mo, _ptr(att), _ptr(frame_in), R, nb, float(relax_ratio), _ptr(coords), _ptr(lo), _ptr(hi),
-                                  _ptr(occ), _ptr(attr), _ptr(frame), _ptr(status), _ptr(ws), _stream(dev))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+        check(lib.goi_field_density(P, ptr(src[0]), ptr(src[1]), ptr(src[2]), ptr(src[3]), ptr(sel), 1 if selection_invert else 0,
+                                    mo, ptr(att), ptr(frame_in), R, nb, float(relax_ratio), ptr(coords), ptr(lo), ptr(hi),
+                                    ptr(occ), ptr(attr), ptr(frame), ptr(status), ptr(ws), stream(dev)))
     return DensityField(occ, attr, frame[:3], frame[3], coords, status[0])
 
 
@@ -215,21 +205,17 @@ def isosurface(grid, thresh, attributes=None, coords=None) -> IsoSurface:
     lib = _lib.load()
     g = grid.detach().contiguous()
     a = attributes.detach().contiguous() if attributes is not None else None
-    ws = torch.empty(int(lib.goi_field_iso_workspace_bytes(X, Y, Z)), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.goi_field_iso_workspace_bytes(X, Y, Z), dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        r = lib.goi_field_iso_count(_ptr(g), X, Y, Z, t, _ptr(ws), _ptr(counts), _stream(dev))
-        if r < 0:
-            raise RuntimeError(_lib.last_error())
+        check(lib.goi_field_iso_count(ptr(g), X, Y, Z, t, ptr(ws), ptr(counts), stream(dev)))
         V, F = (int(n) for n in counts.tolist())  # the one read-back: the outputs' sizes
         vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
         faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
         colors = torch.empty((V, 3), dtype=torch.float32, device=dev) if a is not None else None
         if V > 0 or F > 0:
-            r = lib.goi_field_iso_emit(_ptr(g), _ptr(a), X, Y, Z, t, _ptr(tables[0]), _ptr(tables[1]), _ptr(tables[2]), _ptr(ws),
-                                       V, F, _ptr(vertices), _ptr(faces), _ptr(colors), _stream(dev))
-            if r < 0:
-                raise RuntimeError(_lib.last_error())
+            check(lib.goi_field_iso_emit(ptr(g), ptr(a), X, Y, Z, t, ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), ptr(ws),
+                                         V, F, ptr(vertices), ptr(faces), ptr(colors), stream(dev)))
     return IsoSurface(vertices, faces, colors)
 
 

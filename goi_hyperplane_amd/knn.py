@@ -3,8 +3,6 @@ spatial.cu:15-26).  points [P,3] float32 on the GPU -> [P] float32: mean squared
 nearest other points, used by scene/gaussian_model.py:147 to size the initial Gaussians."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -28,8 +26,5 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
         if pts.numel() != 3 * P:
             raise RuntimeError("distCUDA2: points must have shape (P, 3)")
         ws = torch.empty(lib.goi_knn_workspace_bytes(P), dtype=torch.uint8, device=dev)
-        r = lib.goi_knn_dist2(P, C.c_void_p(pts.data_ptr()), C.c_void_p(means.data_ptr()), C.c_void_p(ws.data_ptr()),
-                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if r < 0:
-            raise RuntimeError(_lib.last_error())
+        _lib.check(lib.goi_knn_dist2(P, _lib.ptr(pts), _lib.ptr(means), _lib.ptr(ws), _lib.stream(dev)))
     return means

@@ -11,12 +11,12 @@ the current stream: none reads anything back to the host.  segmentation_metrics 
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import namedtuple
 
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 MAX_RADIUS = 63  # GOI_MASK_MAX_RADIUS: the row pass takes its carries from the two neighbouring words only
 _F32, _U8 = 0, 1  # GOI_MASK_F32, GOI_MASK_U8
@@ -44,19 +44,6 @@ def radius(kernel_size: int, iterations: int) -> int:
     if r > MAX_RADIUS:
         raise ValueError(f"dilate: the window radius iterations * (kernel_size - 1) / 2 = {r} exceeds {MAX_RADIUS}")
     return r
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _check(r):
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
 
 
 def _hw(x: torch.Tensor):
@@ -94,8 +81,8 @@ def pack_into(x: torch.Tensor, packed: torch.Tensor, counts: torch.Tensor | None
         raise RuntimeError(_NO_CPU)
     dev = src.device
     with torch.cuda.device(dev):
-        _check(_lib.load().goi_semantic_mask_pack(_ptr(src), code, n, H, W, int(first_view), _ptr(packed), _ptr(counts),
-                                                  _stream(dev)))
+        check(_lib.load().goi_semantic_mask_pack(ptr(src), code, n, H, W, int(first_view), ptr(packed), ptr(counts),
+                                                  stream(dev)))
 
 
 def pack(x: torch.Tensor):
@@ -124,7 +111,7 @@ def dilate_packed(packed: torch.Tensor, W: int, r: int) -> torch.Tensor:
     out = torch.empty_like(src)
     dev = src.device
     with torch.cuda.device(dev):
-        _check(_lib.load().goi_semantic_mask_dilate(_ptr(src), _ptr(out), V, H, int(W), int(r), _stream(dev)))
+        check(_lib.load().goi_semantic_mask_dilate(ptr(src), ptr(out), V, H, int(W), int(r), stream(dev)))
     return out
 
 
@@ -143,8 +130,8 @@ def unpack(packed: torch.Tensor, W: int, index: torch.Tensor | None = None) -> t
     out = torch.empty((K, 1, H, int(W)), dtype=torch.bool, device=src.device)
     dev = src.device
     with torch.cuda.device(dev):
-        _check(_lib.load().goi_semantic_mask_unpack(_ptr(src), int(packed.shape[0]), H, int(W), K, _ptr(index), _ptr(out.view(torch.uint8)),
-                                                    _stream(dev)))
+        check(_lib.load().goi_semantic_mask_unpack(ptr(src), int(packed.shape[0]), H, int(W), K, ptr(index), ptr(out.view(torch.uint8)),
+                                                    stream(dev)))
     return out
 
 
@@ -173,7 +160,7 @@ def confusion_packed(pred: torch.Tensor, gt: torch.Tensor, W: int) -> torch.Tens
     out = torch.empty((V, 4), dtype=torch.int64, device=p.device)
     dev = p.device
     with torch.cuda.device(dev):
-        _check(_lib.load().goi_semantic_mask_confusion(_ptr(p), _ptr(g), V, H, int(W), _ptr(out), _stream(dev)))
+        check(_lib.load().goi_semantic_mask_confusion(ptr(p), ptr(g), V, H, int(W), ptr(out), stream(dev)))
     return out
 
 

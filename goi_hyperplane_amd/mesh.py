@@ -29,12 +29,12 @@ texture.bake(pc, mesh.extract(pc, ...), bg_color) -> io.save_mesh_obj.
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import namedtuple
 
 import torch
 
 from . import _lib, field
+from ._lib import check, ptr, stream, workspace
 
 # GOI_MESH_* of include/goi_raster.h
 STATUS_SORT, STATUS_UNION, STATUS_RANGE = 2, 4, 8
@@ -49,14 +49,6 @@ read back, so nothing was raised: check_status(status) where you read the labels
 CleanMesh = namedtuple("CleanMesh", "vertices faces colors vertex_index face_index")
 DecimatedMesh = namedtuple("DecimatedMesh", "vertices faces colors divisions cluster")
 Mesh = namedtuple("Mesh", "vertices faces colors normals center scale")
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def check_status(status, fn="mesh") -> None:
@@ -99,16 +91,6 @@ def _mesh_args(fn, vertices, faces, colors=None, n_vertices=None):
     return V, F, cont[0], cont[1], cont[2], dev
 
 
-def _workspace(nbytes, dev):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-
-
-def _call(r):
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
-    return r
-
-
 def components(faces, n_vertices) -> Components:
     """faces int32 [F, 3], n_vertices = V.  Two vertices are connected when a face names both.  Reads nothing back."""
     fn = "mesh.components"
@@ -117,9 +99,9 @@ def components(faces, n_vertices) -> Components:
     vlabel = torch.empty(V, dtype=torch.int32, device=dev)
     flabel = torch.empty(F, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.goi_mesh_components_workspace_bytes(V, F), dev)
+    ws = workspace(lib.goi_mesh_components_workspace_bytes(V, F), dev)
     with torch.cuda.device(dev):
-        _call(lib.goi_mesh_components(V, F, _ptr(f), _ptr(vlabel), _ptr(flabel), _ptr(status), _ptr(ws), _stream(dev)))
+        check(lib.goi_mesh_components(V, F, ptr(f), ptr(vlabel), ptr(flabel), ptr(status), ptr(ws), stream(dev)))
     return Components(vlabel, flabel, status[0])
 
 
@@ -149,10 +131,10 @@ def clean(vertices, faces, colors=None, min_faces=64, min_diag=0.2) -> CleanMesh
     if V == 0 or F == 0:
         return CleanMesh(*_empty(dev, c, V), torch.empty(0, **i32), torch.empty(0, **i32))
     lib = _lib.load()
-    ws = _workspace(lib.goi_mesh_clean_workspace_bytes(V, F), dev)
+    ws = workspace(lib.goi_mesh_clean_workspace_bytes(V, F), dev)
     counts = torch.empty(3, **i32)
     with torch.cuda.device(dev):
-        _call(lib.goi_mesh_clean_plan(V, F, _ptr(v), _ptr(f), mf, md * md, _ptr(ws), _ptr(counts), _stream(dev)))
+        check(lib.goi_mesh_clean_plan(V, F, ptr(v), ptr(f), mf, md * md, ptr(ws), ptr(counts), stream(dev)))
         nv, nf, st = (int(n) for n in counts.tolist())  # the one read-back: the outputs' sizes (and the status word)
         check_status(st, fn)
         out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
@@ -160,8 +142,8 @@ def clean(vertices, faces, colors=None, min_faces=64, min_diag=0.2) -> CleanMesh
         out_c = torch.empty((nv, 3), dtype=torch.float32, device=dev) if c is not None else None
         vidx, fidx = torch.empty(nv, **i32), torch.empty(nf, **i32)
         if nv > 0 or nf > 0:
-            _call(lib.goi_mesh_clean_emit(V, F, _ptr(v), _ptr(f), _ptr(c), _ptr(ws), nv, nf, _ptr(out_v), _ptr(out_f), _ptr(out_c),
-                                          _ptr(vidx), _ptr(fidx), _stream(dev)))
+            check(lib.goi_mesh_clean_emit(V, F, ptr(v), ptr(f), ptr(c), ptr(ws), nv, nf, ptr(out_v), ptr(out_f), ptr(out_c),
+                                          ptr(vidx), ptr(fidx), stream(dev)))
     return CleanMesh(out_v, out_f, out_c, vidx, fidx)
 
 
@@ -208,28 +190,28 @@ def decimate(vertices, faces, colors=None, divisions=None, target_faces=None) ->
     if V == 0 or F == 0:
         return DecimatedMesh(*_empty(dev, c, V), divisions if divisions is not None else 1, torch.full((V,), -1, **i32))
     lib = _lib.load()
-    ws = _workspace(lib.goi_mesh_decimate_workspace_bytes(V, F), dev)
+    ws = workspace(lib.goi_mesh_decimate_workspace_bytes(V, F), dev)
     counts = torch.empty(3, **i32)
     with torch.cuda.device(dev):
-        s = _stream(dev)
-        _call(lib.goi_mesh_decimate_members(V, F, _ptr(v), _ptr(f), _ptr(ws), s))
+        s = stream(dev)
+        check(lib.goi_mesh_decimate_members(V, F, ptr(v), ptr(f), ptr(ws), s))
         if divisions is None:
             probe = torch.empty(1, **i32)
 
             def count(m):
-                _call(lib.goi_mesh_decimate_probe(V, F, _ptr(v), _ptr(f), m, _ptr(ws), _ptr(probe), s))
+                check(lib.goi_mesh_decimate_probe(V, F, ptr(v), ptr(f), m, ptr(ws), ptr(probe), s))
                 return int(probe.item())  # one integer per probe
 
             n = bisect_divisions(count, target)
-        sorted_in = _call(lib.goi_mesh_decimate_plan(V, F, _ptr(v), _ptr(f), n, _ptr(ws), _ptr(counts), s))
+        sorted_in = check(lib.goi_mesh_decimate_plan(V, F, ptr(v), ptr(f), n, ptr(ws), ptr(counts), s))
         nv, nf, st = (int(k) for k in counts.tolist())  # the outputs' sizes (and the status word)
         check_status(st, fn)
         out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         out_f = torch.empty((nf, 3), **i32)
         out_c = torch.empty((nv, 3), dtype=torch.float32, device=dev) if c is not None else None
         cluster = torch.empty(V, **i32)
-        _call(lib.goi_mesh_decimate_emit(V, F, _ptr(v), _ptr(c), n, sorted_in, _ptr(ws), nv, nf, _ptr(out_v), _ptr(out_f),
-                                         _ptr(out_c), _ptr(cluster), s))
+        check(lib.goi_mesh_decimate_emit(V, F, ptr(v), ptr(c), n, sorted_in, ptr(ws), nv, nf, ptr(out_v), ptr(out_f),
+                                         ptr(out_c), ptr(cluster), s))
     return DecimatedMesh(out_v, out_f, out_c, n, cluster)
 
 
@@ -244,9 +226,9 @@ def vertex_normals(vertices, faces, return_status=False):
     lib = _lib.load()
     out = torch.empty((V, 3), dtype=torch.float32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.goi_mesh_normals_workspace_bytes(V, F), dev)
+    ws = workspace(lib.goi_mesh_normals_workspace_bytes(V, F), dev)
     with torch.cuda.device(dev):
-        _call(lib.goi_mesh_normals(V, F, _ptr(v), _ptr(f), _ptr(out), _ptr(status), _ptr(ws), _stream(dev)))
+        check(lib.goi_mesh_normals(V, F, ptr(v), ptr(f), ptr(out), ptr(status), ptr(ws), stream(dev)))
     return (out, status[0]) if return_status else out
 
 

@@ -12,7 +12,6 @@ differentiable.  fp32 CUDA (ROCm) tensors only; there is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -91,16 +90,15 @@ class FusedAdam(torch.optim.Optimizer):
             # handed over as a foreign pointer
             mask = None if nograd_mask is None else nograd_mask.to(device=dev, dtype=torch.uint8).contiguous()
             with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                stream = _lib.stream(dev)
                 for i in range(0, len(groups), _lib.ADAM_MAX_GROUPS):
                     chunk = groups[i:i + _lib.ADAM_MAX_GROUPS]
                     arr = (_lib.GoiAdamGroup * len(chunk))(*chunk)
-                    mp = C.c_void_p(mask.data_ptr()) if mask is not None else None
+                    mp = _lib.ptr(mask)
                     sp = None
                     if skip_if is not None:
                         if skip_if.device != dev:
                             raise ValueError("skip_if lives on another device than the parameters")
-                        sp = C.c_void_p(skip_if.data_ptr())
-                    if lib.goi_adam_step_guarded(arr, len(chunk), beta1, beta2, eps, mp, sp, stream) < 0:
-                        raise RuntimeError(_lib.last_error())
+                        sp = _lib.ptr(skip_if)
+                    _lib.check(lib.goi_adam_step_guarded(arr, len(chunk), beta1, beta2, eps, mp, sp, stream))
         return loss

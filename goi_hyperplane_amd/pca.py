@@ -26,11 +26,10 @@ and corrected exactly in the solve, so features far from zero lose nothing.  Eve
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 # GOI_PCA_* of include/goi_raster.h
 PLANAR, ROWS = 0, 1
@@ -74,14 +73,6 @@ class PcaBasis:
     @property
     def count(self):
         return self.data[4 * self.S + 4]
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _layout(layout) -> int:
@@ -157,10 +148,8 @@ class Fit:
         m = _mask("pca.fit", mask, n, self.device)
         src = x.contiguous()
         with torch.cuda.device(self.device):
-            r = self._lib.goi_semantic_pca_accumulate(_ptr(src), code, S, n, _ptr(m), 1 if self.calls == 0 else 0,
-                                                      _ptr(self.workspace), _stream(self.device))
-        if r < 0:
-            raise RuntimeError(_lib.last_error())
+            check(self._lib.goi_semantic_pca_accumulate(ptr(src), code, S, n, ptr(m), 1 if self.calls == 0 else 0,
+                                                        ptr(self.workspace), stream(self.device)))
         self.calls += 1
         return self
 
@@ -169,9 +158,7 @@ class Fit:
             raise ValueError("pca.fit: nothing was added")
         data = torch.empty(basis_floats(self.S), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            r = self._lib.goi_semantic_pca_solve(self.S, _ptr(self.workspace), _ptr(data), _stream(self.device))
-        if r < 0:
-            raise RuntimeError(_lib.last_error())
+            check(self._lib.goi_semantic_pca_solve(self.S, ptr(self.workspace), ptr(data), stream(self.device)))
         return PcaBasis(data, self.S)
 
 
@@ -275,10 +262,8 @@ def transform(x: torch.Tensor, basis: PcaBasis, layout="planar", normalize="raw"
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     ws = torch.empty((V, 3, 2), dtype=torch.int32, device=dev) if mode == MINMAX else None
     with torch.cuda.device(dev):
-        r = lib.goi_semantic_pca_apply(_ptr(src), code, S, n, V, _ptr(basis.data), mode, k, _ptr(out), ocode, _ptr(ws),
-                                       _stream(dev))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+        check(lib.goi_semantic_pca_apply(ptr(src), code, S, n, V, ptr(basis.data), mode, k, ptr(out), ocode, ptr(ws),
+                                         stream(dev)))
     return out
 
 

@@ -12,12 +12,12 @@ host.  Sums are formed in a fixed order, so two calls give the same bits.
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import namedtuple
 
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 _NO_CPU = "goi_hyperplane_amd.photometric: tensors must live on a ROCm GPU; there is no CPU fallback"
 
@@ -53,14 +53,6 @@ def _check(img1, img2, fn, window_size=WINDOW_SIZE):
     return a, b
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _forward(a, b, lam, flags, per_image):
     """One fused forward over [N, C, H, W] a, b: (out [3] = loss, L1, SSIM; per-image [3, N] = SSIM, L1, PSNR or None;
     the workspace the backward reads)."""
@@ -74,10 +66,8 @@ def _forward(a, b, lam, flags, per_image):
     out = torch.empty(3, dtype=torch.float32, device=dev)
     imgs = torch.empty(3, N, dtype=torch.float32, device=dev) if per_image else None
     with torch.cuda.device(dev):
-        r = lib.goi_raster_photometric_forward(_p(a), _p(b), N, Ch, H, W, WINDOW_SIZE, float(lam), flags, _p(out), _p(imgs), _p(ws),
-                                        _stream(dev))
-    if r < 0:
-        raise ValueError(_lib.last_error())
+        check(lib.goi_raster_photometric_forward(ptr(a), ptr(b), N, Ch, H, W, WINDOW_SIZE, float(lam), flags, ptr(out), ptr(imgs), ptr(ws),
+                                                 stream(dev)), ValueError)
     return out, imgs, ws
 
 
@@ -90,10 +80,8 @@ def _backward(a, b, lam, flags, grad_out, ws, need1, need2):
     g2 = torch.empty_like(b) if need2 else None
     flags |= (_GRAD1 if need1 else 0) | (_GRAD2 if need2 else 0)
     with torch.cuda.device(dev):
-        r = lib.goi_raster_photometric_backward(_p(a), _p(b), N, Ch, H, W, WINDOW_SIZE, float(lam), flags, _p(g), _p(ws), _p(g1), _p(g2),
-                                         _stream(dev))
-    if r < 0:
-        raise ValueError(_lib.last_error())
+        check(lib.goi_raster_photometric_backward(ptr(a), ptr(b), N, Ch, H, W, WINDOW_SIZE, float(lam), flags, ptr(g), ptr(ws), ptr(g1),
+                                                  ptr(g2), stream(dev)), ValueError)
     return g1, g2
 
 

@@ -28,13 +28,13 @@ split-K MFMA GEMM for dL/dLUT), which is also the cross-check of tests/test_gpu_
 from __future__ import annotations
 
 import ctypes as C
-import ctypes as C_
 from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 
 class FeatureNorm(torch.nn.Module):
@@ -175,12 +175,10 @@ def compute_similarity(sem_chw: torch.Tensor, mlp: SemanticModel, lut: torch.Ten
     sim = torch.empty(HW, dtype=torch.float32, device=dev)
     idx = torch.empty(HW, dtype=torch.int32, device=dev) if return_index else None
     mask = torch.empty(HW, dtype=torch.uint8, device=dev) if out_bg_mask is not None else None
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    p = ptr
     with torch.cuda.device(dev):
-        r = lib.goi_semantic_decode(p(sem), S, HW, p(w), p(b), n_codes, p(table), float(thresh), p(sim), p(idx), p(mask),
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+        check(lib.goi_semantic_decode(p(sem), S, HW, p(w), p(b), n_codes, p(table), float(thresh), p(sim), p(idx), p(mask),
+                                      stream(dev)))
     if out_bg_mask is not None:
         out_bg_mask[:] = mask.bool()
     return (sim, idx) if return_index else sim
@@ -254,8 +252,7 @@ class _FusedCodebookLoss(torch.autograd.Function):
         b = None if bias is None else bias.detach().contiguous().float()
         l1 = lut1.detach().contiguous().float()
         with torch.cuda.device(dev):
-            p = lambda x: None if x is None else C_.c_void_p(x.data_ptr())  # noqa: E731
-            stream = C_.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            p, s = ptr, stream(dev)
             # (the full shape predicate of launch_codebook_fused, csrc/codebook_loss.hip: anything else takes the
             # three-kernel path below instead of raising)
             if (_FUSED_KERNELS["on"] and D == 256 and 288 < C <= 304 and 1 <= S <= 16 and HW % 4 == 0
@@ -265,9 +262,8 @@ class _FusedCodebookLoss(torch.autograd.Function):
                 partials = torch.empty((lib.goi_codebook_fused_partial_rows(), C * (S + 1) + 4), dtype=torch.float32, device=dev)
                 part = torch.empty((lib.goi_codebook_dlut_partial_blocks(), 304, D), dtype=torch.float32, device=dev)
                 ws = torch.empty((int(lib.goi_codebook_fused_workspace_bytes(HW)),), dtype=torch.uint8, device=dev)
-                if lib.goi_codebook_fused(p(g), p(l1), p(sem), p(w), p(b), HW, C, D, S, float(t), p(dsem), p(partials), p(part),
-                                          p(ws), stream) < 0:
-                    raise RuntimeError(_lib.last_error())
+                check(lib.goi_codebook_fused(p(g), p(l1), p(sem), p(w), p(b), HW, C, D, S, float(t), p(dsem), p(partials), p(part),
+                                             p(ws), s))
                 del ws
                 LOSS_PATH_COUNTS["fused"] += 1
                 return _FusedCodebookLoss._finish(ctx, sem_chw, bias, partials, dsem, part.sum(dim=0)[:C].contiguous(), HW, C, S)
@@ -277,8 +273,7 @@ class _FusedCodebookLoss(torch.autograd.Function):
                 sim_raw = torch.empty((HW, C), dtype=torch.float32, device=dev)
                 inv_gnorm = torch.empty((HW,), dtype=torch.float32, device=dev)
                 ws = torch.empty((int(lib.goi_codebook_sim_workspace_bytes()),), dtype=torch.uint8, device=dev)
-                if lib.goi_codebook_sim(p(g), p(l1), HW, C, D, p(sim_raw), p(inv_gnorm), p(ws), stream) < 0:
-                    raise RuntimeError(_lib.last_error())
+                check(lib.goi_codebook_sim(p(g), p(l1), HW, C, D, p(sim_raw), p(inv_gnorm), p(ws), s))
                 LOSS_PATH_COUNTS["three_kernel"] += 1
             else:
                 LOSS_PATH_COUNTS["library_gemm"] += 1
@@ -288,18 +283,14 @@ class _FusedCodebookLoss(torch.autograd.Function):
             dsem = torch.empty((S, HW), dtype=torch.float32, device=dev)
             rows = lib.goi_codebook_loss_partial_rows()
             partials = torch.empty((rows, C * (S + 1) + 4), dtype=torch.float32, device=dev)
-            r = lib.goi_codebook_loss_rows(p(sim_raw), p(inv_gnorm), p(sem), p(w), p(b), HW, C, S, float(t), p(dsim),
-                                           p(dsem), p(partials), C_.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if r < 0:
-                raise RuntimeError(_lib.last_error())
+            check(lib.goi_codebook_loss_rows(p(sim_raw), p(inv_gnorm), p(sem), p(w), p(b), HW, C, S, float(t), p(dsim),
+                                             p(dsem), p(partials), s))
             del sim_raw
             if D == 256 and 288 < C <= 304 and HW % 4 == 0:
                 # split-K MFMA GEMM over the pixel axis with a persistent [304, 256] accumulator per CU
                 blocks = lib.goi_codebook_dlut_partial_blocks()
                 part = torch.empty((blocks, 304, D), dtype=torch.float32, device=dev)
-                if lib.goi_codebook_dlut(p(dsim), p(g), HW, C, D, p(part),
-                                         C_.c_void_p(torch.cuda.current_stream(dev).cuda_stream)) < 0:
-                    raise RuntimeError(_lib.last_error())
+                check(lib.goi_codebook_dlut(p(dsim), p(g), HW, C, D, p(part), s))
                 dl1 = part.sum(dim=0)[:C].contiguous()
             else:
                 dl1 = torch.matmul(dsim.t(), g.t())                                   # [C, D]   (library GEMM)
@@ -358,10 +349,6 @@ OSHFit.__doc__ = ("Result of fit_hyperplane: epochs run, the last epoch's loss (
 _NO_CPU = "goi_hyperplane_amd.semantic: tensors must live on a ROCm GPU; there is no CPU fallback"
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 @torch.no_grad()
 def osh_counts(idx: torch.Tensor, positive: torch.Tensor, n_codes: int) -> torch.Tensor:
     """int32 [2, n_codes]: row 0 the pixels with idx == c and positive != 0, row 1 those with positive == 0 (one HIP
@@ -380,10 +367,7 @@ def osh_counts(idx: torch.Tensor, positive: torch.Tensor, n_codes: int) -> torch
     counts = torch.zeros((2, n_codes), dtype=torch.int32, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        r = lib.goi_semantic_osh_counts(C.c_void_p(idx.data_ptr()), C.c_void_p(pos.data_ptr()), idx.numel(), n_codes,
-                                        C.c_void_p(counts.data_ptr()), _stream(dev))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+        check(lib.goi_semantic_osh_counts(ptr(idx), ptr(pos), idx.numel(), n_codes, ptr(counts), stream(dev)))
     return counts
 
 
@@ -418,13 +402,11 @@ def _osh_launch(lut, counts, HW, w, b, lr, max_epochs, target_iou, return_trace)
     trace = buf[24 * K:].view(torch.float64).view(K, max_epochs, 2) if return_trace else None
     if trace is not None:
         trace.fill_(float("nan"))
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    p = ptr
     lib = _lib.load()
     with torch.cuda.device(dev):
-        r = lib.goi_semantic_osh_fit(p(lut), n_codes, D, p(counts), HW, K, p(w), p(b), float(lr), max_epochs,
-                                     float(target_iou), p(epochs), p(loss), p(iou), p(init_iou), p(trace), _stream(dev))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+        check(lib.goi_semantic_osh_fit(p(lut), n_codes, D, p(counts), HW, K, p(w), p(b), float(lr), max_epochs,
+                                       float(target_iou), p(epochs), p(loss), p(iou), p(init_iou), p(trace), stream(dev)))
     return w, b, buf, trace
 
 
@@ -461,11 +443,8 @@ def _decode_idx(sem_chw, mlp, n_codes):
     bias = (lin.bias.detach() if lin.bias is not None else torch.zeros(n_codes, device=dev)).contiguous().float()
     idx = torch.empty(HW, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        r = _lib.load().goi_semantic_decode(C.c_void_p(sem.data_ptr()), S, HW, C.c_void_p(W.data_ptr()),
-                                            C.c_void_p(bias.data_ptr()), n_codes, None, 0.0, None, C.c_void_p(idx.data_ptr()),
-                                            None, _stream(dev))
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
+        check(_lib.load().goi_semantic_decode(ptr(sem), S, HW, ptr(W), ptr(bias), n_codes, None, 0.0, None, ptr(idx), None,
+                                              stream(dev)))
     return idx
 
 
@@ -726,12 +705,10 @@ class _FrameDecoder:
         sem = sem_chw.contiguous().float()
         HW = int(sem[0].numel())
         dev = sem.device
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        p = ptr
         with torch.cuda.device(dev):
-            r = _lib.load().goi_semantic_decode(p(sem), self.S, HW, p(self.w), p(self.b), self.n_codes, p(self.table), self.thresh,
-                                                p(sim_out), None, p(mask_out), _stream(dev))
-        if r < 0:
-            raise RuntimeError(_lib.last_error())
+            check(_lib.load().goi_semantic_decode(p(sem), self.S, HW, p(self.w), p(self.b), self.n_codes, p(self.table),
+                                                  self.thresh, p(sim_out), None, p(mask_out), stream(dev)))
 
 
 def _alpha_mask(out, pca_mask_alpha):
@@ -860,20 +837,6 @@ _STAGING = {}
 _CODEBOOK_FLAG_NONFINITE = 1  # GOI_CODEBOOK_FLAG_NONFINITE (include/goi_raster.h)
 
 
-class _RowsAlloc:
-    def __init__(self, dev):
-        self.dev, self.tensor, self.error = dev, None, None
-        self.cb = _lib.ALLOC_FN(self._alloc)
-
-    def _alloc(self, _user, nbytes):
-        try:
-            self.tensor = torch.empty(int(nbytes), dtype=torch.uint8, device=self.dev)
-            return self.tensor.data_ptr()
-        except Exception as ex:  # never let an exception cross the C boundary
-            self.error = ex
-            return None
-
-
 def _staging_buffers(nbytes):
     bufs = _STAGING.get("bufs")
     if bufs is None or bufs[0].numel() < nbytes:
@@ -948,12 +911,10 @@ def unique_rows(maps):
         ptrs = (C.c_void_p * V)(*[dmaps[i].data_ptr() for i in idx])
         counts = (C.c_longlong * V)()
         flags = C.c_uint(0)
-        alloc = _RowsAlloc(dev)
+        alloc = _lib.TensorAlloc(lambda nbytes: torch.empty(nbytes, dtype=torch.uint8, device=dev))
         with torch.cuda.device(dev):
-            r = lib.goi_codebook_unique_rows(ptrs, V, D, H, W, counts, C.byref(flags), alloc.cb, None, C.c_void_p(ws.data_ptr()),
-                                             _stream(dev))
-        if r < 0:
-            raise ValueError(_lib.last_error())
+            r = lib.goi_codebook_unique_rows(ptrs, V, D, H, W, counts, C.byref(flags), alloc.cb, None, ptr(ws), stream(dev))
+        check(r, ValueError)
         if alloc.error is not None:
             raise alloc.error
         if flags.value & _CODEBOOK_FLAG_NONFINITE:
@@ -1007,12 +968,10 @@ def spherical_kmeans_batched(xs, ncluster: int, niter: int = 10):
     lib = _lib.load()
     rows = sum(sizes)
     ws = torch.empty(max(int(lib.goi_codebook_kmeans_workspace_bytes(rows, len(xs), ncluster, D)), 1), dtype=torch.uint8, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    p = ptr
     with torch.cuda.device(dev):
-        r = lib.goi_codebook_kmeans(p(xcat), p(offsets), len(xs), max(sizes), rows, D, ncluster, niter, p(perms), p(centers),
-                                    p(status), p(ws), _stream(dev))
-    if r < 0:
-        raise ValueError(_lib.last_error())
+        check(lib.goi_codebook_kmeans(p(xcat), p(offsets), len(xs), max(sizes), rows, D, ncluster, niter, p(perms), p(centers),
+                                      p(status), p(ws), stream(dev)), ValueError)
     start = 0
     for x, n in zip(xs, sizes):  # x /= x.norm(...) is in place in the reference
         if xcat.data_ptr() != x.data_ptr():

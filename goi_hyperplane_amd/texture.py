@@ -51,7 +51,6 @@ reference's MiniCam has commented out: its camera looks away from the orbit's ta
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from collections import namedtuple
 from dataclasses import dataclass
@@ -60,6 +59,7 @@ import numpy as np
 import torch
 
 from . import _lib, scene
+from ._lib import check, ptr, stream, workspace
 from .field import _f32
 
 # GOI_TEXTURE_* of include/goi_raster.h
@@ -80,24 +80,6 @@ float32 [h, w, 3] in [0, 1], mask bool [h, w]: the texels a view reached (the ot
 
 VERS = [0] * 8 + [-45] * 8 + [45] * 8 + [-89.9, 89.9]  # gui/main.py:632-633
 HORS = [0, 45, -45, 90, -90, 135, -135, 180] * 3 + [0, 0]
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _workspace(nbytes, dev):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-
-
-def _call(r):
-    if r < 0:
-        raise RuntimeError(_lib.last_error())
-    return r
 
 
 def _on_device(fn, *tensors):
@@ -259,10 +241,10 @@ def rasterize(v_clip, faces, H, W) -> Raster:
     bary = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
     zw = torch.empty((H, W), dtype=torch.float32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.goi_texture_rasterize_workspace_bytes(F, H, W), dev)
+    ws = workspace(lib.goi_texture_rasterize_workspace_bytes(F, H, W), dev)
     with torch.cuda.device(dev):
-        _call(lib.goi_texture_rasterize(V, F, _ptr(v), _ptr(f), H, W, _ptr(tri), _ptr(bary), _ptr(zw), _ptr(status), _ptr(ws),
-                                        _stream(dev)))
+        check(lib.goi_texture_rasterize(V, F, ptr(v), ptr(f), H, W, ptr(tri), ptr(bary), ptr(zw), ptr(status), ptr(ws),
+                                        stream(dev)))
     return Raster(tri, bary, zw, status[0])
 
 
@@ -291,8 +273,8 @@ def resolve(raster, vt, ft, vn, faces, pose_rot, image, return_status=False):
     valid = torch.empty(H * W, dtype=torch.bool, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _call(lib.goi_texture_resolve(nt, nn, F, H, W, _ptr(tri), _ptr(bary), _ptr(vt_c), _ptr(ft_c), _ptr(vn_c), _ptr(f_c), _ptr(rot),
-                                      _ptr(img), _ptr(coords), _ptr(values), _ptr(valid), _ptr(status), _stream(dev)))
+        check(lib.goi_texture_resolve(nt, nn, F, H, W, ptr(tri), ptr(bary), ptr(vt_c), ptr(ft_c), ptr(vn_c), ptr(f_c), ptr(rot),
+                                      ptr(img), ptr(coords), ptr(values), ptr(valid), ptr(status), stream(dev)))
     return (coords, values, valid, status[0]) if return_status else (coords, values, valid)
 
 
@@ -322,13 +304,13 @@ def _grid_put(fn, H, W, coords, values, valid, min_resolution, acc=None, norm=Fa
     result = torch.empty((H, W, Cn), dtype=torch.float32, device=dev)
     count = torch.empty((H, W, 1), dtype=torch.float32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.goi_texture_grid_put_workspace_bytes(N, Cn, H, W), dev)
+    ws = workspace(lib.goi_texture_grid_put_workspace_bytes(N, Cn, H, W), dev)
     a, ac = acc if acc is not None else (None, None)
     out = torch.empty_like(a) if norm else None
     mask = torch.empty((H, W), dtype=torch.bool, device=dev) if norm else None
     with torch.cuda.device(dev):
-        _call(lib.goi_texture_grid_put(N, Cn, H, W, mr, _ptr(co), _ptr(va), _ptr(valid), _ptr(result), _ptr(count), _ptr(a), _ptr(ac),
-                                       _ptr(out), _ptr(mask), _ptr(status), _ptr(ws), _stream(dev)))
+        check(lib.goi_texture_grid_put(N, Cn, H, W, mr, ptr(co), ptr(va), ptr(valid), ptr(result), ptr(count), ptr(a), ptr(ac),
+                                       ptr(out), ptr(mask), ptr(status), ptr(ws), stream(dev)))
     return (result, count, status[0], out, mask) if norm else (result, count, status[0])
 
 
@@ -369,7 +351,7 @@ def accumulate(albedo, cnt, cur_albedo, cur_cnt) -> None:
     dev = _on_device(fn, albedo, cnt, cur_albedo, cur_cnt)
     cur, cc = cur_albedo.detach().contiguous(), cur_cnt.detach().contiguous()
     with torch.cuda.device(dev):
-        _call(_lib.load().goi_texture_accumulate(h * w, Cn, _ptr(albedo), _ptr(cnt), _ptr(cur), _ptr(cc), _stream(dev)))
+        check(_lib.load().goi_texture_accumulate(h * w, Cn, ptr(albedo), ptr(cnt), ptr(cur), ptr(cc), stream(dev)))
 
 
 def normalize(albedo, cnt):
@@ -381,7 +363,7 @@ def normalize(albedo, cnt):
     out = torch.empty_like(a)
     mask = torch.empty((h, w), dtype=torch.bool, device=dev)
     with torch.cuda.device(dev):
-        _call(_lib.load().goi_texture_normalize(h * w, Cn, _ptr(a), _ptr(c), _ptr(out), _ptr(mask), _stream(dev)))
+        check(_lib.load().goi_texture_normalize(h * w, Cn, ptr(a), ptr(c), ptr(out), ptr(mask), stream(dev)))
     return out, mask
 
 
@@ -407,9 +389,9 @@ def fill(albedo, mask, radius=32, return_index=False):
     lib = _lib.load()
     out = torch.empty_like(a)
     nearest = torch.empty((h, w), dtype=torch.int32, device=dev)
-    ws = _workspace(lib.goi_texture_fill_workspace_bytes(h, w), dev)
+    ws = workspace(lib.goi_texture_fill_workspace_bytes(h, w), dev)
     with torch.cuda.device(dev):
-        _call(lib.goi_texture_fill(h, w, Cn, R, _ptr(a), _ptr(m), _ptr(out), _ptr(nearest), _ptr(ws), _stream(dev)))
+        check(lib.goi_texture_fill(h, w, Cn, R, ptr(a), ptr(m), ptr(out), ptr(nearest), ptr(ws), stream(dev)))
     return (out, nearest) if return_index else out
 
 

@@ -169,6 +169,29 @@ def test_removed_options_are_refused_and_change_nothing(lib, name, value, messag
         _lib.set_option("sort_variant", before.get("sort_variant", 1))
 
 
+def test_shared_binding_helpers(lib):
+    """_lib.check turns a negative return into RuntimeError (or the type asked for) with the library's message and passes
+    anything else through; _lib.ptr(None) is None; the allocation callback keeps its factory's exception on this side."""
+    from goi_hyperplane_amd import _lib
+    with pytest.raises(RuntimeError, match="unknown option no_such_option"):
+        _lib.check(lib.goi_raster_set_option(b"no_such_option", 1))
+    with pytest.raises(ValueError, match="unknown option no_such_option"):
+        _lib.check(lib.goi_raster_set_option(b"no_such_option", 1), ValueError)
+    assert _lib.check(0) == 0 and _lib.check(7) == 7
+    assert _lib.ptr(None) is None
+    x = torch.zeros(4)
+    assert _lib.ptr(x).value == x.data_ptr()
+
+    def refuse(nbytes):
+        raise MemoryError(f"no {nbytes} bytes")
+
+    alloc = _lib.TensorAlloc(refuse)
+    assert alloc.cb(None, 64) is None and alloc.tensor is None
+    assert isinstance(alloc.error, MemoryError) and "no 64 bytes" in str(alloc.error)
+    alloc = _lib.TensorAlloc(lambda nbytes: torch.empty(nbytes, dtype=torch.uint8))
+    assert alloc.cb(None, 64) == alloc.tensor.data_ptr() and alloc.tensor.numel() == 64 and alloc.error is None
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "goi_hyperplane_amd")
     offenders = []
