@@ -184,7 +184,13 @@ TEXTURE_SYMBOLS = {
     "goi_texture_fill_workspace_bytes": (C.c_size_t, [_I, _I]),
     "goi_texture_fill": (C.c_int, [_I, _I, _I, _I] + [_P] * 6),
 }
-SYMBOL_TABLES = (SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS)  # what load() binds
+# the goi_edit_* family (csrc/edit.hip: bounds of a selection, rigid transform in place)
+EDIT_SYMBOLS = {
+    "goi_edit_bounds_workspace_bytes": (C.c_size_t, [_LL]),
+    "goi_edit_bounds": (C.c_int, [_LL, _P, _P, _I, _P, _P, _P, _P]),
+    "goi_edit_transform": (C.c_int, [_LL, _I, _P, _I, _P] + [_P] * 9),
+}
+SYMBOL_TABLES = (SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)  # what load() binds
 
 _lib = None
 
@@ -280,6 +286,15 @@ class GoiDensifyRows(C.Structure):
 
 
 DENSIFY_MAX_GROUPS = 24
+
+
+class GoiEditTransform(C.Structure):
+    """include/goi_raster.h: GoiEditTransform"""
+    _fields_ = [("R", C.c_float * 9), ("q", C.c_float * 4), ("t", C.c_float * 3), ("pivot", C.c_float * 3), ("s", C.c_float),
+                ("log_s", C.c_float), ("flags", C.c_int), ("D1", C.c_float * 9), ("D2", C.c_float * 25), ("D3", C.c_float * 49)]
+
+
+EDIT_ROTATE, EDIT_SCALE = 1, 2  # GOI_EDIT_* of include/goi_raster.h
 
 
 OPTIONS = {}  # the switches set through set_option / GOI_OPTIONS in this process (name -> value)

@@ -50,6 +50,7 @@ UNITS = {
     "field.hip": ["-ffp-contract=off"],  # the iso-surface's vertices are one rounding per operation (the density loop names its FMAs)
     "mesh.hip": ["-ffp-contract=off"],  # null faces, cells, means and normals are compared bit for bit: one rounding per operation
     "texture.hip": ["-ffp-contract=off"],  # barycentrics, splat weights and upsampling are compared bit for bit: no FMA
+    "edit.hip": ["-ffp-contract=off"],  # the edit is compared bit for bit with its numpy restatement: one rounding per operation
 }
 
 

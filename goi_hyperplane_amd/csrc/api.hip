@@ -1480,6 +1480,48 @@ int goi_texture_fill(int h, int w, int C, int radius, const float* albedo, const
     return 0;
 }
 
+size_t goi_edit_bounds_workspace_bytes(long long P) {
+    return (P >= 0 && P < (1ll << 31)) ? edit_bounds_workspace_bytes(P) + 256 : 0;
+}
+
+int goi_edit_bounds(long long P, const float* xyz, const unsigned char* selection, int invert, int* count, float* out,
+                    void* workspace, void* stream) {
+    const char* fn = "goi_edit_bounds";
+    if (P < 0 || P >= (1ll << 31)) return fail(std::string(fn) + ": need 0 <= P < 2^31");
+    if (mesh_workspace(fn, workspace) < 0) return -1;
+    if (!count || !out || (P > 0 && !xyz)) return fail(std::string(fn) + ": a required pointer is NULL");
+    launch_edit_bounds(P, xyz, selection, invert, count, out, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_edit_transform(long long P, int M, const unsigned char* selection, int invert, const GoiEditTransform* t, float* xyz,
+                       float* rotation, float* scaling, float* features_rest, float* m_xyz, float* m_rotation,
+                       float* m_features_rest, const float* pivot_dev, void* stream) {
+    const char* fn = "goi_edit_transform";
+    if (P < 0 || P >= (1ll << 31)) return fail(std::string(fn) + ": need 0 <= P < 2^31");
+    if (M != 1 && M != 4 && M != 9 && M != 16) return fail(std::string(fn) + ": M must be 1, 4, 9 or 16");
+    if (!t) return fail(std::string(fn) + ": the transform is NULL");
+    if (t->flags & ~(GOI_EDIT_ROTATE | GOI_EDIT_SCALE)) return fail(std::string(fn) + ": unknown flag bits");
+    const bool rotate = (t->flags & GOI_EDIT_ROTATE) != 0, scale = (t->flags & GOI_EDIT_SCALE) != 0;
+    if (!rotate && (m_xyz || m_rotation || m_features_rest)) return fail(std::string(fn) + ": moments are only turned by a rotation");
+    if (M == 1 && m_features_rest) return fail(std::string(fn) + ": M = 1 has no features_rest moment");
+    if (P > 0 && (!xyz || (rotate && !rotation) || (scale && !scaling) || (rotate && M > 1 && !features_rest)))
+        return fail(std::string(fn) + ": a required pointer is NULL");
+    EditPointers p;
+    p.xyz = xyz;
+    p.rotation = rotation;
+    p.scaling = scaling;
+    p.rest = M > 1 ? features_rest : nullptr;
+    p.m_xyz = m_xyz;
+    p.m_rotation = m_rotation;
+    p.m_rest = m_features_rest;
+    p.pivot_dev = pivot_dev;
+    launch_edit_transform(P, M, selection, invert, *t, p, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
 static int uniq_dims(const char* fn, int n_views, int D, int H, int W) {
     if (n_views < 0 || D < 1 || H < 1 || W < 1) return fail(std::string(fn) + ": need n_views >= 0 and D, H, W >= 1");
     if ((long long)H * W >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need H * W < 2^30");

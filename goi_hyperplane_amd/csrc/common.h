@@ -425,6 +425,18 @@ void launch_densify_apply(long long P, const GoiDensifyRows* groups, int n_group
                           const float* z, long long n_split, long long kept_children, float split_inv, const DensifyView& v,
                           hipStream_t s);
 
+// rigid edits of a selection (edit.hip)
+struct EditPointers {
+    float *xyz, *rotation, *scaling, *rest;  // parameters (NULL: not written)
+    float *m_xyz, *m_rotation, *m_rest;      // Adam first moments (NULL: none)
+    const float* pivot_dev;                  // NULL: the pivot of the GoiEditTransform
+};
+size_t edit_bounds_workspace_bytes(long long P);
+void launch_edit_bounds(long long P, const float* xyz, const uint8_t* selection, int invert, int* count, float* out, void* ws,
+                        hipStream_t s);
+void launch_edit_transform(long long P, int M, const uint8_t* selection, int invert, const GoiEditTransform& t,
+                           const EditPointers& p, hipStream_t s);
+
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).
 __device__ __forceinline__ void tile_rect(float px, float py, int r, int gx, int gy, int& x0, int& y0, int& x1,
                                           int& y1) {

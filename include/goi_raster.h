@@ -57,7 +57,8 @@ extern "C" {
  *    goi_mesh_decimate_members, goi_mesh_decimate_probe, goi_mesh_decimate_plan, goi_mesh_decimate_emit,
  *    goi_mesh_normals_workspace_bytes, goi_mesh_normals; goi_texture_rasterize_workspace_bytes, goi_texture_rasterize,
  *    goi_texture_resolve, goi_texture_grid_put_workspace_bytes, goi_texture_grid_put, goi_texture_accumulate,
- *    goi_texture_normalize, goi_texture_fill_workspace_bytes, goi_texture_fill
+ *    goi_texture_normalize, goi_texture_fill_workspace_bytes, goi_texture_fill; goi_edit_bounds_workspace_bytes,
+ *    goi_edit_bounds, goi_edit_transform
  * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
  *    goi_raster_backward_scratch_bytes as ever);
@@ -1053,6 +1054,46 @@ int goi_texture_normalize(long long T, int C, const float* albedo, const float* 
 size_t goi_texture_fill_workspace_bytes(int h, int w);
 int goi_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
                      void* workspace, void* stream);
+
+/* ---- Rigid edits of a selection (csrc/edit.hip) -------------------------------------------------------------
+ * x' = p + t + s R (x - p) applied IN PLACE to the selected rows of a model: what gui/main_edit.py:1512-1548 (obj_move) does for a
+ * translation, extended by a rotation (covariances and SH bands 1..3 turn with the object) and a uniform scale.  Every pointer
+ * is a device pointer; every entry point runs on `stream`, returns 0 (or -1: goi_raster_last_error) and never reads the device
+ * back.  No float atomics: two calls give the same bits.  All float arithmetic is one fp32 rounding per operation, dot
+ * products in index order.  selection [P] bytes (non-zero selects; with `invert` a zero byte does) or NULL = every row.
+ *
+ * goi_edit_bounds: over the selected rows of xyz [P][3]: *count, and out[12] = lo[3] (+inf when empty), hi[3] (-inf), centroid[3]
+ *   (the float64 sum in a fixed order -- per-workgroup partials, then one fixed-order pass -- divided by the count and rounded
+ *   once; 0 when empty), center[3] = 0.5 lo + 0.5 hi (0 when empty).  workspace: goi_edit_bounds_workspace_bytes(P) bytes (0: P
+ *   out of range), 256-byte aligned.  0 <= P < 2^31.
+ * goi_edit_transform: per selected row
+ *     xyz       flags == 0: x + t (one add; R, s, pivot are not looked at).  Otherwise d = x - p, r_i = (R[i][0] d_0 + R[i][1] d_1)
+ *               + R[i][2] d_2, x' = (s r + p) + t; p = pivot_dev[0..2] when pivot_dev is not NULL, else t->pivot.
+ *     rotation  (raw (w, x, y, z), GOI_EDIT_ROTATE) q (x) r, the Hamilton product with q = t->q on the left, each component
+ *               summed left to right.
+ *     scaling   (raw log, GOI_EDIT_SCALE) + t->log_s.
+ *     features_rest [P][M-1][3], M in {1, 4, 9, 16} (GOI_EDIT_ROTATE): band l = 1..3 of every channel is multiplied by D1 [3][3],
+ *               D2 [5][5], D3 [7][7] (row-major): c'_i = sum_j D[i][j] c_j, j ascending.
+ *   m_xyz, m_rotation, m_features_rest (each may be NULL; only with GOI_EDIT_ROTATE): Adam first moments of the same shapes, which
+ *   get the linear part only: R m, q (x) m, D m.  A NULL parameter pointer is allowed where its flag is not set (and for
+ *   features_rest with M == 1).  One launch. */
+#define GOI_EDIT_ROTATE 1
+#define GOI_EDIT_SCALE 2
+typedef struct GoiEditTransform {
+    float R[9];      /* row-major rotation */
+    float q[4];      /* the same rotation as (w, x, y, z), unit */
+    float t[3];
+    float pivot[3];
+    float s, log_s;
+    int flags;       /* GOI_EDIT_* bits */
+    float D1[9], D2[25], D3[49];
+} GoiEditTransform;
+size_t goi_edit_bounds_workspace_bytes(long long P);
+int goi_edit_bounds(long long P, const float* xyz, const unsigned char* selection, int invert, int* count, float* out,
+                    void* workspace, void* stream);
+int goi_edit_transform(long long P, int M, const unsigned char* selection, int invert, const GoiEditTransform* t, float* xyz,
+                       float* rotation, float* scaling, float* features_rest, float* m_xyz, float* m_rotation,
+                       float* m_features_rest, const float* pivot_dev, void* stream);
 
 #ifdef __cplusplus
 }
