@@ -1,7 +1,7 @@
 """The hyperplane fine-tune without a GPU: the restated LinearSVM (step / eval_forward / hinge_loss / calculate_iou of
 networks.py:12-67 and utils/image_utils.py:59-70) replays the reference's own loop pinned in
-tests/golden/ref_osh_pins.npz, the float64 per-code form (tests/osh_reference.py) agrees with it, and the OSH entry
-points reject bad input."""
+tests/golden/ref_osh_pins.npz, the float64 per-code form (tests/osh_reference.py) agrees with it, the OSH entry
+points reject bad input, and every direct case of tests/test_gpu_osh_direct.py is far from every decision boundary."""
 from __future__ import annotations
 
 import os
@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.osh_reference import counts_of, fit_per_code, iou_flips
+from tests.osh_reference import (DIRECT_CASES, GUARD_FACTOR, KINK_B0, KINK_SHAPES, counts_of, direct_case, direct_tolerances,
+                                 fit_per_code, iou_flips, kink_case, kink_of, margin_error, reference_fits)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ("a", "b", "c", "d")
@@ -136,3 +137,71 @@ def test_osh_entry_points_reject_bad_input():
         fit_hyperplanes_counts(lut, torch.zeros(1, 2, 29, dtype=torch.int32), 15, w, b)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         fit_hyperplanes_counts(lut, counts, 15, w, b)
+
+
+# ---- the direct cases (tests/osh_reference.py: DIRECT_CASES) ---------------------------------------------------------------
+def test_direct_case_table_covers_the_kernel_shapes():
+    shapes = {(c["n_codes"], c["D"]): c["frac"] for c in DIRECT_CASES.values() if "counts" not in c}
+    want = {(1, 1): 1, (1, 256): 1, (5, 63): 1, (15, 256): 1, (16, 64): 1, (17, 65): 1, (40, 256): 0.3, (319, 256): 1,
+            (320, 256): 1, (321, 256): 1, (1000, 256): 0.31, (1000, 1024): 1, (1000, 1000): 0.5, (999, 33): 1, (640, 512): 1,
+            (37, 100): 1}
+    assert shapes == want
+    for (n, d) in want:
+        eps = {c["epochs"] for c in DIRECT_CASES.values() if (c["n_codes"], c["D"]) == (n, d)}
+        assert eps == ({1, 8, 64} if n <= 320 else {1, 8}), (n, d)
+    big = [c for c in DIRECT_CASES.values() if "counts" in c]
+    assert {c["epochs"] for c in big} == {1, 8, 64}
+    for c in big:
+        assert (c["n_codes"], c["D"], c["HW"]) == (3, 64, 2 ** 31 - 1) and int(np.sum(c["counts"])) == c["HW"]
+    assert all(c["HW"] == 4096 for c in DIRECT_CASES.values() if "counts" not in c)
+
+
+def test_direct_case_presence_is_interleaved():
+    """The sparse cases have absent codes between present ones, the compaction ends where the table says, and every
+    case's counts sum to HW."""
+    for name, m_max, m_min in (("40x256_e1", 15, 1), ("1000x256_e1", 400, 250), ("1000x1000_e1", 600, 400)):
+        case = direct_case(name)
+        present = case["counts"].sum(0) > 0
+        assert m_min <= present.sum() <= m_max, name
+        runs = int((np.diff(present.astype(int)) != 0).sum())  # boundaries between present and absent stretches
+        assert runs >= max(1, present.sum() // 4), name
+    for name in ("1000x1024_e1", "999x33_e1", "320x256_e1", "17x65_e1"):
+        assert (direct_case(name)["counts"].sum(0) > 0).all(), name
+    for name in DIRECT_CASES:
+        case = direct_case(name)
+        assert case["counts"].sum() == case["HW"] and case["counts"].min() >= 0, name
+
+
+@pytest.mark.parametrize("name", sorted(DIRECT_CASES))
+def test_direct_case_is_far_from_every_kink(name):
+    """The kink guard: the float64 fit's smallest distance of a margin to {-1, 0, 1} is at least 32 times the largest
+    margin error of the case's own fp32 restatement, which therefore shows no IoU flip -- and runs the stated epochs."""
+    case = direct_case(name)
+    r64, r32 = reference_fits(case)
+    assert r64["epochs"] == r32["epochs"] == case["epochs"]
+    assert r64["kink"] == kink_of(r64["margins"])
+    assert r64["kink"] >= GUARD_FACTOR * margin_error(r64, r32), (r64["kink"], margin_error(r64, r32))
+    assert iou_flips(r64["trace"][:, 1], r32["trace"][:, 1]) == 0
+    assert r64["init_iou"] == r32["init_iou"] and not np.isnan(r64["trace"][:, 1]).any()
+    tol = direct_tolerances(r64, r32)
+    assert all(0 < t < 1e-4 * s for t, s in ((tol["w"], np.abs(r64["w"]).max()), (tol["trace"], r64["trace"][:, 0].max())))
+
+
+@pytest.mark.parametrize("shape", KINK_SHAPES)
+@pytest.mark.parametrize("b0", KINK_B0)
+def test_kink_case_sits_on_the_kink_and_leaves_it(shape, b0):
+    """w0 = 0: every margin of the first pass is b0 exactly, in both precisions; the margins after the one step pass the
+    guard."""
+    case = kink_case(shape, b0)
+    r64, r32 = reference_fits(case)
+    assert (r64["margins"][0] == b0).all() and (r32["margins"][0] == b0).all()
+    assert kink_of(r64["margins"][1:]) >= GUARD_FACTOR * margin_error(r64, r32, first=1)
+    assert iou_flips(r64["trace"][:, 1], r32["trace"][:, 1]) == 0
+    P, N = case["counts"].astype(np.float64)
+    HW = case["HW"]
+    want_init = P.sum() / HW if b0 > 0 else 0.0        # everything predicted / nothing predicted (positives exist)
+    assert P.sum() > 0 and r64["init_iou"] == r32["init_iou"] == want_init
+    want_loss = {1.0: 2 * N.sum(), -1.0: 2 * P.sum(), 0.0: HW}[b0] / HW
+    assert r64["trace"][0, 0] == pytest.approx(want_loss, rel=1e-12)
+    # both hinges pass their gradient at the kink: b moves by -lr (N - P) / HW
+    assert r64["b"] == pytest.approx(b0 - 0.01 * (N.sum() - P.sum()) / HW, rel=1e-12)
