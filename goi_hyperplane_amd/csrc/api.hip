@@ -29,20 +29,19 @@ int fail(const std::string& msg) {
     return -1;
 }
 
+// The one refusal of a caller's workspace, for every entry: NULL, or not 256-byte aligned (the layouts carve from a 256-byte
+// aligned base: workspace.h).  `what` is the argument's name in the message.
+int check_workspace(const std::string& fn, const void* ws, const char* what = "workspace") {
+    if (!ws) return fail(fn + ": NULL " + what);
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(fn + ": " + what + " must be 256-byte aligned");
+    return 0;
+}
+
 #define GOI_HIP(call)                                       \
     do {                                                    \
         hipError_t e__ = (call);                            \
         if (e__ != hipSuccess) return fail(#call, e__);     \
     } while (0)
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-template <typename T>
-inline void carve(char*& p, T*& out, size_t count) {
-    p = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(p), 256));
-    out = reinterpret_cast<T*>(p);
-    p += count * sizeof(T);
-}
 
 // ---- per-stage timing -------------------------------------------------------------------------
 struct StageEvents {
@@ -125,8 +124,6 @@ int validate(const GoiRasterScene* sc, bool need_sem, bool need_opacity = true) 
         return fail("SH degree must be 0..3 and (D+1)^2 <= M <= 16");
     return 0;
 }
-
-static inline size_t round_up_256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ---- read-back tickets ---------------------------------------------------------------------------
 // num_rendered (and the "prefiltered" error flag) reach the host through a pinned copy of the frame's counters plus an
@@ -411,71 +408,74 @@ static int tile_sort_result_index(int W, int H, int N) {
     return passes & 1;
 }
 
+// The four raster layouts end on an unpadded last piece plus 256 bytes of slack, and tolerate a base that is not 256-byte
+// aligned (the carver rounds it up into that slack).
 size_t geom_layout(int P, char* base, GeomView* v) {
-    char* p = base;
+    Carver c(base);
     const size_t n = (size_t)(P > 0 ? P : 1);
-    GeomView tmp;
-    GeomView& g = v ? *v : tmp;
-    carve(p, g.rec, n);
-    carve(p, g.cov3D, 6 * n);
-    carve(p, g.tiles_touched, n);
-    carve(p, g.clamped, n);
-    carve(p, g.sort_keys[0], n);
-    carve(p, g.sort_keys[1], n);
-    carve(p, g.sort_vals[0], n);
-    carve(p, g.sort_vals[1], n);
+    GeomView g;
+    g.rec = c.take<GaussRec>(n);
+    g.cov3D = c.take<float>(6 * n);
+    g.tiles_touched = c.take<uint32_t>(n);
+    g.clamped = c.take<uint8_t>(n);
+    g.sort_keys[0] = c.take<uint32_t>(n);
+    g.sort_keys[1] = c.take<uint32_t>(n);
+    g.sort_vals[0] = c.take<uint32_t>(n);
+    g.sort_vals[1] = c.take<uint32_t>(n);
     g.bigq = g.sort_keys[1];  // (the raw depth keys are consumed by the compaction, the sort's result is in buffer 0)
-    carve(p, g.offsets, n);
-    carve(p, g.aux, n);
-    carve(p, g.blk_agg, (n + PRE_BLOCK - 1) / PRE_BLOCK);
+    g.offsets = c.take<uint32_t>(n);
+    g.aux = c.take<uint4>(n);
+    g.blk_agg = c.take<uint2>((n + PRE_BLOCK - 1) / PRE_BLOCK);
     // (blk_coarse, counters, sort control words: contiguous, ONE memset clears the three)
-    carve(p, g.blk_coarse, (((n + PRE_BLOCK - 1) / PRE_BLOCK + COARSE_BLOCKS - 1) / COARSE_BLOCKS) * (size_t)COARSE_STRIDE);
-    carve(p, g.counters, COUNTER_WORDS);  // directly in front of the sort scratch: one memset clears both
+    g.blk_coarse = c.take<unsigned long long>((((n + PRE_BLOCK - 1) / PRE_BLOCK + COARSE_BLOCKS - 1) / COARSE_BLOCKS) *
+                                              (size_t)COARSE_STRIDE);
+    g.counters = c.take<uint32_t>(COUNTER_WORDS);  // directly in front of the sort scratch: one memset clears both
     g.scratch_words = sort_scratch_words(n) + scan_scratch_words(n);
-    carve(p, g.scratch, g.scratch_words);
-    return (size_t)(p - base) + 256;
+    g.scratch = c.take<uint32_t>(g.scratch_words);
+    if (v) *v = g;
+    return c.end() + 256;
 }
 
 size_t image_layout(int W, int H, char* base, ImageView* v) {
-    char* p = base;
-    ImageView tmp;
-    ImageView& im = v ? *v : tmp;
+    Carver c(base);
+    ImageView im;
     const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    carve(p, im.n_contrib, (size_t)W * H);
-    carve(p, im.ranges, (size_t)gx * gy);
-    carve(p, im.qcost, (size_t)gx * gy * 4);
-    carve(p, im.qorder, (size_t)gx * gy * 4 + 8);
-    carve(p, im.qmask0, (size_t)gx * gy * 4);
-    return (size_t)(p - base) + 256;
+    im.n_contrib = c.take<uint32_t>((size_t)W * H);
+    im.ranges = c.take<uint2>((size_t)gx * gy);
+    im.qcost = c.take<uint32_t>((size_t)gx * gy * 4);
+    im.qorder = c.take<uint32_t>((size_t)gx * gy * 4 + 8);
+    im.qmask0 = c.take<unsigned long long>((size_t)gx * gy * 4);
+    if (v) *v = im;
+    return c.end() + 256;
 }
 
 size_t bwd_scratch_layout(int N, int S, char* base, BwdScratchView* v) {
-    char* p = base;
+    Carver c(base);
     const size_t n = (size_t)(N > 0 ? N : 1) * 4;
-    BwdScratchView tmp;
-    BwdScratchView& b = v ? *v : tmp;
-    carve(p, b.rows, n * (size_t)bwd_row_floats(S));
-    carve(p, b.flags, n);
+    BwdScratchView b;
+    b.rows = c.take<float>(n * (size_t)bwd_row_floats(S));
+    b.flags = c.take<uint8_t>(n);
     b.cap_big = reduce_cap_big(n / 4);
-    carve(p, b.big_ctl, 8);
-    carve(p, b.big_desc, b.cap_big);
-    carve(p, b.contrib, n / 4);  // (last: everything in front stays where it was)
-    return (size_t)(p - base) + 256;
+    b.big_ctl = c.take<uint32_t>(8);
+    b.big_desc = c.take<uint4>(b.cap_big);
+    b.contrib = c.take<uint8_t>(n / 4);  // (last: everything in front stays where it was)
+    if (v) *v = b;
+    return c.end() + 256;
 }
 
 size_t binning_layout(int N, char* base, BinView* v) {
-    char* p = base;
+    Carver c(base);
     const size_t n = (size_t)(N > 0 ? N : 1);
-    BinView tmp;
-    BinView& b = v ? *v : tmp;
-    carve(p, b.keys[0], n);
-    carve(p, b.keys[1], n);
-    carve(p, b.vals[0], n);
-    carve(p, b.vals[1], n);
+    BinView b;
+    b.keys[0] = c.take<uint32_t>(n);
+    b.keys[1] = c.take<uint32_t>(n);
+    b.vals[0] = c.take<uint32_t>(n);
+    b.vals[1] = c.take<uint32_t>(n);
     b.scratch_words = sort_scratch_words(n) + 8;
-    carve(p, b.scratch, b.scratch_words);
-    carve(p, b.qmask, 4 * (n / 64 + 2));
-    return (size_t)(p - base) + 256;
+    b.scratch = c.take<uint32_t>(b.scratch_words);
+    b.qmask = c.take<unsigned long long>(4 * (n / 64 + 2));
+    if (v) *v = b;
+    return c.end() + 256;
 }
 
 namespace {
@@ -546,8 +546,9 @@ size_t goi_raster_binning_bytes(int N) { return binning_layout(N, nullptr, nullp
 size_t goi_raster_backward_scratch_bytes(int N, int S) { return bwd_scratch_layout(N, S, nullptr, nullptr) + 256; }
 size_t goi_raster_debug_backward_contrib_offset(int N, int S) {
     BwdScratchView v;
-    bwd_scratch_layout(N, S, nullptr, &v);
-    return reinterpret_cast<size_t>(v.contrib);  // (laid out from base 0: the offset in a 256-byte aligned scratch)
+    char* const base = reinterpret_cast<char*>(256);  // (never dereferenced: the carver hands out no pointers from NULL)
+    bwd_scratch_layout(N, S, base, &v);
+    return (size_t)(reinterpret_cast<char*>(v.contrib) - base);  // the offset in a 256-byte aligned scratch
 }
 
 // keep (or NULL) / invert: the per-Gaussian selection of the _selected entry points -- the plain ones pass NULL
@@ -1015,8 +1016,8 @@ int goi_semantic_dbscan(long long n, const float* points, float eps, int min_sam
     const hipStream_t s = static_cast<hipStream_t>(stream);
     GOI_HIP(hipMemsetAsync(result, 0, 2 * sizeof(int), s));
     if (n == 0) return 0;
-    if (!points || !labels || !workspace) return fail("goi_semantic_dbscan: a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("goi_semantic_dbscan: workspace must be 256-byte aligned");
+    if (!points || !labels) return fail("goi_semantic_dbscan: a required pointer is NULL");
+    if (check_workspace("goi_semantic_dbscan", workspace) < 0) return -1;
     if (!(eps >= 0x1p-40f && eps <= 0x1p40f)) {  // outside the range of the grid's exactness argument (csrc/dbscan.hip)
         GOI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(result + 1), DBSCAN_FLAG_RANGE, 1, s));
         return 0;
@@ -1123,8 +1124,8 @@ int goi_semantic_pca_accumulate(const float* x, int layout, int S, long long n, 
     const char* fn = "goi_semantic_pca_accumulate";
     if (pca_dims(fn, S, n) < 0) return -1;
     if (layout != GOI_PCA_PLANAR && layout != GOI_PCA_ROWS) return fail(std::string(fn) + ": layout must be GOI_PCA_PLANAR or GOI_PCA_ROWS");
-    if (!x || !workspace) return fail(std::string(fn) + ": NULL x or workspace");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": the workspace must be 256-byte aligned");
+    if (!x) return fail(std::string(fn) + ": NULL x");
+    if (check_workspace(fn, workspace) < 0) return -1;
     if (reinterpret_cast<uintptr_t>(x) & 3) return fail(std::string(fn) + ": x must be 4-byte aligned");
     launch_pca_accumulate(x, layout, S, n, mask, first ? 1 : 0, workspace, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1134,8 +1135,8 @@ int goi_semantic_pca_accumulate(const float* x, int layout, int S, long long n, 
 int goi_semantic_pca_solve(int S, void* workspace, float* basis, void* stream) {
     const char* fn = "goi_semantic_pca_solve";
     if (pca_dims(fn, S, 1) < 0) return -1;
-    if (!workspace || !basis) return fail(std::string(fn) + ": NULL workspace or basis");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": the workspace must be 256-byte aligned");
+    if (!basis) return fail(std::string(fn) + ": NULL basis");
+    if (check_workspace(fn, workspace) < 0) return -1;
     launch_pca_solve(S, workspace, basis, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
     return 0;
@@ -1204,8 +1205,8 @@ int goi_field_density(long long P, const float* xyz, const float* opacity, const
         }
         return 0;
     }
-    if (!xyz || !opacity || !scaling || !rotation || !workspace) return fail(std::string(fn) + ": a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": the workspace must be 256-byte aligned");
+    if (!xyz || !opacity || !scaling || !rotation) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
     launch_field_density(P, xyz, opacity, scaling, rotation, selection, selection_invert ? 1 : 0, (float)min_opacity, attributes,
                          bounds, resolution, num_blocks, relax_ratio, coords, block_lo, block_hi, occ, attr_out, frame, status,
                          workspace, s);
@@ -1230,8 +1231,8 @@ int goi_field_iso_count(const float* grid, int X, int Y, int Z, double thresh, v
     const char* fn = "goi_field_iso_count";
     if (iso_dims(fn, X, Y, Z) < 0) return -1;
     if (!(thresh == thresh)) return fail(std::string(fn) + ": NaN thresh");
-    if (!grid || !workspace || !counts) return fail(std::string(fn) + ": NULL grid, workspace or counts");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": the workspace must be 256-byte aligned");
+    if (!grid || !counts) return fail(std::string(fn) + ": NULL grid or counts");
+    if (check_workspace(fn, workspace) < 0) return -1;
     launch_field_iso_count(grid, X, Y, Z, (float)thresh, workspace, counts, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
     return 0;
@@ -1245,10 +1246,10 @@ int goi_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z
     if (!(thresh == thresh)) return fail(std::string(fn) + ": NaN thresh");
     if (n_vertices < 0 || n_faces < 0 || n_vertices >= (1ll << 31) || n_faces >= (1ll << 31))
         return fail(std::string(fn) + ": need 0 <= n_vertices, n_faces < 2^31");
-    if (!grid || !workspace) return fail(std::string(fn) + ": NULL grid or workspace");
+    if (!grid) return fail(std::string(fn) + ": NULL grid");
     if ((n_vertices > 0 && !vertices) || (n_faces > 0 && !faces)) return fail(std::string(fn) + ": NULL vertices or faces");
     if (attr && n_vertices > 0 && !colors) return fail(std::string(fn) + ": attr needs colors");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": the workspace must be 256-byte aligned");
+    if (check_workspace(fn, workspace) < 0) return -1;
     launch_field_iso_emit(grid, attr, X, Y, Z, (float)thresh, cx, cy, cz, workspace, n_vertices, n_faces, vertices, faces, colors,
                           static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1264,11 +1265,6 @@ static int mesh_sizes(const char* fn, long long V, long long F, long long min_ea
         return fail(std::string(fn) + ": need " + std::to_string(min_each) + " <= V, F and V, 3 F < 2^30");
     return 0;
 }
-static int mesh_workspace(const char* fn, const void* workspace) {
-    if (!workspace) return fail(std::string(fn) + ": NULL workspace");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": the workspace must be 256-byte aligned");
-    return 0;
-}
 
 size_t goi_mesh_components_workspace_bytes(long long V, long long F) {
     return mesh_sizes_ok(V, F, 0) ? mesh_components_workspace_bytes(V, F) : 0;
@@ -1277,7 +1273,7 @@ size_t goi_mesh_components_workspace_bytes(long long V, long long F) {
 int goi_mesh_components(long long V, long long F, const int* faces, int* vertex_label, int* face_label, int* status,
                         void* workspace, void* stream) {
     const char* fn = "goi_mesh_components";
-    if (mesh_sizes(fn, V, F, 0) < 0 || mesh_workspace(fn, workspace) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 0) < 0 || check_workspace(fn, workspace) < 0) return -1;
     if (!status || (V > 0 && !vertex_label) || (F > 0 && (!faces || !face_label)))
         return fail(std::string(fn) + ": a required pointer is NULL");
     launch_mesh_components(V, F, faces, vertex_label, face_label, status, workspace, static_cast<hipStream_t>(stream));
@@ -1292,7 +1288,7 @@ size_t goi_mesh_clean_workspace_bytes(long long V, long long F) {
 int goi_mesh_clean_plan(long long V, long long F, const float* vertices, const int* faces, long long min_faces, double min_diag2,
                         void* workspace, int* counts, void* stream) {
     const char* fn = "goi_mesh_clean_plan";
-    if (mesh_sizes(fn, V, F, 1) < 0 || mesh_workspace(fn, workspace) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
     if (!vertices || !faces || !counts) return fail(std::string(fn) + ": NULL vertices, faces or counts");
     if (!(min_diag2 >= 0.0)) return fail(std::string(fn) + ": need min_diag2 >= 0");
     launch_mesh_clean_plan(V, F, vertices, faces, min_faces, min_diag2, workspace, counts, static_cast<hipStream_t>(stream));
@@ -1304,7 +1300,7 @@ int goi_mesh_clean_emit(long long V, long long F, const float* vertices, const i
                         const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
                         float* out_colors, int* vertex_index, int* face_index, void* stream) {
     const char* fn = "goi_mesh_clean_emit";
-    if (mesh_sizes(fn, V, F, 1) < 0 || mesh_workspace(fn, workspace) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
     if (n_vertices < 0 || n_vertices > V || n_faces < 0 || n_faces > F) return fail(std::string(fn) + ": counts out of range");
     if (!vertices || !faces) return fail(std::string(fn) + ": NULL vertices or faces");
     if ((n_vertices > 0 && (!out_vertices || !vertex_index)) || (n_faces > 0 && (!out_faces || !face_index)))
@@ -1322,7 +1318,7 @@ size_t goi_mesh_decimate_workspace_bytes(long long V, long long F) {
 
 int goi_mesh_decimate_members(long long V, long long F, const float* vertices, const int* faces, void* workspace, void* stream) {
     const char* fn = "goi_mesh_decimate_members";
-    if (mesh_sizes(fn, V, F, 1) < 0 || mesh_workspace(fn, workspace) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
     if (!vertices || !faces) return fail(std::string(fn) + ": NULL vertices or faces");
     launch_mesh_decimate_members(V, F, vertices, faces, workspace, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1337,7 +1333,7 @@ static int mesh_divisions(const char* fn, int divisions) {
 int goi_mesh_decimate_probe(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
                             int* count, void* stream) {
     const char* fn = "goi_mesh_decimate_probe";
-    if (mesh_sizes(fn, V, F, 1) < 0 || mesh_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
     if (!vertices || !faces || !count) return fail(std::string(fn) + ": NULL vertices, faces or count");
     launch_mesh_decimate_probe(V, F, vertices, faces, divisions, workspace, count, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1347,7 +1343,7 @@ int goi_mesh_decimate_probe(long long V, long long F, const float* vertices, con
 int goi_mesh_decimate_plan(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
                            int* counts, void* stream) {
     const char* fn = "goi_mesh_decimate_plan";
-    if (mesh_sizes(fn, V, F, 1) < 0 || mesh_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
     if (!vertices || !faces || !counts) return fail(std::string(fn) + ": NULL vertices, faces or counts");
     const int fin = launch_mesh_decimate_plan(V, F, vertices, faces, divisions, workspace, counts, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1358,7 +1354,7 @@ int goi_mesh_decimate_emit(long long V, long long F, const float* vertices, cons
                            const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
                            float* out_colors, int* cluster, void* stream) {
     const char* fn = "goi_mesh_decimate_emit";
-    if (mesh_sizes(fn, V, F, 1) < 0 || mesh_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
     if (sorted_in != 0 && sorted_in != 1) return fail(std::string(fn) + ": sorted_in must be what goi_mesh_decimate_plan returned");
     if (n_vertices < 0 || n_vertices > V || n_faces < 0 || n_faces > F) return fail(std::string(fn) + ": counts out of range");
     if (!vertices || !cluster) return fail(std::string(fn) + ": NULL vertices or cluster");
@@ -1377,7 +1373,7 @@ size_t goi_mesh_normals_workspace_bytes(long long V, long long F) {
 int goi_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
                      void* workspace, void* stream) {
     const char* fn = "goi_mesh_normals";
-    if (mesh_sizes(fn, V, F, 0) < 0 || mesh_workspace(fn, workspace) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 0) < 0 || check_workspace(fn, workspace) < 0) return -1;
     if (!status || (V > 0 && (!vertices || !normals)) || (F > 0 && !faces)) return fail(std::string(fn) + ": a required pointer is NULL");
     launch_mesh_normals(V, F, vertices, faces, normals, status, workspace, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1401,7 +1397,7 @@ size_t goi_texture_rasterize_workspace_bytes(long long F, int H, int W) {
 int goi_texture_rasterize(long long V, long long F, const float* v_clip, const int* faces, int H, int W, int* tri, float* bary,
                           float* zw, int* status, void* workspace, void* stream) {
     const char* fn = "goi_texture_rasterize";
-    if (mesh_sizes(fn, V, F, 0) < 0 || texture_size(fn, H, W) < 0 || mesh_workspace(fn, workspace) < 0) return -1;
+    if (mesh_sizes(fn, V, F, 0) < 0 || texture_size(fn, H, W) < 0 || check_workspace(fn, workspace) < 0) return -1;
     if (!status || !tri || !bary || !zw || (F > 0 && (!faces || !v_clip))) return fail(std::string(fn) + ": a required pointer is NULL");
     launch_texture_rasterize(V, F, v_clip, faces, H, W, tri, bary, zw, status, workspace, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1431,7 +1427,7 @@ int goi_texture_grid_put(long long N, int C, int H, int W, int min_resolution, c
     const char* fn = "goi_texture_grid_put";
     if (!texture_put_ok(N, C, H, W)) return fail(std::string(fn) + ": need 0 <= N < 2^28, 1 <= C <= 4 and 1 <= H, W <= 16384");
     if (min_resolution < 1) return fail(std::string(fn) + ": need min_resolution >= 1");
-    if (mesh_workspace(fn, workspace) < 0) return -1;
+    if (check_workspace(fn, workspace) < 0) return -1;
     if (!status || !result || !count || (N > 0 && (!coords || !values))) return fail(std::string(fn) + ": a required pointer is NULL");
     if ((acc == nullptr) != (acc_count == nullptr)) return fail(std::string(fn) + ": give both of acc and acc_count, or neither");
     if ((norm_out == nullptr) != (norm_mask == nullptr) || (norm_out && !acc))
@@ -1472,7 +1468,7 @@ size_t goi_texture_fill_workspace_bytes(int h, int w) { return texture_size_ok(h
 int goi_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
                      void* workspace, void* stream) {
     const char* fn = "goi_texture_fill";
-    if (texture_size(fn, h, w) < 0 || texture_texels(fn, 0, C) < 0 || mesh_workspace(fn, workspace) < 0) return -1;
+    if (texture_size(fn, h, w) < 0 || texture_texels(fn, 0, C) < 0 || check_workspace(fn, workspace) < 0) return -1;
     if (radius < 0 || radius > GOI_TEXTURE_MAX_RADIUS) return fail(std::string(fn) + ": need 0 <= radius <= 127");
     if (!albedo || !mask || !out || !nearest) return fail(std::string(fn) + ": a required pointer is NULL");
     launch_texture_fill(h, w, C, radius, albedo, mask, out, nearest, workspace, static_cast<hipStream_t>(stream));
@@ -1488,7 +1484,7 @@ int goi_edit_bounds(long long P, const float* xyz, const unsigned char* selectio
                     void* workspace, void* stream) {
     const char* fn = "goi_edit_bounds";
     if (P < 0 || P >= (1ll << 31)) return fail(std::string(fn) + ": need 0 <= P < 2^31");
-    if (mesh_workspace(fn, workspace) < 0) return -1;
+    if (check_workspace(fn, workspace) < 0) return -1;
     if (!count || !out || (P > 0 && !xyz)) return fail(std::string(fn) + ": a required pointer is NULL");
     launch_edit_bounds(P, xyz, selection, invert, count, out, workspace, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1538,12 +1534,12 @@ int goi_codebook_unique_rows(const float* const* maps, int n_views, int D, int H
     refresh_options();
     const char* fn = "goi_codebook_unique_rows";
     if (uniq_dims(fn, n_views, D, H, W) < 0) return -1;
-    if (!flags || (n_views > 0 && (!maps || !counts || !alloc || !workspace))) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (!flags || (n_views > 0 && (!maps || !counts || !alloc))) return fail(std::string(fn) + ": a required pointer is NULL");
     *flags = 0;
     if (n_views == 0) return 0;
     for (int v = 0; v < n_views; ++v)
         if (!maps[v]) return fail(std::string(fn) + ": maps[" + std::to_string(v) + "] is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": workspace must be 256-byte aligned");
+    if (check_workspace(fn, workspace) < 0) return -1;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const uint32_t HW = (uint32_t)((long long)H * W);
     launch_uniq_dedup(maps, n_views, D, HW, workspace, s);
@@ -1588,8 +1584,8 @@ int goi_codebook_kmeans(float* x, const long long* row_offsets, int n_problems, 
     if (n_rows < 0 || n_rows >= (1ll << 31) || max_rows < 1 || max_rows > n_rows)
         return fail(std::string(fn) + ": need 1 <= max_rows <= n_rows < 2^31");
     if (n_problems == 0) return 0;
-    if (!x || !row_offsets || !perms || !centers || !status || !workspace) return fail(std::string(fn) + ": a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": workspace must be 256-byte aligned");
+    if (!x || !row_offsets || !perms || !centers || !status) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
     launch_kmeans(x, row_offsets, n_problems, max_rows, n_rows, D, ncluster, niter, perms, centers, status, workspace,
                   static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1617,8 +1613,8 @@ int goi_raster_photometric_forward(const float* img1, const float* img2, long lo
     const std::string fn = "goi_raster_photometric_forward: ";
     const std::string bad = photometric_check(n, c, h, w, window_size);
     if (!bad.empty()) return fail(fn + bad);
-    if (!img1 || !img2 || !out || !workspace) return fail(fn + "a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    if (!img1 || !img2 || !out) return fail(fn + "a required pointer is NULL");
+    if (check_workspace("goi_raster_photometric_forward", workspace) < 0) return -1;
     launch_photometric_forward(img1, img2, n, c, h, w, lambda_dssim, flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2), out,
                                out_images, workspace, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1632,10 +1628,9 @@ int goi_raster_photometric_backward(const float* img1, const float* img2, long l
     const std::string bad = photometric_check(n, c, h, w, window_size);
     if (!bad.empty()) return fail(fn + bad);
     if (!(flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2))) return fail(fn + "no gradient asked for");
-    if (!img1 || !img2 || !grad_out || !workspace || ((flags & GOI_PHOTOMETRIC_GRAD1) && !grad1) ||
-        ((flags & GOI_PHOTOMETRIC_GRAD2) && !grad2))
+    if (!img1 || !img2 || !grad_out || ((flags & GOI_PHOTOMETRIC_GRAD1) && !grad1) || ((flags & GOI_PHOTOMETRIC_GRAD2) && !grad2))
         return fail(fn + "a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    if (check_workspace("goi_raster_photometric_backward", workspace) < 0) return -1;
     launch_photometric_backward(img1, img2, n, c, h, w, lambda_dssim, flags, grad_out, workspace, grad1, grad2,
                                 static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
@@ -1662,8 +1657,8 @@ int goi_raster_densify_plan(long long P, const float* accum, const float* denom,
                             double big_threshold, unsigned* counts, void* workspace, void* stream) {
     const std::string fn = "goi_raster_densify_plan: ";
     if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
-    if (!counts || !workspace || (P > 0 && (!accum || !denom || !scaling || !opacity))) return fail(fn + "a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    if (!counts || (P > 0 && (!accum || !denom || !scaling || !opacity))) return fail(fn + "a required pointer is NULL");
+    if (check_workspace("goi_raster_densify_plan", workspace) < 0) return -1;
     refresh_options();
     DensifyView v;
     densify_layout(P, static_cast<char*>(workspace), &v);
@@ -1683,8 +1678,8 @@ int goi_raster_densify_plan(long long P, const float* accum, const float* denom,
 int goi_raster_densify_prune_plan(long long P, const unsigned char* mask, unsigned* counts, void* workspace, void* stream) {
     const std::string fn = "goi_raster_densify_prune_plan: ";
     if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
-    if (!counts || !workspace || (P > 0 && !mask)) return fail(fn + "a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + "workspace must be 256-byte aligned");
+    if (!counts || (P > 0 && !mask)) return fail(fn + "a required pointer is NULL");
+    if (check_workspace("goi_raster_densify_prune_plan", workspace) < 0) return -1;
     refresh_options();
     DensifyView v;
     densify_layout(P, static_cast<char*>(workspace), &v);
@@ -1700,7 +1695,7 @@ int goi_raster_densify_apply(long long P, const GoiDensifyRows* groups, int n_gr
     if (n_groups < 0 || n_groups > GOI_DENSIFY_MAX_GROUPS) return fail(fn + "n_groups must be 0..24");
     if (n_groups && !groups) return fail(fn + "groups is NULL");
     if (n_split < 0 || n_split > P || kept_children < 0 || kept_children > n_split) return fail(fn + "bad n_split / kept_children");
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255)) return fail(fn + "workspace must be a 256-byte aligned pointer");
+    if (check_workspace("goi_raster_densify_apply", workspace) < 0) return -1;
     for (int k = 0; k < n_groups; k++) {
         const GoiDensifyRows& g = groups[k];
         if (g.row_len < 1 || g.rows < 0 || g.mode < GOI_DENSIFY_PARAM || g.mode > GOI_DENSIFY_ZERO) return fail(fn + "bad group");
@@ -1760,8 +1755,8 @@ int goi_codebook_fused_partial_rows(void) { return codebook_fused_rows(); }
 int goi_codebook_fused(const float* g, const float* lut1, const float* sem, const float* W, const float* bias, long long HW,
                        int C, int D, int S, float t, float* dsem, float* partials, float* dlut_partial, void* workspace,
                        void* stream) {
-    if (!g || !lut1 || !sem || !W || !dsem || !partials || !dlut_partial || !workspace)
-        return fail("goi_codebook_fused: a required pointer is NULL");
+    if (!g || !lut1 || !sem || !W || !dsem || !partials || !dlut_partial) return fail("goi_codebook_fused: a required pointer is NULL");
+    if (check_workspace("goi_codebook_fused", workspace) < 0) return -1;  // (its layout carves from a 256-byte aligned base)
     if (launch_codebook_fused(g, lut1, sem, W, bias, HW, C, D, S, t, dsem, partials, dlut_partial, workspace,
                               static_cast<hipStream_t>(stream)) < 0)
         return fail("goi_codebook_fused: supported shape is D = 256, 288 < C <= 304, 1 <= S <= 16, HW % 4 = 0, HW < 2^25");
@@ -1814,8 +1809,8 @@ int goi_knn_dist2(int P, const float* points, float* mean_dist2, void* workspace
     // (the Morton codes go through radix_sort_pairs, exact below 2^30 keys: common.h)
     if (P >= SORT_MAX_KEYS) return fail("goi_knn_dist2: need P < 2^30");
     if (P == 0) return 0;
-    if (!points || !mean_dist2 || !workspace) return fail("goi_knn_dist2: a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("goi_knn_dist2: workspace must be 256-byte aligned");
+    if (!points || !mean_dist2) return fail("goi_knn_dist2: a required pointer is NULL");
+    if (check_workspace("goi_knn_dist2", workspace) < 0) return -1;
     launch_knn(P, points, mean_dist2, workspace, static_cast<hipStream_t>(stream));
     GOI_HIP(hipGetLastError());
     return 0;
@@ -1950,8 +1945,8 @@ int goi_raster_debug_sort_pairs(uint32_t* keys0, uint32_t* vals0, uint32_t* keys
     const bool onesweep = g_options.sort_variant == 1;
     if ((n_dev || ghist) && !onesweep) return fail(std::string(fn) + ": n_dev and ghist need the onesweep sort (sort_variant 1)");
     if (n == 0) return 0;
-    if (!keys0 || !vals0 || !keys1 || !vals1 || !workspace) return fail(std::string(fn) + ": a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(std::string(fn) + ": workspace must be 256-byte aligned");
+    if (!keys0 || !vals0 || !keys1 || !vals1) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     uint32_t* scratch = static_cast<uint32_t*>(workspace);
     bool cleared = (flags & 1) != 0;
@@ -1990,16 +1985,15 @@ int goi_raster_debug_exclusive_scan(const uint32_t* in, const uint32_t* gather, 
 // The row reduction's workspace: a counter block (the frame words at COUNTER_N / COUNTER_V / COUNTER_OVF, where the launchers
 // read them), big_ctl, big_desc[cap_big] -- the tail of bwd_scratch_layout, with cap_big from the same helper.
 static size_t debug_reduce_layout(long long n_cap, char* base, uint32_t** counters, BwdScratchView* v) {
-    char* p = base;
-    uint32_t* c;
-    carve(p, c, 64);
+    Carver c(base);
+    uint32_t* words = c.take<uint32_t>(64);
     BwdScratchView tmp;
-    BwdScratchView& b = v ? *v : tmp;
+    BwdScratchView& b = v ? *v : tmp;  // (the caller's view keeps its other fields)
     b.cap_big = reduce_cap_big((size_t)n_cap);
-    carve(p, b.big_ctl, 8);
-    carve(p, b.big_desc, b.cap_big);
-    if (counters) *counters = c;
-    return (size_t)(p - base);
+    b.big_ctl = c.take<uint32_t>(8);
+    b.big_desc = c.take<uint4>(b.cap_big);
+    if (counters) *counters = words;
+    return c.end();
 }
 
 int goi_raster_debug_reduce_row_floats(int mode, int S) {
@@ -2026,10 +2020,10 @@ int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const 
     if (P < 0 || n_cap < 0 || n_cap > INT_MAX) return fail(fn + ": need P >= 0 and 0 <= n_cap < 2^31");
     if (P == 0) return 0;
     const bool arrays = mode == 0, per_id = mode == 0 || mode == 3;
-    if (!frame || !order || !offsets || !rows || !flags || !workspace || (per_id && (!tiles_touched || !dL_dsemantic)) ||
+    if (!frame || !order || !offsets || !rows || !flags || (per_id && (!tiles_touched || !dL_dsemantic)) ||
         (arrays && (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_ddepth)))
         return fail(fn + ": a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + ": workspace must be 256-byte aligned");
+    if (check_workspace(fn, workspace) < 0) return -1;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     GoiRasterScene sc{};
     sc.P = P;
@@ -2095,14 +2089,14 @@ int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source
     if (accumulate && source != 1) return fail(fn + ": accumulate needs source 1 (the records)");
     if (accumulate && prev_radii) return fail(fn + ": accumulate with prev_radii");
     if (accumulate && sc.shs && !dL_dsh) return fail(fn + ": accumulate with factored SH (dL_dsh NULL)");
-    if (!frame || !radii || !workspace || !dL_dmean2D || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
+    if (!frame || !radii || !dL_dmean2D || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
         (sc.shs && !clamped))
         return fail(fn + ": a required pointer is NULL");
     if (source == 0 && (!dL_dconic || !dL_ddepth)) return fail(fn + ": source 0 reads dL_dconic and dL_ddepth");
     if (source != 0 && (!aux || !tiles_touched || !rows || !dL_dopacity || !dL_dsemantic))
         return fail(fn + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic");
     if (source == 2 && !row_flags) return fail(fn + ": source 2 needs the validity bytes");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(fn + ": workspace must be 256-byte aligned");
+    if (check_workspace(fn, workspace) < 0) return -1;
     if ((reinterpret_cast<uintptr_t>(dL_drot) & 15u) || (aux && (reinterpret_cast<uintptr_t>(aux) & 15u)) ||
         (rows && (reinterpret_cast<uintptr_t>(rows) & 15u)) || (row_flags && (reinterpret_cast<uintptr_t>(row_flags) & 3u)) ||
         (dL_dsemantic && (reinterpret_cast<uintptr_t>(dL_dsemantic) & 15u)))
@@ -2139,8 +2133,8 @@ int goi_raster_debug_pair_eval(int P, int W, int H, const void* geom_buffer, con
     if (P <= 0 || W <= 0 || H <= 0) return fail(fn + ": bad P/W/H");
     if (n_requests < 0 || n_requests > (1ll << 31)) return fail(fn + ": need 0 <= n_requests <= 2^31");
     if (n_requests == 0) return 0;
-    if (!geom_buffer || !requests || !E || !alpha || !guards) return fail(fn + ": a required pointer is NULL");
-    if (reinterpret_cast<uintptr_t>(geom_buffer) & 255) return fail(fn + ": geom_buffer must be 256-byte aligned");
+    if (!requests || !E || !alpha || !guards) return fail(fn + ": a required pointer is NULL");
+    if (check_workspace(fn, geom_buffer, "geom_buffer") < 0) return -1;
     if (reinterpret_cast<uintptr_t>(requests) & 7u) return fail(fn + ": requests must be 8-byte aligned");
     if ((reinterpret_cast<uintptr_t>(E) & 3u) || (reinterpret_cast<uintptr_t>(alpha) & 3u))
         return fail(fn + ": E and alpha must be 4-byte aligned");
@@ -2171,9 +2165,9 @@ int goi_raster_debug_backward_blend(const GoiRasterScene* scene, int R, int mode
     if ((sc.S & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.semantics) & 15u) != 0)
         return fail(fn + ": semantics must be 16-byte aligned when S is a multiple of 4");
     if (!geom_buffer || !binning_buffer || !image_buffer) return fail(fn + ": workspace pointer is NULL");
-    if ((reinterpret_cast<uintptr_t>(geom_buffer) & 255) || (reinterpret_cast<uintptr_t>(binning_buffer) & 255) ||
-        (reinterpret_cast<uintptr_t>(image_buffer) & 255))
-        return fail(fn + ": the workspaces must be 256-byte aligned");
+    if (check_workspace(fn, geom_buffer, "geom_buffer") < 0 || check_workspace(fn, binning_buffer, "binning_buffer") < 0 ||
+        check_workspace(fn, image_buffer, "image_buffer") < 0)
+        return -1;
     if (!radii || !out_alpha) return fail(fn + ": radii and out_alpha are required");
     if (sem && !dL_dout_semantic) return fail(fn + ": the semantic rows need dL_dout_semantic");
     if (tile) {
@@ -2181,7 +2175,7 @@ int goi_raster_debug_backward_blend(const GoiRasterScene* scene, int R, int mode
             return fail(fn + ": mode 8 writes the six per-id arrays");
     } else {
         if (!scratch) return fail(fn + ": modes 0..7 need the scratch of goi_raster_backward_scratch_bytes");
-        if (reinterpret_cast<uintptr_t>(scratch) & 255) return fail(fn + ": scratch must be 256-byte aligned");
+        if (check_workspace(fn, scratch, "scratch") < 0) return -1;
         if (!rows || !row_flags) return fail(fn + ": modes 0..7 copy out rows and row_flags");
         if (reinterpret_cast<uintptr_t>(rows) & 15u) return fail(fn + ": rows must be 16-byte aligned");
     }

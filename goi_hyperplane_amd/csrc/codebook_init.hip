@@ -46,7 +46,6 @@ constexpr uint64_t SLOT_EMPTY = ~0ull;
 constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
 constexpr int RANK_TILE_WORDS = 8192;  // uniq_rank_k's LDS tile (32 KiB); wider rows take the radix path
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 inline size_t div_up_sz(size_t a, size_t b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ uint32_t order_key(float f) {
@@ -214,7 +213,8 @@ __global__ void __launch_bounds__(UNIQ_THREADS) uniq_write_k(const float* __rest
 struct UniqLayout {
     uint32_t tbits;
     unsigned long long* table;
-    uint32_t *slot_of, *reps, *counts, *keys[2], *vals[2], *rank_keys, *rank_order, *sort_scratch;
+    uint32_t *slot_of, *reps, *counts, *rank_keys, *rank_order;
+    SortBufs sb;  // [HW]; only where a view can take the radix path
     size_t bytes;
 };
 
@@ -223,23 +223,16 @@ UniqLayout uniq_layout(char* base, int V, int D, uint32_t HW) {
     uint32_t tbits = 6;
     while ((1ull << tbits) < 2ull * HW) ++tbits;
     L.tbits = tbits;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    L.table = reinterpret_cast<unsigned long long*>(take(sizeof(uint64_t) << tbits));
-    L.slot_of = reinterpret_cast<uint32_t*>(take(4ull * HW));
-    L.reps = reinterpret_cast<uint32_t*>(take(4ull * HW * V));
-    L.counts = reinterpret_cast<uint32_t*>(take(4ull * (V + 1)));  // [V] counts, then the flag word
+    Carver c(base);
+    L.table = c.take<unsigned long long>((size_t)1 << tbits);
+    L.slot_of = c.take<uint32_t>(HW);
+    L.reps = c.take<uint32_t>((size_t)HW * V);
+    L.counts = c.take<uint32_t>((size_t)V + 1);  // [V] counts, then the flag word
     const size_t nrank = (size_t)HW < (size_t)GOI_CODEBOOK_RANK_MAX ? HW : (size_t)GOI_CODEBOOK_RANK_MAX;
-    L.rank_keys = reinterpret_cast<uint32_t*>(take(4ull * nrank * D));
-    L.rank_order = reinterpret_cast<uint32_t*>(take(4ull * nrank));
-    if (HW > (uint32_t)GOI_CODEBOOK_RANK_MAX || D > RANK_TILE_WORDS) {
-        for (int b = 0; b < 2; ++b) {
-            L.keys[b] = reinterpret_cast<uint32_t*>(take(4ull * HW));
-            L.vals[b] = reinterpret_cast<uint32_t*>(take(4ull * HW));
-        }
-        L.sort_scratch = reinterpret_cast<uint32_t*>(take(4ull * sort_scratch_words(HW)));
-    }
-    L.bytes = off;
+    L.rank_keys = c.take<uint32_t>(nrank * D);
+    L.rank_order = c.take<uint32_t>(nrank);
+    if (HW > (uint32_t)GOI_CODEBOOK_RANK_MAX || D > RANK_TILE_WORDS) carve_sort(c, HW, &L.sb);
+    L.bytes = c.bytes();
     return L;
 }
 
@@ -473,31 +466,38 @@ bool launch_uniq_sort(const float* map, int v, int V, int D, uint32_t HW, uint32
         uniq_write_k<<<gw, UNIQ_THREADS, 0, s>>>(map, D, HW, L.rank_order, N, out);
         return false;
     }
-    uint32_t* keys[2] = {L.keys[0], L.keys[1]};
-    uint32_t* vals[2] = {L.vals[0], L.vals[1]};
     const uint32_t* perm = reps;
     const uint32_t grid = (uint32_t)div_up_sz(N, UNIQ_THREADS);
     for (int c = D - 1; c >= 0; --c) {
-        uniq_channel_keys_k<<<grid, UNIQ_THREADS, 0, s>>>(map + (size_t)c * HW, perm, N, keys[0], vals[0]);
-        const int fin = radix_sort_pairs(keys, vals, N, 0, 32, L.sort_scratch, s, false, false, nullptr, L.counts + V);
-        perm = vals[fin];
+        uniq_channel_keys_k<<<grid, UNIQ_THREADS, 0, s>>>(map + (size_t)c * HW, perm, N, L.sb.keys[0], L.sb.vals[0]);
+        const int fin = radix_sort_pairs(L.sb.keys, L.sb.vals, N, 0, 32, L.sb.scratch, s, false, false, nullptr, L.counts + V);
+        perm = L.sb.vals[fin];
     }
     uniq_write_k<<<gw, UNIQ_THREADS, 0, s>>>(map, D, HW, perm, N, out);
     return true;
 }
 
-size_t kmeans_workspace_bytes(long long rows, int K, int k, int D) {
-    return align256(4ull * K * k * D) + align256(4ull * rows) + align256(4ull * K * k);
+struct KmeansView {
+    float* cn;    // [K k D] normalised centres
+    int* assign;  // [rows]
+    int* dead;    // [K k]
+};
+static size_t kmeans_layout(long long rows, int K, int k, int D, void* base, KmeansView* v) {
+    Carver c(base);
+    KmeansView t;
+    t.cn = c.take<float>((size_t)K * k * D);
+    t.assign = c.take<int>((size_t)rows);
+    t.dead = c.take<int>((size_t)K * k);
+    if (v) *v = t;
+    return c.bytes();
 }
+
+size_t kmeans_workspace_bytes(long long rows, int K, int k, int D) { return kmeans_layout(rows, K, k, D, nullptr, nullptr); }
 
 void launch_kmeans(float* x, const long long* off, int K, long long max_rows, long long total_rows, int D, int k, int niter,
                    const int* perms, float* centers, int* status, void* ws, hipStream_t s) {
-    char* p = static_cast<char*>(ws);
-    float* cn = reinterpret_cast<float*>(p);
-    p += align256(4ull * K * k * D);
-    int* assign = reinterpret_cast<int*>(p);
-    p += align256(4ull * total_rows);
-    int* dead = reinterpret_cast<int*>(p);
+    KmeansView w;
+    kmeans_layout(total_rows, K, k, D, ws, &w);
     (void)hipMemsetAsync(status, 0, sizeof(int) * K, s);
     const int rows_per_block = KM_THREADS / 64;
     if (total_rows > 0)
@@ -507,10 +507,10 @@ void launch_kmeans(float* x, const long long* off, int K, long long max_rows, lo
     const long long crow = (long long)K * k;
     const dim3 agrid((uint32_t)div_up_sz(max_rows, KM_TM), K);
     for (int it = 0; it < niter; ++it) {
-        km_center_norm_k<<<(uint32_t)div_up_sz(crow, rows_per_block), KM_THREADS, 0, s>>>(centers, cn, crow, D);
-        km_assign_k<<<agrid, KM_THREADS, 0, s>>>(x, off, cn, D, k, it == 0, assign);
-        km_mean_k<<<dim3(k, K), KM_THREADS, 0, s>>>(x, off, assign, D, k, centers, dead);
-        km_dead_k<<<K, KM_THREADS, 0, s>>>(x, off, D, k, niter, it, perms, dead, centers, status);
+        km_center_norm_k<<<(uint32_t)div_up_sz(crow, rows_per_block), KM_THREADS, 0, s>>>(centers, w.cn, crow, D);
+        km_assign_k<<<agrid, KM_THREADS, 0, s>>>(x, off, w.cn, D, k, it == 0, w.assign);
+        km_mean_k<<<dim3(k, K), KM_THREADS, 0, s>>>(x, off, w.assign, D, k, centers, w.dead);
+        km_dead_k<<<K, KM_THREADS, 0, s>>>(x, off, D, k, niter, it, perms, w.dead, centers, status);
     }
 }
 

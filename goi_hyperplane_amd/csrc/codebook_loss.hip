@@ -1353,15 +1353,30 @@ int launch_codebook_dlut(const float* dsim, const float* g, long long HW, int C,
 
 // ---- the training half in one call.  workspace: code-book planes | decoder images | per-pixel records | simgrad wave sums |
 // dsim planes (the only large part: 2 x 2 B per (pixel, code))
-static size_t fu_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static long long fu_blocks(long long HW) { return (HW + FU_WG_PIX - 1) / FU_WG_PIX * (FU_WG_PIX / 16); }
 static long long fu_simgrad_wgs(long long HW) { return (HW + FU_WG_PIX - 1) / FU_WG_PIX; }
-size_t codebook_fused_workspace_bytes(long long HW) {
-    const size_t npad = (size_t)16 * fu_blocks(HW);
-    return fu_align((size_t)2 * SIM_NC * SIM_K * 2) + fu_align(FU_WZ_BYTES) + fu_align(FU_WT_BYTES) + 6 * fu_align(npad * 4) +
-           fu_align(npad * FU_TIE_WORDS * 4) + fu_align((size_t)fu_simgrad_wgs(HW) * SG_NW * 16) +
-           (size_t)fu_blocks(HW) * FU_DCHUNK * 2;
+// the pieces land in the kernels' argument block (the per-pixel records, the simgrad sums, both sets of planes)
+static size_t fused_layout(long long HW, void* base, FusedArgs* v) {
+    const size_t blocks = (size_t)fu_blocks(HW), npad = 16 * blocks;
+    Carver c(base);
+    FusedArgs a{};
+    a.planes = c.take<uint16_t>((size_t)2 * SIM_NC * SIM_K);
+    a.wz = c.take<uint16_t>(FU_WZ_BYTES / 2);
+    a.wt = c.take<uint16_t>(FU_WT_BYTES / 2);
+    a.r_mz = c.take<float>(npad);
+    a.r_rzp = c.take<float>(npad);
+    a.r_p2 = c.take<float>(npad);
+    a.r_nl = c.take<float>(npad);
+    a.r_arga = c.take<int>(npad);
+    a.r_args = c.take<int>(npad);
+    a.r_tie = c.take<uint32_t>(npad * FU_TIE_WORDS);
+    a.n_sums_a = (int)(fu_simgrad_wgs(HW) * SG_NW);
+    a.sums_a = c.take<float>((size_t)a.n_sums_a * 4);
+    a.dplanes = c.take<uint16_t>(blocks * FU_DCHUNK);  // (the last and only large piece: 2 x 2 B per (pixel, code); not padded)
+    if (v) *v = a;
+    return c.end();
 }
+size_t codebook_fused_workspace_bytes(long long HW) { return fused_layout(HW, nullptr, nullptr); }
 int codebook_fused_rows() { return 256 * GD_NW; }
 // returns -1 when the shape is not the kernels' (D = 256, C in 289..304, S <= 16, HW % 4 = 0, HW < 2^25)
 int launch_codebook_fused(const float* g, const float* l1, const float* sem, const float* W, const float* bias, long long HW,
@@ -1369,30 +1384,13 @@ int launch_codebook_fused(const float* g, const float* l1, const float* sem, con
                           hipStream_t s) {
     if (D != SIM_K || C > SIM_NC || C <= SIM_NC - 16 || S < 1 || S > 16 || HW < 4 || (HW & 3) != 0 || HW >= (1ll << 25)) return -1;
     const long long blocks = fu_blocks(HW);
-    const size_t npad = (size_t)16 * blocks;
-    char* ws = static_cast<char*>(workspace);
-    auto take = [&](size_t bytes) {
-        char* p = ws;
-        ws += fu_align(bytes);
-        return p;
-    };
     FusedArgs a;
-    uint16_t* planes = reinterpret_cast<uint16_t*>(take((size_t)2 * SIM_NC * SIM_K * 2));
-    uint16_t* wz = reinterpret_cast<uint16_t*>(take(FU_WZ_BYTES));
-    uint16_t* wt = reinterpret_cast<uint16_t*>(take(FU_WT_BYTES));
-    a.r_mz = reinterpret_cast<float*>(take(npad * 4));
-    a.r_rzp = reinterpret_cast<float*>(take(npad * 4));
-    a.r_p2 = reinterpret_cast<float*>(take(npad * 4));
-    a.r_nl = reinterpret_cast<float*>(take(npad * 4));
-    a.r_arga = reinterpret_cast<int*>(take(npad * 4));
-    a.r_args = reinterpret_cast<int*>(take(npad * 4));
-    a.r_tie = reinterpret_cast<uint32_t*>(take(npad * FU_TIE_WORDS * 4));
-    a.n_sums_a = (int)(fu_simgrad_wgs(HW) * SG_NW);
-    a.sums_a = reinterpret_cast<float*>(take((size_t)a.n_sums_a * 16));
-    uint16_t* dplanes = reinterpret_cast<uint16_t*>(ws);
-    codebook_split_k<<<dim3((SIM_NC * SIM_K / 2 + 255) / 256), dim3(256), 0, s>>>(l1, C, planes);
-    decoder_split_k<<<dim3((FU_NJ * 32 * 16 + 255) / 256), dim3(256), 0, s>>>(W, C, S, wz, wt);
-    a.g = g; a.planes = planes; a.wz = wz; a.wt = wt; a.bias = bias; a.sem = sem; a.dplanes = dplanes; a.dsem = dsem;
+    fused_layout(HW, workspace, &a);
+    // (the two split kernels write the operand images every later kernel only reads)
+    codebook_split_k<<<dim3((SIM_NC * SIM_K / 2 + 255) / 256), dim3(256), 0, s>>>(l1, C, const_cast<uint16_t*>(a.planes));
+    decoder_split_k<<<dim3((FU_NJ * 32 * 16 + 255) / 256), dim3(256), 0, s>>>(W, C, S, const_cast<uint16_t*>(a.wz),
+                                                                             const_cast<uint16_t*>(a.wt));
+    a.g = g; a.bias = bias; a.sem = sem; a.dsem = dsem;
     a.partials = partials; a.HW = HW; a.blocks = blocks; a.C = C; a.S = S; a.t = t;
     a.kappa = (float)(2.0 * 50.0 / ((double)HW * (double)C));
     a.inv_hw = (float)(1.0 / (double)HW);
@@ -1401,7 +1399,7 @@ int launch_codebook_fused(const float* g, const float* l1, const float* sem, con
     decoder_stats_k<<<dim3((unsigned)(stat_wgs < 2048 ? stat_wgs : 2048)), dim3(64 * DS_NW), 0, s>>>(a);
     codebook_simgrad_k<<<dim3((unsigned)fu_simgrad_wgs(HW)), dim3(64 * SG_NW), 0, s>>>(a);
     decoder_gd_k<<<dim3(codebook_fused_rows() / GD_NW), dim3(64 * GD_NW), 0, s>>>(a);
-    codebook_dlut2_k<<<dim3(codebook_dlut_blocks()), dim3(64 * DL2_NW), 0, s>>>(dplanes, g, HW, dl1_partial);
+    codebook_dlut2_k<<<dim3(codebook_dlut_blocks()), dim3(64 * DL2_NW), 0, s>>>(a.dplanes, g, HW, dl1_partial);
     return 0;
 }
 }  // namespace goi

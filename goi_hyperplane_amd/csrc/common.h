@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "goi_raster.h"
+#include "workspace.h"
 
 namespace goi {
 
@@ -176,9 +177,21 @@ void exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* ou
 //   frame_error : (onesweep only) a device word that gets bit 1 OR-ed in when a look-back spin runs out of its budget (a
 //                 preempted or wedged GPU): the sort carries on -- it must never hang the device -- but its output is
 //                 garbage and the caller must not use the frame (COUNTER_SORTERR / COUNTER_OVF).
-int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], size_t n, int lo, int hi, uint32_t* scratch,
+int radix_sort_pairs(uint32_t* const keys[2], uint32_t* const vals[2], size_t n, int lo, int hi, uint32_t* scratch,
                      hipStream_t s, bool cleared = false, bool ghist_ready = false, const uint32_t* n_dev = nullptr,
                      uint32_t* frame_error = nullptr);
+// The buffers of one such sort as a module keeps them in its workspace view: pieces keys[0] keys[1] vals[0] vals[1] scratch.
+// (An empty sort still gets a piece per buffer: the workspace of an empty mesh has always counted them.)
+struct SortBufs {
+    uint32_t* keys[2];
+    uint32_t* vals[2];
+    uint32_t* scratch;  // [sort_scratch_words(n)]
+};
+inline void carve_sort(Carver& c, size_t n, SortBufs* sb) {
+    for (int i = 0; i < 2; i++) sb->keys[i] = c.take<uint32_t>(at_least_one(n));
+    for (int i = 0; i < 2; i++) sb->vals[i] = c.take<uint32_t>(at_least_one(n));
+    sb->scratch = c.take<uint32_t>(sort_scratch_words(n));
+}
 size_t radix_sort_control_words(size_t n, int lo, int hi);
 uint32_t* radix_sort_ghist(uint32_t* scratch, size_t n, int lo, int hi);
 // ORs the onesweep sort's own error word (in `scratch`, after a radix_sort_pairs of the same n, lo, hi) into *out (device)

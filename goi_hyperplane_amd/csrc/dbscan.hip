@@ -437,86 +437,75 @@ inline unsigned grid_for(size_t n) { return (unsigned)((n + DB_THREADS - 1) / DB
 
 }  // namespace
 
-// Workspace, 256-byte aligned pieces: control words (bounds, cell count) | keys[2] | vals[2] | sorted points | point keys |
-// head / representative flags | point cells | cell starts | cell keys | cell boxes | cell info | parents | minima | ranks |
-// core flags | sort scratch | scan scratch  (~ 90 bytes per point plus the sort's scratch)
-size_t dbscan_workspace_layout(size_t n, char* base, uint32_t** ctl, uint32_t* keys[2], uint32_t* vals[2], float4** spt,
-                               uint64_t** skey, uint32_t** head, uint32_t** scell, uint32_t** cstart, uint64_t** ckey,
-                               uint32_t** cbox, uint32_t** info, uint32_t** parent, uint32_t** cmin, uint32_t** rank,
-                               uint8_t** score, uint32_t** sort_scratch, uint32_t** scan_scratch) {
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
-    *ctl = reinterpret_cast<uint32_t*>(carve(16 * sizeof(uint32_t)));
-    for (int i = 0; i < 2; i++) keys[i] = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    for (int i = 0; i < 2; i++) vals[i] = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    *spt = reinterpret_cast<float4*>(carve(sizeof(float4) * n));
-    *skey = reinterpret_cast<uint64_t*>(carve(sizeof(uint64_t) * n));
-    *head = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    *scell = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    *cstart = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * (n + 1)));
-    *ckey = reinterpret_cast<uint64_t*>(carve(sizeof(uint64_t) * n));
-    *cbox = reinterpret_cast<uint32_t*>(carve(8 * sizeof(uint32_t) * n));
-    *info = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    *parent = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    *cmin = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    *rank = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * n));
-    *score = reinterpret_cast<uint8_t*>(carve(n));
-    *sort_scratch = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * sort_scratch_words(n)));
-    *scan_scratch = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * scan_scratch_words(n)));
-    return off;
-}
-
-size_t dbscan_workspace_bytes(size_t n) {
-    uint32_t *ctl, *keys[2], *vals[2], *head, *scell, *cstart, *cbox, *info, *parent, *cmin, *rank, *sort_scratch, *scan_scratch;
+// Workspace, 256-byte aligned pieces: control words (bounds, cell count) | keys[2] | vals[2] | sort scratch | sorted points |
+// point keys | head / representative flags | point cells | cell starts | cell keys | cell boxes | cell info | parents | minima |
+// ranks | core flags | scan scratch  (~ 90 bytes per point plus the sort's scratch)
+struct DbscanView {
+    uint32_t* ctl;  // [16]: 0..5 encoded bounds, 8 the cell count
+    SortBufs sb;
     float4* spt;
     uint64_t *skey, *ckey;
+    uint32_t *head, *scell, *cstart, *cbox, *info, *parent, *cmin, *rank, *scan_scratch;
     uint8_t* score;
-    return dbscan_workspace_layout(n, nullptr, &ctl, keys, vals, &spt, &skey, &head, &scell, &cstart, &ckey, &cbox, &info,
-                                   &parent, &cmin, &rank, &score, &sort_scratch, &scan_scratch);
+};
+size_t dbscan_workspace_layout(size_t n, char* base, DbscanView* v) {
+    Carver c(base);
+    DbscanView t;
+    t.ctl = c.take<uint32_t>(16);
+    carve_sort(c, n, &t.sb);
+    t.spt = c.take<float4>(n);
+    t.skey = c.take<uint64_t>(n);
+    t.head = c.take<uint32_t>(n);
+    t.scell = c.take<uint32_t>(n);
+    t.cstart = c.take<uint32_t>(n + 1);
+    t.ckey = c.take<uint64_t>(n);
+    t.cbox = c.take<uint32_t>(8 * n);
+    t.info = c.take<uint32_t>(n);
+    t.parent = c.take<uint32_t>(n);
+    t.cmin = c.take<uint32_t>(n);
+    t.rank = c.take<uint32_t>(n);
+    t.score = c.take<uint8_t>(n);
+    t.scan_scratch = c.take<uint32_t>(scan_scratch_words(n));
+    if (v) *v = t;
+    return c.bytes();
 }
+
+size_t dbscan_workspace_bytes(size_t n) { return dbscan_workspace_layout(n, nullptr, nullptr); }
 
 void launch_dbscan(int n, const float* pts, float eps2, double h, int min_samples, int* labels, uint8_t* core, int* result,
                    void* workspace, hipStream_t s) {
-    uint32_t *ctl, *keys[2], *vals[2], *head, *scell, *cstart, *cbox, *info, *parent, *cmin, *rank, *sort_scratch, *scan_scratch;
-    float4* spt;
-    uint64_t *skey, *ckey;
-    uint8_t* score;
-    dbscan_workspace_layout((size_t)n, static_cast<char*>(workspace), &ctl, keys, vals, &spt, &skey, &head, &scell, &cstart,
-                            &ckey, &cbox, &info, &parent, &cmin, &rank, &score, &sort_scratch, &scan_scratch);
+    DbscanView w;
+    dbscan_workspace_layout((size_t)n, static_cast<char*>(workspace), &w);
     uint32_t* flags = reinterpret_cast<uint32_t*>(result) + 1;
-    uint32_t* enc = ctl;         // [6]
-    uint32_t* ncell = ctl + 8;   // [1]
+    uint32_t* enc = w.ctl;         // [6]
+    uint32_t* ncell = w.ctl + 8;   // [1]
     const unsigned g = grid_for((size_t)n);
     (void)hipMemsetAsync(enc, 0xFF, 3 * sizeof(uint32_t), s);
     (void)hipMemsetAsync(enc + 3, 0x00, 3 * sizeof(uint32_t), s);
     db_bounds_k<<<dim3(g < 1024 ? g : 1024), dim3(DB_THREADS), 0, s>>>(n, pts, enc, flags);
-    db_key_lo_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, pts, enc, h, keys[0], vals[0], flags);
-    const int f1 = radix_sort_pairs(keys, vals, (size_t)n, 0, 32, sort_scratch, s, false, false, nullptr, flags);
-    uint32_t* k2[2] = {keys[f1 ^ 1], keys[f1]};
-    uint32_t* v2[2] = {vals[f1 ^ 1], vals[f1]};
-    db_key_hi_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, pts, enc, h, vals[f1], k2[0], v2[0]);
-    const int f2 = radix_sort_pairs(k2, v2, (size_t)n, 0, 63 - 32, sort_scratch, s, false, false, nullptr, flags);
+    db_key_lo_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, pts, enc, h, w.sb.keys[0], w.sb.vals[0], flags);
+    const int f1 = radix_sort_pairs(w.sb.keys, w.sb.vals, (size_t)n, 0, 32, w.sb.scratch, s, false, false, nullptr, flags);
+    uint32_t* k2[2] = {w.sb.keys[f1 ^ 1], w.sb.keys[f1]};
+    uint32_t* v2[2] = {w.sb.vals[f1 ^ 1], w.sb.vals[f1]};
+    db_key_hi_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, pts, enc, h, w.sb.vals[f1], k2[0], v2[0]);
+    const int f2 = radix_sort_pairs(k2, v2, (size_t)n, 0, 63 - 32, w.sb.scratch, s, false, false, nullptr, flags);
     const uint32_t* order = v2[f2];
-    db_sorted_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, pts, enc, h, order, spt, skey, head);
-    exclusive_scan_u32(head, nullptr, scell, (size_t)n, ncell, scan_scratch, s);
-    db_cells_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, head, scell, skey, cstart, ckey, cbox);
-    db_bbox_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, spt, scell, cbox);
-    db_cell_info_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, cstart, cbox, eps2, min_samples, info, parent, cmin, flags);
-    db_core_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, spt, scell, cstart, ckey, cbox, info, eps2, min_samples, score,
+    db_sorted_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, pts, enc, h, order, w.spt, w.skey, w.head);
+    exclusive_scan_u32(w.head, nullptr, w.scell, (size_t)n, ncell, w.scan_scratch, s);
+    db_cells_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, w.head, w.scell, w.skey, w.cstart, w.ckey, w.cbox);
+    db_bbox_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, w.spt, w.scell, w.cbox);
+    db_cell_info_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, w.cstart, w.cbox, eps2, min_samples, w.info, w.parent, w.cmin, flags);
+    db_core_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, w.spt, w.scell, w.cstart, w.ckey, w.cbox, w.info, eps2, min_samples, w.score,
                                                         flags);
     const size_t union_groups = ((size_t)n * 64 + DB_THREADS - 1) / DB_THREADS;  // one wave per (possible) cell
-    db_union_k<<<dim3((unsigned)union_groups), dim3(DB_THREADS), 0, s>>>(n, ncell, spt, cstart, ckey, cbox, info, score, eps2,
-                                                                         parent, flags);
-    db_flatten_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, info, parent, flags);
-    db_cmin_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, spt, scell, score, parent, cmin, flags);
-    (void)hipMemsetAsync(head, 0, sizeof(uint32_t) * (size_t)n, s);  // head -> representative flags (input order)
-    db_rep_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, info, parent, cmin, head, flags);
-    exclusive_scan_u32(head, nullptr, rank, (size_t)n, reinterpret_cast<uint32_t*>(result), scan_scratch, s);
-    db_label_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, spt, scell, cstart, ckey, cbox, info, score, parent, cmin, rank,
+    db_union_k<<<dim3((unsigned)union_groups), dim3(DB_THREADS), 0, s>>>(n, ncell, w.spt, w.cstart, w.ckey, w.cbox, w.info, w.score, eps2,
+                                                                         w.parent, flags);
+    db_flatten_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, w.info, w.parent, flags);
+    db_cmin_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, w.spt, w.scell, w.score, w.parent, w.cmin, flags);
+    (void)hipMemsetAsync(w.head, 0, sizeof(uint32_t) * (size_t)n, s);  // head -> representative flags (input order)
+    db_rep_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, w.info, w.parent, w.cmin, w.head, flags);
+    exclusive_scan_u32(w.head, nullptr, w.rank, (size_t)n, reinterpret_cast<uint32_t*>(result), w.scan_scratch, s);
+    db_label_k<<<dim3(g), dim3(DB_THREADS), 0, s>>>(n, ncell, w.spt, w.scell, w.cstart, w.ckey, w.cbox, w.info, w.score, w.parent, w.cmin, w.rank,
                                                     eps2, labels, core, flags);
 }
 

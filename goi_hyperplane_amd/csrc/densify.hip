@@ -236,25 +236,18 @@ __global__ __launch_bounds__(DENS_THREADS) void densify_apply_k(const ApplyTable
 
 inline size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
 
-template <typename T>
-inline void carve(char*& p, T*& out, size_t count) {
-    p = reinterpret_cast<char*>((reinterpret_cast<size_t>(p) + 255) & ~(size_t)255);
-    out = reinterpret_cast<T*>(p);
-    p += count * sizeof(T);
-}
-
 }  // namespace
 
 // [P] plan bytes | [4P] streams, scanned in place | scan partials | total
 size_t densify_layout(long long P, char* base, DensifyView* v) {
-    char* p = base;
-    DensifyView tmp;
-    DensifyView& d = v ? *v : tmp;
-    carve(p, d.flags, (size_t)P);
-    carve(p, d.rank, 4 * (size_t)P);
-    carve(p, d.scratch, scan_scratch_words(4 * (size_t)P));
-    carve(p, d.total, 64);
-    return (size_t)(p - base);
+    Carver c(base);
+    DensifyView d;
+    d.flags = c.take<uint8_t>((size_t)P);
+    d.rank = c.take<uint32_t>(4 * (size_t)P);
+    d.scratch = c.take<uint32_t>(scan_scratch_words(4 * (size_t)P));
+    d.total = c.take<uint32_t>(64);
+    if (v) *v = d;
+    return c.end();
 }
 
 void launch_densify_stats(long long P, const float* grad, long long stride, const uint8_t* filter, float* accum, float* denom,

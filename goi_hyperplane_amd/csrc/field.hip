@@ -317,31 +317,23 @@ void launch_density_ppt(int ppt, unsigned blocks, const DensityArgs& A, hipStrea
 
 struct FieldView {
     uint32_t* ctl;  // [16]: 0..2 encoded minima, 3..5 encoded maxima
-    uint32_t *keys[2], *vals[2];
+    SortBufs sb;    // [P] cell keys, Gaussian ids
     float4 *q0, *q1, *q2, *q0s;
     uint32_t* cell_start;  // [ncells + 1]
-    uint32_t* sort_scratch;
 };
 
 size_t field_layout(size_t P, size_t ncells, char* base, FieldView* v) {
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
+    Carver c(base);
     FieldView t;
-    t.ctl = reinterpret_cast<uint32_t*>(carve(16 * sizeof(uint32_t)));
-    for (int i = 0; i < 2; i++) t.keys[i] = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * P));
-    for (int i = 0; i < 2; i++) t.vals[i] = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * P));
-    t.q0 = reinterpret_cast<float4*>(carve(sizeof(float4) * P));
-    t.q1 = reinterpret_cast<float4*>(carve(sizeof(float4) * P));
-    t.q2 = reinterpret_cast<float4*>(carve(sizeof(float4) * P));
-    t.q0s = reinterpret_cast<float4*>(carve(sizeof(float4) * P));
-    t.cell_start = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * (ncells + 1)));
-    t.sort_scratch = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * sort_scratch_words(P)));
+    t.ctl = c.take<uint32_t>(16);
+    carve_sort(c, P, &t.sb);
+    t.q0 = c.take<float4>(P);
+    t.q1 = c.take<float4>(P);
+    t.q2 = c.take<float4>(P);
+    t.q0s = c.take<float4>(P);
+    t.cell_start = c.take<uint32_t>(ncells + 1);
     if (v) *v = t;
-    return off;
+    return c.bytes();
 }
 
 FieldLattice field_lattice(int num_blocks, double relax_ratio) {
@@ -526,19 +518,14 @@ struct IsoView {
 };
 
 size_t iso_layout(size_t N, char* base, IsoView* v) {
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
+    Carver c(base);
     IsoView t;
-    t.counts = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * 2 * N));
-    t.total = reinterpret_cast<uint32_t*>(carve(16 * sizeof(uint32_t)));
-    t.emask = reinterpret_cast<uint8_t*>(carve(N));
-    t.scan_scratch = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * scan_scratch_words(2 * N)));
+    t.counts = c.take<uint32_t>(2 * N);
+    t.total = c.take<uint32_t>(16);
+    t.emask = c.take<uint8_t>(N);
+    t.scan_scratch = c.take<uint32_t>(scan_scratch_words(2 * N));
     if (v) *v = t;
-    return off;
+    return c.bytes();
 }
 
 unsigned blocks_for(long long n) { return (unsigned)((n + FIELD_THREADS - 1) / FIELD_THREADS); }
@@ -565,12 +552,12 @@ void launch_field_density(long long P, const float* xyz, const float* opacity, c
         field_bounds_k<<<dim3(g < 1024 ? g : 1024), dim3(FIELD_THREADS), 0, s>>>(P, xyz, opacity, selection, selection_invert, min_opacity, v.ctl);
     field_frame_k<<<dim3(1), dim3(64), 0, s>>>(v.ctl, bounds, frame);
     field_prep_k<<<dim3(g), dim3(FIELD_THREADS), 0, s>>>(P, xyz, opacity, scaling, rotation, selection, selection_invert, min_opacity,
-                                                         frame, lat, v.q0, v.q1, v.q2, v.keys[0], v.vals[0]);
+                                                         frame, lat, v.q0, v.q1, v.q2, v.sb.keys[0], v.sb.vals[0]);
     const int bits = 32 - __builtin_clz(lat.ncells);  // covers the key ncells of a Gaussian that is not kept
-    const int fin = radix_sort_pairs(v.keys, v.vals, (size_t)P, 0, bits, v.sort_scratch, s, false, false, nullptr,
+    const int fin = radix_sort_pairs(v.sb.keys, v.sb.vals, (size_t)P, 0, bits, v.sb.scratch, s, false, false, nullptr,
                                      reinterpret_cast<uint32_t*>(status));
-    field_gather_k<<<dim3(g), dim3(FIELD_THREADS), 0, s>>>(P, v.vals[fin], v.q0, v.q0s);
-    field_cells_k<<<dim3(blocks_for((long long)lat.ncells + 1)), dim3(FIELD_THREADS), 0, s>>>(P, v.keys[fin], lat.ncells, v.cell_start);
+    field_gather_k<<<dim3(g), dim3(FIELD_THREADS), 0, s>>>(P, v.sb.vals[fin], v.q0, v.q0s);
+    field_cells_k<<<dim3(blocks_for((long long)lat.ncells + 1)), dim3(FIELD_THREADS), 0, s>>>(P, v.sb.keys[fin], lat.ncells, v.cell_start);
     DensityArgs A;
     A.R = R;
     A.split = R / num_blocks;
@@ -581,7 +568,7 @@ void launch_field_density(long long P, const float* xyz, const float* opacity, c
     A.block_hi = block_hi;
     A.cell_start = v.cell_start;
     A.q0s = v.q0s;
-    A.order = v.vals[fin];
+    A.order = v.sb.vals[fin];
     A.q1 = v.q1;
     A.q2 = v.q2;
     A.attr = attributes;

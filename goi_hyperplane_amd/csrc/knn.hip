@@ -212,43 +212,38 @@ __global__ __launch_bounds__(KNN_BOX) void knn_search_k(int P, int nbox, const f
 
 }  // namespace
 
-size_t knn_workspace_layout(int P, char* base, uint32_t** enc, uint32_t* keys[2], uint32_t* vals[2], float4** sorted,
-                            float4** boxes, uint32_t** sort_scratch) {
+// Workspace: bounds (6 encoded words) | Morton keys, ids and the sort's scratch | sorted points, padded to whole boxes | boxes
+struct KnnView {
+    uint32_t* enc;  // [8]
+    SortBufs sb;    // [P]
+    float4 *sorted, *boxes;
+};
+size_t knn_workspace_layout(int P, char* base, KnnView* v) {
     const size_t nbox = ((size_t)P + KNN_BOX - 1) / KNN_BOX;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
-    *enc = reinterpret_cast<uint32_t*>(carve(8 * sizeof(uint32_t)));
-    for (int i = 0; i < 2; i++) keys[i] = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * (size_t)P));
-    for (int i = 0; i < 2; i++) vals[i] = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * (size_t)P));
-    *sorted = reinterpret_cast<float4*>(carve(sizeof(float4) * nbox * KNN_BOX));
-    *boxes = reinterpret_cast<float4*>(carve(sizeof(float4) * 2 * nbox));
-    *sort_scratch = reinterpret_cast<uint32_t*>(carve(sizeof(uint32_t) * sort_scratch_words((size_t)P)));
-    return off;
+    Carver c(base);
+    KnnView t;
+    t.enc = c.take<uint32_t>(8);
+    carve_sort(c, (size_t)P, &t.sb);
+    t.sorted = c.take<float4>(nbox * KNN_BOX);
+    t.boxes = c.take<float4>(2 * nbox);
+    if (v) *v = t;
+    return c.bytes();
 }
 
-size_t knn_workspace_bytes(int P) {
-    uint32_t *enc, *keys[2], *vals[2], *sort_scratch;
-    float4 *sorted, *boxes;
-    return knn_workspace_layout(P, nullptr, &enc, keys, vals, &sorted, &boxes, &sort_scratch);
-}
+size_t knn_workspace_bytes(int P) { return knn_workspace_layout(P, nullptr, nullptr); }
 
 int launch_knn(int P, const float* points, float* mean_dist2, void* workspace, hipStream_t s) {
-    uint32_t *enc, *keys[2], *vals[2], *sort_scratch;
-    float4 *sorted, *boxes;
-    knn_workspace_layout(P, static_cast<char*>(workspace), &enc, keys, vals, &sorted, &boxes, &sort_scratch);
+    KnnView w;
+    knn_workspace_layout(P, static_cast<char*>(workspace), &w);
     const int nbox = (P + KNN_BOX - 1) / KNN_BOX;
-    (void)hipMemsetAsync(enc, 0xFF, 3 * sizeof(uint32_t), s);
-    (void)hipMemsetAsync(enc + 3, 0x00, 3 * sizeof(uint32_t), s);
+    (void)hipMemsetAsync(w.enc, 0xFF, 3 * sizeof(uint32_t), s);
+    (void)hipMemsetAsync(w.enc + 3, 0x00, 3 * sizeof(uint32_t), s);
     const int rb = min(nbox, 1024);
-    knn_bounds_k<<<dim3(rb), dim3(256), 0, s>>>(P, points, enc);
-    knn_morton_k<<<dim3(nbox), dim3(256), 0, s>>>(P, points, enc, keys[0], vals[0]);
-    const int fin = radix_sort_pairs(keys, vals, (size_t)P, 0, 30, sort_scratch, s);
-    knn_boxes_k<<<dim3(nbox), dim3(KNN_BOX), 0, s>>>(P, points, vals[fin], sorted, boxes);
-    knn_search_k<<<dim3(nbox), dim3(KNN_BOX), 0, s>>>(P, nbox, sorted, boxes, mean_dist2);
+    knn_bounds_k<<<dim3(rb), dim3(256), 0, s>>>(P, points, w.enc);
+    knn_morton_k<<<dim3(nbox), dim3(256), 0, s>>>(P, points, w.enc, w.sb.keys[0], w.sb.vals[0]);
+    const int fin = radix_sort_pairs(w.sb.keys, w.sb.vals, (size_t)P, 0, 30, w.sb.scratch, s);
+    knn_boxes_k<<<dim3(nbox), dim3(KNN_BOX), 0, s>>>(P, points, w.sb.vals[fin], w.sorted, w.boxes);
+    knn_search_k<<<dim3(nbox), dim3(KNN_BOX), 0, s>>>(P, nbox, w.sorted, w.boxes, mean_dist2);
     return 0;
 }
 

@@ -159,12 +159,6 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_dedup_mark_k(uint32_t F, co
     alive_out[f] = (uint8_t)keep;
 }
 
-struct SortBufs {
-    uint32_t* keys[2];
-    uint32_t* vals[2];
-    uint32_t* scratch;
-};
-
 // alive_out[f] = alive_in[f] and no lower alive face holds the same set of three indices (all < limit)
 void run_dedup(uint32_t F, const int* tri, const uint8_t* alive_in, uint8_t* alive_out, uint32_t limit, const SortBufs& sb,
                uint32_t* status, hipStream_t s) {
@@ -339,38 +333,21 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_emit_faces_k(long long F, u
     if (index) index[o] = (int)f;
 }
 
-size_t carve_bytes(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <typename T>
-    T* take(size_t n) {
-        char* p = base ? base + off : nullptr;
-        off += carve_bytes(sizeof(T) * (n ? n : 1));
-        return reinterpret_cast<T*>(p);
-    }
-};
-void carve_sort(Carver& c, size_t n, SortBufs* sb) {
-    for (int i = 0; i < 2; i++) {
-        sb->keys[i] = c.take<uint32_t>(n);
-        sb->vals[i] = c.take<uint32_t>(n);
-    }
-    sb->scratch = c.take<uint32_t>(sort_scratch_words(n));
-}
-
+// (components and normals take an empty mesh, V = 0 or F = 0, and each of its arrays still gets a piece: at_least_one.  Clean and
+// decimate need V, F >= 1.)
 struct CompView {
     uint32_t* parent;
     uint8_t* named;
     uint32_t* status;
 };
 size_t comp_layout(size_t V, char* base, CompView* v) {
-    Carver c{base};
+    Carver c(base);
     CompView t;
-    t.parent = c.take<uint32_t>(V);
-    t.named = c.take<uint8_t>(V);
+    t.parent = c.take<uint32_t>(at_least_one(V));
+    t.named = c.take<uint8_t>(at_least_one(V));
     t.status = c.take<uint32_t>(4);
     if (v) *v = t;
-    return c.off;
+    return c.bytes();
 }
 
 struct CleanView {
@@ -380,7 +357,7 @@ struct CleanView {
     SortBufs sb;
 };
 size_t clean_layout(size_t V, size_t F, char* base, CleanView* v) {
-    Carver c{base};
+    Carver c(base);
     CleanView t;
     t.parent = c.take<uint32_t>(V);
     t.cfaces = c.take<uint32_t>(V);
@@ -396,7 +373,7 @@ size_t clean_layout(size_t V, size_t F, char* base, CleanView* v) {
     t.label = c.take<int>(V);
     carve_sort(c, F, &t.sb);
     if (v) *v = t;
-    return c.off;
+    return c.bytes();
 }
 
 // ---- decimate --------------------------------------------------------------------------------------------------------------
@@ -579,7 +556,7 @@ struct DecView {
     SortBufs sbv, sbf;
 };
 size_t dec_layout(size_t V, size_t F, char* base, DecView* v) {
-    Carver c{base};
+    Carver c(base);
     DecView t;
     t.box = c.take<uint32_t>(8);
     t.ctl = c.take<uint32_t>(4);
@@ -595,7 +572,7 @@ size_t dec_layout(size_t V, size_t F, char* base, DecView* v) {
     carve_sort(c, V, &t.sbv);
     carve_sort(c, F, &t.sbf);
     if (v) *v = t;
-    return c.off;
+    return c.bytes();
 }
 
 // ---- normals ---------------------------------------------------------------------------------------------------------------
@@ -651,12 +628,12 @@ struct NormView {
     SortBufs sb;
 };
 size_t norm_layout(size_t C, char* base, NormView* v) {
-    Carver c{base};
+    Carver c(base);
     NormView t;
     t.status = c.take<uint32_t>(4);
     carve_sort(c, C, &t.sb);
     if (v) *v = t;
-    return c.off;
+    return c.bytes();
 }
 
 }  // namespace
@@ -741,12 +718,10 @@ int launch_mesh_decimate_plan(long long V, long long F, const float* vertices, c
     const uint32_t none_key = (uint32_t)divisions * (uint32_t)divisions * (uint32_t)divisions;  // <= 2^30
     mesh_cell_key_k<<<dim3(blocks_for(V)), dim3(MESH_THREADS), 0, s>>>(Vu, vertices, w.member, w.box, divisions, none_key, w.sbv.keys[0],
                                                                       w.sbv.vals[0]);
-    uint32_t* k[2] = {w.sbv.keys[0], w.sbv.keys[1]};
-    uint32_t* v[2] = {w.sbv.vals[0], w.sbv.vals[1]};
-    const int fin = radix_sort_pairs(k, v, (size_t)V, 0, bits_for(none_key), w.sbv.scratch, s, false, false, nullptr, w.ctl);
-    mesh_cell_head_k<<<dim3(blocks_for(V)), dim3(MESH_THREADS), 0, s>>>(Vu, k[fin], none_key, w.rank);
+    const int fin = radix_sort_pairs(w.sbv.keys, w.sbv.vals, (size_t)V, 0, bits_for(none_key), w.sbv.scratch, s, false, false, nullptr, w.ctl);
+    mesh_cell_head_k<<<dim3(blocks_for(V)), dim3(MESH_THREADS), 0, s>>>(Vu, w.sbv.keys[fin], none_key, w.rank);
     exclusive_scan_u32(w.rank, nullptr, w.rank, (size_t)V, nullptr, w.scan_scratch, s);
-    mesh_vertex_cell_k<<<dim3(blocks_for(V)), dim3(MESH_THREADS), 0, s>>>(Vu, k[fin], v[fin], none_key, w.rank, w.vcell, w.cused);
+    mesh_vertex_cell_k<<<dim3(blocks_for(V)), dim3(MESH_THREADS), 0, s>>>(Vu, w.sbv.keys[fin], w.sbv.vals[fin], none_key, w.rank, w.vcell, w.cused);
     mesh_cell_faces_k<<<dim3(blocks_for(F)), dim3(MESH_THREADS), 0, s>>>(F, Vu, faces, w.vcell, w.tri, w.alive0);
     run_dedup(Fu, w.tri, w.alive0, w.alive1, Vu, w.sbf, w.ctl, s);
     mesh_cell_used_k<<<dim3(blocks_for(F)), dim3(MESH_THREADS), 0, s>>>(F, w.tri, w.alive1, w.fflag, w.cused);

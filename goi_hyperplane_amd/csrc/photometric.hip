@@ -38,8 +38,6 @@ constexpr int PH_WAVES = PH_THREADS / WAVE;
 constexpr int PH_ROWS_PER_THREAD = PH_TW * PH_TH / PH_THREADS;  // 4: thread = column tid % 32, rows tid / 32 + 8 j
 constexpr int PH_RED_THREADS = 256;
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 struct PhotoWin {
     float w[2 * PHOTO_RADIUS + 1];
 };
@@ -289,35 +287,28 @@ __global__ void __launch_bounds__(PH_THREADS) photo_bwd_k(const float* __restric
     }
 }
 
-struct PhotoLayout {
-    size_t partials, image_sums, maps, map_bytes, total;
-    int nmaps;
+struct PhotoView {
+    float* partials;     // [n c tiles][3]
+    double* image_sums;  // [n][3]
+    PhotoMaps maps;      // xx, xy and the mean of every image whose gradient is wanted; all NULL when no gradient is
 };
 
-PhotoLayout photo_layout(long long n, int c, int h, int w, unsigned flags) {
+size_t photo_layout(long long n, int c, int h, int w, unsigned flags, void* base, PhotoView* v) {
     const long long tiles = (long long)((w + PH_TW - 1) / PH_TW) * ((h + PH_TH - 1) / PH_TH);
     const size_t numel = (size_t)n * c * h * w;
-    PhotoLayout L;
-    L.nmaps = (flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2))
-                  ? 2 + !!(flags & GOI_PHOTOMETRIC_GRAD1) + !!(flags & GOI_PHOTOMETRIC_GRAD2) : 0;
-    L.partials = 0;
-    L.image_sums = align256((size_t)n * c * tiles * 3 * sizeof(float));
-    L.maps = L.image_sums + align256((size_t)n * 3 * sizeof(double));
-    L.map_bytes = align256(numel * sizeof(float));
-    L.total = L.maps + L.nmaps * L.map_bytes;
-    return L;
-}
-
-PhotoMaps photo_maps(void* ws, const PhotoLayout& L, unsigned flags) {
-    char* p = static_cast<char*>(ws) + L.maps;
-    PhotoMaps m = {nullptr, nullptr, nullptr, nullptr};
-    if (!L.nmaps) return m;
-    m.xx = reinterpret_cast<float*>(p);
-    m.xy = reinterpret_cast<float*>(p + L.map_bytes);
-    int k = 2;
-    if (flags & GOI_PHOTOMETRIC_GRAD1) m.mu1 = reinterpret_cast<float*>(p + L.map_bytes * k++);
-    if (flags & GOI_PHOTOMETRIC_GRAD2) m.mu2 = reinterpret_cast<float*>(p + L.map_bytes * k++);
-    return m;
+    Carver cv(base);
+    PhotoView t;
+    t.partials = cv.take<float>((size_t)n * c * tiles * 3);
+    t.image_sums = cv.take<double>((size_t)n * 3);
+    t.maps = {nullptr, nullptr, nullptr, nullptr};
+    if (flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2)) {
+        t.maps.xx = cv.take<float>(numel);
+        t.maps.xy = cv.take<float>(numel);
+        if (flags & GOI_PHOTOMETRIC_GRAD1) t.maps.mu1 = cv.take<float>(numel);
+        if (flags & GOI_PHOTOMETRIC_GRAD2) t.maps.mu2 = cv.take<float>(numel);
+    }
+    if (v) *v = t;
+    return cv.bytes();
 }
 
 // loss_utils.gaussian(11, 1.5): exp() in double, rounded to fp32, divided by their fp32 sum.  The sum is the correctly
@@ -337,29 +328,31 @@ PhotoWin photo_window() {
 
 }  // namespace
 
-size_t photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags) { return photo_layout(n, c, h, w, flags).total; }
+size_t photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags) {
+    return photo_layout(n, c, h, w, flags, nullptr, nullptr);
+}
 
 void launch_photometric_forward(const float* x, const float* y, long long n, int c, int h, int w, float lambda, unsigned flags,
                                 float* out, float* out_images, void* ws, hipStream_t s) {
-    const PhotoLayout L = photo_layout(n, c, h, w, flags);
+    PhotoView v;
+    photo_layout(n, c, h, w, flags, ws, &v);
     const int tiles_x = (w + PH_TW - 1) / PH_TW, tiles = tiles_x * ((h + PH_TH - 1) / PH_TH);
-    float* partials = reinterpret_cast<float*>(static_cast<char*>(ws) + L.partials);
-    double* image_sums = reinterpret_cast<double*>(static_cast<char*>(ws) + L.image_sums);
     const long long blocks = n * c * tiles;
-    photo_fwd_k<PHOTO_RADIUS><<<dim3((unsigned)blocks), PH_THREADS, 0, s>>>(x, y, h, w, tiles_x, tiles, photo_window(),
-                                                                            photo_maps(ws, L, flags), partials);
+    photo_fwd_k<PHOTO_RADIUS><<<dim3((unsigned)blocks), PH_THREADS, 0, s>>>(x, y, h, w, tiles_x, tiles, photo_window(), v.maps,
+                                                                            v.partials);
     const float kl = (float)(1.0 - (double)lambda), ks = lambda;
     const double per_image = (double)c * h * w;
-    photo_reduce_k<<<dim3((unsigned)n), PH_RED_THREADS, 0, s>>>(partials, c * tiles, per_image, kl, ks, image_sums, out,
+    photo_reduce_k<<<dim3((unsigned)n), PH_RED_THREADS, 0, s>>>(v.partials, c * tiles, per_image, kl, ks, v.image_sums, out,
                                                                  out_images);
-    if (n > 1) photo_total_k<<<1, PH_RED_THREADS, 0, s>>>(image_sums, n, per_image * n, kl, ks, out);
+    if (n > 1) photo_total_k<<<1, PH_RED_THREADS, 0, s>>>(v.image_sums, n, per_image * n, kl, ks, out);
 }
 
 void launch_photometric_backward(const float* x, const float* y, long long n, int c, int h, int w, float lambda, unsigned flags,
                                  const float* grad_out, const void* ws, float* gx, float* gy, hipStream_t s) {
     const unsigned fwd_flags = flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2);
-    const PhotoLayout L = photo_layout(n, c, h, w, fwd_flags);
-    const PhotoMaps maps = photo_maps(const_cast<void*>(ws), L, fwd_flags);
+    PhotoView v;
+    photo_layout(n, c, h, w, fwd_flags, const_cast<void*>(ws), &v);
+    const PhotoMaps& maps = v.maps;
     const int tiles_x = (w + PH_TW - 1) / PH_TW, tiles = tiles_x * ((h + PH_TH - 1) / PH_TH);
     const long long blocks = n * c * tiles;
     const bool per_image = flags & GOI_PHOTOMETRIC_PER_IMAGE;

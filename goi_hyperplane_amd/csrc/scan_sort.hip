@@ -658,7 +658,7 @@ void radix_sort_report_error(const uint32_t* scratch, size_t n, int lo, int hi, 
     or_word_k<<<dim3(1), dim3(1), 0, s>>>(error, out);
 }
 
-int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], size_t n, int lo, int hi, uint32_t* scratch,
+int radix_sort_pairs(uint32_t* const keys[2], uint32_t* const vals[2], size_t n, int lo, int hi, uint32_t* scratch,
                      hipStream_t s, bool cleared, bool ghist_ready, const uint32_t* n_dev, uint32_t* frame_error) {
     int cur = 0;
     if (n == 0) return cur;

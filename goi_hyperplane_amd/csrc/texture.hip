@@ -435,60 +435,44 @@ __global__ void __launch_bounds__(TEX_THREADS) tex_fill_nearest_k(int h, int w, 
     nearest[p] = near;
 }
 
-size_t tcarve_bytes(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-struct TCarver {
-    char* base;
-    size_t off = 0;
-    template <typename T>
-    T* take(size_t n) {
-        char* p = base ? base + off : nullptr;
-        off += tcarve_bytes(sizeof(T) * (n ? n : 1));
-        return reinterpret_cast<T*>(p);
-    }
-};
-
 struct RasterView {
     unsigned long long* zbuf;
     uint32_t *large, *n_large;
 };
 size_t raster_layout(size_t F, size_t HW, char* base, RasterView* v) {
-    TCarver c{base};
+    Carver c(base);
     RasterView t;
     t.zbuf = c.take<unsigned long long>(HW);
-    t.large = c.take<uint32_t>(F);
+    t.large = c.take<uint32_t>(at_least_one(F));  // (F = 0 is a valid mesh; its piece stays)
     t.n_large = c.take<uint32_t>(4);
     if (v) *v = t;
-    return c.off;
+    return c.bytes();
 }
 
 struct PutView {
-    uint32_t *keys[2], *vals[2], *scratch;
+    SortBufs sb;  // [4 N] splat taps
     float *lvl, *lvl_count;
 };
 size_t put_layout(size_t N, size_t C, size_t HW, char* base, PutView* v) {
-    TCarver c{base};
+    Carver c(base);
     PutView t;
-    for (int i = 0; i < 2; i++) {
-        t.keys[i] = c.take<uint32_t>(4 * N);
-        t.vals[i] = c.take<uint32_t>(4 * N);
-    }
-    t.scratch = c.take<uint32_t>(sort_scratch_words(4 * N));
+    carve_sort(c, 4 * N, &t.sb);
     t.lvl = c.take<float>(HW * C);
     t.lvl_count = c.take<float>(HW);
     if (v) *v = t;
-    return c.off;
+    return c.bytes();
 }
 
 struct FillView {
     uint8_t *up, *dn;
 };
 size_t fill_layout(size_t hw, char* base, FillView* v) {
-    TCarver c{base};
+    Carver c(base);
     FillView t;
     t.up = c.take<uint8_t>(hw);
     t.dn = c.take<uint8_t>(hw);
     if (v) *v = t;
-    return c.off;
+    return c.bytes();
 }
 
 template <int C>
@@ -499,11 +483,9 @@ void run_level(long long N, const float* coords, const float* values, const uint
     (void)hipMemsetAsync(w.lvl, 0, T * C * sizeof(float), s);
     (void)hipMemsetAsync(w.lvl_count, 0, T * sizeof(float), s);
     if (N > 0) {
-        tex_splat_key_k<<<dim3(tblocks(4 * N)), dim3(TEX_THREADS), 0, s>>>(N, coords, valid, cH, cW, w.keys[0], w.vals[0]);
-        uint32_t* k[2] = {w.keys[0], w.keys[1]};
-        uint32_t* v[2] = {w.vals[0], w.vals[1]};
-        const int fin = radix_sort_pairs(k, v, (size_t)(4 * N), 0, tbits_for((uint32_t)T), w.scratch, s, false, false, nullptr, status);
-        tex_segment_k<C><<<dim3(tblocks(4 * N)), dim3(TEX_THREADS), 0, s>>>(N, k[fin], v[fin], coords, values, cH, cW, w.lvl, w.lvl_count);
+        tex_splat_key_k<<<dim3(tblocks(4 * N)), dim3(TEX_THREADS), 0, s>>>(N, coords, valid, cH, cW, w.sb.keys[0], w.sb.vals[0]);
+        const int fin = radix_sort_pairs(w.sb.keys, w.sb.vals, (size_t)(4 * N), 0, tbits_for((uint32_t)T), w.sb.scratch, s, false, false, nullptr, status);
+        tex_segment_k<C><<<dim3(tblocks(4 * N)), dim3(TEX_THREADS), 0, s>>>(N, w.sb.keys[fin], w.sb.vals[fin], coords, values, cH, cW, w.lvl, w.lvl_count);
     }
     tex_compose_k<C><<<dim3(tblocks((long long)H * W)), dim3(TEX_THREADS), 0, s>>>(H, W, cH, cW, w.lvl, w.lvl_count, result, count, acc,
                                                                                   acc_count, norm_out, norm_mask);
