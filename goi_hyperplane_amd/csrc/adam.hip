@@ -14,7 +14,9 @@
 //     p   = p + (-lr / (1 - beta1^t)) * (m / den)     _foreach_addcdiv_
 // (scalars are formed in double on the host and rounded to fp32 once, as torch does).  This TU is
 // compiled with -ffp-contract=off so that the spelling is the arithmetic.
+// C entries, with the limits they enforce, at the end of the file: goi_adam_step* (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 
 namespace goi {
 
@@ -84,8 +86,6 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_step_k(const AdamTable t, c
     }
 }
 
-}  // namespace
-
 int launch_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
                      const uint8_t* nograd_mask, const uint32_t* skip_flag, hipStream_t s) {
     AdamTable t;
@@ -112,4 +112,35 @@ int launch_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, dou
     return 0;
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+int goi_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
+                  const unsigned char* nograd_mask, void* stream) {
+    return goi_adam_step_guarded(groups, n_groups, beta1, beta2, eps, nograd_mask, nullptr, stream);
+}
+
+int goi_adam_step_guarded(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
+                          const unsigned char* nograd_mask, const uint32_t* skip_flag, void* stream) {
+    if (n_groups < 0 || n_groups > GOI_ADAM_MAX_GROUPS) return fail("goi_adam_step: n_groups must be 0..8");
+    if (n_groups && !groups) return fail("goi_adam_step: groups is NULL");
+    for (int i = 0; i < n_groups; i++) {
+        const GoiAdamGroup& g = groups[i];
+        if (g.numel < 0 || g.row_len < 1) return fail("goi_adam_step: bad numel / row_len");
+        if (g.numel == 0) continue;
+        if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq) return fail("goi_adam_step: a tensor pointer is NULL");
+        if ((reinterpret_cast<uintptr_t>(g.param) | reinterpret_cast<uintptr_t>(g.grad) |
+             reinterpret_cast<uintptr_t>(g.exp_avg) | reinterpret_cast<uintptr_t>(g.exp_avg_sq)) & 15)
+            return fail("goi_adam_step: tensors must be 16-byte aligned");
+    }
+    launch_adam_step(groups, n_groups, beta1, beta2, eps, nograd_mask, skip_flag, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

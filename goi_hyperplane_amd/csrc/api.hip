@@ -1,5 +1,6 @@
-// extern "C" entry points of libgoi_raster.so (see include/goi_raster.h): workspace layout,
-// stage orchestration on the caller's HIP stream, per-stage event timing.
+// extern "C" entry points of the rasterizer's frame (see include/goi_raster.h): workspace layout, stage orchestration on the
+// caller's HIP stream, read-back tickets, options, per-stage event timing, the goi_raster_debug_* entries -- and the one
+// definition of what every entry refuses a call with (entry.h).  A stand-alone family's entries are in the family's own unit.
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -13,12 +14,12 @@
 #include <vector>
 
 #include "common.h"
+#include "entry.h"
 
 namespace goi {
 
-namespace {
-
-thread_local std::string g_err;
+// entry.h: the refusals of every unit's entries end in this one thread_local message
+static thread_local std::string g_err;
 
 int fail(const char* where, hipError_t e) {
     g_err = std::string(where) + ": " + hipGetErrorString(e);
@@ -28,20 +29,13 @@ int fail(const std::string& msg) {
     g_err = msg;
     return -1;
 }
-
-// The one refusal of a caller's workspace, for every entry: NULL, or not 256-byte aligned (the layouts carve from a 256-byte
-// aligned base: workspace.h).  `what` is the argument's name in the message.
-int check_workspace(const std::string& fn, const void* ws, const char* what = "workspace") {
+int check_workspace(const std::string& fn, const void* ws, const char* what) {
     if (!ws) return fail(fn + ": NULL " + what);
     if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(fn + ": " + what + " must be 256-byte aligned");
     return 0;
 }
 
-#define GOI_HIP(call)                                       \
-    do {                                                    \
-        hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return fail(#call, e__);     \
-    } while (0)
+namespace {
 
 // ---- per-stage timing -------------------------------------------------------------------------
 struct StageEvents {
@@ -959,811 +953,6 @@ int goi_raster_mark_visible(int P, const float* means3D, const float* viewmatrix
     return 0;
 }
 
-int goi_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
-                        const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
-                        void* stream) {
-    refresh_options();
-    if (!sem || !W || !bias) return fail("goi_semantic_decode: NULL input");
-    if (S < 1 || S > 32 || n_codes < 1 || HW < 0) return fail("goi_semantic_decode: need 1 <= S <= 32, n_codes >= 1");
-    if (HW == 0) return 0;
-    if (launch_semantic_decode(sem, S, HW, W, bias, n_codes, code_score, thresh, sim_out, idx_out, bg_mask_out,
-                               static_cast<hipStream_t>(stream)) < 0)
-        return fail("goi_semantic_decode: code book too large for LDS");
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_semantic_osh_counts(const int* idx, const uint8_t* positive, long long HW, int n_codes, int* counts, void* stream) {
-    if (HW < 0) return fail("goi_semantic_osh_counts: bad HW");
-    if (n_codes < 1 || n_codes > osh_max_codes()) return fail("goi_semantic_osh_counts: need 1 <= n_codes <= 1000");
-    if (!counts) return fail("goi_semantic_osh_counts: counts is NULL");
-    if (HW == 0) return 0;
-    if (!idx || !positive) return fail("goi_semantic_osh_counts: NULL input");
-    launch_osh_counts(idx, positive, HW, n_codes, counts, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts, long long HW, int K, float* w, float* b,
-                         float lr, int max_epochs, double target_iou, int* epochs_out, float* loss_out, double* iou_out,
-                         double* init_iou_out, double* trace, void* stream) {
-    refresh_options();
-    if (n_codes < 1 || n_codes > osh_max_codes()) return fail("goi_semantic_osh_fit: need 1 <= n_codes <= 1000");
-    if (D < 1 || D > osh_max_dim()) return fail("goi_semantic_osh_fit: need 1 <= D <= 1024");
-    if (HW < 1 || HW >= (1ll << 31)) return fail("goi_semantic_osh_fit: need 1 <= HW < 2^31");
-    if (K < 0 || K > 65535) return fail("goi_semantic_osh_fit: need 0 <= K <= 65535");
-    if (max_epochs < 1 || max_epochs > GOI_OSH_MAX_EPOCHS) return fail("goi_semantic_osh_fit: need 1 <= max_epochs <= 1000000");
-    if (K == 0) return 0;
-    if (!lut || !counts || !w || !b || !epochs_out || !loss_out || !iou_out || !init_iou_out)
-        return fail("goi_semantic_osh_fit: a required pointer is NULL");
-    launch_osh_fit(lut, n_codes, D, counts, HW, K, w, b, lr, max_epochs, target_iou, epochs_out, loss_out, iou_out,
-                   init_iou_out, trace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_semantic_dbscan_workspace_bytes(long long n) {
-    return (n > 0 && n < SORT_MAX_KEYS) ? dbscan_workspace_bytes((size_t)n) : 0;
-}
-
-int goi_semantic_dbscan(long long n, const float* points, float eps, int min_samples, int* labels, uint8_t* core, int* result,
-                        void* workspace, void* stream) {
-    // (the cell keys go through radix_sort_pairs, exact below 2^30 keys: common.h)
-    if (n < 0 || n >= SORT_MAX_KEYS) return fail("goi_semantic_dbscan: need 0 <= n < 2^30");
-    if (!(eps > 0.f) || !std::isfinite(eps)) return fail("goi_semantic_dbscan: eps must be a finite number > 0");
-    if (min_samples < 1) return fail("goi_semantic_dbscan: min_samples must be >= 1");
-    if (!result) return fail("goi_semantic_dbscan: result is NULL");
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    GOI_HIP(hipMemsetAsync(result, 0, 2 * sizeof(int), s));
-    if (n == 0) return 0;
-    if (!points || !labels) return fail("goi_semantic_dbscan: a required pointer is NULL");
-    if (check_workspace("goi_semantic_dbscan", workspace) < 0) return -1;
-    if (!(eps >= 0x1p-40f && eps <= 0x1p40f)) {  // outside the range of the grid's exactness argument (csrc/dbscan.hip)
-        GOI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(result + 1), DBSCAN_FLAG_RANGE, 1, s));
-        return 0;
-    }
-    const float eps2 = eps * eps;
-    const double h = (double)eps / std::sqrt(3.0) * (1.0 - 1.0 / 4096.0);  // cell side: eps / sqrt(3) less a margin
-    launch_dbscan((int)n, points, eps2, h, min_samples, labels, core, result, workspace, s);
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-static int mask_dims(const char* fn, int H, int W) {
-    if (H < 1 || W < 1) return fail(std::string(fn) + ": need H >= 1 and W >= 1");
-    if ((long long)H * W >= (1ll << 31)) return fail(std::string(fn) + ": need H * W < 2^31");
-    return 0;
-}
-
-int goi_semantic_mask_pack(const void* src, int src_dtype, int n_views, int H, int W, int first_view, uint64_t* packed, long long* counts,
-                  void* stream) {
-    if (mask_dims("goi_semantic_mask_pack", H, W) < 0) return -1;
-    if (src_dtype != GOI_MASK_F32 && src_dtype != GOI_MASK_U8) return fail("goi_semantic_mask_pack: src_dtype must be GOI_MASK_F32 or GOI_MASK_U8");
-    if (n_views < 0 || n_views > 65535 || first_view < 0) return fail("goi_semantic_mask_pack: need 0 <= n_views <= 65535, first_view >= 0");
-    if (n_views == 0) return 0;
-    if (!src || !packed) return fail("goi_semantic_mask_pack: NULL src or packed");
-    launch_mask_pack(src, src_dtype, n_views, H, W, first_view, packed, counts, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_semantic_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, int W, int radius, void* stream) {
-    if (mask_dims("goi_semantic_mask_dilate", H, W) < 0) return -1;
-    if (radius < 0 || radius > GOI_MASK_MAX_RADIUS) return fail("goi_semantic_mask_dilate: need 0 <= radius <= 63");
-    if (n_views < 0) return fail("goi_semantic_mask_dilate: need n_views >= 0");
-    if (n_views == 0) return 0;
-    if (!src || !dst) return fail("goi_semantic_mask_dilate: NULL src or dst");
-    if (src == dst) return fail("goi_semantic_mask_dilate: dst must not be src");
-    launch_mask_dilate(src, dst, n_views, H, W, radius, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_semantic_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
-                             void* stream) {
-    if (mask_dims("goi_semantic_mask_unpack", H, W) < 0) return -1;
-    if (n_out < 0 || n_views < 0) return fail("goi_semantic_mask_unpack: need n_out >= 0 and n_views >= 0");
-    if (n_out == 0) return 0;
-    if (!packed || !out) return fail("goi_semantic_mask_unpack: NULL packed or out");
-    launch_mask_unpack(packed, n_views, H, W, n_out, index, out, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_semantic_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, void* stream) {
-    if (mask_dims("goi_semantic_mask_confusion", H, W) < 0) return -1;
-    if (n_views < 0) return fail("goi_semantic_mask_confusion: need n_views >= 0");
-    if (n_views == 0) return 0;
-    if (!pred || !gt || !out) return fail("goi_semantic_mask_confusion: NULL pred, gt or out");
-    launch_mask_confusion(pred, gt, n_views, H, W, out, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_semantic_frame_workspace_bytes(int n_views) { return n_views < 1 ? 0 : sizeof(uint32_t) * 3 * (size_t)n_views; }
-
-int goi_semantic_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, int H, int W,
-                               int style, int normalize, double overlay_ratio, double heat_thresh, const float* table,
-                               int n_colors, void* out, int out_dtype, void* workspace, void* stream) {
-    const char* fn = "goi_semantic_frame_compose";
-    if (mask_dims(fn, H, W) < 0) return -1;
-    if (style < GOI_FRAME_NONE || style > GOI_FRAME_HEAT_FT) return fail(std::string(fn) + ": unknown style");
-    if (out_dtype != GOI_FRAME_F32 && out_dtype != GOI_FRAME_U8) return fail(std::string(fn) + ": out_dtype must be GOI_FRAME_F32 or GOI_FRAME_U8");
-    if (channels != 1 && channels != 3) return fail(std::string(fn) + ": channels must be 1 or 3");
-    if (n_views < 0 || n_views > 65535) return fail(std::string(fn) + ": need 0 <= n_views <= 65535");
-    if (n_views == 0) return 0;
-    const bool heat = style == GOI_FRAME_HEAT || style == GOI_FRAME_HEAT_FT;
-    const bool need_base = style != GOI_FRAME_BINARY;
-    if (!out || (need_base && !base)) return fail(std::string(fn) + ": NULL base or out");
-    if ((heat || style == GOI_FRAME_BINARY) && !sim) return fail(std::string(fn) + ": this style needs sim");
-    if ((heat || style == GOI_FRAME_WHITEN) && !bg_mask) return fail(std::string(fn) + ": this style needs bg_mask");
-    if (heat && (!table || n_colors < 2 || n_colors > GOI_FRAME_MAX_COLORS))
-        return fail(std::string(fn) + ": the heat styles need a table of 2 .. GOI_FRAME_MAX_COLORS (1024) colours");
-    if (((normalize && need_base) || style == GOI_FRAME_HEAT) && !workspace) return fail(std::string(fn) + ": NULL workspace");
-    if (!(overlay_ratio == overlay_ratio) || !(heat_thresh == heat_thresh)) return fail(std::string(fn) + ": NaN overlay_ratio or heat_thresh");
-    launch_frame_compose(base, channels, sim, bg_mask, n_views, (long long)H * W, style, normalize, (float)overlay_ratio,
-                         (float)(1.0 - overlay_ratio), (float)heat_thresh, table, n_colors, out, out_dtype,
-                         static_cast<uint32_t*>(workspace), static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-static int pca_dims(const char* fn, int S, long long n) {
-    if (S < GOI_PCA_MIN_DIM || S > GOI_PCA_MAX_DIM) return fail(std::string(fn) + ": need 3 <= S <= 32");
-    if (n < 1 || n >= (1ll << 31)) return fail(std::string(fn) + ": need 1 <= n < 2^31");
-    return 0;
-}
-
-size_t goi_semantic_pca_workspace_bytes(int S, int n_views) {
-    if (S < 0 || n_views < 0 || (S > 0 && (S < GOI_PCA_MIN_DIM || S > GOI_PCA_MAX_DIM)) || n_views > 65535) return 0;
-    return (S > 0 ? pca_fit_workspace_bytes(S) : 0) + (n_views > 0 ? pca_stats_bytes(n_views) : 0);
-}
-
-int goi_semantic_pca_accumulate(const float* x, int layout, int S, long long n, const uint8_t* mask, int first, void* workspace,
-                                void* stream) {
-    const char* fn = "goi_semantic_pca_accumulate";
-    if (pca_dims(fn, S, n) < 0) return -1;
-    if (layout != GOI_PCA_PLANAR && layout != GOI_PCA_ROWS) return fail(std::string(fn) + ": layout must be GOI_PCA_PLANAR or GOI_PCA_ROWS");
-    if (!x) return fail(std::string(fn) + ": NULL x");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    if (reinterpret_cast<uintptr_t>(x) & 3) return fail(std::string(fn) + ": x must be 4-byte aligned");
-    launch_pca_accumulate(x, layout, S, n, mask, first ? 1 : 0, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_semantic_pca_solve(int S, void* workspace, float* basis, void* stream) {
-    const char* fn = "goi_semantic_pca_solve";
-    if (pca_dims(fn, S, 1) < 0) return -1;
-    if (!basis) return fail(std::string(fn) + ": NULL basis");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    launch_pca_solve(S, workspace, basis, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_semantic_pca_apply(const float* x, int in_layout, int S, long long n, int n_views, const float* basis, int normalize,
-                           double k_sigma, float* out, int out_layout, void* workspace, void* stream) {
-    const char* fn = "goi_semantic_pca_apply";
-    if (pca_dims(fn, S, n) < 0) return -1;
-    if ((in_layout != GOI_PCA_PLANAR && in_layout != GOI_PCA_ROWS) || (out_layout != GOI_PCA_PLANAR && out_layout != GOI_PCA_ROWS))
-        return fail(std::string(fn) + ": layouts must be GOI_PCA_PLANAR or GOI_PCA_ROWS");
-    if (normalize != GOI_PCA_RAW && normalize != GOI_PCA_SIGMA && normalize != GOI_PCA_MINMAX)
-        return fail(std::string(fn) + ": normalize must be GOI_PCA_RAW, GOI_PCA_SIGMA or GOI_PCA_MINMAX");
-    if (n_views < 0 || n_views > 65535) return fail(std::string(fn) + ": need 0 <= n_views <= 65535");
-    if (n_views == 0) return 0;
-    if (!x || !basis || !out) return fail(std::string(fn) + ": NULL x, basis or out");
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(basis)) & 3)
-        return fail(std::string(fn) + ": x, basis and out must be 4-byte aligned");
-    if (normalize == GOI_PCA_MINMAX && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3)))
-        return fail(std::string(fn) + ": GOI_PCA_MINMAX needs a 4-byte aligned workspace");
-    if (normalize == GOI_PCA_SIGMA && !(k_sigma > 0.0 && k_sigma <= 3.0e38)) return fail(std::string(fn) + ": need a finite k_sigma > 0");
-    const float kf = (float)k_sigma;
-    launch_pca_apply(x, in_layout, S, n, n_views, basis, normalize, 2.0f * kf, out, out_layout, static_cast<uint32_t*>(workspace),
-                     static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-static int field_dims(int R, int num_blocks, double relax_ratio) {
-    if (num_blocks < 1 || R < 1 || R > GOI_FIELD_MAX_RESOLUTION || R % num_blocks != 0) return -1;
-    const int split = R / num_blocks;
-    if (split < GOI_FIELD_MIN_SPLIT || split > GOI_FIELD_MAX_SPLIT) return -1;
-    if (!(relax_ratio >= 0.0 && relax_ratio <= GOI_FIELD_MAX_RELAX)) return -1;
-    return 0;
-}
-
-size_t goi_field_density_workspace_bytes(long long P, int resolution, int num_blocks, double relax_ratio) {
-    if (P < 1 || P >= SORT_MAX_KEYS || field_dims(resolution, num_blocks, relax_ratio) < 0) return 0;
-    return field_density_workspace_bytes(P, num_blocks, relax_ratio);
-}
-
-int goi_field_density(long long P, const float* xyz, const float* opacity, const float* scaling, const float* rotation,
-                      const uint8_t* selection, int selection_invert, double min_opacity, const float* attributes,
-                      const float* bounds, int resolution, int num_blocks, double relax_ratio, const float* coords,
-                      const float* block_lo, const float* block_hi, float* occ, float* attr_out, float* frame, int* status,
-                      void* workspace, void* stream) {
-    const char* fn = "goi_field_density";
-    if (P < 0 || P >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need 0 <= P < 2^30");
-    if (field_dims(resolution, num_blocks, relax_ratio) < 0)
-        return fail(std::string(fn) + ": need resolution <= 256, resolution % num_blocks == 0, 4 <= resolution / num_blocks <= 16 "
-                                      "and 0 <= relax_ratio <= 4");
-    if (!(min_opacity == min_opacity)) return fail(std::string(fn) + ": NaN min_opacity");
-    if (!occ || !frame || !status || !coords || !block_lo || !block_hi) return fail(std::string(fn) + ": a required pointer is NULL");
-    if (attributes && !attr_out) return fail(std::string(fn) + ": attributes need attr_out");
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t vol = (size_t)resolution * resolution * resolution;
-    if (P == 0) {  // an empty model: zero grids, the caller's frame or (0, 0, 0, 1)
-        GOI_HIP(hipMemsetAsync(occ, 0, sizeof(float) * vol, s));
-        if (attr_out) GOI_HIP(hipMemsetAsync(attr_out, 0, sizeof(float) * 3 * vol, s));
-        GOI_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
-        if (bounds) {
-            GOI_HIP(hipMemcpyAsync(frame, bounds, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        } else {
-            GOI_HIP(hipMemsetAsync(frame, 0, 3 * sizeof(float), s));
-            GOI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(frame + 3), 0x3F800000, 1, s));  // 1.0f
-        }
-        return 0;
-    }
-    if (!xyz || !opacity || !scaling || !rotation) return fail(std::string(fn) + ": a required pointer is NULL");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    launch_field_density(P, xyz, opacity, scaling, rotation, selection, selection_invert ? 1 : 0, (float)min_opacity, attributes,
-                         bounds, resolution, num_blocks, relax_ratio, coords, block_lo, block_hi, occ, attr_out, frame, status,
-                         workspace, s);
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-static int iso_dims(const char* fn, int X, int Y, int Z) {
-    // at most 7 crossings per point and 12 triangles per cube: 19 * 2^26 < 2^32 keeps the one scan over both streams, and each
-    // count (< 2^31) an int32
-    if (X < 1 || Y < 1 || Z < 1 || (long long)X * Y * Z > GOI_FIELD_MAX_GRID_POINTS)
-        return fail(std::string(fn) + ": need X, Y, Z >= 1 and X Y Z <= 2^26");
-    return 0;
-}
-
-size_t goi_field_iso_workspace_bytes(int X, int Y, int Z) {
-    if (X < 1 || Y < 1 || Z < 1 || (long long)X * Y * Z > GOI_FIELD_MAX_GRID_POINTS) return 0;
-    return field_iso_workspace_bytes((long long)X * Y * Z);
-}
-
-int goi_field_iso_count(const float* grid, int X, int Y, int Z, double thresh, void* workspace, int* counts, void* stream) {
-    const char* fn = "goi_field_iso_count";
-    if (iso_dims(fn, X, Y, Z) < 0) return -1;
-    if (!(thresh == thresh)) return fail(std::string(fn) + ": NaN thresh");
-    if (!grid || !counts) return fail(std::string(fn) + ": NULL grid or counts");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    launch_field_iso_count(grid, X, Y, Z, (float)thresh, workspace, counts, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z, double thresh, const float* cx, const float* cy,
-                       const float* cz, const void* workspace, long long n_vertices, long long n_faces, float* vertices, int* faces,
-                       float* colors, void* stream) {
-    const char* fn = "goi_field_iso_emit";
-    if (iso_dims(fn, X, Y, Z) < 0) return -1;
-    if (!(thresh == thresh)) return fail(std::string(fn) + ": NaN thresh");
-    if (n_vertices < 0 || n_faces < 0 || n_vertices >= (1ll << 31) || n_faces >= (1ll << 31))
-        return fail(std::string(fn) + ": need 0 <= n_vertices, n_faces < 2^31");
-    if (!grid) return fail(std::string(fn) + ": NULL grid");
-    if ((n_vertices > 0 && !vertices) || (n_faces > 0 && !faces)) return fail(std::string(fn) + ": NULL vertices or faces");
-    if (attr && n_vertices > 0 && !colors) return fail(std::string(fn) + ": attr needs colors");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    launch_field_iso_emit(grid, attr, X, Y, Z, (float)thresh, cx, cy, cz, workspace, n_vertices, n_faces, vertices, faces, colors,
-                          static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- mesh clean-up (mesh.hip) ----------------------------------------------------------------------------------------------
-static bool mesh_sizes_ok(long long V, long long F, long long min_each) {
-    return V >= min_each && F >= min_each && V < SORT_MAX_KEYS && 3 * F < SORT_MAX_KEYS;
-}
-static int mesh_sizes(const char* fn, long long V, long long F, long long min_each) {
-    if (!mesh_sizes_ok(V, F, min_each))
-        return fail(std::string(fn) + ": need " + std::to_string(min_each) + " <= V, F and V, 3 F < 2^30");
-    return 0;
-}
-
-size_t goi_mesh_components_workspace_bytes(long long V, long long F) {
-    return mesh_sizes_ok(V, F, 0) ? mesh_components_workspace_bytes(V, F) : 0;
-}
-
-int goi_mesh_components(long long V, long long F, const int* faces, int* vertex_label, int* face_label, int* status,
-                        void* workspace, void* stream) {
-    const char* fn = "goi_mesh_components";
-    if (mesh_sizes(fn, V, F, 0) < 0 || check_workspace(fn, workspace) < 0) return -1;
-    if (!status || (V > 0 && !vertex_label) || (F > 0 && (!faces || !face_label)))
-        return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_mesh_components(V, F, faces, vertex_label, face_label, status, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_mesh_clean_workspace_bytes(long long V, long long F) {
-    return mesh_sizes_ok(V, F, 1) ? mesh_clean_workspace_bytes(V, F) : 0;
-}
-
-int goi_mesh_clean_plan(long long V, long long F, const float* vertices, const int* faces, long long min_faces, double min_diag2,
-                        void* workspace, int* counts, void* stream) {
-    const char* fn = "goi_mesh_clean_plan";
-    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
-    if (!vertices || !faces || !counts) return fail(std::string(fn) + ": NULL vertices, faces or counts");
-    if (!(min_diag2 >= 0.0)) return fail(std::string(fn) + ": need min_diag2 >= 0");
-    launch_mesh_clean_plan(V, F, vertices, faces, min_faces, min_diag2, workspace, counts, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_mesh_clean_emit(long long V, long long F, const float* vertices, const int* faces, const float* colors,
-                        const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
-                        float* out_colors, int* vertex_index, int* face_index, void* stream) {
-    const char* fn = "goi_mesh_clean_emit";
-    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
-    if (n_vertices < 0 || n_vertices > V || n_faces < 0 || n_faces > F) return fail(std::string(fn) + ": counts out of range");
-    if (!vertices || !faces) return fail(std::string(fn) + ": NULL vertices or faces");
-    if ((n_vertices > 0 && (!out_vertices || !vertex_index)) || (n_faces > 0 && (!out_faces || !face_index)))
-        return fail(std::string(fn) + ": NULL output");
-    if (colors && n_vertices > 0 && !out_colors) return fail(std::string(fn) + ": colors need out_colors");
-    launch_mesh_clean_emit(V, F, vertices, faces, colors, workspace, n_vertices, n_faces, out_vertices, out_faces, out_colors,
-                           vertex_index, face_index, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_mesh_decimate_workspace_bytes(long long V, long long F) {
-    return mesh_sizes_ok(V, F, 1) ? mesh_decimate_workspace_bytes(V, F) : 0;
-}
-
-int goi_mesh_decimate_members(long long V, long long F, const float* vertices, const int* faces, void* workspace, void* stream) {
-    const char* fn = "goi_mesh_decimate_members";
-    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
-    if (!vertices || !faces) return fail(std::string(fn) + ": NULL vertices or faces");
-    launch_mesh_decimate_members(V, F, vertices, faces, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-static int mesh_divisions(const char* fn, int divisions) {
-    if (divisions < 1 || divisions > GOI_MESH_MAX_DIVISIONS) return fail(std::string(fn) + ": need 1 <= divisions <= 1024");
-    return 0;
-}
-
-int goi_mesh_decimate_probe(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
-                            int* count, void* stream) {
-    const char* fn = "goi_mesh_decimate_probe";
-    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
-    if (!vertices || !faces || !count) return fail(std::string(fn) + ": NULL vertices, faces or count");
-    launch_mesh_decimate_probe(V, F, vertices, faces, divisions, workspace, count, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_mesh_decimate_plan(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
-                           int* counts, void* stream) {
-    const char* fn = "goi_mesh_decimate_plan";
-    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
-    if (!vertices || !faces || !counts) return fail(std::string(fn) + ": NULL vertices, faces or counts");
-    const int fin = launch_mesh_decimate_plan(V, F, vertices, faces, divisions, workspace, counts, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return fin;
-}
-
-int goi_mesh_decimate_emit(long long V, long long F, const float* vertices, const float* colors, int divisions, int sorted_in,
-                           const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
-                           float* out_colors, int* cluster, void* stream) {
-    const char* fn = "goi_mesh_decimate_emit";
-    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
-    if (sorted_in != 0 && sorted_in != 1) return fail(std::string(fn) + ": sorted_in must be what goi_mesh_decimate_plan returned");
-    if (n_vertices < 0 || n_vertices > V || n_faces < 0 || n_faces > F) return fail(std::string(fn) + ": counts out of range");
-    if (!vertices || !cluster) return fail(std::string(fn) + ": NULL vertices or cluster");
-    if ((n_vertices > 0 && !out_vertices) || (n_faces > 0 && !out_faces)) return fail(std::string(fn) + ": NULL output");
-    if (colors && n_vertices > 0 && !out_colors) return fail(std::string(fn) + ": colors need out_colors");
-    launch_mesh_decimate_emit(V, F, vertices, colors, divisions, sorted_in, workspace, n_vertices, n_faces, out_vertices, out_faces,
-                              out_colors, cluster, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_mesh_normals_workspace_bytes(long long V, long long F) {
-    return mesh_sizes_ok(V, F, 0) ? mesh_normals_workspace_bytes(V, F) : 0;
-}
-
-int goi_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
-                     void* workspace, void* stream) {
-    const char* fn = "goi_mesh_normals";
-    if (mesh_sizes(fn, V, F, 0) < 0 || check_workspace(fn, workspace) < 0) return -1;
-    if (!status || (V > 0 && (!vertices || !normals)) || (F > 0 && !faces)) return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_mesh_normals(V, F, vertices, faces, normals, status, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- texture bake (texture.hip) --------------------------------------------------------------------------------------------
-static bool texture_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= GOI_TEXTURE_MAX_SIZE && W <= GOI_TEXTURE_MAX_SIZE; }
-static int texture_size(const char* fn, int H, int W) {
-    if (!texture_size_ok(H, W)) return fail(std::string(fn) + ": need 1 <= H, W <= 16384");
-    return 0;
-}
-static bool texture_put_ok(long long N, int C, int H, int W) {
-    return N >= 0 && 4 * N < SORT_MAX_KEYS && C >= 1 && C <= GOI_TEXTURE_MAX_CHANNELS && texture_size_ok(H, W);
-}
-
-size_t goi_texture_rasterize_workspace_bytes(long long F, int H, int W) {
-    return F >= 0 && 3 * F < SORT_MAX_KEYS && texture_size_ok(H, W) ? texture_rasterize_workspace_bytes(F, H, W) : 0;
-}
-
-int goi_texture_rasterize(long long V, long long F, const float* v_clip, const int* faces, int H, int W, int* tri, float* bary,
-                          float* zw, int* status, void* workspace, void* stream) {
-    const char* fn = "goi_texture_rasterize";
-    if (mesh_sizes(fn, V, F, 0) < 0 || texture_size(fn, H, W) < 0 || check_workspace(fn, workspace) < 0) return -1;
-    if (!status || !tri || !bary || !zw || (F > 0 && (!faces || !v_clip))) return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_texture_rasterize(V, F, v_clip, faces, H, W, tri, bary, zw, status, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_texture_resolve(long long n_vt, long long n_vn, long long F, int H, int W, const int* tri, const float* bary,
-                        const float* vt, const int* ft, const float* vn, const int* faces, const float* pose_rot,
-                        const float* image, float* coords, float* values, unsigned char* valid, int* status, void* stream) {
-    const char* fn = "goi_texture_resolve";
-    if (mesh_sizes(fn, n_vt, F, 0) < 0 || mesh_sizes(fn, n_vn, F, 0) < 0 || texture_size(fn, H, W) < 0) return -1;
-    if (!status || !tri || !bary || !pose_rot || !image || !coords || !values || !valid || (F > 0 && (!vt || !ft || !vn || !faces)))
-        return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_texture_resolve(n_vt, n_vn, F, H, W, tri, bary, vt, ft, vn, faces, pose_rot, image, coords, values, valid, status,
-                           static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_texture_grid_put_workspace_bytes(long long N, int C, int H, int W) {
-    return texture_put_ok(N, C, H, W) ? texture_grid_put_workspace_bytes(N, C, H, W) : 0;
-}
-
-int goi_texture_grid_put(long long N, int C, int H, int W, int min_resolution, const float* coords, const float* values,
-                         const unsigned char* valid, float* result, float* count, float* acc, float* acc_count, float* norm_out,
-                         unsigned char* norm_mask, int* status, void* workspace, void* stream) {
-    const char* fn = "goi_texture_grid_put";
-    if (!texture_put_ok(N, C, H, W)) return fail(std::string(fn) + ": need 0 <= N < 2^28, 1 <= C <= 4 and 1 <= H, W <= 16384");
-    if (min_resolution < 1) return fail(std::string(fn) + ": need min_resolution >= 1");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    if (!status || !result || !count || (N > 0 && (!coords || !values))) return fail(std::string(fn) + ": a required pointer is NULL");
-    if ((acc == nullptr) != (acc_count == nullptr)) return fail(std::string(fn) + ": give both of acc and acc_count, or neither");
-    if ((norm_out == nullptr) != (norm_mask == nullptr) || (norm_out && !acc))
-        return fail(std::string(fn) + ": give both of norm_out and norm_mask, with acc, or neither");
-    launch_texture_grid_put(N, C, H, W, min_resolution, coords, values, valid, result, count, acc, acc_count, norm_out, norm_mask,
-                            status, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-static int texture_texels(const char* fn, long long T, int C) {
-    if (T < 0 || T > (long long)GOI_TEXTURE_MAX_SIZE * GOI_TEXTURE_MAX_SIZE || C < 1 || C > GOI_TEXTURE_MAX_CHANNELS)
-        return fail(std::string(fn) + ": need 0 <= T <= 16384^2 and 1 <= C <= 4");
-    return 0;
-}
-
-int goi_texture_accumulate(long long T, int C, float* albedo, float* cnt, const float* cur, const float* cur_cnt, void* stream) {
-    const char* fn = "goi_texture_accumulate";
-    if (texture_texels(fn, T, C) < 0) return -1;
-    if (T > 0 && (!albedo || !cnt || !cur || !cur_cnt)) return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_texture_accumulate(T, C, albedo, cnt, cur, cur_cnt, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_texture_normalize(long long T, int C, const float* albedo, const float* cnt, float* out, unsigned char* mask,
-                          void* stream) {
-    const char* fn = "goi_texture_normalize";
-    if (texture_texels(fn, T, C) < 0) return -1;
-    if (T > 0 && (!albedo || !cnt || !out || !mask)) return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_texture_normalize(T, C, albedo, cnt, out, mask, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_texture_fill_workspace_bytes(int h, int w) { return texture_size_ok(h, w) ? texture_fill_workspace_bytes(h, w) : 0; }
-
-int goi_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
-                     void* workspace, void* stream) {
-    const char* fn = "goi_texture_fill";
-    if (texture_size(fn, h, w) < 0 || texture_texels(fn, 0, C) < 0 || check_workspace(fn, workspace) < 0) return -1;
-    if (radius < 0 || radius > GOI_TEXTURE_MAX_RADIUS) return fail(std::string(fn) + ": need 0 <= radius <= 127");
-    if (!albedo || !mask || !out || !nearest) return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_texture_fill(h, w, C, radius, albedo, mask, out, nearest, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_edit_bounds_workspace_bytes(long long P) {
-    return (P >= 0 && P < (1ll << 31)) ? edit_bounds_workspace_bytes(P) + 256 : 0;
-}
-
-int goi_edit_bounds(long long P, const float* xyz, const unsigned char* selection, int invert, int* count, float* out,
-                    void* workspace, void* stream) {
-    const char* fn = "goi_edit_bounds";
-    if (P < 0 || P >= (1ll << 31)) return fail(std::string(fn) + ": need 0 <= P < 2^31");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    if (!count || !out || (P > 0 && !xyz)) return fail(std::string(fn) + ": a required pointer is NULL");
-    launch_edit_bounds(P, xyz, selection, invert, count, out, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_edit_transform(long long P, int M, const unsigned char* selection, int invert, const GoiEditTransform* t, float* xyz,
-                       float* rotation, float* scaling, float* features_rest, float* m_xyz, float* m_rotation,
-                       float* m_features_rest, const float* pivot_dev, void* stream) {
-    const char* fn = "goi_edit_transform";
-    if (P < 0 || P >= (1ll << 31)) return fail(std::string(fn) + ": need 0 <= P < 2^31");
-    if (M != 1 && M != 4 && M != 9 && M != 16) return fail(std::string(fn) + ": M must be 1, 4, 9 or 16");
-    if (!t) return fail(std::string(fn) + ": the transform is NULL");
-    if (t->flags & ~(GOI_EDIT_ROTATE | GOI_EDIT_SCALE)) return fail(std::string(fn) + ": unknown flag bits");
-    const bool rotate = (t->flags & GOI_EDIT_ROTATE) != 0, scale = (t->flags & GOI_EDIT_SCALE) != 0;
-    if (!rotate && (m_xyz || m_rotation || m_features_rest)) return fail(std::string(fn) + ": moments are only turned by a rotation");
-    if (M == 1 && m_features_rest) return fail(std::string(fn) + ": M = 1 has no features_rest moment");
-    if (P > 0 && (!xyz || (rotate && !rotation) || (scale && !scaling) || (rotate && M > 1 && !features_rest)))
-        return fail(std::string(fn) + ": a required pointer is NULL");
-    EditPointers p;
-    p.xyz = xyz;
-    p.rotation = rotation;
-    p.scaling = scaling;
-    p.rest = M > 1 ? features_rest : nullptr;
-    p.m_xyz = m_xyz;
-    p.m_rotation = m_rotation;
-    p.m_rest = m_features_rest;
-    p.pivot_dev = pivot_dev;
-    launch_edit_transform(P, M, selection, invert, *t, p, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-static int uniq_dims(const char* fn, int n_views, int D, int H, int W) {
-    if (n_views < 0 || D < 1 || H < 1 || W < 1) return fail(std::string(fn) + ": need n_views >= 0 and D, H, W >= 1");
-    if ((long long)H * W >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need H * W < 2^30");
-    return 0;
-}
-
-size_t goi_codebook_unique_rows_workspace_bytes(int n_views, int D, int H, int W) {
-    if (n_views < 1 || D < 1 || H < 1 || W < 1 || (long long)H * W >= SORT_MAX_KEYS) return 0;
-    return uniq_workspace_bytes(n_views, D, (uint32_t)((long long)H * W));
-}
-
-int goi_codebook_unique_rows(const float* const* maps, int n_views, int D, int H, int W, long long* counts, unsigned* flags,
-                             goi_alloc_fn alloc, void* alloc_user, void* workspace, void* stream) {
-    refresh_options();
-    const char* fn = "goi_codebook_unique_rows";
-    if (uniq_dims(fn, n_views, D, H, W) < 0) return -1;
-    if (!flags || (n_views > 0 && (!maps || !counts || !alloc))) return fail(std::string(fn) + ": a required pointer is NULL");
-    *flags = 0;
-    if (n_views == 0) return 0;
-    for (int v = 0; v < n_views; ++v)
-        if (!maps[v]) return fail(std::string(fn) + ": maps[" + std::to_string(v) + "] is NULL");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t HW = (uint32_t)((long long)H * W);
-    launch_uniq_dedup(maps, n_views, D, HW, workspace, s);
-    GOI_HIP(hipGetLastError());
-    std::vector<uint32_t> host(n_views + 1);
-    uint32_t* dev_counts = uniq_counts(workspace, n_views, D, HW);
-    GOI_HIP(hipMemcpyAsync(host.data(), dev_counts, sizeof(uint32_t) * (n_views + 1), hipMemcpyDeviceToHost, s));
-    GOI_HIP(hipStreamSynchronize(s));  // the one read-back: counts and flag word of every view
-    *flags = host[n_views];
-    long long total = 0;
-    for (int v = 0; v < n_views; ++v) total += (counts[v] = host[v]);
-    if (*flags) return 0;
-    float* out = static_cast<float*>(alloc(alloc_user, (size_t)total * D * sizeof(float) + 1));
-    if (!out) return fail(std::string(fn) + ": output allocation failed");
-    bool sorted = false;
-    for (int v = 0; v < n_views; ++v) {
-        sorted |= launch_uniq_sort(maps[v], v, n_views, D, HW, host[v], out, workspace, s);
-        GOI_HIP(hipGetLastError());
-        out += (size_t)host[v] * D;
-    }
-    if (sorted) {  // the radix sorts OR their look-back error into the flag word
-        uint32_t f = 0;
-        GOI_HIP(hipMemcpyAsync(&f, dev_counts + n_views, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        GOI_HIP(hipStreamSynchronize(s));
-        *flags = f;
-    }
-    return 0;
-}
-
-size_t goi_codebook_kmeans_workspace_bytes(long long n_rows, int n_problems, int ncluster, int D) {
-    if (n_rows < 0 || n_problems < 1 || ncluster < 1 || D < 1) return 0;
-    return kmeans_workspace_bytes(n_rows, n_problems, ncluster, D);
-}
-
-int goi_codebook_kmeans(float* x, const long long* row_offsets, int n_problems, long long max_rows, long long n_rows, int D,
-                        int ncluster, int niter, const int* perms, float* centers, int* status, void* workspace, void* stream) {
-    const char* fn = "goi_codebook_kmeans";
-    if (n_problems < 0 || n_problems > 65535) return fail(std::string(fn) + ": need 0 <= n_problems <= 65535");
-    if (ncluster < 1 || ncluster > GOI_CODEBOOK_KMEANS_MAX_K) return fail(std::string(fn) + ": need 1 <= ncluster <= 4096");
-    if (D < 1 || D > GOI_CODEBOOK_KMEANS_MAX_DIM) return fail(std::string(fn) + ": need 1 <= D <= 1024");
-    if (niter < 0) return fail(std::string(fn) + ": need niter >= 0");
-    if (n_rows < 0 || n_rows >= (1ll << 31) || max_rows < 1 || max_rows > n_rows)
-        return fail(std::string(fn) + ": need 1 <= max_rows <= n_rows < 2^31");
-    if (n_problems == 0) return 0;
-    if (!x || !row_offsets || !perms || !centers || !status) return fail(std::string(fn) + ": a required pointer is NULL");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    launch_kmeans(x, row_offsets, n_problems, max_rows, n_rows, D, ncluster, niter, perms, centers, status, workspace,
-                  static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-namespace {
-// the shape limits of goi_raster_photometric_*: "" when the call may go ahead
-std::string photometric_check(long long n, int c, int h, int w, int window_size) {
-    if (window_size != GOI_PHOTOMETRIC_WINDOW) return "window_size " + std::to_string(window_size) + " is not supported (only 11)";
-    if (n < 1 || c < 1 || h < 1 || w < 1) return "need n, c, h, w >= 1";
-    if ((long long)h * w >= (1ll << 31)) return "need h * w < 2^31";
-    if (n * c * ((h + 31) / 32) * (long long)((w + 31) / 32) >= (1ll << 31)) return "need n * c * ceil(h/32) * ceil(w/32) < 2^31";
-    return "";
-}
-}  // namespace
-
-size_t goi_raster_photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags) {
-    if (!photometric_check(n, c, h, w, GOI_PHOTOMETRIC_WINDOW).empty()) return 0;
-    return photometric_workspace_bytes(n, c, h, w, flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2));
-}
-
-int goi_raster_photometric_forward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
-                                   float lambda_dssim, unsigned flags, float* out, float* out_images, void* workspace, void* stream) {
-    const std::string fn = "goi_raster_photometric_forward: ";
-    const std::string bad = photometric_check(n, c, h, w, window_size);
-    if (!bad.empty()) return fail(fn + bad);
-    if (!img1 || !img2 || !out) return fail(fn + "a required pointer is NULL");
-    if (check_workspace("goi_raster_photometric_forward", workspace) < 0) return -1;
-    launch_photometric_forward(img1, img2, n, c, h, w, lambda_dssim, flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2), out,
-                               out_images, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_photometric_backward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
-                                    float lambda_dssim, unsigned flags, const float* grad_out, const void* workspace, float* grad1,
-                                    float* grad2, void* stream) {
-    const std::string fn = "goi_raster_photometric_backward: ";
-    const std::string bad = photometric_check(n, c, h, w, window_size);
-    if (!bad.empty()) return fail(fn + bad);
-    if (!(flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2))) return fail(fn + "no gradient asked for");
-    if (!img1 || !img2 || !grad_out || ((flags & GOI_PHOTOMETRIC_GRAD1) && !grad1) || ((flags & GOI_PHOTOMETRIC_GRAD2) && !grad2))
-        return fail(fn + "a required pointer is NULL");
-    if (check_workspace("goi_raster_photometric_backward", workspace) < 0) return -1;
-    launch_photometric_backward(img1, img2, n, c, h, w, lambda_dssim, flags, grad_out, workspace, grad1, grad2,
-                                static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_raster_densify_workspace_bytes(long long P) {
-    return (P >= 0 && P < (1ll << 30)) ? densify_layout(P, nullptr, nullptr) + 256 : 0;
-}
-
-int goi_raster_densify_stats(long long P, const float* grad, long long grad_stride, const unsigned char* filter, float* accum,
-                             float* denom, void* stream) {
-    const std::string fn = "goi_raster_densify_stats: ";
-    if (P < 0 || P >= (1ll << 31)) return fail(fn + "need 0 <= P < 2^31");
-    if (grad_stride < 2) return fail(fn + "grad_stride must be >= 2");
-    if (P > 0 && (!grad || !filter || !accum || !denom)) return fail(fn + "a required pointer is NULL");
-    launch_densify_stats(P, grad, grad_stride, filter, accum, denom, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_densify_plan(long long P, const float* accum, const float* denom, const float* scaling, const float* opacity,
-                            double max_grad, double scale_threshold, double min_opacity, int screen_test, double max_screen_size,
-                            double big_threshold, unsigned* counts, void* workspace, void* stream) {
-    const std::string fn = "goi_raster_densify_plan: ";
-    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
-    if (!counts || (P > 0 && (!accum || !denom || !scaling || !opacity))) return fail(fn + "a required pointer is NULL");
-    if (check_workspace("goi_raster_densify_plan", workspace) < 0) return -1;
-    refresh_options();
-    DensifyView v;
-    densify_layout(P, static_cast<char*>(workspace), &v);
-    DensifyThresholds t;
-    t.max_grad = (float)max_grad;  // a Python scalar meets an fp32 tensor: rounded to fp32 once
-    t.thr_scale = (float)scale_threshold;
-    t.min_opacity = (float)min_opacity;
-    t.big_world = (float)big_threshold;
-    t.split_inv = 1.0f / (float)(0.8 * 2);  // torch's reciprocal of the CPU scalar 0.8 * N
-    t.screen = screen_test != 0;
-    t.screen_all = 0.0f > (float)max_screen_size;  // max_radii2D is all zeros when the reference tests it
-    launch_densify_plan(P, accum, denom, scaling, opacity, t, counts, v, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_densify_prune_plan(long long P, const unsigned char* mask, unsigned* counts, void* workspace, void* stream) {
-    const std::string fn = "goi_raster_densify_prune_plan: ";
-    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
-    if (!counts || (P > 0 && !mask)) return fail(fn + "a required pointer is NULL");
-    if (check_workspace("goi_raster_densify_prune_plan", workspace) < 0) return -1;
-    refresh_options();
-    DensifyView v;
-    densify_layout(P, static_cast<char*>(workspace), &v);
-    launch_prune_plan(P, mask, counts, v, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_densify_apply(long long P, const GoiDensifyRows* groups, int n_groups, const float* rotation, const float* scaling,
-                             const float* z, long long n_split, long long kept_children, const void* workspace, void* stream) {
-    const std::string fn = "goi_raster_densify_apply: ";
-    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
-    if (n_groups < 0 || n_groups > GOI_DENSIFY_MAX_GROUPS) return fail(fn + "n_groups must be 0..24");
-    if (n_groups && !groups) return fail(fn + "groups is NULL");
-    if (n_split < 0 || n_split > P || kept_children < 0 || kept_children > n_split) return fail(fn + "bad n_split / kept_children");
-    if (check_workspace("goi_raster_densify_apply", workspace) < 0) return -1;
-    for (int k = 0; k < n_groups; k++) {
-        const GoiDensifyRows& g = groups[k];
-        if (g.row_len < 1 || g.rows < 0 || g.mode < GOI_DENSIFY_PARAM || g.mode > GOI_DENSIFY_ZERO) return fail(fn + "bad group");
-        if (g.mode != GOI_DENSIFY_ZERO && g.rows != P) return fail(fn + "a copied group must have P source rows");
-        if (g.rows > 0 && (!g.dst || (g.mode != GOI_DENSIFY_ZERO && !g.src))) return fail(fn + "a group pointer is NULL");
-        if ((g.mode == GOI_DENSIFY_XYZ || g.mode == GOI_DENSIFY_SCALING) && g.row_len != 3) return fail(fn + "xyz / scaling rows are 3 floats");
-        if (g.mode == GOI_DENSIFY_XYZ && kept_children > 0 && (!rotation || !scaling || !z))
-            return fail(fn + "children's xyz need rotation, scaling and z");
-    }
-    DensifyView v;
-    densify_layout(P, static_cast<char*>(const_cast<void*>(workspace)), &v);
-    launch_densify_apply(P, groups, n_groups, rotation, scaling, z, n_split, kept_children, 1.0f / (float)(0.8 * 2), v,
-                         static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_codebook_loss_partial_rows(void) { return codebook_loss_waves(); }
-
-int goi_codebook_loss_rows(const float* sim_raw, const float* inv_gnorm, const float* sem, const float* W,
-                           const float* bias, long long HW, int C, int S, float t, float* dsim, float* dsem,
-                           float* partials, void* stream) {
-    if (HW < 0) return fail("goi_codebook_loss_rows: bad HW");
-    if (!sim_raw || !inv_gnorm || !sem || !W || !dsim || !dsem || !partials)
-        return fail("goi_codebook_loss_rows: a required pointer is NULL");
-    if (launch_codebook_rows(sim_raw, inv_gnorm, sem, W, bias, HW, C, S, t, dsim, dsem, partials,
-                             static_cast<hipStream_t>(stream)) < 0)
-        return fail("goi_codebook_loss_rows: supported sizes are 1 <= S <= 16, 1 <= C <= 512");
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_codebook_sim_workspace_bytes(void) { return codebook_sim_workspace_bytes(); }
-
-int goi_codebook_sim(const float* g, const float* lut1, long long HW, int C, int D, float* sim, float* inv_gnorm,
-                     void* workspace, void* stream) {
-    if (!g || !lut1 || !sim || !inv_gnorm || !workspace) return fail("goi_codebook_sim: a required pointer is NULL");
-    if (launch_codebook_sim(g, lut1, HW, C, D, sim, inv_gnorm, workspace, static_cast<hipStream_t>(stream)) < 0)
-        return fail("goi_codebook_sim: supported shape is D = 256, C <= 304, C % 4 = 0");
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_codebook_dlut_partial_blocks(void) { return codebook_dlut_blocks(); }
-
-int goi_codebook_dlut(const float* dsim, const float* g, long long HW, int C, int D, float* partial, void* stream) {
-    if (!dsim || !g || !partial || HW < 0) return fail("goi_codebook_dlut: bad arguments");
-    if (launch_codebook_dlut(dsim, g, HW, C, D, partial, static_cast<hipStream_t>(stream)) < 0)
-        return fail("goi_codebook_dlut: supported shape is D = 256, 288 < C <= 304, HW % 4 = 0");
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_codebook_fused_workspace_bytes(long long HW) { return HW < 0 ? 0 : codebook_fused_workspace_bytes(HW); }
-int goi_codebook_fused_partial_rows(void) { return codebook_fused_rows(); }
-
-int goi_codebook_fused(const float* g, const float* lut1, const float* sem, const float* W, const float* bias, long long HW,
-                       int C, int D, int S, float t, float* dsem, float* partials, float* dlut_partial, void* workspace,
-                       void* stream) {
-    if (!g || !lut1 || !sem || !W || !dsem || !partials || !dlut_partial) return fail("goi_codebook_fused: a required pointer is NULL");
-    if (check_workspace("goi_codebook_fused", workspace) < 0) return -1;  // (its layout carves from a 256-byte aligned base)
-    if (launch_codebook_fused(g, lut1, sem, W, bias, HW, C, D, S, t, dsem, partials, dlut_partial, workspace,
-                              static_cast<hipStream_t>(stream)) < 0)
-        return fail("goi_codebook_fused: supported shape is D = 256, 288 < C <= 304, 1 <= S <= 16, HW % 4 = 0, HW < 2^25");
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
 int goi_raster_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* campos, const float* gcol,
                            float* dL_dsh, void* stream) {
     if (P <= 0 || V <= 0) return 0;
@@ -1774,46 +963,9 @@ int goi_raster_sh_grad_from_views(int P, int D, int M, int V, const float* means
     return 0;
 }
 
-int goi_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
-                  const unsigned char* nograd_mask, void* stream) {
-    return goi_adam_step_guarded(groups, n_groups, beta1, beta2, eps, nograd_mask, nullptr, stream);
-}
-
 const uint32_t* goi_raster_truncated_flag(const void* geom_buffer, int P) {
     if (!geom_buffer || P <= 0) return nullptr;
     return frame_views(P, 0, 0, 0, geom_buffer, nullptr, nullptr).g.counters + COUNTER_OVF;
-}
-
-int goi_adam_step_guarded(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
-                          const unsigned char* nograd_mask, const uint32_t* skip_flag, void* stream) {
-    if (n_groups < 0 || n_groups > GOI_ADAM_MAX_GROUPS) return fail("goi_adam_step: n_groups must be 0..8");
-    if (n_groups && !groups) return fail("goi_adam_step: groups is NULL");
-    for (int i = 0; i < n_groups; i++) {
-        const GoiAdamGroup& g = groups[i];
-        if (g.numel < 0 || g.row_len < 1) return fail("goi_adam_step: bad numel / row_len");
-        if (g.numel == 0) continue;
-        if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq) return fail("goi_adam_step: a tensor pointer is NULL");
-        if ((reinterpret_cast<uintptr_t>(g.param) | reinterpret_cast<uintptr_t>(g.grad) |
-             reinterpret_cast<uintptr_t>(g.exp_avg) | reinterpret_cast<uintptr_t>(g.exp_avg_sq)) & 15)
-            return fail("goi_adam_step: tensors must be 16-byte aligned");
-    }
-    launch_adam_step(groups, n_groups, beta1, beta2, eps, nograd_mask, skip_flag, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t goi_knn_workspace_bytes(int P) { return P > 0 && P < SORT_MAX_KEYS ? knn_workspace_bytes(P) : 0; }
-
-int goi_knn_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream) {
-    if (P < 0) return fail("goi_knn_dist2: bad P");
-    // (the Morton codes go through radix_sort_pairs, exact below 2^30 keys: common.h)
-    if (P >= SORT_MAX_KEYS) return fail("goi_knn_dist2: need P < 2^30");
-    if (P == 0) return 0;
-    if (!points || !mean_dist2) return fail("goi_knn_dist2: a required pointer is NULL");
-    if (check_workspace("goi_knn_dist2", workspace) < 0) return -1;
-    launch_knn(P, points, mean_dist2, workspace, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
 }
 
 void goi_raster_profile_enable(int on) { g_profile_mask.store(on ? ~0u : 0u); }

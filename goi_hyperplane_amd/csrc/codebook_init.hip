@@ -30,7 +30,11 @@
 //                       atomics: bit-reproducible), divided by the count; 0 members or a NaN makes the centre dead
 //     km_dead_k         dead centres in index order take x[perm_{it+1}[0 .. ndead)]; ndead > N is the reference's
 //                       shape-mismatch RuntimeError and is recorded in status[p] (first iteration + 1)
+// C entries, with the limits they enforce, at the end of the file: goi_codebook_unique_rows* / _kmeans* (declared in include/goi_raster.h).
+#include <vector>
+
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
@@ -435,8 +439,6 @@ __global__ void __launch_bounds__(KM_THREADS) km_dead_k(const float* __restrict_
     }
 }
 
-}  // namespace
-
 size_t uniq_workspace_bytes(int V, int D, uint32_t HW) { return uniq_layout(nullptr, V, D, HW).bytes; }
 
 uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW) {
@@ -482,7 +484,7 @@ struct KmeansView {
     int* assign;  // [rows]
     int* dead;    // [K k]
 };
-static size_t kmeans_layout(long long rows, int K, int k, int D, void* base, KmeansView* v) {
+size_t kmeans_layout(long long rows, int K, int k, int D, void* base, KmeansView* v) {
     Carver c(base);
     KmeansView t;
     t.cn = c.take<float>((size_t)K * k * D);
@@ -514,4 +516,86 @@ void launch_kmeans(float* x, const long long* off, int K, long long max_rows, lo
     }
 }
 
+int uniq_dims(const char* fn, int n_views, int D, int H, int W) {
+    if (n_views < 0 || D < 1 || H < 1 || W < 1) return fail(std::string(fn) + ": need n_views >= 0 and D, H, W >= 1");
+    if ((long long)H * W >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need H * W < 2^30");
+    return 0;
+}
+
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_codebook_unique_rows_workspace_bytes(int n_views, int D, int H, int W) {
+    if (n_views < 1 || D < 1 || H < 1 || W < 1 || (long long)H * W >= SORT_MAX_KEYS) return 0;
+    return uniq_workspace_bytes(n_views, D, (uint32_t)((long long)H * W));
+}
+
+int goi_codebook_unique_rows(const float* const* maps, int n_views, int D, int H, int W, long long* counts, unsigned* flags,
+                             goi_alloc_fn alloc, void* alloc_user, void* workspace, void* stream) {
+    refresh_options();
+    const char* fn = "goi_codebook_unique_rows";
+    if (uniq_dims(fn, n_views, D, H, W) < 0) return -1;
+    if (!flags || (n_views > 0 && (!maps || !counts || !alloc))) return fail(std::string(fn) + ": a required pointer is NULL");
+    *flags = 0;
+    if (n_views == 0) return 0;
+    for (int v = 0; v < n_views; ++v)
+        if (!maps[v]) return fail(std::string(fn) + ": maps[" + std::to_string(v) + "] is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t HW = (uint32_t)((long long)H * W);
+    launch_uniq_dedup(maps, n_views, D, HW, workspace, s);
+    GOI_HIP(hipGetLastError());
+    std::vector<uint32_t> host(n_views + 1);
+    uint32_t* dev_counts = uniq_counts(workspace, n_views, D, HW);
+    GOI_HIP(hipMemcpyAsync(host.data(), dev_counts, sizeof(uint32_t) * (n_views + 1), hipMemcpyDeviceToHost, s));
+    GOI_HIP(hipStreamSynchronize(s));  // the one read-back: counts and flag word of every view
+    *flags = host[n_views];
+    long long total = 0;
+    for (int v = 0; v < n_views; ++v) total += (counts[v] = host[v]);
+    if (*flags) return 0;
+    float* out = static_cast<float*>(alloc(alloc_user, (size_t)total * D * sizeof(float) + 1));
+    if (!out) return fail(std::string(fn) + ": output allocation failed");
+    bool sorted = false;
+    for (int v = 0; v < n_views; ++v) {
+        sorted |= launch_uniq_sort(maps[v], v, n_views, D, HW, host[v], out, workspace, s);
+        GOI_HIP(hipGetLastError());
+        out += (size_t)host[v] * D;
+    }
+    if (sorted) {  // the radix sorts OR their look-back error into the flag word
+        uint32_t f = 0;
+        GOI_HIP(hipMemcpyAsync(&f, dev_counts + n_views, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        GOI_HIP(hipStreamSynchronize(s));
+        *flags = f;
+    }
+    return 0;
+}
+
+size_t goi_codebook_kmeans_workspace_bytes(long long n_rows, int n_problems, int ncluster, int D) {
+    if (n_rows < 0 || n_problems < 1 || ncluster < 1 || D < 1) return 0;
+    return kmeans_workspace_bytes(n_rows, n_problems, ncluster, D);
+}
+
+int goi_codebook_kmeans(float* x, const long long* row_offsets, int n_problems, long long max_rows, long long n_rows, int D,
+                        int ncluster, int niter, const int* perms, float* centers, int* status, void* workspace, void* stream) {
+    const char* fn = "goi_codebook_kmeans";
+    if (n_problems < 0 || n_problems > 65535) return fail(std::string(fn) + ": need 0 <= n_problems <= 65535");
+    if (ncluster < 1 || ncluster > GOI_CODEBOOK_KMEANS_MAX_K) return fail(std::string(fn) + ": need 1 <= ncluster <= 4096");
+    if (D < 1 || D > GOI_CODEBOOK_KMEANS_MAX_DIM) return fail(std::string(fn) + ": need 1 <= D <= 1024");
+    if (niter < 0) return fail(std::string(fn) + ": need niter >= 0");
+    if (n_rows < 0 || n_rows >= (1ll << 31) || max_rows < 1 || max_rows > n_rows)
+        return fail(std::string(fn) + ": need 1 <= max_rows <= n_rows < 2^31");
+    if (n_problems == 0) return 0;
+    if (!x || !row_offsets || !perms || !centers || !status) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    launch_kmeans(x, row_offsets, n_problems, max_rows, n_rows, D, ncluster, niter, perms, centers, status, workspace,
+                  static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

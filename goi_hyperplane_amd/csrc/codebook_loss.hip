@@ -24,9 +24,11 @@
 // The pixel's feature is wave-uniform (SGPRs, read with v_readlane from a 64-pixel register tile).
 // Row statistics are DPP wave reductions whose results are wave-uniform.  All sums have a fixed
 // order: the losses and gradients are bit-reproducible.
+// C entries, with the limits they enforce, at the end of the file: goi_codebook_loss_* / _sim* / _dlut* / _fused* (declared in include/goi_raster.h).
 #include <float.h>
 
 #include "blend_common.h"
+#include "entry.h"
 
 namespace goi {
 
@@ -1295,8 +1297,6 @@ __global__ __launch_bounds__(64 * DL2_NW, 1) void codebook_dlut2_k(const uint16_
             for (int r = 0; r < 4; r++) out[(size_t)(16 * cb + 4 * kq + r) * 256 + 32 * w + 16 * j + mm] = acc[cb][j][r];
 }
 
-}  // namespace
-
 int codebook_loss_waves() { return 256 * 8; }  // persistent: 8 waves per CU (2 per SIMD at ~230 VGPRs)
 
 int launch_codebook_rows(const float* sim, const float* inv_gnorm, const float* sem, const float* W, const float* bias,
@@ -1322,10 +1322,6 @@ int launch_codebook_rows(const float* sim, const float* inv_gnorm, const float* 
     return 0;
 }
 
-
-}  // namespace goi
-
-namespace goi {
 size_t codebook_sim_workspace_bytes() { return (size_t)2 * SIM_NC * SIM_K * sizeof(uint16_t); }
 // sim [HW][C] and inv_gnorm [HW] from g [256][HW] (channel-major) and l1 [C][256]; workspace: codebook_sim_workspace_bytes().
 // Returns -1 when the shape is not the kernel's (D = 256, C <= 304, C % 4 = 0): the caller then uses the library GEMM.
@@ -1402,4 +1398,64 @@ int launch_codebook_fused(const float* g, const float* l1, const float* sem, con
     codebook_dlut2_k<<<dim3(codebook_dlut_blocks()), dim3(64 * DL2_NW), 0, s>>>(a.dplanes, g, HW, dl1_partial);
     return 0;
 }
+
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+int goi_codebook_loss_partial_rows(void) { return codebook_loss_waves(); }
+
+int goi_codebook_loss_rows(const float* sim_raw, const float* inv_gnorm, const float* sem, const float* W,
+                           const float* bias, long long HW, int C, int S, float t, float* dsim, float* dsem,
+                           float* partials, void* stream) {
+    if (HW < 0) return fail("goi_codebook_loss_rows: bad HW");
+    if (!sim_raw || !inv_gnorm || !sem || !W || !dsim || !dsem || !partials)
+        return fail("goi_codebook_loss_rows: a required pointer is NULL");
+    if (launch_codebook_rows(sim_raw, inv_gnorm, sem, W, bias, HW, C, S, t, dsim, dsem, partials,
+                             static_cast<hipStream_t>(stream)) < 0)
+        return fail("goi_codebook_loss_rows: supported sizes are 1 <= S <= 16, 1 <= C <= 512");
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_codebook_sim_workspace_bytes(void) { return codebook_sim_workspace_bytes(); }
+
+int goi_codebook_sim(const float* g, const float* lut1, long long HW, int C, int D, float* sim, float* inv_gnorm,
+                     void* workspace, void* stream) {
+    if (!g || !lut1 || !sim || !inv_gnorm || !workspace) return fail("goi_codebook_sim: a required pointer is NULL");
+    if (launch_codebook_sim(g, lut1, HW, C, D, sim, inv_gnorm, workspace, static_cast<hipStream_t>(stream)) < 0)
+        return fail("goi_codebook_sim: supported shape is D = 256, C <= 304, C % 4 = 0");
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_codebook_dlut_partial_blocks(void) { return codebook_dlut_blocks(); }
+
+int goi_codebook_dlut(const float* dsim, const float* g, long long HW, int C, int D, float* partial, void* stream) {
+    if (!dsim || !g || !partial || HW < 0) return fail("goi_codebook_dlut: bad arguments");
+    if (launch_codebook_dlut(dsim, g, HW, C, D, partial, static_cast<hipStream_t>(stream)) < 0)
+        return fail("goi_codebook_dlut: supported shape is D = 256, 288 < C <= 304, HW % 4 = 0");
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_codebook_fused_workspace_bytes(long long HW) { return HW < 0 ? 0 : codebook_fused_workspace_bytes(HW); }
+int goi_codebook_fused_partial_rows(void) { return codebook_fused_rows(); }
+
+int goi_codebook_fused(const float* g, const float* lut1, const float* sem, const float* W, const float* bias, long long HW,
+                       int C, int D, int S, float t, float* dsem, float* partials, float* dlut_partial, void* workspace,
+                       void* stream) {
+    if (!g || !lut1 || !sem || !W || !dsem || !partials || !dlut_partial) return fail("goi_codebook_fused: a required pointer is NULL");
+    if (check_workspace("goi_codebook_fused", workspace) < 0) return -1;  // (its layout carves from a 256-byte aligned base)
+    if (launch_codebook_fused(g, lut1, sem, W, bias, HW, C, D, S, t, dsem, partials, dlut_partial, workspace,
+                              static_cast<hipStream_t>(stream)) < 0)
+        return fail("goi_codebook_fused: supported shape is D = 256, 288 < C <= 304, 1 <= S <= 16, HW % 4 = 0, HW < 2^25");
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -306,149 +306,7 @@ struct PreprocessBwdArgs {
 };
 void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, const PreprocessBwdArgs& args,
                            hipStream_t s);
-int launch_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
-                           const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
-                           hipStream_t s);
-int codebook_loss_waves();
-int launch_codebook_rows(const float* sim, const float* inv_gnorm, const float* sem, const float* W, const float* bias,
-                         long long HW, int C, int S, float t, float* dsim, float* dsem, float* partials, hipStream_t s);
-size_t codebook_sim_workspace_bytes();
-int launch_codebook_sim(const float* g, const float* l1, long long HW, int C, int D, float* sim, float* inv_gnorm,
-                        void* workspace, hipStream_t s);
-int codebook_dlut_blocks();
-size_t codebook_fused_workspace_bytes(long long HW);
-int codebook_fused_rows();
-int launch_codebook_fused(const float* g, const float* l1, const float* sem, const float* W, const float* bias, long long HW,
-                          int C, int D, int S, float t, float* dsem, float* partials, float* dl1_partial, void* workspace,
-                          hipStream_t s);
-int launch_codebook_dlut(const float* dsim, const float* g, long long HW, int C, int D, float* partial, hipStream_t s);
-int osh_max_codes();
-int osh_max_dim();
-bool osh_register_path(int n_codes, int D);
-void launch_osh_counts(const int* idx, const uint8_t* positive, long long HW, int n_codes, int* counts, hipStream_t s);
-void launch_osh_fit(const float* lut, int n_codes, int D, const int* counts, long long HW, int K, float* w, float* b,
-                    float lr, int max_epochs, double target_iou, int* epochs_out, float* loss_out, double* iou_out,
-                    double* init_iou_out, double* trace, hipStream_t s);
-int launch_adam_step(const GoiAdamGroup* groups, int n_groups, double beta1, double beta2, double eps,
-                     const uint8_t* nograd_mask, const uint32_t* skip_flag, hipStream_t s);
-size_t knn_workspace_bytes(int P);
-int launch_knn(int P, const float* points, float* mean_dist2, void* workspace, hipStream_t s);
-size_t dbscan_workspace_bytes(size_t n);
-void launch_dbscan(int n, const float* pts, float eps2, double h, int min_samples, int* labels, uint8_t* core, int* result,
-                   void* workspace, hipStream_t s);
-void launch_mask_pack(const void* src, int src_dtype, int n_views, int H, int W, int first_view, uint64_t* packed,
-                      long long* counts, hipStream_t s);
-void launch_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, int W, int radius, hipStream_t s);
-void launch_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
-                        hipStream_t s);
-void launch_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, hipStream_t s);
-void launch_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, long long HW,
-                          int style, int normalize, float ratio, float one_minus_ratio, float heat_thresh, const float* table,
-                          int n_colors, void* out, int out_dtype, uint32_t* stats, hipStream_t s);
-size_t pca_fit_workspace_bytes(int S);
-size_t pca_stats_bytes(int n_views);
-void launch_pca_accumulate(const float* x, int layout, int S, long long n, const uint8_t* mask, int first, void* workspace,
-                           hipStream_t s);
-void launch_pca_solve(int S, void* workspace, float* basis, hipStream_t s);
-void launch_pca_apply(const float* x, int in_layout, int S, long long n, int n_views, const float* basis, int normalize,
-                      float two_k, float* out, int out_layout, uint32_t* stats, hipStream_t s);
-size_t field_density_workspace_bytes(long long P, int num_blocks, double relax_ratio);
-void launch_field_density(long long P, const float* xyz, const float* opacity, const float* scaling, const float* rotation,
-                          const uint8_t* selection, int selection_invert, float min_opacity, const float* attributes,
-                          const float* bounds, int R, int num_blocks, double relax_ratio, const float* coords,
-                          const float* block_lo, const float* block_hi, float* occ, float* attr_out, float* frame, int* status,
-                          void* workspace, hipStream_t s);
-size_t field_iso_workspace_bytes(long long N);
-void launch_field_iso_count(const float* grid, int X, int Y, int Z, float thresh, void* workspace, int* counts, hipStream_t s);
-void launch_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z, float thresh, const float* cx,
-                           const float* cy, const float* cz, const void* workspace, long long V, long long F, float* vertices,
-                           int* faces, float* colors, hipStream_t s);
-// mesh clean-up (mesh.hip); V, F >= 0, the sizes checked by api.hip
-size_t mesh_components_workspace_bytes(long long V, long long F);
-void launch_mesh_components(long long V, long long F, const int* faces, int* vertex_label, int* face_label, int* status,
-                            void* workspace, hipStream_t s);
-size_t mesh_clean_workspace_bytes(long long V, long long F);
-void launch_mesh_clean_plan(long long V, long long F, const float* vertices, const int* faces, long long min_faces,
-                            double min_diag2, void* workspace, int* counts, hipStream_t s);
-void launch_mesh_clean_emit(long long V, long long F, const float* vertices, const int* faces, const float* colors,
-                            const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
-                            float* out_colors, int* vertex_index, int* face_index, hipStream_t s);
-size_t mesh_decimate_workspace_bytes(long long V, long long F);
-void launch_mesh_decimate_members(long long V, long long F, const float* vertices, const int* faces, void* workspace, hipStream_t s);
-void launch_mesh_decimate_probe(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
-                                int* count, hipStream_t s);
-int launch_mesh_decimate_plan(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
-                              int* counts, hipStream_t s);
-void launch_mesh_decimate_emit(long long V, long long F, const float* vertices, const float* colors, int divisions, int sorted_in,
-                               const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
-                               float* out_colors, int* cluster, hipStream_t s);
-size_t mesh_normals_workspace_bytes(long long V, long long F);
-void launch_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
-                         void* workspace, hipStream_t s);
-// texture bake (texture.hip); the sizes checked by api.hip
-size_t texture_rasterize_workspace_bytes(long long F, int H, int W);
-void launch_texture_rasterize(long long V, long long F, const float* v_clip, const int* faces, int H, int W, int* tri, float* bary,
-                              float* zw, int* status, void* workspace, hipStream_t s);
-void launch_texture_resolve(long long n_vt, long long n_vn, long long F, int H, int W, const int* tri, const float* bary,
-                            const float* vt, const int* ft, const float* vn, const int* faces, const float* pose_rot,
-                            const float* image, float* coords, float* values, unsigned char* valid, int* status, hipStream_t s);
-size_t texture_grid_put_workspace_bytes(long long N, int C, int H, int W);
-void launch_texture_grid_put(long long N, int C, int H, int W, int min_resolution, const float* coords, const float* values,
-                             const unsigned char* valid, float* result, float* count, float* acc, float* acc_count, float* norm_out,
-                             unsigned char* norm_mask, int* status, void* workspace, hipStream_t s);
-void launch_texture_accumulate(long long T, int C, float* albedo, float* cnt, const float* cur, const float* cur_cnt, hipStream_t s);
-void launch_texture_normalize(long long T, int C, const float* albedo, const float* cnt, float* out, unsigned char* mask, hipStream_t s);
-size_t texture_fill_workspace_bytes(int h, int w);
-void launch_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
-                         void* workspace, hipStream_t s);
-size_t uniq_workspace_bytes(int V, int D, uint32_t HW);
-uint32_t* uniq_counts(void* ws, int V, int D, uint32_t HW);  // [V] counts, then the flag word
-void launch_uniq_dedup(const float* const* maps, int V, int D, uint32_t HW, void* ws, hipStream_t s);
-// true when the view went through the radix sorts (whose error bit lands in the flag word)
-bool launch_uniq_sort(const float* map, int v, int V, int D, uint32_t HW, uint32_t N, float* out, void* ws, hipStream_t s);
-size_t kmeans_workspace_bytes(long long rows, int K, int k, int D);
-void launch_kmeans(float* x, const long long* off, int K, long long max_rows, long long total_rows, int D, int k, int niter,
-                   const int* perms, float* centers, int* status, void* ws, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
-constexpr int PHOTO_RADIUS = GOI_PHOTOMETRIC_WINDOW / 2;  // the only window instantiated (photometric.hip)
-size_t photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags);
-void launch_photometric_forward(const float* x, const float* y, long long n, int c, int h, int w, float lambda, unsigned flags,
-                                float* out, float* out_images, void* ws, hipStream_t s);
-void launch_photometric_backward(const float* x, const float* y, long long n, int c, int h, int w, float lambda, unsigned flags,
-                                 const float* grad_out, const void* ws, float* gx, float* gy, hipStream_t s);
-
-// densification (densify.hip): thresholds rounded to fp32 once, and the workspace of a plan
-struct DensifyThresholds {
-    float max_grad, thr_scale, min_opacity, big_world, split_inv;
-    int screen, screen_all;  // max_screen_size truthy; 0 > max_screen_size (the zeroed radii test prunes every row)
-};
-struct DensifyView {
-    uint8_t* flags;     // [P] plan byte per original Gaussian
-    uint32_t* rank;     // [4P] keep / clone / children / split streams, scanned in place: destination rows
-    uint32_t* scratch;  // scan partials
-    uint32_t* total;
-};
-size_t densify_layout(long long P, char* base, DensifyView* v);
-void launch_densify_stats(long long P, const float* grad, long long stride, const uint8_t* filter, float* accum, float* denom,
-                          hipStream_t s);
-void launch_densify_plan(long long P, const float* accum, const float* denom, const float* scaling, const float* opacity,
-                         const DensifyThresholds& t, uint32_t* counts, const DensifyView& v, hipStream_t s);
-void launch_prune_plan(long long P, const uint8_t* mask, uint32_t* counts, const DensifyView& v, hipStream_t s);
-void launch_densify_apply(long long P, const GoiDensifyRows* groups, int n_groups, const float* rotation, const float* scaling,
-                          const float* z, long long n_split, long long kept_children, float split_inv, const DensifyView& v,
-                          hipStream_t s);
-
-// rigid edits of a selection (edit.hip)
-struct EditPointers {
-    float *xyz, *rotation, *scaling, *rest;  // parameters (NULL: not written)
-    float *m_xyz, *m_rotation, *m_rest;      // Adam first moments (NULL: none)
-    const float* pivot_dev;                  // NULL: the pivot of the GoiEditTransform
-};
-size_t edit_bounds_workspace_bytes(long long P);
-void launch_edit_bounds(long long P, const float* xyz, const uint8_t* selection, int invert, int* count, float* out, void* ws,
-                        hipStream_t s);
-void launch_edit_transform(long long P, int M, const uint8_t* selection, int invert, const GoiEditTransform& t,
-                           const EditPointers& p, hipStream_t s);
 
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).
 __device__ __forceinline__ void tile_rect(float px, float py, int r, int gx, int gy, int& x0, int& y0, int& x1,

@@ -39,9 +39,13 @@
 // Device flag word (result[1]): DBSCAN_FLAG_NONFINITE (NaN / inf input), DBSCAN_FLAG_SORT (a radix-sort look-back ran out of
 // its budget), DBSCAN_FLAG_RANGE (more than 2^21 cells on an axis), DBSCAN_FLAG_GRID (see C), DBSCAN_FLAG_UNION (a union-find
 // loop met its bound: cannot happen, see above).  Whenever it is non-zero the labels are not to be used.
+// C entries, with the limits they enforce, at the end of the file: goi_semantic_dbscan* (declared in include/goi_raster.h).
 #include <float.h>
 
+#include <cmath>
+
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
@@ -435,8 +439,6 @@ __global__ __launch_bounds__(DB_THREADS) void db_label_k(int n, const uint32_t* 
 
 inline unsigned grid_for(size_t n) { return (unsigned)((n + DB_THREADS - 1) / DB_THREADS); }
 
-}  // namespace
-
 // Workspace, 256-byte aligned pieces: control words (bounds, cell count) | keys[2] | vals[2] | sort scratch | sorted points |
 // point keys | head / representative flags | point cells | cell starts | cell keys | cell boxes | cell info | parents | minima |
 // ranks | core flags | scan scratch  (~ 90 bytes per point plus the sort's scratch)
@@ -509,4 +511,39 @@ void launch_dbscan(int n, const float* pts, float eps2, double h, int min_sample
                                                     eps2, labels, core, flags);
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_semantic_dbscan_workspace_bytes(long long n) {
+    return (n > 0 && n < SORT_MAX_KEYS) ? dbscan_workspace_bytes((size_t)n) : 0;
+}
+
+int goi_semantic_dbscan(long long n, const float* points, float eps, int min_samples, int* labels, uint8_t* core, int* result,
+                        void* workspace, void* stream) {
+    // (the cell keys go through radix_sort_pairs, exact below 2^30 keys: common.h)
+    if (n < 0 || n >= SORT_MAX_KEYS) return fail("goi_semantic_dbscan: need 0 <= n < 2^30");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail("goi_semantic_dbscan: eps must be a finite number > 0");
+    if (min_samples < 1) return fail("goi_semantic_dbscan: min_samples must be >= 1");
+    if (!result) return fail("goi_semantic_dbscan: result is NULL");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    GOI_HIP(hipMemsetAsync(result, 0, 2 * sizeof(int), s));
+    if (n == 0) return 0;
+    if (!points || !labels) return fail("goi_semantic_dbscan: a required pointer is NULL");
+    if (check_workspace("goi_semantic_dbscan", workspace) < 0) return -1;
+    if (!(eps >= 0x1p-40f && eps <= 0x1p40f)) {  // outside the range of the grid's exactness argument (top of this file)
+        GOI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(result + 1), DBSCAN_FLAG_RANGE, 1, s));
+        return 0;
+    }
+    const float eps2 = eps * eps;
+    const double h = (double)eps / std::sqrt(3.0) * (1.0 - 1.0 / 4096.0);  // cell side: eps / sqrt(3) less a margin
+    launch_dbscan((int)n, points, eps2, h, min_samples, labels, core, result, workspace, s);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -27,9 +27,23 @@
 //          reciprocal); its prune test takes exp of that again
 //   child xyz = build_rotation(q) (utils/general_utils.py:89-110) @ (Z * exp(s) + 0) + xyz
 // Thresholds arrive rounded to fp32 once, as torch rounds a Python scalar for a comparison with an fp32 tensor.
+// C entries, with the limits they enforce, at the end of the file: goi_raster_densify_* (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 
 namespace goi {
+
+// thresholds rounded to fp32 once, and the workspace of a plan
+struct DensifyThresholds {
+    float max_grad, thr_scale, min_opacity, big_world, split_inv;
+    int screen, screen_all;  // max_screen_size truthy; 0 > max_screen_size (the zeroed radii test prunes every row)
+};
+struct DensifyView {
+    uint8_t* flags;     // [P] plan byte per original Gaussian
+    uint32_t* rank;     // [4P] keep / clone / children / split streams, scanned in place: destination rows
+    uint32_t* scratch;  // scan partials
+    uint32_t* total;
+};
 
 namespace {
 
@@ -236,8 +250,6 @@ __global__ __launch_bounds__(DENS_THREADS) void densify_apply_k(const ApplyTable
 
 inline size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
 
-}  // namespace
-
 // [P] plan bytes | [4P] streams, scanned in place | scan partials | total
 size_t densify_layout(long long P, char* base, DensifyView* v) {
     Carver c(base);
@@ -248,13 +260,6 @@ size_t densify_layout(long long P, char* base, DensifyView* v) {
     d.total = c.take<uint32_t>(64);
     if (v) *v = d;
     return c.end();
-}
-
-void launch_densify_stats(long long P, const float* grad, long long stride, const uint8_t* filter, float* accum, float* denom,
-                          hipStream_t s) {
-    if (P <= 0) return;
-    densify_stats_k<<<dim3((unsigned)div_up((size_t)P, DENS_THREADS)), dim3(DENS_THREADS), 0, s>>>(P, grad, stride, filter, accum,
-                                                                                                    denom);
 }
 
 void launch_densify_plan(long long P, const float* accum, const float* denom, const float* scaling, const float* opacity,
@@ -310,4 +315,90 @@ void launch_densify_apply(long long P, const GoiDensifyRows* groups, int n_group
     densify_apply_k<<<dim3(gx, gy), dim3(DENS_THREADS), 0, s>>>(t, a, blocks);
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_raster_densify_workspace_bytes(long long P) {
+    return (P >= 0 && P < (1ll << 30)) ? densify_layout(P, nullptr, nullptr) + 256 : 0;
+}
+
+int goi_raster_densify_stats(long long P, const float* grad, long long grad_stride, const unsigned char* filter, float* accum,
+                             float* denom, void* stream) {
+    const std::string fn = "goi_raster_densify_stats: ";
+    if (P < 0 || P >= (1ll << 31)) return fail(fn + "need 0 <= P < 2^31");
+    if (grad_stride < 2) return fail(fn + "grad_stride must be >= 2");
+    if (P > 0 && (!grad || !filter || !accum || !denom)) return fail(fn + "a required pointer is NULL");
+    if (P > 0)
+        densify_stats_k<<<dim3((unsigned)div_up((size_t)P, DENS_THREADS)), dim3(DENS_THREADS), 0, static_cast<hipStream_t>(stream)>>>(
+            P, grad, grad_stride, filter, accum, denom);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_densify_plan(long long P, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                            double max_grad, double scale_threshold, double min_opacity, int screen_test, double max_screen_size,
+                            double big_threshold, unsigned* counts, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_densify_plan: ";
+    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
+    if (!counts || (P > 0 && (!accum || !denom || !scaling || !opacity))) return fail(fn + "a required pointer is NULL");
+    if (check_workspace("goi_raster_densify_plan", workspace) < 0) return -1;
+    refresh_options();
+    DensifyView v;
+    densify_layout(P, static_cast<char*>(workspace), &v);
+    DensifyThresholds t;
+    t.max_grad = (float)max_grad;  // a Python scalar meets an fp32 tensor: rounded to fp32 once
+    t.thr_scale = (float)scale_threshold;
+    t.min_opacity = (float)min_opacity;
+    t.big_world = (float)big_threshold;
+    t.split_inv = 1.0f / (float)(0.8 * 2);  // torch's reciprocal of the CPU scalar 0.8 * N
+    t.screen = screen_test != 0;
+    t.screen_all = 0.0f > (float)max_screen_size;  // max_radii2D is all zeros when the reference tests it
+    launch_densify_plan(P, accum, denom, scaling, opacity, t, counts, v, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_densify_prune_plan(long long P, const unsigned char* mask, unsigned* counts, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_densify_prune_plan: ";
+    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
+    if (!counts || (P > 0 && !mask)) return fail(fn + "a required pointer is NULL");
+    if (check_workspace("goi_raster_densify_prune_plan", workspace) < 0) return -1;
+    refresh_options();
+    DensifyView v;
+    densify_layout(P, static_cast<char*>(workspace), &v);
+    launch_prune_plan(P, mask, counts, v, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_densify_apply(long long P, const GoiDensifyRows* groups, int n_groups, const float* rotation, const float* scaling,
+                             const float* z, long long n_split, long long kept_children, const void* workspace, void* stream) {
+    const std::string fn = "goi_raster_densify_apply: ";
+    if (P < 0 || P >= (1ll << 30)) return fail(fn + "need 0 <= P < 2^30");
+    if (n_groups < 0 || n_groups > GOI_DENSIFY_MAX_GROUPS) return fail(fn + "n_groups must be 0..24");
+    if (n_groups && !groups) return fail(fn + "groups is NULL");
+    if (n_split < 0 || n_split > P || kept_children < 0 || kept_children > n_split) return fail(fn + "bad n_split / kept_children");
+    if (check_workspace("goi_raster_densify_apply", workspace) < 0) return -1;
+    for (int k = 0; k < n_groups; k++) {
+        const GoiDensifyRows& g = groups[k];
+        if (g.row_len < 1 || g.rows < 0 || g.mode < GOI_DENSIFY_PARAM || g.mode > GOI_DENSIFY_ZERO) return fail(fn + "bad group");
+        if (g.mode != GOI_DENSIFY_ZERO && g.rows != P) return fail(fn + "a copied group must have P source rows");
+        if (g.rows > 0 && (!g.dst || (g.mode != GOI_DENSIFY_ZERO && !g.src))) return fail(fn + "a group pointer is NULL");
+        if ((g.mode == GOI_DENSIFY_XYZ || g.mode == GOI_DENSIFY_SCALING) && g.row_len != 3) return fail(fn + "xyz / scaling rows are 3 floats");
+        if (g.mode == GOI_DENSIFY_XYZ && kept_children > 0 && (!rotation || !scaling || !z))
+            return fail(fn + "children's xyz need rotation, scaling and z");
+    }
+    DensifyView v;
+    densify_layout(P, static_cast<char*>(const_cast<void*>(workspace)), &v);
+    launch_densify_apply(P, groups, n_groups, rotation, scaling, z, n_split, kept_children, 1.0f / (float)(0.8 * 2), v,
+                         static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -30,7 +30,9 @@
 //                    is clamped into [0, K-1] and a NaN rel takes index 0: no input reads outside the table.
 //
 // Neither allocates, copies or synchronises: both are asynchronous on the caller's stream.
+// C entries, with the limits they enforce, at the end of the file: goi_semantic_frame_* (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
@@ -271,8 +273,6 @@ void compose_dispatch(const FrameParams& p, int out_dtype, dim3 grid, hipStream_
 
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
-}  // namespace
-
 void launch_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, long long HW,
                           int style, int normalize, float ratio, float one_minus_ratio, float heat_thresh, const float* table,
                           int n_colors, void* out, int out_dtype, uint32_t* stats, hipStream_t s) {
@@ -317,4 +317,40 @@ void launch_frame_compose(const float* base, int channels, const float* sim, con
     }
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_semantic_frame_workspace_bytes(int n_views) { return n_views < 1 ? 0 : sizeof(uint32_t) * 3 * (size_t)n_views; }
+
+int goi_semantic_frame_compose(const float* base, int channels, const float* sim, const uint8_t* bg_mask, int n_views, int H, int W,
+                               int style, int normalize, double overlay_ratio, double heat_thresh, const float* table,
+                               int n_colors, void* out, int out_dtype, void* workspace, void* stream) {
+    const char* fn = "goi_semantic_frame_compose";
+    if (mask_dims(fn, H, W) < 0) return -1;
+    if (style < GOI_FRAME_NONE || style > GOI_FRAME_HEAT_FT) return fail(std::string(fn) + ": unknown style");
+    if (out_dtype != GOI_FRAME_F32 && out_dtype != GOI_FRAME_U8) return fail(std::string(fn) + ": out_dtype must be GOI_FRAME_F32 or GOI_FRAME_U8");
+    if (channels != 1 && channels != 3) return fail(std::string(fn) + ": channels must be 1 or 3");
+    if (n_views < 0 || n_views > 65535) return fail(std::string(fn) + ": need 0 <= n_views <= 65535");
+    if (n_views == 0) return 0;
+    const bool heat = style == GOI_FRAME_HEAT || style == GOI_FRAME_HEAT_FT;
+    const bool need_base = style != GOI_FRAME_BINARY;
+    if (!out || (need_base && !base)) return fail(std::string(fn) + ": NULL base or out");
+    if ((heat || style == GOI_FRAME_BINARY) && !sim) return fail(std::string(fn) + ": this style needs sim");
+    if ((heat || style == GOI_FRAME_WHITEN) && !bg_mask) return fail(std::string(fn) + ": this style needs bg_mask");
+    if (heat && (!table || n_colors < 2 || n_colors > GOI_FRAME_MAX_COLORS))
+        return fail(std::string(fn) + ": the heat styles need a table of 2 .. GOI_FRAME_MAX_COLORS (1024) colours");
+    if (((normalize && need_base) || style == GOI_FRAME_HEAT) && !workspace) return fail(std::string(fn) + ": NULL workspace");
+    if (!(overlay_ratio == overlay_ratio) || !(heat_thresh == heat_thresh)) return fail(std::string(fn) + ": NaN overlay_ratio or heat_thresh");
+    launch_frame_compose(base, channels, sim, bg_mask, n_views, (long long)H * W, style, normalize, (float)overlay_ratio,
+                         (float)(1.0 - overlay_ratio), (float)heat_thresh, table, n_colors, out, out_dtype,
+                         static_cast<uint32_t*>(workspace), static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

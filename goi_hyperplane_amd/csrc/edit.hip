@@ -19,9 +19,17 @@
 //
 // This TU is compiled with -ffp-contract=off: every product and every sum below rounds once, in the order written, which is the
 // order of tests/edit_reference.py.  No float atomics, no inline assembly.
+// C entries, with the limits they enforce, at the end of the file: goi_edit_* (declared in include/goi_raster.h).
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
+
+struct EditPointers {
+    float *xyz, *rotation, *scaling, *rest;  // parameters (NULL: not written)
+    float *m_xyz, *m_rotation, *m_rest;      // Adam first moments (NULL: none)
+    const float* pivot_dev;                  // NULL: the pivot of the GoiEditTransform
+};
 
 namespace {
 
@@ -256,8 +264,6 @@ __global__ __launch_bounds__(EDIT_WAVE) void edit_transform_k(long long P, const
     }
 }
 
-}  // namespace
-
 size_t edit_bounds_workspace_bytes(long long P) { return (size_t)(bounds_blocks(P) + 1) * sizeof(BoundsPartial); }
 
 void launch_edit_bounds(long long P, const float* xyz, const uint8_t* selection, int invert, int* count, float* out, void* ws,
@@ -284,4 +290,54 @@ void launch_edit_transform(long long P, int M, const uint8_t* selection, int inv
         edit_transform_k<0><<<grid, block, 0, s>>>(P, selection, invert, t, p);
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_edit_bounds_workspace_bytes(long long P) {
+    return (P >= 0 && P < (1ll << 31)) ? edit_bounds_workspace_bytes(P) + 256 : 0;
+}
+
+int goi_edit_bounds(long long P, const float* xyz, const unsigned char* selection, int invert, int* count, float* out,
+                    void* workspace, void* stream) {
+    const char* fn = "goi_edit_bounds";
+    if (P < 0 || P >= (1ll << 31)) return fail(std::string(fn) + ": need 0 <= P < 2^31");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    if (!count || !out || (P > 0 && !xyz)) return fail(std::string(fn) + ": a required pointer is NULL");
+    launch_edit_bounds(P, xyz, selection, invert, count, out, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_edit_transform(long long P, int M, const unsigned char* selection, int invert, const GoiEditTransform* t, float* xyz,
+                       float* rotation, float* scaling, float* features_rest, float* m_xyz, float* m_rotation,
+                       float* m_features_rest, const float* pivot_dev, void* stream) {
+    const char* fn = "goi_edit_transform";
+    if (P < 0 || P >= (1ll << 31)) return fail(std::string(fn) + ": need 0 <= P < 2^31");
+    if (M != 1 && M != 4 && M != 9 && M != 16) return fail(std::string(fn) + ": M must be 1, 4, 9 or 16");
+    if (!t) return fail(std::string(fn) + ": the transform is NULL");
+    if (t->flags & ~(GOI_EDIT_ROTATE | GOI_EDIT_SCALE)) return fail(std::string(fn) + ": unknown flag bits");
+    const bool rotate = (t->flags & GOI_EDIT_ROTATE) != 0, scale = (t->flags & GOI_EDIT_SCALE) != 0;
+    if (!rotate && (m_xyz || m_rotation || m_features_rest)) return fail(std::string(fn) + ": moments are only turned by a rotation");
+    if (M == 1 && m_features_rest) return fail(std::string(fn) + ": M = 1 has no features_rest moment");
+    if (P > 0 && (!xyz || (rotate && !rotation) || (scale && !scaling) || (rotate && M > 1 && !features_rest)))
+        return fail(std::string(fn) + ": a required pointer is NULL");
+    EditPointers p;
+    p.xyz = xyz;
+    p.rotation = rotation;
+    p.scaling = scaling;
+    p.rest = M > 1 ? features_rest : nullptr;
+    p.m_xyz = m_xyz;
+    p.m_rotation = m_rotation;
+    p.m_rest = m_features_rest;
+    p.pivot_dev = pivot_dev;
+    launch_edit_transform(P, M, selection, invert, *t, p, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

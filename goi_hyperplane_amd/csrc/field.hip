@@ -28,7 +28,9 @@
 // the permutation, a lone vertex at tetrahedron index m gives the triangle (m j, m k, m l), j < k < l, the orientation
 // s (-1)^m (positive: its normal points away from m); two inside vertices a < b against c < d give the quad
 // (ac, ad, bd, bc) with orientation s sign(a b c d) (positive: towards c d).
+// C entries, with the limits they enforce, at the end of the file: goi_field_* (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 #include <math.h>
@@ -530,8 +532,6 @@ size_t iso_layout(size_t N, char* base, IsoView* v) {
 
 unsigned blocks_for(long long n) { return (unsigned)((n + FIELD_THREADS - 1) / FIELD_THREADS); }
 
-}  // namespace
-
 size_t field_density_workspace_bytes(long long P, int num_blocks, double relax_ratio) {
     return field_layout((size_t)P, field_lattice(num_blocks, relax_ratio).ncells, nullptr, nullptr);
 }
@@ -604,4 +604,103 @@ void launch_field_iso_emit(const float* grid, const float* attr, int X, int Y, i
     if (F > 0) iso_face_k<<<dim3(blocks_for(D.N)), dim3(FIELD_THREADS), 0, s>>>(grid, D, thresh, v.counts, v.emask, V, F, faces);
 }
 
+int field_dims(int R, int num_blocks, double relax_ratio) {
+    if (num_blocks < 1 || R < 1 || R > GOI_FIELD_MAX_RESOLUTION || R % num_blocks != 0) return -1;
+    const int split = R / num_blocks;
+    if (split < GOI_FIELD_MIN_SPLIT || split > GOI_FIELD_MAX_SPLIT) return -1;
+    if (!(relax_ratio >= 0.0 && relax_ratio <= GOI_FIELD_MAX_RELAX)) return -1;
+    return 0;
+}
+
+int iso_dims(const char* fn, int X, int Y, int Z) {
+    // at most 7 crossings per point and 12 triangles per cube: 19 * 2^26 < 2^32 keeps the one scan over both streams, and each
+    // count (< 2^31) an int32
+    if (X < 1 || Y < 1 || Z < 1 || (long long)X * Y * Z > GOI_FIELD_MAX_GRID_POINTS)
+        return fail(std::string(fn) + ": need X, Y, Z >= 1 and X Y Z <= 2^26");
+    return 0;
+}
+
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_field_density_workspace_bytes(long long P, int resolution, int num_blocks, double relax_ratio) {
+    if (P < 1 || P >= SORT_MAX_KEYS || field_dims(resolution, num_blocks, relax_ratio) < 0) return 0;
+    return field_density_workspace_bytes(P, num_blocks, relax_ratio);
+}
+
+int goi_field_density(long long P, const float* xyz, const float* opacity, const float* scaling, const float* rotation,
+                      const uint8_t* selection, int selection_invert, double min_opacity, const float* attributes,
+                      const float* bounds, int resolution, int num_blocks, double relax_ratio, const float* coords,
+                      const float* block_lo, const float* block_hi, float* occ, float* attr_out, float* frame, int* status,
+                      void* workspace, void* stream) {
+    const char* fn = "goi_field_density";
+    if (P < 0 || P >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need 0 <= P < 2^30");
+    if (field_dims(resolution, num_blocks, relax_ratio) < 0)
+        return fail(std::string(fn) + ": need resolution <= 256, resolution % num_blocks == 0, 4 <= resolution / num_blocks <= 16 "
+                                      "and 0 <= relax_ratio <= 4");
+    if (!(min_opacity == min_opacity)) return fail(std::string(fn) + ": NaN min_opacity");
+    if (!occ || !frame || !status || !coords || !block_lo || !block_hi) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (attributes && !attr_out) return fail(std::string(fn) + ": attributes need attr_out");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t vol = (size_t)resolution * resolution * resolution;
+    if (P == 0) {  // an empty model: zero grids, the caller's frame or (0, 0, 0, 1)
+        GOI_HIP(hipMemsetAsync(occ, 0, sizeof(float) * vol, s));
+        if (attr_out) GOI_HIP(hipMemsetAsync(attr_out, 0, sizeof(float) * 3 * vol, s));
+        GOI_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
+        if (bounds) {
+            GOI_HIP(hipMemcpyAsync(frame, bounds, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        } else {
+            GOI_HIP(hipMemsetAsync(frame, 0, 3 * sizeof(float), s));
+            GOI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(frame + 3), 0x3F800000, 1, s));  // 1.0f
+        }
+        return 0;
+    }
+    if (!xyz || !opacity || !scaling || !rotation) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    launch_field_density(P, xyz, opacity, scaling, rotation, selection, selection_invert ? 1 : 0, (float)min_opacity, attributes,
+                         bounds, resolution, num_blocks, relax_ratio, coords, block_lo, block_hi, occ, attr_out, frame, status,
+                         workspace, s);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_field_iso_workspace_bytes(int X, int Y, int Z) {
+    if (X < 1 || Y < 1 || Z < 1 || (long long)X * Y * Z > GOI_FIELD_MAX_GRID_POINTS) return 0;
+    return field_iso_workspace_bytes((long long)X * Y * Z);
+}
+
+int goi_field_iso_count(const float* grid, int X, int Y, int Z, double thresh, void* workspace, int* counts, void* stream) {
+    const char* fn = "goi_field_iso_count";
+    if (iso_dims(fn, X, Y, Z) < 0) return -1;
+    if (!(thresh == thresh)) return fail(std::string(fn) + ": NaN thresh");
+    if (!grid || !counts) return fail(std::string(fn) + ": NULL grid or counts");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    launch_field_iso_count(grid, X, Y, Z, (float)thresh, workspace, counts, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_field_iso_emit(const float* grid, const float* attr, int X, int Y, int Z, double thresh, const float* cx, const float* cy,
+                       const float* cz, const void* workspace, long long n_vertices, long long n_faces, float* vertices, int* faces,
+                       float* colors, void* stream) {
+    const char* fn = "goi_field_iso_emit";
+    if (iso_dims(fn, X, Y, Z) < 0) return -1;
+    if (!(thresh == thresh)) return fail(std::string(fn) + ": NaN thresh");
+    if (n_vertices < 0 || n_faces < 0 || n_vertices >= (1ll << 31) || n_faces >= (1ll << 31))
+        return fail(std::string(fn) + ": need 0 <= n_vertices, n_faces < 2^31");
+    if (!grid) return fail(std::string(fn) + ": NULL grid");
+    if ((n_vertices > 0 && !vertices) || (n_faces > 0 && !faces)) return fail(std::string(fn) + ": NULL vertices or faces");
+    if (attr && n_vertices > 0 && !colors) return fail(std::string(fn) + ": attr needs colors");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    launch_field_iso_emit(grid, attr, X, Y, Z, (float)thresh, cx, cy, cz, workspace, n_vertices, n_faces, vertices, faces, colors,
+                          static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

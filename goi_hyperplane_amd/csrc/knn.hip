@@ -21,9 +21,11 @@
 //     third best sits the box out.
 // Distances are evaluated as fma(dz,dz, fma(dx,dx, dy*dy)) (this TU is compiled with
 // -ffp-contract=off so that the spelling is the arithmetic), the form oracle/knn_oracle.cpp mirrors.
+// C entries, with the limits they enforce, at the end of the file: goi_knn_* (declared in include/goi_raster.h).
 #include <float.h>
 
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
@@ -210,8 +212,6 @@ __global__ __launch_bounds__(KNN_BOX) void knn_search_k(int P, int nbox, const f
     if (live) out[__float_as_uint(q.w)] = (b0 + b1 + b2) / 3.0f;
 }
 
-}  // namespace
-
 // Workspace: bounds (6 encoded words) | Morton keys, ids and the sort's scratch | sorted points, padded to whole boxes | boxes
 struct KnnView {
     uint32_t* enc;  // [8]
@@ -247,4 +247,26 @@ int launch_knn(int P, const float* points, float* mean_dist2, void* workspace, h
     return 0;
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_knn_workspace_bytes(int P) { return P > 0 && P < SORT_MAX_KEYS ? knn_workspace_bytes(P) : 0; }
+
+int goi_knn_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream) {
+    if (P < 0) return fail("goi_knn_dist2: bad P");
+    // (the Morton codes go through radix_sort_pairs, exact below 2^30 keys: common.h)
+    if (P >= SORT_MAX_KEYS) return fail("goi_knn_dist2: need P < 2^30");
+    if (P == 0) return 0;
+    if (!points || !mean_dist2) return fail("goi_knn_dist2: a required pointer is NULL");
+    if (check_workspace("goi_knn_dist2", workspace) < 0) return -1;
+    launch_knn(P, points, mean_dist2, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

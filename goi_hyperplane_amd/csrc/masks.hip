@@ -17,7 +17,9 @@
 //   mask_confusion_k  TP / FP / FN / TN per view by popcounts; one workgroup per view, a fixed reduction order.
 //
 // None of them allocates, copies or synchronises: every launch is asynchronous on the caller's stream.
+// C entries, with the limits they enforce, at the end of the file: goi_semantic_mask_* (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
@@ -173,8 +175,20 @@ inline int grid_for(long long items, int per_block, int cap) {
 
 }  // namespace
 
-void launch_mask_pack(const void* src, int src_dtype, int n_views, int H, int W, int first_view, uint64_t* packed,
-                      long long* counts, hipStream_t s) {
+}  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+int goi_semantic_mask_pack(const void* src, int src_dtype, int n_views, int H, int W, int first_view, uint64_t* packed, long long* counts,
+                  void* stream) {
+    if (mask_dims("goi_semantic_mask_pack", H, W) < 0) return -1;
+    if (src_dtype != GOI_MASK_F32 && src_dtype != GOI_MASK_U8) return fail("goi_semantic_mask_pack: src_dtype must be GOI_MASK_F32 or GOI_MASK_U8");
+    if (n_views < 0 || n_views > 65535 || first_view < 0) return fail("goi_semantic_mask_pack: need 0 <= n_views <= 65535, first_view >= 0");
+    if (n_views == 0) return 0;
+    if (!src || !packed) return fail("goi_semantic_mask_pack: NULL src or packed");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
     const int Wwords = (W + 63) / 64;
     const dim3 grid(grid_for((long long)H * Wwords, PACK_WAVES * PACK_UNROLL, 64), n_views);
     auto* c = reinterpret_cast<unsigned long long*>(counts);
@@ -182,25 +196,49 @@ void launch_mask_pack(const void* src, int src_dtype, int n_views, int H, int W,
         mask_pack_k<float><<<grid, PACK_THREADS, 0, s>>>(static_cast<const float*>(src), H, W, Wwords, first_view, packed, c);
     else
         mask_pack_k<uint8_t><<<grid, PACK_THREADS, 0, s>>>(static_cast<const uint8_t*>(src), H, W, Wwords, first_view, packed, c);
+    GOI_HIP(hipGetLastError());
+    return 0;
 }
 
-void launch_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, int W, int radius, hipStream_t s) {
+int goi_semantic_mask_dilate(const uint64_t* src, uint64_t* dst, int n_views, int H, int W, int radius, void* stream) {
+    if (mask_dims("goi_semantic_mask_dilate", H, W) < 0) return -1;
+    if (radius < 0 || radius > GOI_MASK_MAX_RADIUS) return fail("goi_semantic_mask_dilate: need 0 <= radius <= 63");
+    if (n_views < 0) return fail("goi_semantic_mask_dilate: need n_views >= 0");
+    if (n_views == 0) return 0;
+    if (!src || !dst) return fail("goi_semantic_mask_dilate: NULL src or dst");
+    if (src == dst) return fail("goi_semantic_mask_dilate: dst must not be src");
     const int Wwords = (W + 63) / 64;
     const long long total = (long long)n_views * H * Wwords;
-    mask_dilate_k<<<grid_for(total, MASK_THREADS, 4096), MASK_THREADS, 0, s>>>(src, dst, total, H, W, Wwords, radius);
+    mask_dilate_k<<<grid_for(total, MASK_THREADS, 4096), MASK_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+        src, dst, total, H, W, Wwords, radius);
+    GOI_HIP(hipGetLastError());
+    return 0;
 }
 
-void launch_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
-                        hipStream_t s) {
+int goi_semantic_mask_unpack(const uint64_t* packed, int n_views, int H, int W, int n_out, const long long* index, uint8_t* out,
+                             void* stream) {
+    if (mask_dims("goi_semantic_mask_unpack", H, W) < 0) return -1;
+    if (n_out < 0 || n_views < 0) return fail("goi_semantic_mask_unpack: need n_out >= 0 and n_views >= 0");
+    if (n_out == 0) return 0;
+    if (!packed || !out) return fail("goi_semantic_mask_unpack: NULL packed or out");
     const int Wwords = (W + 63) / 64;
     const long long total = (long long)n_out * H * W;
-    mask_unpack_k<<<grid_for(total, MASK_THREADS, 8192), MASK_THREADS, 0, s>>>(packed, n_views, index, total, H, W, Wwords, out);
+    mask_unpack_k<<<grid_for(total, MASK_THREADS, 8192), MASK_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+        packed, n_views, index, total, H, W, Wwords, out);
+    GOI_HIP(hipGetLastError());
+    return 0;
 }
 
-void launch_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, hipStream_t s) {
+int goi_semantic_mask_confusion(const uint64_t* pred, const uint64_t* gt, int n_views, int H, int W, long long* out, void* stream) {
+    if (mask_dims("goi_semantic_mask_confusion", H, W) < 0) return -1;
+    if (n_views < 0) return fail("goi_semantic_mask_confusion: need n_views >= 0");
+    if (n_views == 0) return 0;
+    if (!pred || !gt || !out) return fail("goi_semantic_mask_confusion: NULL pred, gt or out");
     const int Wwords = (W + 63) / 64;
     const uint64_t tail = (W & 63) ? ((1ull << (W & 63)) - 1ull) : ~0ull;
-    mask_confusion_k<<<n_views, MASK_THREADS, 0, s>>>(pred, gt, H, Wwords, tail, out);
+    mask_confusion_k<<<n_views, MASK_THREADS, 0, static_cast<hipStream_t>(stream)>>>(pred, gt, H, Wwords, tail, out);
+    GOI_HIP(hipGetLastError());
+    return 0;
 }
 
-}  // namespace goi
+}  // extern "C"

@@ -20,7 +20,9 @@
 //                faces mapped through the cells, dedup, two scans.
 //   normals      a stable sort of (vertex, 3 face + corner); one lane per vertex finds its run by binary search and adds the
 //                faces' cross products in ascending (face, corner) order.
+// C entries, with the limits they enforce, at the end of the file: goi_mesh_* (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 #include <math.h>
@@ -636,8 +638,6 @@ size_t norm_layout(size_t C, char* base, NormView* v) {
     return c.bytes();
 }
 
-}  // namespace
-
 size_t mesh_components_workspace_bytes(long long V, long long F) { return comp_layout((size_t)V, nullptr, nullptr); }
 
 void launch_mesh_components(long long V, long long F, const int* faces, int* vertex_label, int* face_label, int* status,
@@ -767,4 +767,135 @@ void launch_mesh_normals(long long V, long long F, const float* vertices, const 
                                                                         w.sb.vals[fin], normals);
 }
 
+bool mesh_sizes_ok(long long V, long long F, long long min_each) {
+    return V >= min_each && F >= min_each && V < SORT_MAX_KEYS && 3 * F < SORT_MAX_KEYS;
+}
+int mesh_divisions(const char* fn, int divisions) {
+    if (divisions < 1 || divisions > GOI_MESH_MAX_DIVISIONS) return fail(std::string(fn) + ": need 1 <= divisions <= 1024");
+    return 0;
+}
+
+}  // namespace
+
+int mesh_sizes(const char* fn, long long V, long long F, long long min_each) {
+    if (!mesh_sizes_ok(V, F, min_each))
+        return fail(std::string(fn) + ": need " + std::to_string(min_each) + " <= V, F and V, 3 F < 2^30");
+    return 0;
+}
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_mesh_components_workspace_bytes(long long V, long long F) {
+    return mesh_sizes_ok(V, F, 0) ? mesh_components_workspace_bytes(V, F) : 0;
+}
+
+int goi_mesh_components(long long V, long long F, const int* faces, int* vertex_label, int* face_label, int* status,
+                        void* workspace, void* stream) {
+    const char* fn = "goi_mesh_components";
+    if (mesh_sizes(fn, V, F, 0) < 0 || check_workspace(fn, workspace) < 0) return -1;
+    if (!status || (V > 0 && !vertex_label) || (F > 0 && (!faces || !face_label)))
+        return fail(std::string(fn) + ": a required pointer is NULL");
+    launch_mesh_components(V, F, faces, vertex_label, face_label, status, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_mesh_clean_workspace_bytes(long long V, long long F) {
+    return mesh_sizes_ok(V, F, 1) ? mesh_clean_workspace_bytes(V, F) : 0;
+}
+
+int goi_mesh_clean_plan(long long V, long long F, const float* vertices, const int* faces, long long min_faces, double min_diag2,
+                        void* workspace, int* counts, void* stream) {
+    const char* fn = "goi_mesh_clean_plan";
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
+    if (!vertices || !faces || !counts) return fail(std::string(fn) + ": NULL vertices, faces or counts");
+    if (!(min_diag2 >= 0.0)) return fail(std::string(fn) + ": need min_diag2 >= 0");
+    launch_mesh_clean_plan(V, F, vertices, faces, min_faces, min_diag2, workspace, counts, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_mesh_clean_emit(long long V, long long F, const float* vertices, const int* faces, const float* colors,
+                        const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
+                        float* out_colors, int* vertex_index, int* face_index, void* stream) {
+    const char* fn = "goi_mesh_clean_emit";
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
+    if (n_vertices < 0 || n_vertices > V || n_faces < 0 || n_faces > F) return fail(std::string(fn) + ": counts out of range");
+    if (!vertices || !faces) return fail(std::string(fn) + ": NULL vertices or faces");
+    if ((n_vertices > 0 && (!out_vertices || !vertex_index)) || (n_faces > 0 && (!out_faces || !face_index)))
+        return fail(std::string(fn) + ": NULL output");
+    if (colors && n_vertices > 0 && !out_colors) return fail(std::string(fn) + ": colors need out_colors");
+    launch_mesh_clean_emit(V, F, vertices, faces, colors, workspace, n_vertices, n_faces, out_vertices, out_faces, out_colors,
+                           vertex_index, face_index, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_mesh_decimate_workspace_bytes(long long V, long long F) {
+    return mesh_sizes_ok(V, F, 1) ? mesh_decimate_workspace_bytes(V, F) : 0;
+}
+
+int goi_mesh_decimate_members(long long V, long long F, const float* vertices, const int* faces, void* workspace, void* stream) {
+    const char* fn = "goi_mesh_decimate_members";
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0) return -1;
+    if (!vertices || !faces) return fail(std::string(fn) + ": NULL vertices or faces");
+    launch_mesh_decimate_members(V, F, vertices, faces, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_mesh_decimate_probe(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
+                            int* count, void* stream) {
+    const char* fn = "goi_mesh_decimate_probe";
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
+    if (!vertices || !faces || !count) return fail(std::string(fn) + ": NULL vertices, faces or count");
+    launch_mesh_decimate_probe(V, F, vertices, faces, divisions, workspace, count, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_mesh_decimate_plan(long long V, long long F, const float* vertices, const int* faces, int divisions, void* workspace,
+                           int* counts, void* stream) {
+    const char* fn = "goi_mesh_decimate_plan";
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
+    if (!vertices || !faces || !counts) return fail(std::string(fn) + ": NULL vertices, faces or counts");
+    const int fin = launch_mesh_decimate_plan(V, F, vertices, faces, divisions, workspace, counts, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return fin;
+}
+
+int goi_mesh_decimate_emit(long long V, long long F, const float* vertices, const float* colors, int divisions, int sorted_in,
+                           const void* workspace, long long n_vertices, long long n_faces, float* out_vertices, int* out_faces,
+                           float* out_colors, int* cluster, void* stream) {
+    const char* fn = "goi_mesh_decimate_emit";
+    if (mesh_sizes(fn, V, F, 1) < 0 || check_workspace(fn, workspace) < 0 || mesh_divisions(fn, divisions) < 0) return -1;
+    if (sorted_in != 0 && sorted_in != 1) return fail(std::string(fn) + ": sorted_in must be what goi_mesh_decimate_plan returned");
+    if (n_vertices < 0 || n_vertices > V || n_faces < 0 || n_faces > F) return fail(std::string(fn) + ": counts out of range");
+    if (!vertices || !cluster) return fail(std::string(fn) + ": NULL vertices or cluster");
+    if ((n_vertices > 0 && !out_vertices) || (n_faces > 0 && !out_faces)) return fail(std::string(fn) + ": NULL output");
+    if (colors && n_vertices > 0 && !out_colors) return fail(std::string(fn) + ": colors need out_colors");
+    launch_mesh_decimate_emit(V, F, vertices, colors, divisions, sorted_in, workspace, n_vertices, n_faces, out_vertices, out_faces,
+                              out_colors, cluster, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_mesh_normals_workspace_bytes(long long V, long long F) {
+    return mesh_sizes_ok(V, F, 0) ? mesh_normals_workspace_bytes(V, F) : 0;
+}
+
+int goi_mesh_normals(long long V, long long F, const float* vertices, const int* faces, float* normals, int* status,
+                     void* workspace, void* stream) {
+    const char* fn = "goi_mesh_normals";
+    if (mesh_sizes(fn, V, F, 0) < 0 || check_workspace(fn, workspace) < 0) return -1;
+    if (!status || (V > 0 && (!vertices || !normals)) || (F > 0 && !faces)) return fail(std::string(fn) + ": a required pointer is NULL");
+    launch_mesh_normals(V, F, vertices, faces, normals, status, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -19,7 +19,9 @@
 // LDS (16 x D floats, summed in wave order by the thread owning d) and the SGD step.  The margins of the NEW w are
 // the next epoch's margins, so each epoch is one pass and two barriers.  Every reduction has a fixed order: runs are
 // bit-reproducible, and the two paths agree bit for bit where both apply.
+// C entries, with the limits they enforce, at the end of the file: goi_semantic_osh_counts / _fit (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 
 namespace goi {
 
@@ -327,17 +329,6 @@ __global__ __launch_bounds__(COUNTS_THREADS) void osh_counts_k(const int* __rest
         if (h[i]) atomicAdd(&counts[i], h[i]);
 }
 
-}  // namespace
-
-int osh_max_codes() { return OSH_MAX_CODES; }
-int osh_max_dim() { return OSH_GEN_DMAX; }
-
-void launch_osh_counts(const int* idx, const uint8_t* positive, long long HW, int n_codes, int* counts, hipStream_t s) {
-    const long long per_block = (long long)COUNTS_THREADS * 8;
-    const long long blocks = std::min<long long>((HW + per_block - 1) / per_block, 1024);
-    osh_counts_k<<<dim3((unsigned)blocks), dim3(COUNTS_THREADS), 0, s>>>(idx, positive, HW, n_codes, counts);
-}
-
 bool osh_register_path(int n_codes, int D) {
     return g_options.osh_path == 0 && D == OSH_REG_D && n_codes <= OSH_WAVES * OSH_REG_CPW;
 }
@@ -353,4 +344,44 @@ void launch_osh_fit(const float* lut, int n_codes, int D, const int* counts, lon
                                                               epochs_out, loss_out, iou_out, init_iou_out, trace);
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+int goi_semantic_osh_counts(const int* idx, const uint8_t* positive, long long HW, int n_codes, int* counts, void* stream) {
+    if (HW < 0) return fail("goi_semantic_osh_counts: bad HW");
+    if (n_codes < 1 || n_codes > OSH_MAX_CODES) return fail("goi_semantic_osh_counts: need 1 <= n_codes <= 1000");
+    if (!counts) return fail("goi_semantic_osh_counts: counts is NULL");
+    if (HW == 0) return 0;
+    if (!idx || !positive) return fail("goi_semantic_osh_counts: NULL input");
+    const long long per_block = (long long)COUNTS_THREADS * 8;
+    const long long blocks = std::min<long long>((HW + per_block - 1) / per_block, 1024);
+    osh_counts_k<<<dim3((unsigned)blocks), dim3(COUNTS_THREADS), 0, static_cast<hipStream_t>(stream)>>>(
+        idx, positive, HW, n_codes, counts);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_semantic_osh_fit(const float* lut, int n_codes, int D, const int* counts, long long HW, int K, float* w, float* b,
+                         float lr, int max_epochs, double target_iou, int* epochs_out, float* loss_out, double* iou_out,
+                         double* init_iou_out, double* trace, void* stream) {
+    refresh_options();
+    if (n_codes < 1 || n_codes > OSH_MAX_CODES) return fail("goi_semantic_osh_fit: need 1 <= n_codes <= 1000");
+    if (D < 1 || D > OSH_GEN_DMAX) return fail("goi_semantic_osh_fit: need 1 <= D <= 1024");
+    if (HW < 1 || HW >= (1ll << 31)) return fail("goi_semantic_osh_fit: need 1 <= HW < 2^31");
+    if (K < 0 || K > 65535) return fail("goi_semantic_osh_fit: need 0 <= K <= 65535");
+    if (max_epochs < 1 || max_epochs > GOI_OSH_MAX_EPOCHS) return fail("goi_semantic_osh_fit: need 1 <= max_epochs <= 1000000");
+    if (K == 0) return 0;
+    if (!lut || !counts || !w || !b || !epochs_out || !loss_out || !iou_out || !init_iou_out)
+        return fail("goi_semantic_osh_fit: a required pointer is NULL");
+    launch_osh_fit(lut, n_codes, D, counts, HW, K, w, b, lr, max_epochs, target_iou, epochs_out, loss_out, iou_out,
+                   init_iou_out, trace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

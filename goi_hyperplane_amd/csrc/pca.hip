@@ -28,9 +28,11 @@
 //                     n % 4 == 0 take 16-byte loads and stores, everything else one sample per thread with the same bits.
 //
 // Nothing here allocates, copies or synchronises.
+// C entries, with the limits they enforce, at the end of the file: goi_semantic_pca_* (declared in include/goi_raster.h).
 #include <cfloat>
 
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
@@ -577,8 +579,6 @@ __global__ void __launch_bounds__(APPLY_THREADS) pca_apply_k(const ApplyParams p
     }
 }
 
-}  // namespace
-
 size_t pca_fit_workspace_bytes(int S) { return WS_SLOTS_OFFSET + sizeof(double) * (size_t)PCA_SLOTS * slot_words(S); }
 size_t pca_stats_bytes(int n_views) { return sizeof(uint32_t) * 6 * (size_t)n_views; }
 
@@ -639,4 +639,69 @@ void launch_pca_apply(const float* x, int in_layout, int S, long long n, int n_v
     pca_apply_k<1><<<grid, APPLY_THREADS, 0, s>>>(p);
 }
 
+int pca_dims(const char* fn, int S, long long n) {
+    if (S < GOI_PCA_MIN_DIM || S > GOI_PCA_MAX_DIM) return fail(std::string(fn) + ": need 3 <= S <= 32");
+    if (n < 1 || n >= (1ll << 31)) return fail(std::string(fn) + ": need 1 <= n < 2^31");
+    return 0;
+}
+
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_semantic_pca_workspace_bytes(int S, int n_views) {
+    if (S < 0 || n_views < 0 || (S > 0 && (S < GOI_PCA_MIN_DIM || S > GOI_PCA_MAX_DIM)) || n_views > 65535) return 0;
+    return (S > 0 ? pca_fit_workspace_bytes(S) : 0) + (n_views > 0 ? pca_stats_bytes(n_views) : 0);
+}
+
+int goi_semantic_pca_accumulate(const float* x, int layout, int S, long long n, const uint8_t* mask, int first, void* workspace,
+                                void* stream) {
+    const char* fn = "goi_semantic_pca_accumulate";
+    if (pca_dims(fn, S, n) < 0) return -1;
+    if (layout != GOI_PCA_PLANAR && layout != GOI_PCA_ROWS) return fail(std::string(fn) + ": layout must be GOI_PCA_PLANAR or GOI_PCA_ROWS");
+    if (!x) return fail(std::string(fn) + ": NULL x");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    if (reinterpret_cast<uintptr_t>(x) & 3) return fail(std::string(fn) + ": x must be 4-byte aligned");
+    launch_pca_accumulate(x, layout, S, n, mask, first ? 1 : 0, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_semantic_pca_solve(int S, void* workspace, float* basis, void* stream) {
+    const char* fn = "goi_semantic_pca_solve";
+    if (pca_dims(fn, S, 1) < 0) return -1;
+    if (!basis) return fail(std::string(fn) + ": NULL basis");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    launch_pca_solve(S, workspace, basis, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_semantic_pca_apply(const float* x, int in_layout, int S, long long n, int n_views, const float* basis, int normalize,
+                           double k_sigma, float* out, int out_layout, void* workspace, void* stream) {
+    const char* fn = "goi_semantic_pca_apply";
+    if (pca_dims(fn, S, n) < 0) return -1;
+    if ((in_layout != GOI_PCA_PLANAR && in_layout != GOI_PCA_ROWS) || (out_layout != GOI_PCA_PLANAR && out_layout != GOI_PCA_ROWS))
+        return fail(std::string(fn) + ": layouts must be GOI_PCA_PLANAR or GOI_PCA_ROWS");
+    if (normalize != GOI_PCA_RAW && normalize != GOI_PCA_SIGMA && normalize != GOI_PCA_MINMAX)
+        return fail(std::string(fn) + ": normalize must be GOI_PCA_RAW, GOI_PCA_SIGMA or GOI_PCA_MINMAX");
+    if (n_views < 0 || n_views > 65535) return fail(std::string(fn) + ": need 0 <= n_views <= 65535");
+    if (n_views == 0) return 0;
+    if (!x || !basis || !out) return fail(std::string(fn) + ": NULL x, basis or out");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(basis)) & 3)
+        return fail(std::string(fn) + ": x, basis and out must be 4-byte aligned");
+    if (normalize == GOI_PCA_MINMAX && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3)))
+        return fail(std::string(fn) + ": GOI_PCA_MINMAX needs a 4-byte aligned workspace");
+    if (normalize == GOI_PCA_SIGMA && !(k_sigma > 0.0 && k_sigma <= 3.0e38)) return fail(std::string(fn) + ": need a finite k_sigma > 0");
+    const float kf = (float)k_sigma;
+    launch_pca_apply(x, in_layout, S, n, n_views, basis, normalize, 2.0f * kf, out, out_layout, static_cast<uint32_t*>(workspace),
+                     static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -22,16 +22,19 @@
 //                     with ks = -lambda, kl = 1 - lambda for the loss, ks = 1, kl = 0 for SSIM itself.  The upstream
 //                     gradient g is read from device memory.
 // No float atomics anywhere: two calls give the same bits.  Nothing synchronises the host.
+// C entries, with the limits they enforce, at the end of the file: goi_raster_photometric_* (declared in include/goi_raster.h).
 #include <climits>
 #include <cmath>
 
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 namespace goi {
 
 namespace {
 
+constexpr int PHOTO_RADIUS = GOI_PHOTOMETRIC_WINDOW / 2;  // the only window instantiated
 constexpr int PH_TW = 32, PH_TH = 32;  // output tile
 constexpr int PH_THREADS = 256;
 constexpr int PH_WAVES = PH_THREADS / WAVE;
@@ -326,8 +329,6 @@ PhotoWin photo_window() {
     return win;
 }
 
-}  // namespace
-
 size_t photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags) {
     return photo_layout(n, c, h, w, flags, nullptr, nullptr);
 }
@@ -373,4 +374,55 @@ void launch_photometric_backward(const float* x, const float* y, long long n, in
                                                                             grad_out, inv_m, ks, kl, gx, gy);
 }
 
+// the shape limits of goi_raster_photometric_*: "" when the call may go ahead
+std::string photometric_check(long long n, int c, int h, int w, int window_size) {
+    if (window_size != GOI_PHOTOMETRIC_WINDOW) return "window_size " + std::to_string(window_size) + " is not supported (only 11)";
+    if (n < 1 || c < 1 || h < 1 || w < 1) return "need n, c, h, w >= 1";
+    if ((long long)h * w >= (1ll << 31)) return "need h * w < 2^31";
+    if (n * c * ((h + 31) / 32) * (long long)((w + 31) / 32) >= (1ll << 31)) return "need n * c * ceil(h/32) * ceil(w/32) < 2^31";
+    return "";
+}
+
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_raster_photometric_workspace_bytes(long long n, int c, int h, int w, unsigned flags) {
+    if (!photometric_check(n, c, h, w, GOI_PHOTOMETRIC_WINDOW).empty()) return 0;
+    return photometric_workspace_bytes(n, c, h, w, flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2));
+}
+
+int goi_raster_photometric_forward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
+                                   float lambda_dssim, unsigned flags, float* out, float* out_images, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_photometric_forward: ";
+    const std::string bad = photometric_check(n, c, h, w, window_size);
+    if (!bad.empty()) return fail(fn + bad);
+    if (!img1 || !img2 || !out) return fail(fn + "a required pointer is NULL");
+    if (check_workspace("goi_raster_photometric_forward", workspace) < 0) return -1;
+    launch_photometric_forward(img1, img2, n, c, h, w, lambda_dssim, flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2), out,
+                               out_images, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_raster_photometric_backward(const float* img1, const float* img2, long long n, int c, int h, int w, int window_size,
+                                    float lambda_dssim, unsigned flags, const float* grad_out, const void* workspace, float* grad1,
+                                    float* grad2, void* stream) {
+    const std::string fn = "goi_raster_photometric_backward: ";
+    const std::string bad = photometric_check(n, c, h, w, window_size);
+    if (!bad.empty()) return fail(fn + bad);
+    if (!(flags & (GOI_PHOTOMETRIC_GRAD1 | GOI_PHOTOMETRIC_GRAD2))) return fail(fn + "no gradient asked for");
+    if (!img1 || !img2 || !grad_out || ((flags & GOI_PHOTOMETRIC_GRAD1) && !grad1) || ((flags & GOI_PHOTOMETRIC_GRAD2) && !grad2))
+        return fail(fn + "a required pointer is NULL");
+    if (check_workspace("goi_raster_photometric_backward", workspace) < 0) return -1;
+    launch_photometric_backward(img1, img2, n, c, h, w, lambda_dssim, flags, grad_out, workspace, grad1, grad2,
+                                static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -15,7 +15,9 @@
 // logits, the [HW, 256] gathered features or the permuted [HW, S] copy of the rasterizer output:
 // the kernel reads the rasterizer's channel-major [S, H, W] tensor directly (A operand: 16
 // consecutive pixels of one channel = one 64-byte segment) and writes 4-8 bytes per pixel.
+// C entries, with the limits they enforce, at the end of the file: goi_semantic_decode (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 
 namespace goi {
 
@@ -326,8 +328,6 @@ __global__ __launch_bounds__(256, 2) void semantic_decode3n_k(const float* __res
 #undef GOI_DPP_I
 #undef GOI_DPP_F
 
-}  // namespace
-
 int launch_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
                            const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
                            hipStream_t s) {
@@ -399,4 +399,22 @@ int launch_semantic_decode(const float* sem, int S, long long HW, const float* W
     return 0;
 }
 
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" int goi_semantic_decode(const float* sem, int S, long long HW, const float* W, const float* bias, int n_codes,
+                                   const float* code_score, float thresh, float* sim_out, int* idx_out, uint8_t* bg_mask_out,
+                                   void* stream) {
+    refresh_options();
+    if (!sem || !W || !bias) return fail("goi_semantic_decode: NULL input");
+    if (S < 1 || S > 32 || n_codes < 1 || HW < 0) return fail("goi_semantic_decode: need 1 <= S <= 32, n_codes >= 1");
+    if (HW == 0) return 0;
+    if (launch_semantic_decode(sem, S, HW, W, bias, n_codes, code_score, thresh, sim_out, idx_out, bg_mask_out,
+                               static_cast<hipStream_t>(stream)) < 0)
+        return fail("goi_semantic_decode: code book too large for LDS");
+    GOI_HIP(hipGetLastError());
+    return 0;
+}

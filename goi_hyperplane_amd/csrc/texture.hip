@@ -19,7 +19,9 @@
 //                for a bake's last view, normalizes that).
 //   fill         tex_fill_columns_k: per texel the nearest mask texel above / below within the radius; tex_fill_nearest_k:
 //                the minimum over the 2 R + 1 columns of (dx^2 + dy^2, row, column), the L1 test carried along.
+// C entries, with the limits they enforce, at the end of the file: goi_texture_* (declared in include/goi_raster.h).
 #include "common.h"
+#include "entry.h"
 #include "wave_util.h"
 
 #include <math.h>
@@ -491,8 +493,6 @@ void run_level(long long N, const float* coords, const float* values, const uint
                                                                                   acc_count, norm_out, norm_mask);
 }
 
-}  // namespace
-
 size_t texture_rasterize_workspace_bytes(long long F, int H, int W) { return raster_layout((size_t)F, (size_t)H * W, nullptr, nullptr); }
 
 void launch_texture_rasterize(long long V, long long F, const float* v_clip, const int* faces, int H, int W, int* tri, float* bary,
@@ -558,14 +558,6 @@ void launch_texture_grid_put(long long N, int C, int H, int W, int min_resolutio
     }
 }
 
-void launch_texture_accumulate(long long T, int C, float* albedo, float* cnt, const float* cur, const float* cur_cnt, hipStream_t s) {
-    if (T > 0) tex_accumulate_k<<<dim3(tblocks(T)), dim3(TEX_THREADS), 0, s>>>(T, C, albedo, cnt, cur, cur_cnt);
-}
-
-void launch_texture_normalize(long long T, int C, const float* albedo, const float* cnt, float* out, unsigned char* mask, hipStream_t s) {
-    if (T > 0) tex_normalize_k<<<dim3(tblocks(T)), dim3(TEX_THREADS), 0, s>>>(T, C, albedo, cnt, out, mask);
-}
-
 size_t texture_fill_workspace_bytes(int h, int w) { return fill_layout((size_t)h * w, nullptr, nullptr); }
 
 void launch_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
@@ -577,4 +569,108 @@ void launch_texture_fill(int h, int w, int C, int radius, const float* albedo, c
     tex_fill_nearest_k<<<dim3(tblocks(T)), dim3(TEX_THREADS), 0, s>>>(h, w, radius, C, mask, v.up, v.dn, albedo, out, nearest);
 }
 
+bool texture_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= GOI_TEXTURE_MAX_SIZE && W <= GOI_TEXTURE_MAX_SIZE; }
+int texture_size(const char* fn, int H, int W) {
+    if (!texture_size_ok(H, W)) return fail(std::string(fn) + ": need 1 <= H, W <= 16384");
+    return 0;
+}
+bool texture_put_ok(long long N, int C, int H, int W) {
+    return N >= 0 && 4 * N < SORT_MAX_KEYS && C >= 1 && C <= GOI_TEXTURE_MAX_CHANNELS && texture_size_ok(H, W);
+}
+int texture_texels(const char* fn, long long T, int C) {
+    if (T < 0 || T > (long long)GOI_TEXTURE_MAX_SIZE * GOI_TEXTURE_MAX_SIZE || C < 1 || C > GOI_TEXTURE_MAX_CHANNELS)
+        return fail(std::string(fn) + ": need 0 <= T <= 16384^2 and 1 <= C <= 4");
+    return 0;
+}
+
+}  // namespace
+
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+size_t goi_texture_rasterize_workspace_bytes(long long F, int H, int W) {
+    return F >= 0 && 3 * F < SORT_MAX_KEYS && texture_size_ok(H, W) ? texture_rasterize_workspace_bytes(F, H, W) : 0;
+}
+
+int goi_texture_rasterize(long long V, long long F, const float* v_clip, const int* faces, int H, int W, int* tri, float* bary,
+                          float* zw, int* status, void* workspace, void* stream) {
+    const char* fn = "goi_texture_rasterize";
+    if (mesh_sizes(fn, V, F, 0) < 0 || texture_size(fn, H, W) < 0 || check_workspace(fn, workspace) < 0) return -1;
+    if (!status || !tri || !bary || !zw || (F > 0 && (!faces || !v_clip))) return fail(std::string(fn) + ": a required pointer is NULL");
+    launch_texture_rasterize(V, F, v_clip, faces, H, W, tri, bary, zw, status, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_texture_resolve(long long n_vt, long long n_vn, long long F, int H, int W, const int* tri, const float* bary,
+                        const float* vt, const int* ft, const float* vn, const int* faces, const float* pose_rot,
+                        const float* image, float* coords, float* values, unsigned char* valid, int* status, void* stream) {
+    const char* fn = "goi_texture_resolve";
+    if (mesh_sizes(fn, n_vt, F, 0) < 0 || mesh_sizes(fn, n_vn, F, 0) < 0 || texture_size(fn, H, W) < 0) return -1;
+    if (!status || !tri || !bary || !pose_rot || !image || !coords || !values || !valid || (F > 0 && (!vt || !ft || !vn || !faces)))
+        return fail(std::string(fn) + ": a required pointer is NULL");
+    launch_texture_resolve(n_vt, n_vn, F, H, W, tri, bary, vt, ft, vn, faces, pose_rot, image, coords, values, valid, status,
+                           static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_texture_grid_put_workspace_bytes(long long N, int C, int H, int W) {
+    return texture_put_ok(N, C, H, W) ? texture_grid_put_workspace_bytes(N, C, H, W) : 0;
+}
+
+int goi_texture_grid_put(long long N, int C, int H, int W, int min_resolution, const float* coords, const float* values,
+                         const unsigned char* valid, float* result, float* count, float* acc, float* acc_count, float* norm_out,
+                         unsigned char* norm_mask, int* status, void* workspace, void* stream) {
+    const char* fn = "goi_texture_grid_put";
+    if (!texture_put_ok(N, C, H, W)) return fail(std::string(fn) + ": need 0 <= N < 2^28, 1 <= C <= 4 and 1 <= H, W <= 16384");
+    if (min_resolution < 1) return fail(std::string(fn) + ": need min_resolution >= 1");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    if (!status || !result || !count || (N > 0 && (!coords || !values))) return fail(std::string(fn) + ": a required pointer is NULL");
+    if ((acc == nullptr) != (acc_count == nullptr)) return fail(std::string(fn) + ": give both of acc and acc_count, or neither");
+    if ((norm_out == nullptr) != (norm_mask == nullptr) || (norm_out && !acc))
+        return fail(std::string(fn) + ": give both of norm_out and norm_mask, with acc, or neither");
+    launch_texture_grid_put(N, C, H, W, min_resolution, coords, values, valid, result, count, acc, acc_count, norm_out, norm_mask,
+                            status, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_texture_accumulate(long long T, int C, float* albedo, float* cnt, const float* cur, const float* cur_cnt, void* stream) {
+    const char* fn = "goi_texture_accumulate";
+    if (texture_texels(fn, T, C) < 0) return -1;
+    if (T > 0 && (!albedo || !cnt || !cur || !cur_cnt)) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (T > 0)
+        tex_accumulate_k<<<dim3(tblocks(T)), dim3(TEX_THREADS), 0, static_cast<hipStream_t>(stream)>>>(T, C, albedo, cnt, cur, cur_cnt);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+int goi_texture_normalize(long long T, int C, const float* albedo, const float* cnt, float* out, unsigned char* mask,
+                          void* stream) {
+    const char* fn = "goi_texture_normalize";
+    if (texture_texels(fn, T, C) < 0) return -1;
+    if (T > 0 && (!albedo || !cnt || !out || !mask)) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (T > 0)
+        tex_normalize_k<<<dim3(tblocks(T)), dim3(TEX_THREADS), 0, static_cast<hipStream_t>(stream)>>>(T, C, albedo, cnt, out, mask);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t goi_texture_fill_workspace_bytes(int h, int w) { return texture_size_ok(h, w) ? texture_fill_workspace_bytes(h, w) : 0; }
+
+int goi_texture_fill(int h, int w, int C, int radius, const float* albedo, const unsigned char* mask, float* out, int* nearest,
+                     void* workspace, void* stream) {
+    const char* fn = "goi_texture_fill";
+    if (texture_size(fn, h, w) < 0 || texture_texels(fn, 0, C) < 0 || check_workspace(fn, workspace) < 0) return -1;
+    if (radius < 0 || radius > GOI_TEXTURE_MAX_RADIUS) return fail(std::string(fn) + ": need 0 <= radius <= 127");
+    if (!albedo || !mask || !out || !nearest) return fail(std::string(fn) + ": a required pointer is NULL");
+    launch_texture_fill(h, w, C, radius, albedo, mask, out, nearest, workspace, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -56,7 +56,7 @@ def class_values(eps):
 
 
 def cell_side(eps) -> float:
-    """The grid's cell side as csrc/api.hip computes it (float64)."""
+    """The grid's cell side as goi_semantic_dbscan (csrc/dbscan.hip) computes it (float64)."""
     return float(F64(F32(eps)) / np.sqrt(F64(3.0)) * (1.0 - 1.0 / 4096.0))
 
 
