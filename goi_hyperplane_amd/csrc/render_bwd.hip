@@ -442,13 +442,15 @@ __global__ GOI_BWD_LAUNCH_BOUNDS void render_bwd_rows_k(
             coef_decode(g, g2, ca, cb, cc, inv_o);
             float m0, sx, sy, sxx, sxy, syy;
             // moments (1, u, v, uu, uv, vv) of h about a point (Dx, Dy) away from the Gaussian's centre -> sums of h dx^k dy^l
+            // (every rounding spelled out, like the pair loop's recurrence: the forms are the ones the rows have always had)
             auto shift = [&](const float4& a, const float2& b, float DX, float DY) {
+#pragma clang fp contract(off)
                 m0 += a.x;
-                sx += DX * a.x - a.y;                                  // sum h dx
-                sy += DY * a.x - a.z;                                  // sum h dy
-                sxx += DX * DX * a.x - 2.f * DX * a.y + a.w;           // sum h dx^2
-                sxy += DX * DY * a.x - DX * a.z - DY * a.y + b.x;      // sum h dx dy
-                syy += DY * DY * a.x - 2.f * DY * a.z + b.y;           // sum h dy^2
+                sx += __builtin_fmaf(DX, a.x, -a.y);                                                  // sum h dx
+                sy += __builtin_fmaf(DY, a.x, -a.z);                                                  // sum h dy
+                sxx += __builtin_fmaf(-(2.f * DX), a.y, (DX * DX) * a.x) + a.w;                       // sum h dx^2
+                sxy += __builtin_fmaf(-DY, a.y, __builtin_fmaf(DX * DY, a.x, -(DX * a.z))) + b.x;     // sum h dx dy
+                syy += ((DY * DY) * a.x - (2.f * DY) * a.z) + b.y;                                    // sum h dy^2
             };
             m0 = sx = sy = sxx = sxy = syy = 0.f;
             if constexpr (F16) {
@@ -572,8 +574,13 @@ __global__ GOI_BWD_LAUNCH_BOUNDS void render_bwd_rows_k(
             const float Tn = T * inv;
             float wgt = 0.f, hval = 0.f;
             if (c) {
-                const float dL_dopa = (dotv - R) * Tn - (T_final * inv) * bg_dot;
-                R = e.alpha * dotv + one_m_a * R;
+                // The roundings of these two lines are spelled out: this TU used to be built with the SLP vectoriser, which
+                // packed the pairs of products below into v_pk_mul_f32 -- rounding each product -- at the price of six
+                // register moves per pair; built without it, the contraction into FMAs would pick other roundings.  The
+                // bits are the ones every frame has had: (dotv - R) Tn rounded, then one FMA; both products of R rounded.
+#pragma clang fp contract(off)
+                const float dL_dopa = __builtin_fmaf(-bg_dot, T_final * inv, (dotv - R) * Tn);
+                R = one_m_a * R + e.alpha * dotv;
                 T = Tn;
                 wgt = e.alpha * Tn;
                 hval = e.E * dL_dopa;  // opacity * G * dL/dalpha: the moments carry the factor `opacity`

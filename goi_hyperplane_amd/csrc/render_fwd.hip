@@ -40,10 +40,14 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
                                                    uint32_t* __restrict__ host_words, uint32_t stamp) {
     constexpr int NF4 = TRACE ? 1 : 1 + S4;  // float4 words staged per Gaussian: (r,g,b,depth) + semantics
     constexpr int NSEM = TRACE ? 0 : 4 * S4;
-    __shared__ f32x4 s_geo[64];   // (A3, A5, A1, A2) of the quadrant-centred log2-alpha polynomial (blend_common.h)
-    __shared__ f32x4 s_geo2[64];  // (A0, A4, lim, -)
-    __shared__ float4 s_feat[64 * NF4];
-    const f32x4* s_feat4 = reinterpret_cast<const f32x4*>(s_feat);
+    // one record per staged slot: (A3, A5, A1, A2), (A0, A4, lim, -) of the quadrant-centred log2-alpha polynomial
+    // (blend_common.h), then (r, g, b, depth) and the semantics: the pair loop addresses a slot with ONE base register and
+    // immediate offsets.  The loop's reads are wave-uniform broadcasts; the staging writes (ds_write_b128, banked per 8 lanes
+    // over 32 dwords) are conflict-free when the record's quad count REC4 is odd, i.e. for even S4 -- as with the separate
+    // arrays before (feature stride NF4 quads).
+    constexpr int REC4 = NF4 + 2;
+    __shared__ float4 s_rec[64 * REC4];
+    const f32x4* s_rec4 = reinterpret_cast<const f32x4*>(s_rec);
     __shared__ uint32_t s_id[TRACE ? 64 : 1];
 
     // the frame's counters for the host (speculative forward): final before this kernel starts (frame_flags - COUNTER_OVF is
@@ -66,12 +70,16 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
     const size_t pix_id = (size_t)W * t.py + t.px;
     const int lane = t.lane;
 
-    float T = 1.0f;                         // transmittance that is written out (frozen once the pixel is done)
-    float T_live = t.inside ? 1.0f : 0.0f;  // == T while the pixel is live, 0 once it is done: a finished pixel fails
-                                            // the T(1-alpha) >= 1e-4 test by itself, no separate flag to test
-    auto all_done = [&]() { return __builtin_amdgcn_ballot_w64(T_live != 0.0f) == 0; };
+    float T_live = t.inside ? 1.0f : 0.0f;  // the pixel's transmittance while it is live (>= 1e-4 then), 0 once it is done: a
+                                            // finished pixel fails the T(1-alpha) >= 1e-4 test by itself, no separate flag to test
+    float T_end = 1.0f;                     // the transmittance a finished pixel ended with (written only where a pixel ends)
+    // the wave's live pixels (T_live != 0), in SGPRs: rebuilt only where a pixel ends; empty: the wave is done
+    unsigned long long live = __builtin_amdgcn_ballot_w64(T_live != 0.0f);
+    auto all_done = [&]() { return live == 0; };
     uint32_t last_contributor = 0;
-    uint32_t stop_pos = 0;  // 1-based list position of the entry that ENDED this pixel (T (1 - alpha) < 1e-4); 0: still live
+    // 1-based list position of the last entry that hit this pixel and failed T (1 - alpha) >= 1e-4: the entry that ended it, or
+    // a later one the wave still walked; 0: still live
+    uint32_t stop_pos = 0;
     // accumulators as register pairs: one v_pk_fma_f32 adds two channels (this TU is compiled with the SLP
     // vectoriser off -- it packs the alpha evaluations of two candidates at the price of six moves -- so the
     // packing is spelled out)
@@ -127,16 +135,17 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
         // ---- stage the hits (slot = lane)
         if (m != 0 && hit) {
             const PolyCoef pc = poly_coefs(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, QCX, QCY);
-            s_geo[lane] = f32x4{pc.A35.x, pc.A35.y, pc.A12.x, pc.A12.y};
-            s_geo2[lane] = f32x4{pc.A0, pc.A4, pc.lim, 0.f};
-            s_feat[lane * NF4] = q2;  // r, g, b, depth
+            float4* slot = s_rec + lane * REC4;
+            slot[0] = make_float4(pc.A35.x, pc.A35.y, pc.A12.x, pc.A12.y);
+            slot[1] = make_float4(pc.A0, pc.A4, pc.lim, 0.f);
+            slot[2] = q2;  // r, g, b, depth
             if constexpr (TRACE) {
                 s_id[lane] = id;
             } else {
                 const float* srow = semantics + (size_t)id * S;
                 if ((S & 3) == 0) {
 #pragma unroll
-                    for (int i = 0; i < S4; i++) s_feat[lane * NF4 + 1 + i] = reinterpret_cast<const float4*>(srow)[i];
+                    for (int i = 0; i < S4; i++) slot[3 + i] = reinterpret_cast<const float4*>(srow)[i];
                 } else {
 #pragma unroll
                     for (int i = 0; i < S4; i++) {
@@ -145,7 +154,7 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
                         v.y = (4 * i + 1 < S) ? srow[4 * i + 1] : 0.f;
                         v.z = (4 * i + 2 < S) ? srow[4 * i + 2] : 0.f;
                         v.w = (4 * i + 3 < S) ? srow[4 * i + 3] : 0.f;
-                        s_feat[lane * NF4 + 1 + i] = v;
+                        slot[3 + i] = v;
                     }
                 }
             }
@@ -153,43 +162,58 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
         __builtin_amdgcn_wave_barrier();  // single-wave workgroup: LDS is in order, only the compiler must not reorder
 
         // ---- pair loop over the hits, front to back
-        // applies one candidate to the per-pixel state (sequential part) and accumulates its features
-        auto apply = [&](int j, const PairEval& e, bool valid) {
+        // applies one candidate to the per-pixel state (sequential part) and accumulates its features.  Everything a pair does
+        // to a pixel happens under the pixel's own condition (EXEC), nothing by select: a lane the Gaussian does not reach
+        // executes no FMA -- it used to add feature * 0, which leaves an fp32 sum that started at +0 unchanged for a finite
+        // feature and poisons it for a non-finite one (the reference skips such a pixel) -- and the live transmittance and the
+        // last contributor are plain moves on the lanes that contribute.
+        auto apply = [&](const f32x4* r, int j, const PairEval& e) {
             const float test_T = T_live * (1.f - e.alpha);
-            const bool c0 = valid && e.hit;
             const bool ok = test_T >= kTMin;  // CR/forward.cu:352-356: a failing contributor ends the pixel
-            const bool c = c0 && ok;
-            const bool some = any_all(e.below, e.seen, ok);  // (taken where the comparisons are: their masks are used as they are)
-            if (valid && some) {                             // (valid is wave-uniform)
+            // (the masks are taken where the comparisons are: each ballot IS the mask the v_cmp wrote, the ANDs are scalar)
+            const unsigned long long hm = __builtin_amdgcn_ballot_w64(e.below) & __builtin_amdgcn_ballot_w64(e.seen);
+            const unsigned long long om = __builtin_amdgcn_ballot_w64(ok);
+            if ((hm & om) != 0) {
                 if constexpr (MASKS) asm("s_bitset1_b64 %0, %1" : "+s"(members) : "s"(j));  // members |= 1 << j, pinned to SGPRs
-                const float wgt = c ? e.alpha * T_live : 0.f;
-                const f32x2 w2 = {wgt, wgt};
-                const f32x4 f0 = s_feat4[j * NF4];
-                C2[0] = __builtin_elementwise_fma(f0.xy, w2, C2[0]);
-                C2[1] = __builtin_elementwise_fma(f0.zw, w2, C2[1]);
-                if constexpr (!TRACE) {
+                if (e.hit && ok) {
+                    const float wgt = e.alpha * T_live;
+                    const f32x2 w2 = {wgt, wgt};
+                    const f32x4 f0 = r[2];
+                    C2[0] = __builtin_elementwise_fma(f0.xy, w2, C2[0]);
+                    C2[1] = __builtin_elementwise_fma(f0.zw, w2, C2[1]);
+                    if constexpr (!TRACE) {
 #pragma unroll
-                    for (int i = 0; i < S4; i++) {
-                        const f32x4 f = s_feat4[j * NF4 + 1 + i];
-                        Cs2[2 * i] = __builtin_elementwise_fma(f.xy, w2, Cs2[2 * i]);
-                        Cs2[2 * i + 1] = __builtin_elementwise_fma(f.zw, w2, Cs2[2 * i + 1]);
+                        for (int i = 0; i < S4; i++) {
+                            const f32x4 f = r[3 + i];
+                            Cs2[2 * i] = __builtin_elementwise_fma(f.xy, w2, Cs2[2 * i]);
+                            Cs2[2 * i + 1] = __builtin_elementwise_fma(f.zw, w2, Cs2[2 * i + 1]);
+                        }
+                    } else {
+                        if ((double)e.alpha > 0.005) {
+                            const uint32_t gid = s_id[j];
+                            for (int ch = 0; ch < S; ch++)
+                                atomicAdd(&gau_sem[(size_t)gid * S + ch], img_sem[ch * HW + pix_id]);
+                            atomicAdd(&num_gsem[gid], S);
+                        }
                     }
-                } else {
-                    if (c && (double)e.alpha > 0.005) {
-                        const uint32_t gid = s_id[j];
-                        for (int ch = 0; ch < S; ch++)
-                            atomicAdd(&gau_sem[(size_t)gid * S + ch], img_sem[ch * HW + pix_id]);
-                        atomicAdd(&num_gsem[gid], S);
-                    }
-                }
-                if (c) {
-                    T = test_T;
+                    T_live = test_T;
                     last_contributor = (uint32_t)(b * 64 + j + 1);
                 }
             }
+            // a pixel can only end at a pair where a LIVE lane hits and fails the transmittance test (a finished pixel fails it at
+            // every later hit): the three masks are in SGPRs already, so the common pair pays two scalar ANDs for the whole
+            // ending path, the wave's exit test included
+            const unsigned long long em = hm & ~om;
             if constexpr (LEARN)
-                if (c0 && !ok) stop_pos = (uint32_t)(b * 64 + j + 1);  // (the depth cut-off must keep this entry)
-            T_live = c0 ? (ok ? test_T : 0.0f) : T_live;
+                if (em != 0 && e.hit && !ok) stop_pos = (uint32_t)(b * 64 + j + 1);  // (the depth cut-off must keep this entry)
+            if ((em & live) != 0) {
+                if (e.hit && !ok && T_live != 0.0f) {
+                    T_end = T_live;
+                    T_live = 0.0f;
+                }
+                live = __builtin_amdgcn_ballot_w64(T_live != 0.0f);
+                if (live == 0) m = 0;
+            }
         };
         if constexpr (UNROLL2) {
             // two candidates per trip: their alpha evaluations are independent (ILP, half the
@@ -200,23 +224,23 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
                 const bool has1 = m != 0;
                 const int j1 = has1 ? __builtin_ctzll(m) : j0;
                 if (has1) m &= m - 1;
-                const f32x4 ga = s_geo[j0], gb = s_geo[j1];
-                const f32x4 ha = s_geo2[j0], hb = s_geo2[j1];
+                const f32x4 *ra = s_rec4 + j0 * REC4, *rb = s_rec4 + j1 * REC4;
+                const f32x4 ga = ra[0], gb = rb[0];
+                const f32x4 ha = ra[1], hb = rb[1];
                 const PairEval e0 = eval_poly(ga.xy, ga.zw, ha.x, ha.y, ha.z, uv);
                 const PairEval e1 = eval_poly(gb.xy, gb.zw, hb.x, hb.y, hb.z, uv);
-                apply(j0, e0, true);
-                apply(j1, e1, has1);
-                if (all_done()) m = 0;
+                apply(ra, j0, e0);
+                if (has1) apply(rb, j1, e1);  // (after the wave's last pixel has ended nothing passes the transmittance test)
             }
         } else {
             while (m) {
                 const int j = __builtin_ctzll(m);
                 m &= m - 1;
-                const f32x4 g = s_geo[j];
-                const f32x4 g2 = s_geo2[j];
+                const f32x4* r = s_rec4 + j * REC4;
+                const f32x4 g = r[0];
+                const f32x4 g2 = r[1];
                 const PairEval e = eval_poly(g.xy, g.zw, g2.x, g2.y, g2.z, uv);
-                apply(j, e, true);
-                if (all_done()) m = 0;
+                apply(r, j, e);
             }
         }
         store_members(b, members);
@@ -265,6 +289,7 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
         if (qcost && lane == 0) qcost[tq] = (uint32_t)qc;
     }
     if (t.inside) {
+        const float T = T_live != 0.0f ? T_live : T_end;  // transmittance that is written out: frozen where the pixel ended
         n_contrib[pix_id] = last_contributor;
         out_color[0 * HW + pix_id] = C2[0].x + T * bg[0];
         out_color[1 * HW + pix_id] = C2[0].y + T * bg[1];
