@@ -32,6 +32,7 @@ UNITS = {
     "reduce_rows.hip": [],
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "blend_stats.hip": [],
+    "contrib.hip": [],
     "render_bwd.hip": ["-fno-slp-vectorize"],  # the vectoriser's packing costs the pair loop six moves and four VGPRs (the loop spells its roundings)
     "render_bwd_tile.hip": [],
     "render_bwd_sem.hip": [],

@@ -1045,6 +1045,24 @@ int goi_raster_blend_stats(int P, int W, int H, int R, const void* geom_buffer, 
     return 0;
 }
 
+int goi_raster_contrib_frame(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
+                             const void* image_buffer, float* peak, int* top_id, float* top_w, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P <= 0 || W <= 0 || H <= 0 || R < 0) return fail("goi_raster_contrib_frame: bad P/W/H/R");
+    if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail("goi_raster_contrib_frame: workspace pointer is NULL");
+    if (!peak && !top_id && !top_w) return fail("goi_raster_contrib_frame: peak, top_id and top_w are all NULL");
+    if (R == 0) {  // nothing listed: peak stays as it is, no pixel has a contributor
+        const size_t HW = (size_t)W * H;
+        if (top_id) GOI_HIP(hipMemsetAsync(top_id, 0xFF, HW * sizeof(int), s));
+        if (top_w) GOI_HIP(hipMemsetAsync(top_w, 0, HW * sizeof(float), s));
+        return 0;
+    }
+    const FrameViews f = frame_views(P, W, H, R, geom_buffer, image_buffer, binning_buffer);
+    launch_contrib(P, W, H, f.g, f.im, f.plist, peak, top_id, top_w, s);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
 int goi_raster_debug_views(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
                            const void* image_buffer, float* depths, float* means2D, float* conic_opacity, float* rgb,
                            uint32_t* tiles_touched, uint32_t* point_list, uint32_t* ranges, uint32_t* n_contrib,

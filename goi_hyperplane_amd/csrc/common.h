@@ -231,6 +231,10 @@ constexpr int HOST_STAMP_WORD = 33;
 // lane utilisation of the blend kernels counted from a forward's member masks / n_contrib (blend_stats.hip): out[GOI_BLEND_STATS_WORDS]
 void launch_blend_stats(int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                         const unsigned long long* qmask, unsigned long long* out, hipStream_t s);
+// peak blend weight per Gaussian (max-merged into peak[P]) and the dominant contributor per pixel (top_id / top_w [H*W]) of a
+// finished frame, by one replay of its tile lists (contrib.hip); any of the three may be NULL
+void launch_contrib(int P, int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list, float* peak,
+                    int* top_id, float* top_w, hipStream_t s);
 // one wave per request (Gaussian id, 4 tile + quadrant): E, alpha and the guard bits of the quadrant's 64 pixels through
 // poly_coefs / eval_poly (blend_stats.hip; tests only)
 void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* requests, long long n, float* E, float* alpha,

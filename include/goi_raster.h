@@ -58,7 +58,7 @@ extern "C" {
  *    goi_mesh_normals_workspace_bytes, goi_mesh_normals; goi_texture_rasterize_workspace_bytes, goi_texture_rasterize,
  *    goi_texture_resolve, goi_texture_grid_put_workspace_bytes, goi_texture_grid_put, goi_texture_accumulate,
  *    goi_texture_normalize, goi_texture_fill_workspace_bytes, goi_texture_fill; goi_edit_bounds_workspace_bytes,
- *    goi_edit_bounds, goi_edit_transform
+ *    goi_edit_bounds, goi_edit_transform; goi_raster_contrib_frame
  * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
  *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
  *    goi_raster_backward_scratch_bytes as ever);
@@ -778,6 +778,21 @@ int goi_raster_densify_apply(long long P, const GoiDensifyRows* groups, int n_gr
 #define GOI_BLEND_STATS_WORDS 16
 int goi_raster_blend_stats(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
                            const void* image_buffer, unsigned long long* counters, void* stream);
+
+/* Peak blend weight per Gaussian and the dominant contributor per pixel of a finished frame: one replay of its tile lists with
+ * the forward's own pair evaluation (candidates by the quadrant hit test; a pixel is live until a pair that passes both alpha
+ * guards fails T (1 - alpha) >= 1e-4), no feature arithmetic.  Not part of the reference's interface.  R / the three buffers:
+ * as for goi_raster_backward of the same frame.  DEVICE outputs, written on `stream`; each may be NULL, not all three:
+ *   peak   [P] float32: merged BY MAXIMUM with what is there (zero it once, sweep any number of views): the largest
+ *          w = alpha * T of the Gaussian over every live pixel inside the image -- over its contributions and over the pair that
+ *          ended a pixel, whose w is what the Gaussian would have added.  peak == 0 over a set of frames: the Gaussian never
+ *          passed the guards on a live pixel of any of them; removing it changes no output map of those frames in any bit.
+ *          Merged with an integer atomic maximum on the bit patterns (w >= 0): the same bits whatever the order.
+ *   top_id [H*W] int32, top_w [H*W] float32: the pixel's contributor of largest w (the front-most of equals; the pair that
+ *          ended the pixel added nothing and is not one) and that w; -1 and 0 where nothing contributed.
+ * A truncated frame (goi_raster_truncated_flag) merges nothing into peak and writes -1 / 0; so does R == 0, without a launch. */
+int goi_raster_contrib_frame(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
+                             const void* image_buffer, float* peak, int* top_id, float* top_w, void* stream);
 
 /* Inspection of the opaque workspaces (tests only): copies device -> caller DEVICE buffers.
  * Any pointer may be NULL.  point_list is in final sorted order. */
