@@ -27,7 +27,8 @@ COMMON = ["--offload-arch=" + ARCH] + os.environ.get("GOI_EXTRA_FLAGS", "").spli
 UNITS = {
     "api.hip": [],
     "scan_sort.hip": [],
-    "preprocess.hip": ["-ffp-contract=off"],  # only the per-Gaussian arithmetic: radii / rectangles / depth keys integer-exact
+    "preprocess_fwd.hip": ["-ffp-contract=off"],  # only the per-Gaussian arithmetic: radii / rectangles / depth keys integer-exact
+    "preprocess_bwd.hip": ["-ffp-contract=off"],  # only the per-Gaussian arithmetic: radii / rectangles / depth keys integer-exact
     "binning.hip": [],
     "reduce_rows.hip": [],
     "render_fwd.hip": ["-fno-slp-vectorize"],
@@ -109,6 +110,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     with ThreadPoolExecutor(max_workers=4) as ex:
         results = list(ex.map(compile_one, UNITS.items()))
     objs = [o for o, _ in results]
+    for stale in {f for f in os.listdir(objdir) if f.endswith(".hip.o")} - {os.path.basename(o) for o in objs}:
+        os.remove(os.path.join(objdir, stale))  # a unit that left UNITS: tools/build_variant.sh links every object in here
     if force or any(c for _, c in results) or not os.path.exists(LIB):
         cmd = [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
         if verbose:

@@ -1,7 +1,8 @@
 // extern "C" entry points of the rasterizer's frame (see include/goi_raster.h): workspace layout, stage orchestration on the
-// caller's HIP stream, read-back tickets, options, per-stage event timing, the goi_raster_debug_* entries -- and the one
-// definition of what every entry refuses a call with (entry.h).  A stand-alone family's entries are in the family's own unit.
-#include <climits>
+// caller's HIP stream, read-back tickets, options, per-stage event timing -- and the one definition of what every entry
+// refuses a call with (entry.h).  A stand-alone family's entries are in the family's own unit, and so is an entry that drives one
+// kernel family of the rasterizer directly (tests, diagnostics).  The goi_raster_debug_* entries left here belong to no single
+// unit: the backward blend's drives three, the others answer questions about the layouts.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -106,7 +107,7 @@ int validate(const GoiRasterScene* sc, bool need_sem, bool need_opacity = true) 
     if ((sc->shs == nullptr) == (sc->colors_precomp == nullptr))
         return fail("Please provide excatly one of either SHs or precomputed colors!");
     // (an SH row whose 3 M floats are a whole number of 16-byte words -- M = 4, 8, 12, 16 -- is moved as such by both per-Gaussian
-    // kernels: preprocess.hip, row16 / the backward's hoist)
+    // kernels: preprocess_fwd.hip, row16 / preprocess_bwd.hip, the hoist)
     if (sc->shs && (3 * sc->M) % 4 == 0 && (reinterpret_cast<uintptr_t>(sc->shs) & 15u) != 0)
         return fail("shs must be 16-byte aligned when 3 M is a multiple of 4 (its rows are moved as 16-byte words)");
     if (((sc->scales == nullptr || sc->rotations == nullptr) && sc->cov3D_precomp == nullptr) ||
@@ -472,17 +473,7 @@ size_t binning_layout(int N, char* base, BinView* v) {
     return c.end() + 256;
 }
 
-namespace {
-
-// What a finished forward left in the caller's opaque workspaces: the geometry state, the image state and the binning state of
-// the R instances the forward returned, with the final (tile-sorted) point list.  The image view stays zero where image is
-// NULL, the binning view and the list where binning is NULL (only a frame with R == 0 may come without one: callers check).
-struct FrameViews {
-    GeomView g;
-    ImageView im;
-    BinView bv;
-    const uint32_t* plist;
-};
+// common.h: the views of a finished frame, for every entry that takes its three workspaces
 FrameViews frame_views(int P, int W, int H, int R, const void* geom, const void* image, const void* binning) {
     FrameViews f{};
     // (the views are the forward's, hence writable.  Through a const workspace an entry writes only what the frame keeps for
@@ -495,6 +486,8 @@ FrameViews frame_views(int P, int W, int H, int R, const void* geom, const void*
     }
     return f;
 }
+
+namespace {
 
 // Starts a row backward on a scratch laid out for `cap` instances: the validity bytes of the slots this frame can use and
 // big_ctl are cleared by extra workgroups of the quadrant-order launch (count on the device: 4 x num_rendered bytes, not
@@ -942,27 +935,6 @@ int goi_raster_backward_semantics(const GoiRasterScene* scene, int R, const void
     return 0;
 }
 
-int goi_raster_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
-                            uint8_t* present, void* stream) {
-    (void)projmatrix;
-    if (P < 0) return fail("bad P");
-    if (P == 0) return 0;
-    if (!means3D || !viewmatrix || !present) return fail("NULL pointer");
-    launch_mark_visible(P, means3D, viewmatrix, present, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* campos, const float* gcol,
-                           float* dL_dsh, void* stream) {
-    if (P <= 0 || V <= 0) return 0;
-    if (D < 0 || D > 3 || M < (D + 1) * (D + 1) || M > 16) return fail("goi_raster_sh_grad_from_views: need 0 <= D <= 3 and (D+1)^2 <= M <= 16");
-    if (!means3D || !campos || !gcol || !dL_dsh) return fail("goi_raster_sh_grad_from_views: NULL pointer");
-    launch_sh_grad_from_views(P, D, M, V, means3D, campos, gcol, dL_dsh, static_cast<hipStream_t>(stream));
-    if (hipGetLastError() != hipSuccess) return fail("goi_raster_sh_grad_from_views: launch failed");
-    return 0;
-}
-
 const uint32_t* goi_raster_truncated_flag(const void* geom_buffer, int P) {
     if (!geom_buffer || P <= 0) return nullptr;
     return frame_views(P, 0, 0, 0, geom_buffer, nullptr, nullptr).g.counters + COUNTER_OVF;
@@ -1032,37 +1004,6 @@ int goi_raster_profile_collect(double* ms, int* calls) {
     return 0;
 }
 
-int goi_raster_blend_stats(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
-                           const void* image_buffer, unsigned long long* counters, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (P <= 0 || W <= 0 || H <= 0 || R < 0) return fail("goi_raster_blend_stats: bad P/W/H/R");
-    if (!geom_buffer || !image_buffer || !counters || (R > 0 && !binning_buffer)) return fail("workspace pointer is NULL");
-    GOI_HIP(hipMemsetAsync(counters, 0, GOI_BLEND_STATS_WORDS * sizeof(unsigned long long), s));
-    if (R == 0) return 0;
-    const FrameViews f = frame_views(P, W, H, R, geom_buffer, image_buffer, binning_buffer);
-    launch_blend_stats(W, H, f.g, f.im, f.plist, f.bv.qmask, counters, s);
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_contrib_frame(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
-                             const void* image_buffer, float* peak, int* top_id, float* top_w, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (P <= 0 || W <= 0 || H <= 0 || R < 0) return fail("goi_raster_contrib_frame: bad P/W/H/R");
-    if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail("goi_raster_contrib_frame: workspace pointer is NULL");
-    if (!peak && !top_id && !top_w) return fail("goi_raster_contrib_frame: peak, top_id and top_w are all NULL");
-    if (R == 0) {  // nothing listed: peak stays as it is, no pixel has a contributor
-        const size_t HW = (size_t)W * H;
-        if (top_id) GOI_HIP(hipMemsetAsync(top_id, 0xFF, HW * sizeof(int), s));
-        if (top_w) GOI_HIP(hipMemsetAsync(top_w, 0, HW * sizeof(float), s));
-        return 0;
-    }
-    const FrameViews f = frame_views(P, W, H, R, geom_buffer, image_buffer, binning_buffer);
-    launch_contrib(P, W, H, f.g, f.im, f.plist, peak, top_id, top_w, s);
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
 int goi_raster_debug_views(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
                            const void* image_buffer, float* depths, float* means2D, float* conic_opacity, float* rgb,
                            uint32_t* tiles_touched, uint32_t* point_list, uint32_t* ranges, uint32_t* n_contrib,
@@ -1091,226 +1032,6 @@ int goi_raster_debug_views(int P, int W, int H, int R, const void* geom_buffer, 
         GOI_HIP(hipMemcpyAsync(n_contrib, im.n_contrib, sizeof(uint32_t) * (size_t)W * H, hipMemcpyDeviceToDevice, s));
     if (point_list && R > 0)
         GOI_HIP(hipMemcpyAsync(point_list, f.plist, sizeof(uint32_t) * (size_t)R, hipMemcpyDeviceToDevice, s));
-    return 0;
-}
-
-static int debug_sort_args(const char* fn, long long n, int lo, int hi) {
-    if (n < 0 || n >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need 0 <= n < 2^30");
-    if (lo < 0 || hi > 32 || lo >= hi) return fail(std::string(fn) + ": need 0 <= lo < hi <= 32");
-    return 0;
-}
-
-size_t goi_raster_debug_sort_workspace_bytes(long long n, int lo, int hi) {
-    if (n < 0 || n >= SORT_MAX_KEYS || lo < 0 || hi > 32 || lo >= hi) return 0;
-    return sort_scratch_words((size_t)(n > 0 ? n : 1)) * sizeof(uint32_t) + 256;
-}
-
-int goi_raster_debug_sort_pairs(uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, uint32_t* vals1, long long n, int lo, int hi,
-                                const uint32_t* n_dev, const uint32_t* ghist, int flags, uint32_t* error_out, void* workspace,
-                                void* stream) {
-    refresh_options();
-    const char* fn = "goi_raster_debug_sort_pairs";
-    if (debug_sort_args(fn, n, lo, hi) < 0) return -1;
-    if (flags & ~1) return fail(std::string(fn) + ": unknown flags");
-    const bool onesweep = g_options.sort_variant == 1;
-    if ((n_dev || ghist) && !onesweep) return fail(std::string(fn) + ": n_dev and ghist need the onesweep sort (sort_variant 1)");
-    if (n == 0) return 0;
-    if (!keys0 || !vals0 || !keys1 || !vals1) return fail(std::string(fn) + ": a required pointer is NULL");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    uint32_t* scratch = static_cast<uint32_t*>(workspace);
-    bool cleared = (flags & 1) != 0;
-    if (ghist) {  // the rasterizer's convention: control words cleared, then the histograms written by the caller's own kernel
-        const size_t passes = (size_t)(hi - lo + 7) / 8;
-        GOI_HIP(hipMemsetAsync(scratch, 0, radix_sort_control_words((size_t)n, lo, hi) * sizeof(uint32_t), s));
-        GOI_HIP(hipMemcpyAsync(radix_sort_ghist(scratch, (size_t)n, lo, hi), ghist, passes * 256 * sizeof(uint32_t),
-                               hipMemcpyDeviceToDevice, s));
-        cleared = true;
-    }
-    uint32_t* keys[2] = {keys0, keys1};
-    uint32_t* vals[2] = {vals0, vals1};
-    const int fin = radix_sort_pairs(keys, vals, (size_t)n, lo, hi, scratch, s, cleared, ghist != nullptr, n_dev, error_out);
-    GOI_HIP(hipGetLastError());
-    if (error_out) radix_sort_report_error(scratch, (size_t)n, lo, hi, error_out, s);
-    GOI_HIP(hipGetLastError());
-    return fin;
-}
-
-size_t goi_raster_debug_scan_workspace_bytes(long long n) {
-    return (n >= 0 && n < (1ll << 32)) ? scan_scratch_words((size_t)n) * sizeof(uint32_t) + 256 : 0;
-}
-
-int goi_raster_debug_exclusive_scan(const uint32_t* in, const uint32_t* gather, uint32_t* out, long long n, const uint32_t* n_dev,
-                                    uint32_t* total, void* workspace, void* stream) {
-    refresh_options();
-    if (n < 0 || n >= (1ll << 32)) return fail("goi_raster_debug_exclusive_scan: need 0 <= n < 2^32");
-    if (gather && out == in) return fail("goi_raster_debug_exclusive_scan: out == in with a gather is a data race");
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n > 0 && (!in || !out || !workspace)) return fail("goi_raster_debug_exclusive_scan: a required pointer is NULL");
-    exclusive_scan_u32(in, gather, out, (size_t)n, total, static_cast<uint32_t*>(workspace), s, n_dev);
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-// The row reduction's workspace: a counter block (the frame words at COUNTER_N / COUNTER_V / COUNTER_OVF, where the launchers
-// read them), big_ctl, big_desc[cap_big] -- the tail of bwd_scratch_layout, with cap_big from the same helper.
-static size_t debug_reduce_layout(long long n_cap, char* base, uint32_t** counters, BwdScratchView* v) {
-    Carver c(base);
-    uint32_t* words = c.take<uint32_t>(64);
-    BwdScratchView tmp;
-    BwdScratchView& b = v ? *v : tmp;  // (the caller's view keeps its other fields)
-    b.cap_big = reduce_cap_big((size_t)n_cap);
-    b.big_ctl = c.take<uint32_t>(8);
-    b.big_desc = c.take<uint4>(b.cap_big);
-    if (counters) *counters = words;
-    return c.end();
-}
-
-int goi_raster_debug_reduce_row_floats(int mode, int S) {
-    if (mode < 0 || mode > 3) return fail("goi_raster_debug_reduce_rows: unknown mode");
-    if (S < 1 || S > 32) return fail("goi_raster_debug_reduce_rows: need 1 <= S <= 32");
-    if (mode == 3) return bwd_sem_row_floats(S);
-    const int rf = bwd_row_floats(S);
-    if (mode == 2 && rf != 32) return fail("goi_raster_debug_reduce_rows: mode 2 sums 128-byte rows only (S = 5 .. 20)");
-    return rf;
-}
-
-size_t goi_raster_debug_reduce_workspace_bytes(long long n_cap) {
-    if (n_cap < 0 || n_cap > INT_MAX) return 0;
-    return debug_reduce_layout(n_cap, /*base=*/nullptr, /*counters=*/nullptr, /*v=*/nullptr) + 256;  // (sizes only)
-}
-
-int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const uint32_t* frame, const uint32_t* order,
-                                 const uint32_t* offsets, const uint32_t* tiles_touched, float* rows, const uint8_t* flags,
-                                 float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
-                                 float* dL_ddepth, void* workspace, void* stream) {
-    const std::string fn = "goi_raster_debug_reduce_rows";
-    const int rf = goi_raster_debug_reduce_row_floats(mode, S);
-    if (rf < 0) return -1;
-    if (P < 0 || n_cap < 0 || n_cap > INT_MAX) return fail(fn + ": need P >= 0 and 0 <= n_cap < 2^31");
-    if (P == 0) return 0;
-    const bool arrays = mode == 0, per_id = mode == 0 || mode == 3;
-    if (!frame || !order || !offsets || !rows || !flags || (per_id && (!tiles_touched || !dL_dsemantic)) ||
-        (arrays && (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_ddepth)))
-        return fail(fn + ": a required pointer is NULL");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    GoiRasterScene sc{};
-    sc.P = P;
-    sc.S = S;
-    GeomView g{};
-    BwdScratchView scr{};
-    debug_reduce_layout(n_cap, static_cast<char*>(workspace), &g.counters, &scr);
-    g.sort_vals[depth_sort_result_index()] = const_cast<uint32_t*>(order);
-    g.offsets = const_cast<uint32_t*>(offsets);
-    g.tiles_touched = const_cast<uint32_t*>(tiles_touched);
-    scr.rows = rows;
-    scr.flags = const_cast<uint8_t*>(flags);
-    // frame = {count, listed V, overflow}; big_ctl cleared as launch_quad_order's extra workgroups (or the memset) do
-    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_N, frame + 0, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_V, frame + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_OVF, frame + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
-    const int N = (int)n_cap;
-    if (mode == 0)
-        launch_reduce_rows(sc, g, N, scr, BlendGrads{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth}, s);
-    else if (mode == 1)
-        launch_reduce_rows(sc, g, N, scr, BlendGrads{}, s, true);
-    else if (mode == 2)
-        launch_reduce_big_only(sc, g, N, scr, s);
-    else
-        launch_reduce_sem_rows(sc, g, N, scr, rf, dL_dsemantic, s);
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source, int flags, int max_blocks, long long n_cap,
-                                         const uint32_t* frame, const int* radii, const uint8_t* clamped, const float* cov3D,
-                                         const int* prev_radii, const uint32_t* aux, const uint32_t* tiles_touched,
-                                         const float* rows, const uint8_t* row_flags, float* dL_dmean2D, const float* dL_dconic,
-                                         float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, const float* dL_ddepth,
-                                         float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                                         void* workspace, void* stream) {
-    const std::string fn = "goi_raster_debug_preprocess_backward";
-    if (!scene) return fail(fn + ": scene is NULL");
-    const GoiRasterScene& sc = *scene;
-    if (sc.P < 0 || sc.W <= 0 || sc.H <= 0) return fail(fn + ": bad P/W/H");
-    if (sc.S < 1 || sc.S > 32) return fail(fn + ": need 1 <= S <= 32");
-    if (source < 0 || source > 2) return fail(fn + ": unknown source (0 per-id arrays, 1 records, 2 rows summed in the kernel)");
-    if (flags & ~GOI_BACKWARD_ACCUMULATE) return fail(fn + ": unknown flag bits");
-    if (max_blocks < 0) return fail(fn + ": max_blocks must be >= 0 (0: the product's grid)");
-    if (n_cap < 0 || n_cap > INT_MAX) return fail(fn + ": need 0 <= n_cap < 2^31");
-    if (source == 2 && bwd_row_floats(sc.S) != 32) return fail(fn + ": source 2 sums 128-byte rows only (S = 5 .. 20)");
-    if (sc.P == 0) return 0;
-    if (!(sc.tan_fovx > 0.f) || !(sc.tan_fovy > 0.f)) return fail(fn + ": tan_fovx / tan_fovy must be positive");
-    if (!sc.means3D || !sc.viewmatrix || !sc.projmatrix || !sc.campos) return fail(fn + ": a required scene pointer is NULL");
-    if (sc.shs && sc.colors_precomp) return fail(fn + ": shs and colors_precomp are both given");
-    if (sc.shs && (sc.D < 0 || sc.D > 3 || sc.M < (sc.D + 1) * (sc.D + 1) || sc.M > 16))
-        return fail(fn + ": SH degree must be 0..3 and (D+1)^2 <= M <= 16");
-    if (sc.shs && (3 * sc.M) % 4 == 0 && (reinterpret_cast<uintptr_t>(sc.shs) & 15u) != 0)
-        return fail(fn + ": shs must be 16-byte aligned when 3 M is a multiple of 4");
-    if (!sc.shs && dL_dsh) return fail(fn + ": dL_dsh without shs");
-    if ((sc.scales == nullptr) != (sc.rotations == nullptr)) return fail(fn + ": scales and rotations go together");
-    if ((sc.scales != nullptr) == (sc.cov3D_precomp != nullptr))
-        return fail(fn + ": exactly one of the scale/rotation pair and cov3D_precomp");
-    if (sc.scales && !cov3D) return fail(fn + ": cov3D (what the forward computed from scale/rotation) is NULL");
-    if (sc.rotations && (reinterpret_cast<uintptr_t>(sc.rotations) & 15u) != 0) return fail(fn + ": rotations must be 16-byte aligned");
-    const bool accumulate = (flags & GOI_BACKWARD_ACCUMULATE) != 0;
-    if (accumulate && source != 1) return fail(fn + ": accumulate needs source 1 (the records)");
-    if (accumulate && prev_radii) return fail(fn + ": accumulate with prev_radii");
-    if (accumulate && sc.shs && !dL_dsh) return fail(fn + ": accumulate with factored SH (dL_dsh NULL)");
-    if (!frame || !radii || !dL_dmean2D || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
-        (sc.shs && !clamped))
-        return fail(fn + ": a required pointer is NULL");
-    if (source == 0 && (!dL_dconic || !dL_ddepth)) return fail(fn + ": source 0 reads dL_dconic and dL_ddepth");
-    if (source != 0 && (!aux || !tiles_touched || !rows || !dL_dopacity || !dL_dsemantic))
-        return fail(fn + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic");
-    if (source == 2 && !row_flags) return fail(fn + ": source 2 needs the validity bytes");
-    if (check_workspace(fn, workspace) < 0) return -1;
-    if ((reinterpret_cast<uintptr_t>(dL_drot) & 15u) || (aux && (reinterpret_cast<uintptr_t>(aux) & 15u)) ||
-        (rows && (reinterpret_cast<uintptr_t>(rows) & 15u)) || (row_flags && (reinterpret_cast<uintptr_t>(row_flags) & 3u)) ||
-        (dL_dsemantic && (reinterpret_cast<uintptr_t>(dL_dsemantic) & 15u)))
-        return fail(fn + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned");
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    GeomView g{};
-    g.counters = static_cast<uint32_t*>(workspace);  // a 256-byte counter block: the frame words where the kernel reads them
-    g.cov3D = const_cast<float*>(cov3D);
-    g.clamped = const_cast<uint8_t*>(clamped);
-    g.aux = reinterpret_cast<uint4*>(const_cast<uint32_t*>(aux));
-    g.tiles_touched = const_cast<uint32_t*>(tiles_touched);
-    static_assert(COUNTER_N < 64 && COUNTER_V < 64 && COUNTER_OVF < 64, "the frame words fit the 256-byte counter block");
-    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_N, frame + 0, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_V, frame + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_OVF, frame + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    PreprocessBwdArgs pa;
-    pa.blend = BlendGrads{dL_dmean2D, const_cast<float*>(dL_dconic), dL_dopacity, dL_dcolor, dL_dsemantic,
-                          const_cast<float*>(dL_ddepth)};  // (dL_dconic and dL_ddepth are only ever read)
-    pa.out = GaussGrads{dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
-    pa.rows = source != 0 ? rows : nullptr;
-    pa.flags = source == 2 ? row_flags : nullptr;
-    pa.n_cap = (int)n_cap;
-    pa.prev_radii = prev_radii;
-    pa.accumulate = accumulate;
-    pa.max_blocks = max_blocks;
-    launch_preprocess_bwd(sc, g, radii, pa, s);
-    GOI_HIP(hipGetLastError());
-    return 0;
-}
-
-int goi_raster_debug_pair_eval(int P, int W, int H, const void* geom_buffer, const uint32_t* requests, long long n_requests,
-                               float* E, float* alpha, uint8_t* guards, void* stream) {
-    const std::string fn = "goi_raster_debug_pair_eval";
-    if (P <= 0 || W <= 0 || H <= 0) return fail(fn + ": bad P/W/H");
-    if (n_requests < 0 || n_requests > (1ll << 31)) return fail(fn + ": need 0 <= n_requests <= 2^31");
-    if (n_requests == 0) return 0;
-    if (!requests || !E || !alpha || !guards) return fail(fn + ": a required pointer is NULL");
-    if (check_workspace(fn, geom_buffer, "geom_buffer") < 0) return -1;
-    if (reinterpret_cast<uintptr_t>(requests) & 7u) return fail(fn + ": requests must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(E) & 3u) || (reinterpret_cast<uintptr_t>(alpha) & 3u))
-        return fail(fn + ": E and alpha must be 4-byte aligned");
-    const GeomView g = frame_views(P, W, H, 0, geom_buffer, nullptr, nullptr).g;
-    launch_pair_eval(P, W, H, g, requests, n_requests, E, alpha, guards, static_cast<hipStream_t>(stream));
-    GOI_HIP(hipGetLastError());
     return 0;
 }
 

@@ -1,7 +1,7 @@
 // Binning between the per-Gaussian preprocess and the tile blend: compaction of the listed Gaussians for the depth sort,
 // the load-balanced emit of (tile, Gaussian) instances in depth order, tile ranges.  Integer work (the one float divide in
 // emit is corrected to the exact quotient), so this unit is compiled with the default contraction -- only the per-Gaussian
-// arithmetic of preprocess.hip needs -ffp-contract=off to keep the reference's operation order.
+// arithmetic of preprocess_fwd.hip / preprocess_bwd.hip needs -ffp-contract=off to keep the reference's operation order.
 // Reference: duplicateWithKeys / identifyTileRanges, cuda_rasterizer/rasterizer_impl.cu:70-138.
 #include <algorithm>
 

@@ -11,6 +11,7 @@
 // that each walk their own list: the number of (block, Gaussian) pairs with at least one live lane -- and how many
 // candidates pass the forward's quadrant hit test (its evaluated pairs).
 #include "blend_common.h"
+#include "entry.h"
 
 namespace goi {
 
@@ -136,8 +137,8 @@ __global__ __launch_bounds__(64) void pair_eval_k(const uint2* __restrict__ req,
 
 }  // namespace
 
-void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* requests, long long n, float* E, float* alpha,
-                      uint8_t* guards, hipStream_t s) {
+static void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* requests, long long n, float* E,
+                             float* alpha, uint8_t* guards, hipStream_t s) {
     const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
     constexpr long long CHUNK = 1ll << 20;  // requests per launch: a whole frame's member pairs go through in a few launches
     for (long long first = 0; first < n; first += CHUNK) {
@@ -147,12 +148,43 @@ void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* re
     }
 }
 
-void launch_blend_stats(int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list,
-                        const unsigned long long* qmask, unsigned long long* out, hipStream_t s) {
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    const int n_quads = gx * gy * 4;
-    blend_stats_k<<<dim3(quad_grid(n_quads)), dim3(64), 0, s>>>(im.ranges, point_list, W, H, gx, n_quads, g.rec, im.n_contrib,
-                                                                 im.qcost, im.qmask0, qmask, out);
+}  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+int goi_raster_debug_pair_eval(int P, int W, int H, const void* geom_buffer, const uint32_t* requests, long long n_requests,
+                               float* E, float* alpha, uint8_t* guards, void* stream) {
+    const std::string fn = "goi_raster_debug_pair_eval";
+    if (P <= 0 || W <= 0 || H <= 0) return fail(fn + ": bad P/W/H");
+    if (n_requests < 0 || n_requests > (1ll << 31)) return fail(fn + ": need 0 <= n_requests <= 2^31");
+    if (n_requests == 0) return 0;
+    if (!requests || !E || !alpha || !guards) return fail(fn + ": a required pointer is NULL");
+    if (check_workspace(fn, geom_buffer, "geom_buffer") < 0) return -1;
+    if (reinterpret_cast<uintptr_t>(requests) & 7u) return fail(fn + ": requests must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(E) & 3u) || (reinterpret_cast<uintptr_t>(alpha) & 3u))
+        return fail(fn + ": E and alpha must be 4-byte aligned");
+    const GeomView g = frame_views(P, W, H, 0, geom_buffer, nullptr, nullptr).g;
+    launch_pair_eval(P, W, H, g, requests, n_requests, E, alpha, guards, static_cast<hipStream_t>(stream));
+    GOI_HIP(hipGetLastError());
+    return 0;
 }
 
-}  // namespace goi
+int goi_raster_blend_stats(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
+                           const void* image_buffer, unsigned long long* counters, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P <= 0 || W <= 0 || H <= 0 || R < 0) return fail("goi_raster_blend_stats: bad P/W/H/R");
+    if (!geom_buffer || !image_buffer || !counters || (R > 0 && !binning_buffer)) return fail("workspace pointer is NULL");
+    GOI_HIP(hipMemsetAsync(counters, 0, GOI_BLEND_STATS_WORDS * sizeof(unsigned long long), s));
+    if (R == 0) return 0;
+    const FrameViews f = frame_views(P, W, H, R, geom_buffer, image_buffer, binning_buffer);
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    const int n_quads = gx * gy * 4;
+    blend_stats_k<<<dim3(quad_grid(n_quads)), dim3(64), 0, s>>>(f.im.ranges, f.plist, W, H, gx, n_quads, f.g.rec, f.im.n_contrib,
+                                                                 f.im.qcost, f.im.qmask0, f.bv.qmask, counters);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

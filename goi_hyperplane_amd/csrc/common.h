@@ -119,6 +119,17 @@ size_t geom_layout(int P, char* base, GeomView* v);
 size_t image_layout(int W, int H, char* base, ImageView* v);
 size_t binning_layout(int N, char* base, BinView* v);
 
+// What a finished forward left in the caller's opaque workspaces: the geometry state, the image state and the binning state of
+// the R instances the forward returned, with the final (tile-sorted) point list.  The image view stays zero where image is
+// NULL, the binning view and the list where binning is NULL (only a frame with R == 0 may come without one: callers check).
+struct FrameViews {
+    GeomView g;
+    ImageView im;
+    BinView bv;
+    const uint32_t* plist;
+};
+FrameViews frame_views(int P, int W, int H, int R, const void* geom, const void* image, const void* binning);  // api.hip
+
 // Tuning / experiment switches (goi_raster_set_option); defaults are the shipped configuration.
 struct Options {
     int fwd_variant = 1;  // 0: one candidate per loop trip, 1: two candidates per trip (default)
@@ -228,17 +239,6 @@ void launch_render_fwd(const GoiRasterScene& sc, const GeomView& g, const ImageV
                        uint32_t* host_words = nullptr,  // host_words: pinned, device-mapped words that get counters[0 .. 32) ...
                        uint32_t stamp = 0);  // ... and, behind a system-scope fence, `stamp` in word HOST_STAMP_WORD (api.hip: tickets)
 constexpr int HOST_STAMP_WORD = 33;
-// lane utilisation of the blend kernels counted from a forward's member masks / n_contrib (blend_stats.hip): out[GOI_BLEND_STATS_WORDS]
-void launch_blend_stats(int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list,
-                        const unsigned long long* qmask, unsigned long long* out, hipStream_t s);
-// peak blend weight per Gaussian (max-merged into peak[P]) and the dominant contributor per pixel (top_id / top_w [H*W]) of a
-// finished frame, by one replay of its tile lists (contrib.hip); any of the three may be NULL
-void launch_contrib(int P, int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list, float* peak,
-                    int* top_id, float* top_w, hipStream_t s);
-// one wave per request (Gaussian id, 4 tile + quadrant): E, alpha and the guard bits of the quadrant's 64 pixels through
-// poly_coefs / eval_poly (blend_stats.hip; tests only)
-void launch_pair_eval(int P, int W, int H, const GeomView& g, const uint32_t* requests, long long n, float* E, float* alpha,
-                      uint8_t* guards, hipStream_t s);
 void launch_trace_fwd(const GoiRasterScene& sc, const float* img_sem, const GeomView& g, const ImageView& im,
                       const uint32_t* point_list, float* out_color, float* gau_sem, int* num_gsem, hipStream_t s);
 // ---- the backward's three gradient sets ---------------------------------------------------------
@@ -286,8 +286,6 @@ void launch_reduce_rows(const GoiRasterScene& sc, const GeomView& g, int N, cons
                         uint8_t* contrib = nullptr);  // (records only) BwdScratchView::contrib, or NULL: every record is stored, no byte
 void launch_render_bwd_tile(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                             const float* out_alpha, const PixelGrads& dpix, const BlendGrads& out, hipStream_t s);
-void launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* campos, const float* gcol,
-                               float* dL_dsh, hipStream_t s);
 // What launch_preprocess_bwd works on besides the scene and the forward's geometry state.  Value-initialised: a caller names
 // what it uses.
 struct PreprocessBwdArgs {
@@ -301,7 +299,7 @@ struct PreprocessBwdArgs {
     const uint8_t* flags = nullptr;  // ... or, with its validity bytes given, the rows themselves: the kernel sums them (bwd_records 2)
     int n_cap = 0;                   // (with flags) instances the row scratch was laid out for
     const uint8_t* contrib = nullptr;  // (records only) BwdScratchView::contrib: idle visible Gaussians skip the chain
-    // What the output buffers already hold (BwdArgs in preprocess.hip):
+    // What the output buffers already hold (BwdArgs in preprocess_bwd.hip):
     const int* prev_radii = nullptr;     // rows that already hold zeros
     const uint8_t* prev_mask = nullptr;  // the same per row ...
     uint8_t* row_mask = nullptr;         // ... and what this call leaves (may be the same array)
@@ -310,7 +308,6 @@ struct PreprocessBwdArgs {
 };
 void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, const PreprocessBwdArgs& args,
                            hipStream_t s);
-void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
 // Tile rectangle of a Gaussian (restates getRect, CR/auxiliary.h:46-56: float divide, truncation).
 __device__ __forceinline__ void tile_rect(float px, float py, int r, int gx, int gy, int& x0, int& y0, int& x1,

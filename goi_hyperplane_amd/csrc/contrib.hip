@@ -18,6 +18,7 @@
 // A Gaussian whose peak is 0 over a camera set never passed the guards on a live pixel of any of those frames: without it
 // every pixel's sequence of live hits, and therefore every output map, is unchanged bit for bit.
 #include "blend_common.h"
+#include "entry.h"
 
 namespace goi {
 
@@ -138,13 +139,32 @@ __global__ __launch_bounds__(64) void contrib_k(const uint2* __restrict__ ranges
 
 }  // namespace
 
-void launch_contrib(int P, int W, int H, const GeomView& g, const ImageView& im, const uint32_t* point_list, float* peak,
-                    int* top_id, float* top_w, hipStream_t s) {
+}  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+int goi_raster_contrib_frame(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
+                             const void* image_buffer, float* peak, int* top_id, float* top_w, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P <= 0 || W <= 0 || H <= 0 || R < 0) return fail("goi_raster_contrib_frame: bad P/W/H/R");
+    if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail("goi_raster_contrib_frame: workspace pointer is NULL");
+    if (!peak && !top_id && !top_w) return fail("goi_raster_contrib_frame: peak, top_id and top_w are all NULL");
+    if (R == 0) {  // nothing listed: peak stays as it is, no pixel has a contributor
+        const size_t HW = (size_t)W * H;
+        if (top_id) GOI_HIP(hipMemsetAsync(top_id, 0xFF, HW * sizeof(int), s));
+        if (top_w) GOI_HIP(hipMemsetAsync(top_w, 0, HW * sizeof(float), s));
+        return 0;
+    }
+    const FrameViews f = frame_views(P, W, H, R, geom_buffer, image_buffer, binning_buffer);
     const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
     const int n_quads = gx * gy * 4;
-    contrib_k<<<dim3(quad_grid(n_quads)), dim3(64), 0, s>>>(im.ranges, point_list, P, W, H, gx, n_quads, g.rec,
-                                                            g.counters + COUNTER_OVF, reinterpret_cast<uint32_t*>(peak), top_id,
+    contrib_k<<<dim3(quad_grid(n_quads)), dim3(64), 0, s>>>(f.im.ranges, f.plist, P, W, H, gx, n_quads, f.g.rec,
+                                                            f.g.counters + COUNTER_OVF, reinterpret_cast<uint32_t*>(peak), top_id,
                                                             top_w);
+    GOI_HIP(hipGetLastError());
+    return 0;
 }
 
-}  // namespace goi
+}  // extern "C"

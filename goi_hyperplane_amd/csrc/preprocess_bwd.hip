@@ -1,393 +1,24 @@
-// Per-Gaussian kernels: forward preprocess (project, EWA cov2D, conic, radius, tile rectangle,
-// SH -> RGB, render record) and its backward (conic -> cov3D/mean, projection, depth, SH, cov3D ->
-// scale/rotation).  Compiled with -ffp-contract=off: these stages are HBM-bound streaming, and
-// keeping the reference's operation order makes radii / tile rectangles / depth keys integer-exact.
+// Per-Gaussian backward kernel: the backward of the forward preprocess in preprocess_fwd.hip (conic -> cov3D/mean, projection,
+// depth, SH, cov3D -> scale/rotation), with the factored dL/dSH kernel beside it and the two entries that drive them directly
+// (goi_raster_debug_preprocess_backward, goi_raster_sh_grad_from_views).  What the two per-Gaussian kernels share is
+// preprocess_common.h.  Compiled with -ffp-contract=off: these stages are HBM-bound streaming, and
+// keeping the reference's operation order keeps the gradients those of the reference's statement sequence.
 //
 // Behaviour restated from the reference (paths relative to submodules/diff-gaussian-rasterization/):
-//   forward : cuda_rasterizer/forward.cu:155-256 (+ :20-71 SH, :74-113 cov2D, :118-152 cov3D),
-//             cuda_rasterizer/auxiliary.h:41-56,139-164
 //   backward: cuda_rasterizer/backward.cu:144-274 (cov2D), :346-412 (projection/depth),
 //             :20-139 (SH), :278-341 (cov3D)
-// Layout is this library's own: one 48-byte GaussRec per Gaussian instead of five arrays, depth
-// keys for the per-Gaussian depth sort, 3 clamp bits in one byte.
+// Layout is this library's own: one 48-byte GaussRec per Gaussian instead of five arrays, 3 clamp bits in one byte.
 #include <algorithm>
-#include <type_traits>
+#include <climits>
 
 #include "common.h"
-#include "gmath.h"
+#include "entry.h"
+#include "preprocess_common.h"
 #include "row_sum.h"
 
 namespace goi {
 
 namespace {
-
-__device__ __forceinline__ float ndc_to_pix(float v, int S) { return (float)(((v + 1.0) * S - 1.0) * 0.5); }
-
-__device__ __forceinline__ M3 rotation_from_quat(float r, float x, float y, float z) {
-    return make_m3(1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
-                   2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
-                   2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y));
-}
-
-struct Cov2D {
-    M3 T, Vrk, W;
-    V3 t;
-    float txtz, tytz, limx, limy;
-    M3 cov;
-};
-
-__device__ __forceinline__ void ewa_cov2d(V3 mean, float fx, float fy, float tan_fovx, float tan_fovy,
-                                          const float* cov3D, const float* view, Cov2D& c) {
-    V3 t = xform_point_4x3(mean, view);
-    c.limx = 1.3f * tan_fovx;
-    c.limy = 1.3f * tan_fovy;
-    c.txtz = t.x / t.z;
-    c.tytz = t.y / t.z;
-    t.x = fminf(c.limx, fmaxf(-c.limx, c.txtz)) * t.z;
-    t.y = fminf(c.limy, fmaxf(-c.limy, c.tytz)) * t.z;
-    c.t = t;
-    M3 J = make_m3(fx / t.z, 0.0f, -(fx * t.x) / (t.z * t.z), 0.0f, fy / t.z, -(fy * t.y) / (t.z * t.z), 0.f, 0.f, 0.f);
-    c.W = make_m3(view[0], view[4], view[8], view[1], view[5], view[9], view[2], view[6], view[10]);
-    c.T = mul(c.W, J);
-    c.Vrk = make_m3(cov3D[0], cov3D[1], cov3D[2], cov3D[1], cov3D[3], cov3D[4], cov3D[2], cov3D[4], cov3D[5]);
-    c.cov = mul(mul(transpose(c.T), transpose(c.Vrk)), c.T);
-}
-
-struct PreArgs {
-    int P, D, M, W, H, gx, gy, prefiltered, cull;
-    const float* means3D;
-    const float* shs;
-    const float* colors_precomp;
-    const float* opacities;
-    const float* scales;
-    const float* rotations;
-    const float* cov3D_precomp;
-    float scale_modifier, tan_fovx, tan_fovy, focal_x, focal_y;
-    const float* view_p;    // device, [16]
-    const float* proj_p;    // device, [16]
-    const float* campos_p;  // device, [3]
-    // speculative depth cut-off of the tile lists (api.hip, goi_raster_forward_async_cut): zcut[t] = view depth beyond which
-    // tile t's list was never walked when this camera was rendered last (NULL: no cut); zlearn[t]: what this frame learns
-    // (cleared here, written by the forward blend)
-    const float* zcut;
-    uint32_t* zlearn;
-    // per-Gaussian SELECTION (goi_raster_forward_selected; read by preprocess_fwd_k<true> only): keep[id] is one byte per Gaussian,
-    // and Gaussian id is UNSELECTED when (keep[id] != 0) == (keep_invert != 0) -- keep_invert = 0 renders the Gaussians whose byte
-    // is set, keep_invert = 1 the others.  NULL: no selection (preprocess_fwd_k<false>).
-    const uint8_t* keep;
-    int keep_invert;
-};
-
-// The camera arrays are tiny, uniform device arrays: every thread reads them through the scalar
-// cache into registers once.
-struct Camera {
-    float view[16], proj[16], campos[3];
-};
-__device__ __forceinline__ Camera load_camera(const float* __restrict__ v, const float* __restrict__ p,
-                                              const float* __restrict__ c) {
-    Camera cam;
-#pragma unroll
-    for (int i = 0; i < 16; i++) cam.view[i] = v[i];
-#pragma unroll
-    for (int i = 0; i < 16; i++) cam.proj[i] = p[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) cam.campos[i] = c[i];
-    return cam;
-}
-
-template <typename SHK_T>
-__device__ __forceinline__ V3 sh_to_rgb_sum(int D, const V3& dir, SHK_T SHK) {
-    V3 res = kSH0 * SHK(0);
-    if (D > 0) {
-        const float x = dir.x, y = dir.y, z = dir.z;
-        res = res - kSH1 * y * SHK(1) + kSH1 * z * SHK(2) - kSH1 * x * SHK(3);
-        if (D > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            res = res + kSH2[0] * xy * SHK(4) + kSH2[1] * yz * SHK(5) + kSH2[2] * (2.0f * zz - xx - yy) * SHK(6) +
-                  kSH2[3] * xz * SHK(7) + kSH2[4] * (xx - yy) * SHK(8);
-            if (D > 2) {
-                res = res + kSH3[0] * y * (3.0f * xx - yy) * SHK(9) + kSH3[1] * xy * z * SHK(10) +
-                      kSH3[2] * y * (4.0f * zz - xx - yy) * SHK(11) +
-                      kSH3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * SHK(12) +
-                      kSH3[4] * x * (4.0f * zz - xx - yy) * SHK(13) + kSH3[5] * z * (xx - yy) * SHK(14) +
-                      kSH3[6] * x * (xx - 3.0f * yy) * SHK(15);
-            }
-        }
-    }
-    return res + V3{0.5f, 0.5f, 0.5f};
-}
-
-#ifndef GOI_PRE_MINBLOCKS
-#define GOI_PRE_MINBLOCKS 1
-#endif
-// SELECT: the frame renders a SELECTION of the Gaussians (PreArgs::keep).  An unselected Gaussian leaves phase A where one behind
-// the near plane does, before anything of it has been loaded -- its selection byte is all the kernel ever reads of it -- and is
-// from there on what a frustum-culled Gaussian is: radius 0, no tiles, key 0xFFFFFFFF, no record, no instance.  Nothing
-// downstream of this kernel knows about selections.  SELECT == false is the kernel as it was.
-template <bool SELECT>
-__global__ __launch_bounds__(256, GOI_PRE_MINBLOCKS) void preprocess_fwd_k(const PreArgs args, GaussRec* __restrict__ rec,
-                                                        float* __restrict__ cov3D_out,
-                                                        uint32_t* __restrict__ tiles_touched,
-                                                        uint8_t* __restrict__ clamped, uint32_t* __restrict__ raw_key,
-                                                        uint4* __restrict__ aux,
-                                                        uint2* __restrict__ blk_agg,
-                                                        unsigned long long* __restrict__ blk_coarse, int* __restrict__ radii,
-                                                        uint32_t* __restrict__ counters, uint2* __restrict__ ranges,
-                                                        int n_tiles) {
-    const int gtid = blockIdx.x * blockDim.x + threadIdx.x;
-    // the tile ranges start from zero (emit accumulates per-tile counts into them): cleared here for free
-    for (int t = gtid; t < n_tiles; t += gridDim.x * blockDim.x) ranges[t] = make_uint2(0u, 0u);
-    if (args.zlearn)
-        for (int t = gtid; t < n_tiles; t += gridDim.x * blockDim.x) args.zlearn[t] = 0u;
-    if (gtid == 0) counters[COUNTER_CULL] = (uint32_t)args.cull;  // emit and the backward list the same rectangles
-    // every lane reaches the wave reduction at the end: lanes past P redo the last Gaussian and write nothing
-    const bool live = gtid < args.P;
-    const int idx = live ? gtid : args.P - 1;
-    const Camera cam = load_camera(args.view_p, args.proj_p, args.campos_p);
-    struct : PreArgs {
-        const float *view, *proj, *campos;
-    } a;
-    static_cast<PreArgs&>(a) = args;
-    a.view = cam.view;
-    a.proj = cam.proj;
-    a.campos = cam.campos;
-    int my_radius_i = 0;
-    unsigned long long tmask_v = TMASK_FULL;
-    uint32_t touched = 0, key = 0xFFFFFFFFu;
-    uint8_t clamp_bits = 0;
-
-    // (a lane past P looks at the byte of Gaussian P - 1, as it redoes that Gaussian: in bounds, and if that one is unselected
-    // the lane leaves phase A with it)
-    bool unselected = false;
-    if constexpr (SELECT) unselected = (args.keep[idx] != 0) == (args.keep_invert != 0);
-    V3 p = {0.f, 0.f, 0.f};
-    if (!SELECT || !unselected) p = V3{a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]};
-    const V3 p_view = xform_point_4x3(p, a.view);
-    // ---- phase A: projection, covariance, conic, radius, 3-sigma rectangle: is the Gaussian rendered at all?
-    bool vis = false;
-    float pix = 0.f, piy = 0.f, con_a = 0.f, con_b = 0.f, con_c = 0.f, my_radius = 0.f;
-    do {
-        if (SELECT && unselected) break;  // (not the caller's "prefiltered" promise broken: no trap)
-        if (p_view.z <= 0.2f) {
-            if (a.prefiltered) atomicOr(&counters[1], 1u);  // the reference traps here
-            break;
-        }
-        const float4 p_hom = xform_point_4x4(p, a.proj);
-        const float p_w = 1.0f / (p_hom.w + 0.0000001f);
-        const float projx = p_hom.x * p_w, projy = p_hom.y * p_w;
-
-        float cov3D[6];
-        if (a.cov3D_precomp) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) cov3D[i] = a.cov3D_precomp[(size_t)6 * idx + i];
-        } else {
-            M3 S = make_m3(1, 0, 0, 0, 1, 0, 0, 0, 1);
-            S.c[0][0] = a.scale_modifier * a.scales[3 * idx];
-            S.c[1][1] = a.scale_modifier * a.scales[3 * idx + 1];
-            S.c[2][2] = a.scale_modifier * a.scales[3 * idx + 2];
-            const float4 q = reinterpret_cast<const float4*>(a.rotations)[idx];  // (r,x,y,z), not normalised
-            M3 R = rotation_from_quat(q.x, q.y, q.z, q.w);
-            M3 Mm = mul(S, R);
-            M3 Sg = mul(transpose(Mm), Mm);
-            cov3D[0] = Sg.c[0][0]; cov3D[1] = Sg.c[0][1]; cov3D[2] = Sg.c[0][2];
-            cov3D[3] = Sg.c[1][1]; cov3D[4] = Sg.c[1][2]; cov3D[5] = Sg.c[2][2];
-#pragma unroll
-            for (int i = 0; i < 6; i++) cov3D_out[(size_t)6 * idx + i] = cov3D[i];
-        }
-        Cov2D c2;
-        ewa_cov2d(p, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, a.view, c2);
-        const float cx = c2.cov.c[0][0] + 0.3f, cy = c2.cov.c[0][1], cz = c2.cov.c[1][1] + 0.3f;
-        const float det = cx * cz - cy * cy;
-        if (det == 0.0f) break;
-        const float det_inv = 1.f / det;
-        con_a = cz * det_inv;
-        con_b = -cy * det_inv;
-        con_c = cx * det_inv;
-        const float mid = 0.5f * (cx + cz);
-        const float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
-        const float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
-        my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
-        pix = ndc_to_pix(projx, a.W);
-        piy = ndc_to_pix(projy, a.H);
-        int x0, y0, x1, y1;
-        tile_rect(pix, piy, (int)my_radius, a.gx, a.gy, x0, y0, x1, y1);
-        if ((x1 - x0) * (y1 - y0) == 0) break;
-        vis = live;  // (a lane past P has redone the last Gaussian up to here: it must not store anything)
-    } while (false);
-
-    // ---- phase B: contribution box, listed rectangle, ellipse tile mask (nothing here needs the colour)
-    float hx = -1.f, hy = -1.f, o = 0.f;
-    if (vis) {
-        // Box outside which alpha = min(0.99, o*exp(power)) < 1/255 is certain (see DESIGN.md,
-        // "exact contribution box"): the ellipse power >= -tau of the COMPUTED conic, tau inflated.
-        o = a.opacities[idx];
-        if (o >= 1.0f / 255.0f) {
-            // In single precision, every rounding pushed OUTWARD (the box only has to contain the region; its size
-            // decides nothing but how many tiles and quadrants are looked at): the double-precision log / sqrt / divide
-            // this replaces were software routines of a few hundred instructions on the critical path of every visible lane.
-            //   tau = 1.01 ln(255 o) + 0.01, rounded up;  det = a c - b b by Kahan's difference of products (within
-            //   1.5 ulp even when the two products cancel: a needle), rounded down;  h = sqrt(2 tau c / det), rounded up.
-            const float tau = fmaf(1.01f, logf(255.0f * o), 0.01f) * 1.000002f + 1e-6f;
-            const float bb = con_b * con_b;
-            const float detc = (fmaf(con_a, con_c, -bb) + fmaf(-con_b, con_b, bb));
-            const float det_lo = detc - 4e-7f * fabsf(detc);
-            if (det_lo > 0.f && con_a > 0.f && con_c > 0.f) {
-                hx = sqrtf(2.0f * tau * con_c / det_lo) * 1.000002f + 1e-3f;
-                hy = sqrtf(2.0f * tau * con_a / det_lo) * 1.000002f + 1e-3f;
-                if (!(hx == hx) || !(hy == hy)) hx = hy = __builtin_inff();
-            } else {
-                hx = hy = __builtin_inff();
-            }
-        }
-        my_radius_i = (int)my_radius;
-        int x0, y0, x1, y1;
-        listed_rect(pix, piy, my_radius_i, hx, hy, a.cull != 0, a.gx, a.gy, x0, y0, x1, y1);
-        touched = (uint32_t)((y1 - y0) * (x1 - x0));  // may be 0 for a visible Gaussian (radius stays > 0)
-        // cull_variant 2: of that rectangle, only the tiles the contribution ELLIPSE  1/2 d^T C d <= tau  reaches (the
-        // box over-covers by 1 - pi/4 for a round Gaussian, by most of its area for an elongated diagonal one: x0.80
-        // instances on the headline scene).  Exact for a convex set, one tile row at a time: over the row's pixel-centre
-        // band y in [16 t, 16 t + 15], clipped to the ellipse's own extent, the ellipse spans x in [L, R] with
-        //     R(dy) = (-b dy + sqrt(2 a tau - det dy^2)) / a   (concave: its maximum over the band is at the band's
-        // point nearest to the ellipse's rightmost point dy = -(b/c) hx), L likewise (convex, leftmost point); the row's
-        // tiles are those whose pixel-centre range [16 t, 16 t + 15] meets [L, R].  tau carries the box's inflation (1 % +
-        // 0.01: the blend kernels' evaluation error of `power` can never move a contributing pixel outside), every
-        // rounding here is pushed outward, and a NaN keeps the whole row.  A tile that is dropped can not receive a
-        // contribution; the per-pixel sequences of contributing Gaussians, hence all outputs and gradients, are untouched.
-        if (a.cull >= 2 && touched > 0 && touched <= 64 && hx < 1e30f && hy < 1e30f) {
-            const int w = x1 - x0;
-            const float tau = (fmaf(1.01f, logf(255.0f * o), 0.01f) * 1.000002f + 1e-6f) * 1.0001f + 1e-4f;
-            const float bb = con_b * con_b;
-            const float det = fmaxf((fmaf(con_a, con_c, -bb) + fmaf(-con_b, con_b, bb)) * (1.f - 4e-7f), 0.f);
-            const float inv_a = 1.f / con_a;
-            const float dyR = -(con_b / con_c) * hx, dyL = -dyR;  // where the ellipse is rightmost / leftmost
-            unsigned long long mask = 0ull;
-            for (int ry = 0; ry < y1 - y0; ry++) {
-                const float lo = fmaxf((float)((y0 + ry) * TILE) - piy, -hy), hi = fminf((float)((y0 + ry) * TILE + TILE - 1) - piy, hy);
-                if (!(lo <= hi)) {
-                    if (lo == lo && hi == hi) continue;  // the band misses the ellipse's extent
-                }
-                const float d1 = fminf(fmaxf(dyR, lo), hi), d2 = fminf(fmaxf(dyL, lo), hi);
-                const float s1 = sqrtf(fmaxf(2.f * con_a * tau - det * d1 * d1, 0.f));
-                const float s2 = sqrtf(fmaxf(2.f * con_a * tau - det * d2 * d2, 0.f));
-                float R = (-con_b * d1 + s1) * inv_a, L = (-con_b * d2 - s2) * inv_a;
-                R += 1e-3f + 4e-6f * fabsf(R);
-                L -= 1e-3f + 4e-6f * fabsf(L);
-                // columns t with 16 t <= pix + R and 16 t + 15 >= pix + L
-                int c0 = (int)ceilf((pix + L - (float)(TILE - 1)) / TILE), c1 = (int)floorf((pix + R) / TILE) + 1;
-                if (!(R == R) || !(L == L)) {
-                    c0 = x0;
-                    c1 = x1;
-                }
-                c0 = max(c0, x0);
-                c1 = min(c1, x1);
-                if (c1 > c0) mask |= ((c1 - c0 >= 64) ? ~0ull : ((1ull << (c1 - c0)) - 1ull)) << (ry * w + (c0 - x0));
-            }
-            // speculative depth cut-off: a tile whose list was not needed beyond depth zcut[t] the last time this camera was
-            // rendered does not list a deeper Gaussian (the forward blend raises the frame's flag if a pixel of such a tile
-            // turns out to want more: api.hip).  Eight tiles per trip, their cut depths requested together (one load round
-            // trip for the typical 3 x 3 rectangle; tile by tile this loop cost the kernel 28 us).
-            if (a.zcut) {
-                unsigned long long todo = mask;
-                while (todo) {
-                    int bits[8];
-                    float zc[8];
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        bits[i] = todo ? __builtin_ctzll(todo) : -1;
-                        if (todo) todo &= todo - 1;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const int bsafe = max(bits[i], 0);
-                        zc[i] = a.zcut[(size_t)(y0 + bsafe / w) * a.gx + (x0 + bsafe % w)];
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; i++)
-                        if (bits[i] >= 0 && zc[i] < p_view.z) mask &= ~(1ull << bits[i]);
-                }
-            }
-            tmask_v = mask;
-            touched = (uint32_t)__popcll(mask);
-        }
-        key = __float_as_uint(p_view.z);
-    }
-
-    // everything that does not depend on the colour leaves NOW: the values are dead while the SH rows are in registers
-    if (vis) {
-        float4* r4 = reinterpret_cast<float4*>(rec + idx);
-        r4[0] = make_float4(pix, piy, con_a, con_b);
-        r4[1] = make_float4(con_c, o, hx, hy);       // what the hit test needs beside q0: fetched for every CANDIDATE
-    }
-    if (live) {
-        radii[idx] = my_radius_i;
-        tiles_touched[idx] = touched;
-        raw_key[idx] = key;  // depth bits by Gaussian id; compact_listed_k keeps the listed ones for the depth sort
-        aux[idx] = make_uint4(0u, (uint32_t)my_radius_i, (uint32_t)tmask_v, (uint32_t)(tmask_v >> 32));  // (.x: emit)
-    }
-
-    // ---- phase C: the colour
-    float cr = 0.f, cg = 0.f, cb = 0.f;
-    V3 dir = {0.f, 0.f, 0.f};
-    if (vis && !a.colors_precomp) {
-        const V3 campos = {a.campos[0], a.campos[1], a.campos[2]};
-        dir = p - campos;
-        dir = dir / sqrtf(dot3(dir, dir));
-    }
-    auto finish_colour = [&](const V3& res) {
-        clamp_bits = (uint8_t)((res.x < 0 ? 1 : 0) | (res.y < 0 ? 2 : 0) | (res.z < 0 ? 4 : 0));
-        cr = fmaxf(res.x, 0.0f);
-        cg = fmaxf(res.y, 0.0f);
-        cb = fmaxf(res.z, 0.0f);
-    };
-    if (vis) {
-        if (a.colors_precomp) {
-            cr = a.colors_precomp[3 * idx];
-            cg = a.colors_precomp[3 * idx + 1];
-            cb = a.colors_precomp[3 * idx + 2];
-        } else {
-            // A degree-3 row (M = 16: 192 bytes, 16-byte aligned) is fetched as TWELVE 16-byte loads instead of sixteen 12-byte ones
-            float rowf[48];
-            const bool row16 = a.M == 16;
-            if (row16) {
-                const float4* r4 = reinterpret_cast<const float4*>(a.shs + (size_t)idx * 48);
-#pragma unroll
-                for (int i = 0; i < 12; i++) {
-                    const float4 v = r4[i];
-                    rowf[4 * i] = v.x;
-                    rowf[4 * i + 1] = v.y;
-                    rowf[4 * i + 2] = v.z;
-                    rowf[4 * i + 3] = v.w;
-                }
-            }
-            const V3* shg = reinterpret_cast<const V3*>(a.shs) + (size_t)idx * a.M;
-            finish_colour(sh_to_rgb_sum(a.D, dir, [&](int k) { return row16 ? V3{rowf[3 * k], rowf[3 * k + 1], rowf[3 * k + 2]} : shg[k]; }));
-        }
-    }
-    // what only a HIT needs (r, g, b, depth: the first staged feature quad as it is)
-    if (vis) reinterpret_cast<float4*>(rec + idx)[2] = make_float4(cr, cg, cb, p_view.z);
-    if (live) clamped[idx] = clamp_bits;
-    // num_rendered = sum of tiles_touched: order-independent, so it is formed HERE (one integer atomic per wave)
-    // instead of falling out of the prefix sum after the depth sort -- the host can read it while the sort runs
-    __shared__ uint32_t s_wsum[4], s_wvis[4];
-    uint32_t wsum = live ? touched : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wsum += (uint32_t)__shfl_xor((int)wsum, d, 64);
-    const uint32_t wvis = (uint32_t)__popcll(__ballot(live && touched > 0));  // LISTED Gaussians of this wave
-    if ((threadIdx.x & 63) == 0) {
-        s_wsum[threadIdx.x >> 6] = wsum;
-        s_wvis[threadIdx.x >> 6] = wvis;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t bsum = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
-        if (bsum) atomicAdd(&counters[NR_BASE + NR_STRIDE * (blockIdx.x % NR_STRIPES)], bsum);
-        // the block's aggregate: compact_listed_k ranks the listed Gaussians with it
-        const uint32_t bvis = s_wvis[0] + s_wvis[1] + s_wvis[2] + s_wvis[3];
-        blk_agg[blockIdx.x] = make_uint2(bvis, bsum);
-        // ... and the sum over COARSE_BLOCKS consecutive blocks (compact_listed_k's base rank), packed: one integer atomic
-        if (bvis) atomicAdd(&blk_coarse[(size_t)(blockIdx.x / COARSE_BLOCKS) * COARSE_STRIDE], ((unsigned long long)bvis << 40) | bsum);
-    }
-}
 
 struct BwdArgs {
     int P, D, M, W, H;
@@ -1141,46 +772,7 @@ __global__ __launch_bounds__(256) void sh_grad_from_views_k(int P, int D, int M,
     }
 }
 
-__global__ __launch_bounds__(256) void mark_visible_k(int P, const float* __restrict__ means3D, const float* view,
-                                                      uint8_t* __restrict__ present) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= P) return;
-    const V3 p = {means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]};
-    float m[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) m[i] = view[i];
-    present[idx] = xform_point_4x3(p, m).z > 0.2f ? 1 : 0;
-}
-
 }  // namespace
-
-void launch_preprocess_fwd(const GoiRasterScene& sc, const GeomView& g, int* radii, uint2* ranges, int n_tiles,
-                           hipStream_t s, const float* zcut, uint32_t* zlearn, const uint8_t* keep, int keep_invert) {
-    PreArgs a;
-    a.keep = keep;
-    a.keep_invert = keep_invert;
-    a.zcut = g_options.cull_variant >= 2 ? zcut : nullptr;  // (the cut lives in the ellipse tile masks)
-    a.zlearn = zlearn;
-    a.P = sc.P; a.D = sc.D; a.M = sc.M; a.W = sc.W; a.H = sc.H;
-    a.gx = (sc.W + TILE - 1) / TILE;
-    a.gy = (sc.H + TILE - 1) / TILE;
-    a.prefiltered = sc.prefiltered;
-    a.cull = g_options.cull_variant;
-    a.means3D = sc.means3D; a.shs = sc.shs; a.colors_precomp = sc.colors_precomp; a.opacities = sc.opacities;
-    a.scales = sc.scales; a.rotations = sc.rotations; a.cov3D_precomp = sc.cov3D_precomp;
-    a.scale_modifier = sc.scale_modifier; a.tan_fovx = sc.tan_fovx; a.tan_fovy = sc.tan_fovy;
-    a.focal_y = sc.H / (2.0f * sc.tan_fovy);
-    a.focal_x = sc.W / (2.0f * sc.tan_fovx);
-    a.view_p = sc.viewmatrix; a.proj_p = sc.projmatrix; a.campos_p = sc.campos;
-    static_assert(PRE_BLOCK == 256, "preprocess_fwd_k is written for 256-thread workgroups");
-    const dim3 grid((sc.P + PRE_BLOCK - 1) / PRE_BLOCK);
-#define GOI_PRE(SELECT)                                                                                                          \
-    preprocess_fwd_k<SELECT><<<grid, dim3(PRE_BLOCK), 0, s>>>(a, g.rec, g.cov3D, g.tiles_touched, g.clamped, g.sort_keys[1], g.aux, \
-                                                              g.blk_agg, g.blk_coarse, radii, g.counters, ranges, n_tiles)
-    if (keep) GOI_PRE(true);
-    else GOI_PRE(false);
-#undef GOI_PRE
-}
 
 void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const int* radii, const PreprocessBwdArgs& args,
                            hipStream_t s) {
@@ -1234,14 +826,95 @@ void launch_preprocess_bwd(const GoiRasterScene& sc, const GeomView& g, const in
 #undef GOI_PBWD
 }
 
-void launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* campos, const float* gcol,
-                               float* dL_dsh, hipStream_t s) {
-    const size_t lds = (size_t)256 * (3 * M + 1) * sizeof(float);
-    sh_grad_from_views_k<<<dim3((P + 255) / 256), dim3(256), lds, s>>>(P, D, M, V, means3D, campos, gcol, dL_dsh);
-}
-
-void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s) {
-    mark_visible_k<<<dim3((P + 255) / 256), dim3(256), 0, s>>>(P, means3D, view, present);
-}
-
 }  // namespace goi
+
+using namespace goi;
+
+extern "C" {
+
+int goi_raster_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* campos, const float* gcol,
+                           float* dL_dsh, void* stream) {
+    if (P <= 0 || V <= 0) return 0;
+    if (D < 0 || D > 3 || M < (D + 1) * (D + 1) || M > 16) return fail("goi_raster_sh_grad_from_views: need 0 <= D <= 3 and (D+1)^2 <= M <= 16");
+    if (!means3D || !campos || !gcol || !dL_dsh) return fail("goi_raster_sh_grad_from_views: NULL pointer");
+    const size_t lds = (size_t)256 * (3 * M + 1) * sizeof(float);
+    sh_grad_from_views_k<<<dim3((P + 255) / 256), dim3(256), lds, static_cast<hipStream_t>(stream)>>>(P, D, M, V, means3D, campos,
+                                                                                                      gcol, dL_dsh);
+    if (hipGetLastError() != hipSuccess) return fail("goi_raster_sh_grad_from_views: launch failed");
+    return 0;
+}
+
+int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source, int flags, int max_blocks, long long n_cap,
+                                         const uint32_t* frame, const int* radii, const uint8_t* clamped, const float* cov3D,
+                                         const int* prev_radii, const uint32_t* aux, const uint32_t* tiles_touched,
+                                         const float* rows, const uint8_t* row_flags, float* dL_dmean2D, const float* dL_dconic,
+                                         float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic, const float* dL_ddepth,
+                                         float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                         void* workspace, void* stream) {
+    const std::string fn = "goi_raster_debug_preprocess_backward";
+    if (!scene) return fail(fn + ": scene is NULL");
+    const GoiRasterScene& sc = *scene;
+    if (sc.P < 0 || sc.W <= 0 || sc.H <= 0) return fail(fn + ": bad P/W/H");
+    if (sc.S < 1 || sc.S > 32) return fail(fn + ": need 1 <= S <= 32");
+    if (source < 0 || source > 2) return fail(fn + ": unknown source (0 per-id arrays, 1 records, 2 rows summed in the kernel)");
+    if (flags & ~GOI_BACKWARD_ACCUMULATE) return fail(fn + ": unknown flag bits");
+    if (max_blocks < 0) return fail(fn + ": max_blocks must be >= 0 (0: the product's grid)");
+    if (n_cap < 0 || n_cap > INT_MAX) return fail(fn + ": need 0 <= n_cap < 2^31");
+    if (source == 2 && bwd_row_floats(sc.S) != 32) return fail(fn + ": source 2 sums 128-byte rows only (S = 5 .. 20)");
+    if (sc.P == 0) return 0;
+    if (!(sc.tan_fovx > 0.f) || !(sc.tan_fovy > 0.f)) return fail(fn + ": tan_fovx / tan_fovy must be positive");
+    if (!sc.means3D || !sc.viewmatrix || !sc.projmatrix || !sc.campos) return fail(fn + ": a required scene pointer is NULL");
+    if (sc.shs && sc.colors_precomp) return fail(fn + ": shs and colors_precomp are both given");
+    if (sc.shs && (sc.D < 0 || sc.D > 3 || sc.M < (sc.D + 1) * (sc.D + 1) || sc.M > 16))
+        return fail(fn + ": SH degree must be 0..3 and (D+1)^2 <= M <= 16");
+    if (sc.shs && (3 * sc.M) % 4 == 0 && (reinterpret_cast<uintptr_t>(sc.shs) & 15u) != 0)
+        return fail(fn + ": shs must be 16-byte aligned when 3 M is a multiple of 4");
+    if (!sc.shs && dL_dsh) return fail(fn + ": dL_dsh without shs");
+    if ((sc.scales == nullptr) != (sc.rotations == nullptr)) return fail(fn + ": scales and rotations go together");
+    if ((sc.scales != nullptr) == (sc.cov3D_precomp != nullptr))
+        return fail(fn + ": exactly one of the scale/rotation pair and cov3D_precomp");
+    if (sc.scales && !cov3D) return fail(fn + ": cov3D (what the forward computed from scale/rotation) is NULL");
+    if (sc.rotations && (reinterpret_cast<uintptr_t>(sc.rotations) & 15u) != 0) return fail(fn + ": rotations must be 16-byte aligned");
+    const bool accumulate = (flags & GOI_BACKWARD_ACCUMULATE) != 0;
+    if (accumulate && source != 1) return fail(fn + ": accumulate needs source 1 (the records)");
+    if (accumulate && prev_radii) return fail(fn + ": accumulate with prev_radii");
+    if (accumulate && sc.shs && !dL_dsh) return fail(fn + ": accumulate with factored SH (dL_dsh NULL)");
+    if (!frame || !radii || !dL_dmean2D || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
+        (sc.shs && !clamped))
+        return fail(fn + ": a required pointer is NULL");
+    if (source == 0 && (!dL_dconic || !dL_ddepth)) return fail(fn + ": source 0 reads dL_dconic and dL_ddepth");
+    if (source != 0 && (!aux || !tiles_touched || !rows || !dL_dopacity || !dL_dsemantic))
+        return fail(fn + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic");
+    if (source == 2 && !row_flags) return fail(fn + ": source 2 needs the validity bytes");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    if ((reinterpret_cast<uintptr_t>(dL_drot) & 15u) || (aux && (reinterpret_cast<uintptr_t>(aux) & 15u)) ||
+        (rows && (reinterpret_cast<uintptr_t>(rows) & 15u)) || (row_flags && (reinterpret_cast<uintptr_t>(row_flags) & 3u)) ||
+        (dL_dsemantic && (reinterpret_cast<uintptr_t>(dL_dsemantic) & 15u)))
+        return fail(fn + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    GeomView g{};
+    g.counters = static_cast<uint32_t*>(workspace);  // a 256-byte counter block: the frame words where the kernel reads them
+    g.cov3D = const_cast<float*>(cov3D);
+    g.clamped = const_cast<uint8_t*>(clamped);
+    g.aux = reinterpret_cast<uint4*>(const_cast<uint32_t*>(aux));
+    g.tiles_touched = const_cast<uint32_t*>(tiles_touched);
+    static_assert(COUNTER_N < 64 && COUNTER_V < 64 && COUNTER_OVF < 64, "the frame words fit the 256-byte counter block");
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_N, frame + 0, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_V, frame + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_OVF, frame + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    PreprocessBwdArgs pa;
+    pa.blend = BlendGrads{dL_dmean2D, const_cast<float*>(dL_dconic), dL_dopacity, dL_dcolor, dL_dsemantic,
+                          const_cast<float*>(dL_ddepth)};  // (dL_dconic and dL_ddepth are only ever read)
+    pa.out = GaussGrads{dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
+    pa.rows = source != 0 ? rows : nullptr;
+    pa.flags = source == 2 ? row_flags : nullptr;
+    pa.n_cap = (int)n_cap;
+    pa.prev_radii = prev_radii;
+    pa.accumulate = accumulate;
+    pa.max_blocks = max_blocks;
+    launch_preprocess_bwd(sc, g, radii, pa, s);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

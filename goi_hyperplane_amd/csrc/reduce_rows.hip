@@ -1,11 +1,13 @@
 // Row reduction of the atomic-free backward: sums the partial-gradient rows render_bwd_rows_k (render_bwd.hip) leaves per
 // (emit-order instance, quadrant) into one record (or six per-id arrays) per Gaussian, in a fixed order.  Pure additions:
-// compiled with the default flags (it used to sit in preprocess.hip under -ffp-contract=off for no reason).
+// compiled with the default flags (it used to sit with the per-Gaussian kernels under -ffp-contract=off for no reason).
 // Reference: the float atomicAdd accumulation of cuda_rasterizer/backward.cu:565-621, which this replaces.
 #include <algorithm>
+#include <climits>
 #include <type_traits>
 
 #include "common.h"
+#include "entry.h"
 #include "row_sum.h"
 
 namespace goi {
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(256) void reduce_rows_k(int P, int S, int nch, uint
     }
 }
 
-// bwd_records 2 (the per-Gaussian backward sums its Gaussians' rows itself: preprocess.hip): nobody walks the listed Gaussians
+// bwd_records 2 (the per-Gaussian backward sums its Gaussians' rows itself: preprocess_bwd.hip): nobody walks the listed Gaussians
 // in here any more, so the BIG ones are registered by this kernel -- one thread per listed Gaussian in depth order, the same
 // threshold from the same frame counters, the same descriptors -- and reduce_big_k leaves their records in the row scratch as
 // before.  (The order of the descriptors differs from run to run; every Gaussian's sum is its own: bit-reproducible.)
@@ -376,3 +378,82 @@ void launch_reduce_sem_rows(const GoiRasterScene& sc, const GeomView& g, int N, 
 }
 
 }  // namespace goi
+
+using namespace goi;
+
+// The four launchers above on caller buffers (tests: tests/test_gpu_reduce_rows.py).
+extern "C" {
+
+// The row reduction's workspace: a counter block (the frame words at COUNTER_N / COUNTER_V / COUNTER_OVF, where the launchers
+// read them), big_ctl, big_desc[cap_big] -- the tail of bwd_scratch_layout, with cap_big from the same helper.
+static size_t debug_reduce_layout(long long n_cap, char* base, uint32_t** counters, BwdScratchView* v) {
+    Carver c(base);
+    uint32_t* words = c.take<uint32_t>(64);
+    BwdScratchView tmp;
+    BwdScratchView& b = v ? *v : tmp;  // (the caller's view keeps its other fields)
+    b.cap_big = reduce_cap_big((size_t)n_cap);
+    b.big_ctl = c.take<uint32_t>(8);
+    b.big_desc = c.take<uint4>(b.cap_big);
+    if (counters) *counters = words;
+    return c.end();
+}
+
+int goi_raster_debug_reduce_row_floats(int mode, int S) {
+    if (mode < 0 || mode > 3) return fail("goi_raster_debug_reduce_rows: unknown mode");
+    if (S < 1 || S > 32) return fail("goi_raster_debug_reduce_rows: need 1 <= S <= 32");
+    if (mode == 3) return bwd_sem_row_floats(S);
+    const int rf = bwd_row_floats(S);
+    if (mode == 2 && rf != 32) return fail("goi_raster_debug_reduce_rows: mode 2 sums 128-byte rows only (S = 5 .. 20)");
+    return rf;
+}
+
+size_t goi_raster_debug_reduce_workspace_bytes(long long n_cap) {
+    if (n_cap < 0 || n_cap > INT_MAX) return 0;
+    return debug_reduce_layout(n_cap, /*base=*/nullptr, /*counters=*/nullptr, /*v=*/nullptr) + 256;  // (sizes only)
+}
+
+int goi_raster_debug_reduce_rows(int mode, int P, int S, long long n_cap, const uint32_t* frame, const uint32_t* order,
+                                 const uint32_t* offsets, const uint32_t* tiles_touched, float* rows, const uint8_t* flags,
+                                 float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
+                                 float* dL_ddepth, void* workspace, void* stream) {
+    const std::string fn = "goi_raster_debug_reduce_rows";
+    const int rf = goi_raster_debug_reduce_row_floats(mode, S);
+    if (rf < 0) return -1;
+    if (P < 0 || n_cap < 0 || n_cap > INT_MAX) return fail(fn + ": need P >= 0 and 0 <= n_cap < 2^31");
+    if (P == 0) return 0;
+    const bool arrays = mode == 0, per_id = mode == 0 || mode == 3;
+    if (!frame || !order || !offsets || !rows || !flags || (per_id && (!tiles_touched || !dL_dsemantic)) ||
+        (arrays && (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_ddepth)))
+        return fail(fn + ": a required pointer is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    GoiRasterScene sc{};
+    sc.P = P;
+    sc.S = S;
+    GeomView g{};
+    BwdScratchView scr{};
+    debug_reduce_layout(n_cap, static_cast<char*>(workspace), &g.counters, &scr);
+    g.sort_vals[depth_sort_result_index()] = const_cast<uint32_t*>(order);
+    g.offsets = const_cast<uint32_t*>(offsets);
+    g.tiles_touched = const_cast<uint32_t*>(tiles_touched);
+    scr.rows = rows;
+    scr.flags = const_cast<uint8_t*>(flags);
+    // frame = {count, listed V, overflow}; big_ctl cleared as launch_quad_order's extra workgroups (or the memset) do
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_N, frame + 0, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_V, frame + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemcpyAsync(g.counters + COUNTER_OVF, frame + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GOI_HIP(hipMemsetAsync(scr.big_ctl, 0, 8 * sizeof(uint32_t), s));
+    const int N = (int)n_cap;
+    if (mode == 0)
+        launch_reduce_rows(sc, g, N, scr, BlendGrads{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth}, s);
+    else if (mode == 1)
+        launch_reduce_rows(sc, g, N, scr, BlendGrads{}, s, true);
+    else if (mode == 2)
+        launch_reduce_big_only(sc, g, N, scr, s);
+    else
+        launch_reduce_sem_rows(sc, g, N, scr, rf, dL_dsemantic, s);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Row summation of the atomic-free backward, shared by reduce_rows.hip (reduce_rows_k, reduce_big_k) and preprocess.hip (the
+// Row summation of the atomic-free backward, shared by reduce_rows.hip (reduce_rows_k, reduce_big_k) and preprocess_bwd.hip (the
 // per-Gaussian backward that sums its Gaussians' rows itself: bwd_records 2).  Pure fp32 additions in a fixed order: the
 // instances in chunks of 16 counted from the first one, inside a chunk QUADRANT-major (the quadrant-0 rows of the chunk's
 // instances in instance order, then quadrant 1, ..) -- not slot order (slot = instance * 4 + quadrant).

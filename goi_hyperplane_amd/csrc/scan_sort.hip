@@ -13,6 +13,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "entry.h"
 
 namespace goi {
 
@@ -732,3 +733,68 @@ int radix_sort_pairs(uint32_t* const keys[2], uint32_t* const vals[2], size_t n,
 }
 
 }  // namespace goi
+
+using namespace goi;
+
+// The scan and the sort on caller buffers, at any size and bit range (tests: tests/test_gpu_scan_sort.py).
+extern "C" {
+
+static int debug_sort_args(const char* fn, long long n, int lo, int hi) {
+    if (n < 0 || n >= SORT_MAX_KEYS) return fail(std::string(fn) + ": need 0 <= n < 2^30");
+    if (lo < 0 || hi > 32 || lo >= hi) return fail(std::string(fn) + ": need 0 <= lo < hi <= 32");
+    return 0;
+}
+
+size_t goi_raster_debug_sort_workspace_bytes(long long n, int lo, int hi) {
+    if (n < 0 || n >= SORT_MAX_KEYS || lo < 0 || hi > 32 || lo >= hi) return 0;
+    return sort_scratch_words((size_t)(n > 0 ? n : 1)) * sizeof(uint32_t) + 256;
+}
+
+int goi_raster_debug_sort_pairs(uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, uint32_t* vals1, long long n, int lo, int hi,
+                                const uint32_t* n_dev, const uint32_t* ghist, int flags, uint32_t* error_out, void* workspace,
+                                void* stream) {
+    refresh_options();
+    const char* fn = "goi_raster_debug_sort_pairs";
+    if (debug_sort_args(fn, n, lo, hi) < 0) return -1;
+    if (flags & ~1) return fail(std::string(fn) + ": unknown flags");
+    const bool onesweep = g_options.sort_variant == 1;
+    if ((n_dev || ghist) && !onesweep) return fail(std::string(fn) + ": n_dev and ghist need the onesweep sort (sort_variant 1)");
+    if (n == 0) return 0;
+    if (!keys0 || !vals0 || !keys1 || !vals1) return fail(std::string(fn) + ": a required pointer is NULL");
+    if (check_workspace(fn, workspace) < 0) return -1;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t* scratch = static_cast<uint32_t*>(workspace);
+    bool cleared = (flags & 1) != 0;
+    if (ghist) {  // the rasterizer's convention: control words cleared, then the histograms written by the caller's own kernel
+        const size_t passes = (size_t)(hi - lo + 7) / 8;
+        GOI_HIP(hipMemsetAsync(scratch, 0, radix_sort_control_words((size_t)n, lo, hi) * sizeof(uint32_t), s));
+        GOI_HIP(hipMemcpyAsync(radix_sort_ghist(scratch, (size_t)n, lo, hi), ghist, passes * 256 * sizeof(uint32_t),
+                               hipMemcpyDeviceToDevice, s));
+        cleared = true;
+    }
+    uint32_t* keys[2] = {keys0, keys1};
+    uint32_t* vals[2] = {vals0, vals1};
+    const int fin = radix_sort_pairs(keys, vals, (size_t)n, lo, hi, scratch, s, cleared, ghist != nullptr, n_dev, error_out);
+    GOI_HIP(hipGetLastError());
+    if (error_out) radix_sort_report_error(scratch, (size_t)n, lo, hi, error_out, s);
+    GOI_HIP(hipGetLastError());
+    return fin;
+}
+
+size_t goi_raster_debug_scan_workspace_bytes(long long n) {
+    return (n >= 0 && n < (1ll << 32)) ? scan_scratch_words((size_t)n) * sizeof(uint32_t) + 256 : 0;
+}
+
+int goi_raster_debug_exclusive_scan(const uint32_t* in, const uint32_t* gather, uint32_t* out, long long n, const uint32_t* n_dev,
+                                    uint32_t* total, void* workspace, void* stream) {
+    refresh_options();
+    if (n < 0 || n >= (1ll << 32)) return fail("goi_raster_debug_exclusive_scan: need 0 <= n < 2^32");
+    if (gather && out == in) return fail("goi_raster_debug_exclusive_scan: out == in with a gather is a data race");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n > 0 && (!in || !out || !workspace)) return fail("goi_raster_debug_exclusive_scan: a required pointer is NULL");
+    exclusive_scan_u32(in, gather, out, (size_t)n, total, static_cast<uint32_t*>(workspace), s, n_dev);
+    GOI_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-"""Float64 (or float32) reference of the per-Gaussian backward (csrc/preprocess.hip: preprocess_bwd_k; the oracle's
+"""Float64 (or float32) reference of the per-Gaussian backward (csrc/preprocess_bwd.hip: preprocess_bwd_k; the oracle's
 goi_oracle_preprocess_backward), written from the mathematics: the FORWARD of one Gaussian -- NDC mean, conic, SH colour
 + 0.5 under a given clamp mask, view depth -- is stated in torch for all Gaussians at once and the gradients of
 sum(upstream . outputs) come from autograd.  Nothing of the oracle's backward formulas is restated here.

@@ -3,6 +3,9 @@
 csrc/api.hip that goi_raster_last_error returns.  Per entry: the message of its first refusal; where it takes a workspace, the
 messages for a NULL and for a misaligned one; per size function, the 0 it returns for an argument out of range.  The strings
 were recorded from the library as it was when every one of these entries still lived in csrc/api.hip.
+
+The same for the rasterizer's direct-test and diagnostic entries that live beside their kernels (the RASTER tables below): for
+those, every refusal and every return of 0 that comes before the entry's first HIP call.
 """
 import ctypes as C
 import threading
@@ -189,6 +192,222 @@ SIZES = [
 ]
 
 
+# ---- the rasterizer's direct-test and diagnostic entries, which live beside the kernels they drive (csrc/scan_sort.hip,
+# reduce_rows.hip, preprocess_fwd.hip, preprocess_bwd.hip, blend_stats.hip, contrib.hip).  Per entry EVERY refusal it can reach
+# before its first HIP call, in the order of its checks -- each row passes all earlier checks and fails exactly this one -- and
+# every return of 0 that comes before a HIP call.  Recorded from the library as it was when these entries lived in csrc/api.hip.
+A16 = C.c_void_p((1 << 20) + 4)  # 4-byte aligned, not 8 or 16
+A2 = C.c_void_p((1 << 20) + 2)  # 2-byte aligned, not 4
+_NAN = float("nan")
+
+_SCENE = dict(P=4, D=3, M=16, S=16, W=16, H=16, bg=F, means3D=F, shs=F, colors_precomp=N, semantics=F, opacities=F, scales=F,
+              scale_modifier=1.0, rotations=F, cov3D_precomp=N, viewmatrix=F, projmatrix=F, campos=F, tan_fovx=1.0, tan_fovy=1.0,
+              prefiltered=0, debug=0)
+# goi_raster_debug_preprocess_backward's arguments behind the scene, a call that passes every check (source 1: the records)
+_PBWD = dict(source=1, flags=0, max_blocks=0, n_cap=8, frame=F, radii=F, clamped=F, cov3D=F, prev_radii=N, aux=F, tiles_touched=F,
+             rows=F, row_flags=F, dL_dmean2D=F, dL_dconic=F, dL_dopacity=F, dL_dcolor=F, dL_dsemantic=F, dL_ddepth=F, dL_dmean3D=F,
+             dL_dcov3D=F, dL_dsh=F, dL_dscale=F, dL_drot=F, workspace=F, stream=N)
+
+
+def _pbwd(scene=None, **over):
+    """The argument list of goi_raster_debug_preprocess_backward: the passing call with scene fields (`scene`: a dict, or "null")
+    and arguments replaced."""
+    from goi_hyperplane_amd import _lib
+    assert set(over) <= set(_PBWD) and (scene == "null" or set(scene or {}) <= set(_SCENE))
+    sc = N
+    if scene != "null":
+        fields = dict(_SCENE, **(scene or {}))
+        sc = C.byref(_lib.GoiRasterScene(**{k: (v.value if isinstance(v, C.c_void_p) else v) for k, v in fields.items()}))
+    return (sc,) + tuple(dict(_PBWD, **over).values())
+
+
+_PB = "goi_raster_debug_preprocess_backward"
+_NOSH = dict(shs=N, colors_precomp=F)
+_SORT, _SCAN, _RED, _PAIR = ("goi_raster_debug_sort_pairs", "goi_raster_debug_exclusive_scan", "goi_raster_debug_reduce_rows",
+                             "goi_raster_debug_pair_eval")
+_RED_MSG = "goi_raster_debug_reduce_rows: "
+_SH = "goi_raster_sh_grad_from_views"
+_SH_MSG = "goi_raster_sh_grad_from_views: need 0 <= D <= 3 and (D+1)^2 <= M <= 16"
+
+# entry, arguments (a tuple, or a function that makes one once the library is there), return value, message (None: no refusal)
+RASTER = [
+    (_SORT, (F, F, F, F, -1, 0, 32, N, N, 0, N, F, N), -1, _SORT + ": need 0 <= n < 2^30"),
+    (_SORT, (F, F, F, F, 1 << 30, 0, 32, N, N, 0, N, F, N), -1, _SORT + ": need 0 <= n < 2^30"),
+    (_SORT, (F, F, F, F, 8, -1, 32, N, N, 0, N, F, N), -1, _SORT + ": need 0 <= lo < hi <= 32"),
+    (_SORT, (F, F, F, F, 8, 0, 33, N, N, 0, N, F, N), -1, _SORT + ": need 0 <= lo < hi <= 32"),
+    (_SORT, (F, F, F, F, 8, 8, 8, N, N, 0, N, F, N), -1, _SORT + ": need 0 <= lo < hi <= 32"),
+    (_SORT, (F, F, F, F, 8, 0, 32, N, N, 2, N, F, N), -1, _SORT + ": unknown flags"),
+    (_SORT, (N, N, N, N, 0, 0, 32, F, F, 1, N, N, N), 0, None),  # n == 0: nothing to sort, nothing looked at
+    (_SORT, (F, N, F, F, 8, 0, 32, N, N, 0, N, F, N), -1, _SORT + ": a required pointer is NULL"),
+    (_SORT, (F, F, F, N, 8, 0, 32, N, N, 0, N, F, N), -1, _SORT + ": a required pointer is NULL"),
+    (_SCAN, (F, N, F, -1, N, N, F, N), -1, _SCAN + ": need 0 <= n < 2^32"),
+    (_SCAN, (F, N, F, 1 << 32, N, N, F, N), -1, _SCAN + ": need 0 <= n < 2^32"),
+    (_SCAN, (F, F, F, 8, N, N, F, N), -1, _SCAN + ": out == in with a gather is a data race"),
+    (_SCAN, (N, N, F, 8, N, N, F, N), -1, _SCAN + ": a required pointer is NULL"),
+    (_SCAN, (F, N, N, 8, N, N, F, N), -1, _SCAN + ": a required pointer is NULL"),
+    (_SCAN, (F, N, A16, 8, N, N, N, N), -1, _SCAN + ": a required pointer is NULL"),  # (its workspace: a NULL check only)
+    ("goi_raster_debug_reduce_row_floats", (-1, 16), -1, _RED_MSG + "unknown mode"),
+    ("goi_raster_debug_reduce_row_floats", (4, 16), -1, _RED_MSG + "unknown mode"),
+    ("goi_raster_debug_reduce_row_floats", (0, 0), -1, _RED_MSG + "need 1 <= S <= 32"),
+    ("goi_raster_debug_reduce_row_floats", (3, 33), -1, _RED_MSG + "need 1 <= S <= 32"),
+    ("goi_raster_debug_reduce_row_floats", (2, 4), -1, _RED_MSG + "mode 2 sums 128-byte rows only (S = 5 .. 20)"),
+    ("goi_raster_debug_reduce_row_floats", (2, 21), -1, _RED_MSG + "mode 2 sums 128-byte rows only (S = 5 .. 20)"),
+    ("goi_raster_debug_reduce_row_floats", (0, 4), 16, None),
+    ("goi_raster_debug_reduce_row_floats", (1, 16), 32, None),
+    ("goi_raster_debug_reduce_row_floats", (2, 20), 32, None),
+    ("goi_raster_debug_reduce_row_floats", (0, 32), 48, None),
+    ("goi_raster_debug_reduce_row_floats", (3, 16), 16, None),
+    ("goi_raster_debug_reduce_row_floats", (3, 17), 32, None),
+    (_RED, (4, 4, 16, 8) + (F,) * 13 + (N,), -1, _RED_MSG + "unknown mode"),
+    (_RED, (0, 4, 0, 8) + (F,) * 13 + (N,), -1, _RED_MSG + "need 1 <= S <= 32"),
+    (_RED, (2, 4, 4, 8) + (F,) * 13 + (N,), -1, _RED_MSG + "mode 2 sums 128-byte rows only (S = 5 .. 20)"),
+    (_RED, (0, -1, 16, 8) + (F,) * 13 + (N,), -1, _RED_MSG + "need P >= 0 and 0 <= n_cap < 2^31"),
+    (_RED, (0, 4, 16, -1) + (F,) * 13 + (N,), -1, _RED_MSG + "need P >= 0 and 0 <= n_cap < 2^31"),
+    (_RED, (0, 4, 16, 1 << 31) + (F,) * 13 + (N,), -1, _RED_MSG + "need P >= 0 and 0 <= n_cap < 2^31"),
+    (_RED, (1, 0, 16, 8) + (N,) * 14, 0, None),  # P == 0: nothing to sum, nothing looked at
+    (_RED, (1, 4, 16, 8, N) + (F,) * 12 + (N,), -1, _RED_MSG + "a required pointer is NULL"),  # frame
+    (_RED, (1, 4, 16, 8, F, F, F, N, F, N, N, N, N, N, N, N, F, N), -1, _RED_MSG + "a required pointer is NULL"),  # flags
+    (_RED, (0, 4, 16, 8, F, F, F, N) + (F,) * 9 + (N,), -1, _RED_MSG + "a required pointer is NULL"),  # mode 0: tiles_touched
+    (_RED, (0, 4, 16, 8, F, F, F, F, F, F, N) + (F,) * 6 + (N,), -1, _RED_MSG + "a required pointer is NULL"),  # mode 0: dL_dmean2D
+    (_RED, (0, 4, 16, 8, F, F, F, F, F, F, F, F, F, F, F, N, F, N), -1, _RED_MSG + "a required pointer is NULL"),  # mode 0: dL_ddepth
+    (_RED, (3, 4, 16, 8, F, F, F, F, F, F, N, N, N, N, N, N, F, N), -1, _RED_MSG + "a required pointer is NULL"),  # mode 3: dL_dsemantic
+    (_PB, lambda: _pbwd("null"), -1, _PB + ": scene is NULL"),
+    (_PB, lambda: _pbwd(dict(P=-1)), -1, _PB + ": bad P/W/H"),
+    (_PB, lambda: _pbwd(dict(W=0)), -1, _PB + ": bad P/W/H"),
+    (_PB, lambda: _pbwd(dict(H=0)), -1, _PB + ": bad P/W/H"),
+    (_PB, lambda: _pbwd(dict(S=0)), -1, _PB + ": need 1 <= S <= 32"),
+    (_PB, lambda: _pbwd(dict(S=33)), -1, _PB + ": need 1 <= S <= 32"),
+    (_PB, lambda: _pbwd(source=-1), -1, _PB + ": unknown source (0 per-id arrays, 1 records, 2 rows summed in the kernel)"),
+    (_PB, lambda: _pbwd(source=3), -1, _PB + ": unknown source (0 per-id arrays, 1 records, 2 rows summed in the kernel)"),
+    (_PB, lambda: _pbwd(flags=2), -1, _PB + ": unknown flag bits"),
+    (_PB, lambda: _pbwd(max_blocks=-1), -1, _PB + ": max_blocks must be >= 0 (0: the product's grid)"),
+    (_PB, lambda: _pbwd(n_cap=-1), -1, _PB + ": need 0 <= n_cap < 2^31"),
+    (_PB, lambda: _pbwd(n_cap=1 << 31), -1, _PB + ": need 0 <= n_cap < 2^31"),
+    (_PB, lambda: _pbwd(dict(S=4), source=2), -1, _PB + ": source 2 sums 128-byte rows only (S = 5 .. 20)"),
+    (_PB, lambda: _pbwd(dict(S=21), source=2), -1, _PB + ": source 2 sums 128-byte rows only (S = 5 .. 20)"),
+    # P == 0: nothing to do, whatever else the scene and the arguments hold
+    (_PB, lambda: _pbwd(dict(P=0, tan_fovx=0.0, means3D=N), frame=N, workspace=N), 0, None),
+    (_PB, lambda: _pbwd(dict(tan_fovx=0.0)), -1, _PB + ": tan_fovx / tan_fovy must be positive"),
+    (_PB, lambda: _pbwd(dict(tan_fovy=-1.0)), -1, _PB + ": tan_fovx / tan_fovy must be positive"),
+    (_PB, lambda: _pbwd(dict(tan_fovx=_NAN)), -1, _PB + ": tan_fovx / tan_fovy must be positive"),
+    (_PB, lambda: _pbwd(dict(means3D=N)), -1, _PB + ": a required scene pointer is NULL"),
+    (_PB, lambda: _pbwd(dict(viewmatrix=N)), -1, _PB + ": a required scene pointer is NULL"),
+    (_PB, lambda: _pbwd(dict(projmatrix=N)), -1, _PB + ": a required scene pointer is NULL"),
+    (_PB, lambda: _pbwd(dict(campos=N)), -1, _PB + ": a required scene pointer is NULL"),
+    (_PB, lambda: _pbwd(dict(colors_precomp=F)), -1, _PB + ": shs and colors_precomp are both given"),
+    (_PB, lambda: _pbwd(dict(D=-1)), -1, _PB + ": SH degree must be 0..3 and (D+1)^2 <= M <= 16"),
+    (_PB, lambda: _pbwd(dict(D=4, M=25)), -1, _PB + ": SH degree must be 0..3 and (D+1)^2 <= M <= 16"),
+    (_PB, lambda: _pbwd(dict(D=3, M=15)), -1, _PB + ": SH degree must be 0..3 and (D+1)^2 <= M <= 16"),
+    (_PB, lambda: _pbwd(dict(D=0, M=17)), -1, _PB + ": SH degree must be 0..3 and (D+1)^2 <= M <= 16"),
+    (_PB, lambda: _pbwd(dict(shs=A16)), -1, _PB + ": shs must be 16-byte aligned when 3 M is a multiple of 4"),
+    (_PB, lambda: _pbwd(_NOSH), -1, _PB + ": dL_dsh without shs"),
+    (_PB, lambda: _pbwd(dict(rotations=N)), -1, _PB + ": scales and rotations go together"),
+    (_PB, lambda: _pbwd(dict(scales=N)), -1, _PB + ": scales and rotations go together"),
+    (_PB, lambda: _pbwd(dict(cov3D_precomp=F)), -1, _PB + ": exactly one of the scale/rotation pair and cov3D_precomp"),
+    (_PB, lambda: _pbwd(dict(scales=N, rotations=N)), -1, _PB + ": exactly one of the scale/rotation pair and cov3D_precomp"),
+    (_PB, lambda: _pbwd(cov3D=N), -1, _PB + ": cov3D (what the forward computed from scale/rotation) is NULL"),
+    (_PB, lambda: _pbwd(dict(rotations=A16)), -1, _PB + ": rotations must be 16-byte aligned"),
+    (_PB, lambda: _pbwd(flags=1, source=0), -1, _PB + ": accumulate needs source 1 (the records)"),
+    (_PB, lambda: _pbwd(flags=1, source=2), -1, _PB + ": accumulate needs source 1 (the records)"),
+    (_PB, lambda: _pbwd(flags=1, prev_radii=F), -1, _PB + ": accumulate with prev_radii"),
+    (_PB, lambda: _pbwd(flags=1, dL_dsh=N), -1, _PB + ": accumulate with factored SH (dL_dsh NULL)"),
+    (_PB, lambda: _pbwd(frame=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(radii=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(dL_dmean2D=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(dL_dcolor=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(dL_dmean3D=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(dL_dcov3D=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(dL_dscale=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(dL_drot=N), -1, _PB + ": a required pointer is NULL"),
+    (_PB, lambda: _pbwd(clamped=N), -1, _PB + ": a required pointer is NULL"),  # (SH colours: the clamp bits)
+    (_PB, lambda: _pbwd(source=0, dL_dconic=N), -1, _PB + ": source 0 reads dL_dconic and dL_ddepth"),
+    (_PB, lambda: _pbwd(source=0, dL_ddepth=N), -1, _PB + ": source 0 reads dL_dconic and dL_ddepth"),
+    (_PB, lambda: _pbwd(aux=N), -1, _PB + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic"),
+    (_PB, lambda: _pbwd(tiles_touched=N), -1, _PB + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic"),
+    (_PB, lambda: _pbwd(source=2, rows=N), -1, _PB + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic"),
+    (_PB, lambda: _pbwd(dL_dopacity=N), -1, _PB + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic"),
+    (_PB, lambda: _pbwd(source=2, dL_dsemantic=N), -1,
+     _PB + ": sources 1 and 2 need aux, tiles_touched, rows, dL_dopacity and dL_dsemantic"),
+    (_PB, lambda: _pbwd(source=2, row_flags=N), -1, _PB + ": source 2 needs the validity bytes"),
+    # (what a source does not read may be NULL: the call gets as far as its workspace)
+    (_PB, lambda: _pbwd(_NOSH, source=0, clamped=N, aux=N, tiles_touched=N, rows=N, row_flags=N, dL_dopacity=N, dL_dsemantic=N,
+                        dL_dsh=N, workspace=N), -1, _PB + ": NULL workspace"),
+    (_PB, lambda: _pbwd(dict(scales=N, rotations=N, cov3D_precomp=F), cov3D=N, row_flags=N, dL_dconic=N, dL_ddepth=N,
+                        workspace=MIS), -1, _PB + ": workspace must be 256-byte aligned"),
+    (_PB, lambda: _pbwd(dL_drot=A16), -1,
+     _PB + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned"),
+    (_PB, lambda: _pbwd(aux=A16), -1,
+     _PB + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned"),
+    (_PB, lambda: _pbwd(rows=A16), -1,
+     _PB + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned"),
+    (_PB, lambda: _pbwd(source=2, row_flags=A2), -1,
+     _PB + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned"),
+    (_PB, lambda: _pbwd(dL_dsemantic=A16), -1,
+     _PB + ": dL_drot, aux, rows and dL_dsemantic must be 16-byte aligned, the validity bytes 4-byte aligned"),
+    (_SH, (0, 3, 16, 2, N, N, N, N, N), 0, None),  # P <= 0 or V <= 0: nothing to add, nothing looked at
+    (_SH, (-1, 9, 0, 2, N, N, N, N, N), 0, None),
+    (_SH, (4, 3, 16, 0, N, N, N, N, N), 0, None),
+    (_SH, (4, -1, 16, 2, F, F, F, F, N), -1, _SH_MSG),
+    (_SH, (4, 4, 25, 2, F, F, F, F, N), -1, _SH_MSG),
+    (_SH, (4, 2, 8, 2, F, F, F, F, N), -1, _SH_MSG),
+    (_SH, (4, 0, 17, 2, F, F, F, F, N), -1, _SH_MSG),
+    (_SH, (4, 3, 16, 2, N, F, F, F, N), -1, _SH + ": NULL pointer"),
+    (_SH, (4, 3, 16, 2, F, N, F, F, N), -1, _SH + ": NULL pointer"),
+    (_SH, (4, 3, 16, 2, F, F, N, F, N), -1, _SH + ": NULL pointer"),
+    (_SH, (4, 3, 16, 2, F, F, F, N, N), -1, _SH + ": NULL pointer"),
+    ("goi_raster_mark_visible", (-1, F, F, F, F, N), -1, "bad P"),
+    ("goi_raster_mark_visible", (0, N, N, N, N, N), 0, None),  # P == 0
+    ("goi_raster_mark_visible", (4, N, F, N, F, N), -1, "NULL pointer"),
+    ("goi_raster_mark_visible", (4, F, N, N, F, N), -1, "NULL pointer"),
+    ("goi_raster_mark_visible", (4, F, F, N, N, N), -1, "NULL pointer"),
+    (_PAIR, (0, 16, 16, F, F, 8, F, F, F, N), -1, _PAIR + ": bad P/W/H"),
+    (_PAIR, (4, 0, 16, F, F, 8, F, F, F, N), -1, _PAIR + ": bad P/W/H"),
+    (_PAIR, (4, 16, -1, F, F, 8, F, F, F, N), -1, _PAIR + ": bad P/W/H"),
+    (_PAIR, (4, 16, 16, F, F, -1, F, F, F, N), -1, _PAIR + ": need 0 <= n_requests <= 2^31"),
+    (_PAIR, (4, 16, 16, F, F, (1 << 31) + 1, F, F, F, N), -1, _PAIR + ": need 0 <= n_requests <= 2^31"),
+    (_PAIR, (4, 16, 16, N, N, 0, N, N, N, N), 0, None),  # no requests: nothing looked at
+    (_PAIR, (4, 16, 16, F, N, 8, F, F, F, N), -1, _PAIR + ": a required pointer is NULL"),
+    (_PAIR, (4, 16, 16, F, F, 8, N, F, F, N), -1, _PAIR + ": a required pointer is NULL"),
+    (_PAIR, (4, 16, 16, F, F, 8, F, N, F, N), -1, _PAIR + ": a required pointer is NULL"),
+    (_PAIR, (4, 16, 16, F, F, 8, F, F, N, N), -1, _PAIR + ": a required pointer is NULL"),
+    (_PAIR, (4, 16, 16, F, A16, 8, F, F, F, N), -1, _PAIR + ": requests must be 8-byte aligned"),
+    (_PAIR, (4, 16, 16, F, F, 8, A2, F, F, N), -1, _PAIR + ": E and alpha must be 4-byte aligned"),
+    (_PAIR, (4, 16, 16, F, F, 8, F, A2, F, N), -1, _PAIR + ": E and alpha must be 4-byte aligned"),
+    ("goi_raster_blend_stats", (0, 16, 16, 8, F, F, F, F, N), -1, "goi_raster_blend_stats: bad P/W/H/R"),
+    ("goi_raster_blend_stats", (4, 0, 16, 8, F, F, F, F, N), -1, "goi_raster_blend_stats: bad P/W/H/R"),
+    ("goi_raster_blend_stats", (4, 16, 0, 8, F, F, F, F, N), -1, "goi_raster_blend_stats: bad P/W/H/R"),
+    ("goi_raster_blend_stats", (4, 16, 16, -1, F, F, F, F, N), -1, "goi_raster_blend_stats: bad P/W/H/R"),
+    ("goi_raster_blend_stats", (4, 16, 16, 8, N, F, F, F, N), -1, "workspace pointer is NULL"),
+    ("goi_raster_blend_stats", (4, 16, 16, 8, F, N, F, F, N), -1, "workspace pointer is NULL"),
+    ("goi_raster_blend_stats", (4, 16, 16, 0, F, N, N, F, N), -1, "workspace pointer is NULL"),
+    ("goi_raster_blend_stats", (4, 16, 16, 8, F, F, F, N, N), -1, "workspace pointer is NULL"),  # (the counters)
+    ("goi_raster_contrib_frame", (0, 16, 16, 8, F, F, F, F, F, F, N), -1, "goi_raster_contrib_frame: bad P/W/H/R"),
+    ("goi_raster_contrib_frame", (4, 16, 16, -1, F, F, F, F, F, F, N), -1, "goi_raster_contrib_frame: bad P/W/H/R"),
+    ("goi_raster_contrib_frame", (4, 16, 16, 8, N, F, F, F, F, F, N), -1, "goi_raster_contrib_frame: workspace pointer is NULL"),
+    ("goi_raster_contrib_frame", (4, 16, 16, 8, F, N, F, F, F, F, N), -1, "goi_raster_contrib_frame: workspace pointer is NULL"),
+    ("goi_raster_contrib_frame", (4, 16, 16, 0, F, N, N, F, F, F, N), -1, "goi_raster_contrib_frame: workspace pointer is NULL"),
+    ("goi_raster_contrib_frame", (4, 16, 16, 8, F, F, F, N, N, N, N), -1,
+     "goi_raster_contrib_frame: peak, top_id and top_w are all NULL"),
+]
+
+# the same entries' workspaces, through check_workspace (goi_raster_debug_preprocess_backward: RASTER, between its pointer checks)
+WORKSPACE += [
+    (_SORT, (F, F, F, F, 8, 0, 32, N, N, 0, N, WS, N), _SORT + ": NULL workspace", _SORT + ": workspace must be 256-byte aligned"),
+    (_RED, (1, 4, 16, 8, F, F, F, N, F, F, N, N, N, N, N, N, WS, N),
+     _RED_MSG + "NULL workspace", _RED_MSG + "workspace must be 256-byte aligned"),
+    (_PAIR, (4, 16, 16, WS, F, 8, F, F, F, N), _PAIR + ": NULL geom_buffer", _PAIR + ": geom_buffer must be 256-byte aligned"),
+]
+
+# their size functions: 0 for an argument out of range
+RASTER_SIZES = [
+    ("goi_raster_debug_sort_workspace_bytes", (-1, 0, 32)), ("goi_raster_debug_sort_workspace_bytes", (1 << 30, 0, 32)),
+    ("goi_raster_debug_sort_workspace_bytes", (8, -1, 32)), ("goi_raster_debug_sort_workspace_bytes", (8, 0, 33)),
+    ("goi_raster_debug_sort_workspace_bytes", (8, 8, 8)), ("goi_raster_debug_scan_workspace_bytes", (-1,)),
+    ("goi_raster_debug_scan_workspace_bytes", (1 << 32,)), ("goi_raster_debug_reduce_workspace_bytes", (-1,)),
+    ("goi_raster_debug_reduce_workspace_bytes", (1 << 31,)),
+]
+
+
 def _ids(table):
     seen = {}
     out = []
@@ -215,6 +434,44 @@ def test_workspace_refusals(lib, fn, args, null_message, misaligned_message):
 @pytest.mark.parametrize("fn,args", SIZES, ids=_ids(SIZES))
 def test_size_out_of_range_is_zero(lib, fn, args):
     assert getattr(lib, fn)(*args) == 0
+
+
+@pytest.mark.parametrize("fn,args,rc,message", RASTER, ids=_ids(RASTER))
+def test_raster_entry_refusals_and_early_returns(lib, fn, args, rc, message):
+    assert lib.goi_knn_dist2(-1, F, F, F, N) < 0  # (a message of another unit's: a return of 0 must leave it alone)
+    assert _call(lib, fn, args() if callable(args) else args) == rc
+    assert _err(lib) == (message if message is not None else "goi_knn_dist2: bad P")
+
+
+@pytest.mark.parametrize("fn,args", RASTER_SIZES, ids=_ids(RASTER_SIZES))
+def test_raster_size_out_of_range_is_zero(lib, fn, args):
+    assert getattr(lib, fn)(*args) == 0
+
+
+def test_sort_entry_refuses_device_counts_without_the_onesweep_sort(lib):
+    """n_dev and ghist belong to the onesweep sort: with sort_variant 0 the entry refuses them, behind its flags check and
+    before it looks at n, the pointers or the workspace."""
+    message = _SORT + ": n_dev and ghist need the onesweep sort (sort_variant 1)"
+    assert lib.goi_raster_set_option(b"sort_variant", 0) == 0
+    try:
+        for n_dev, ghist in ((F, N), (N, F)):
+            assert lib.goi_raster_debug_sort_pairs(N, N, N, N, 0, 0, 32, n_dev, ghist, 0, N, N, N) < 0
+            assert _err(lib) == message
+        assert lib.goi_raster_debug_sort_pairs(N, N, N, N, 0, 0, 32, N, N, 0, N, N, N) == 0
+    finally:
+        assert lib.goi_raster_set_option(b"sort_variant", 1) == 0
+
+
+def test_every_raster_test_entry_is_covered():
+    from goi_hyperplane_amd import _lib
+    beside_kernels = {n for n in _lib.SYMBOLS if n.startswith(("goi_raster_debug_sort_", "goi_raster_debug_scan_",
+                                                                "goi_raster_debug_exclusive_scan", "goi_raster_debug_reduce_",
+                                                                "goi_raster_debug_preprocess_", "goi_raster_debug_pair_"))}
+    beside_kernels |= {"goi_raster_blend_stats", "goi_raster_contrib_frame", "goi_raster_mark_visible",
+                       "goi_raster_sh_grad_from_views"}
+    assert len(beside_kernels) == 13
+    assert beside_kernels == {row[0] for row in RASTER + RASTER_SIZES}
+    assert {n for n in beside_kernels if n.endswith("_bytes")} == {row[0] for row in RASTER_SIZES}
 
 
 def test_every_moved_entry_is_covered():

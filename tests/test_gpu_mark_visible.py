@@ -1,4 +1,4 @@
-"""markVisible (csrc/preprocess.hip: mark_visible_k) at its threshold: view depth > 0.2f, the depth formed as gmath.h's
+"""markVisible (csrc/preprocess_fwd.hip: mark_visible_k) at its threshold: view depth > 0.2f, the depth formed as gmath.h's
 xform_point_4x3 forms it -- m[2] x + m[6] y + m[10] z + m[14], left to right, one rounding per operation (the file is built without
 contraction).
 

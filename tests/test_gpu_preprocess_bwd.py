@@ -1,4 +1,4 @@
-"""The per-Gaussian backward kernel (csrc/preprocess.hip: preprocess_bwd_k) called directly, against the oracle's fp32
+"""The per-Gaussian backward kernel (csrc/preprocess_bwd.hip: preprocess_bwd_k) called directly, against the oracle's fp32
 chain, bit for bit.
 
 goi_raster_debug_preprocess_backward (include/goi_raster.h) runs the product's own launch_preprocess_bwd on buffers built

@@ -1,4 +1,4 @@
-"""The culled tile lists (cull_variant 1: contribution box, cull_variant 2, the default: ellipse tile masks -- preprocess.hip
+"""The culled tile lists (cull_variant 1: contribution box, cull_variant 2, the default: ellipse tile masks -- preprocess_fwd.hip
 phase B, listed_rect / tile_instance / select_bit in common.h, emit_k / emit_big_k) looked at AS LISTS, against the float64
 contribution set of tests/tile_list_reference.py, on the adversarial case list of tests/tile_list_cases.py (whose coverage
 tests/test_tile_lists_cpu.py asserts).  Every assertion on a list is exact:
