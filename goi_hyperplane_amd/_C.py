@@ -380,7 +380,7 @@ class LazyCount:
         fl = C.c_uint(0)
         if wait:
             SPECULATION_STATS["waits"] += 1
-        r = lib.goi_raster_ticket_result2(self.ticket, 1 if wait else 0, C.byref(n), C.byref(fl))
+        r = lib.goi_raster_ticket_result(self.ticket, 1 if wait else 0, C.byref(n), C.byref(fl))
         if r == 0:
             return False
         self.ticket = None
@@ -489,8 +489,8 @@ class LazyCount:
         SPECULATION_STATS["redone"] += 1
 
     def _render_again_uncut(self):
-        """The frame once more, whole and exact (_launch_exact: goi_raster_forward_selected without a selection, which is
-        goi_raster_forward), into the same outputs and workspaces."""
+        """The frame once more, whole and exact (_launch_exact: goi_raster_forward without a selection), into the same outputs and
+        workspaces."""
         trouble = "a frame's depth cut-off was too tight and the frame cannot be rendered again"
         if self._full_args is None or self._redo is None:
             raise RasterOverflowError(f"{trouble}: its inputs have been released (the count was read too late -- the last "
@@ -601,7 +601,7 @@ def truncated_flag(accumulated: bool = False):
     return _flag_view(last[0], last[1])
 
 
-# ---- speculative depth cut-off of the tile lists (include/goi_raster.h, goi_raster_forward_async_cut) ----------------------------
+# ---- speculative depth cut-off of the tile lists (include/goi_raster.h, goi_raster_forward_async: zcut_in / zcut_out) ------------
 # On an opaque scene three quarters of the (tile, Gaussian) instances lie behind their tile's saturation front: emitted, sorted
 # and never looked at.  A training loop renders the same cameras epoch after epoch, so every speculative training frame LEARNS, per
 # tile, the depth up to which its list was worth listing (with a margin of a quarter + 64 list positions), and the next frame of
@@ -666,7 +666,7 @@ SCRATCH_STATS = {"sized_by_count": 0, "sized_by_capacity": 0}  # full backwards 
 
 
 def _scratch_instances(R, layout: int) -> int:
-    """Instances the backward's row scratch is laid out for (goi_raster_backward3).  A speculative frame's workspaces are sized
+    """Instances the backward's row scratch is laid out for (goi_raster_backward, scratch_instances).  A speculative frame's workspaces are sized
     for its CAPACITY; if its count has reached the host by now (the free look of _layout_of: the loss usually sits between the
     forward and this call) the scratch -- 129 bytes per instance and quadrant, the largest workspace of a step -- only has to
     hold the COUNT.  0 = as the binning layout."""
@@ -784,7 +784,7 @@ def rasterize_gaussians_selected(background, means3D, colors, semantics, opacity
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
                                  degree, campos, prefiltered, debug, selection, selection_invert):
     """rasterize_gaussians over a SELECTION of the Gaussians, rendered in place (include/goi_raster.h,
-    goi_raster_forward_selected; not in the reference's pybind module, whose callers index-select the operands first,
+    goi_raster_forward: keep / invert; not in the reference's pybind module, whose callers index-select the operands first,
     gui/gs_renderer.py:315-321).  selection: bool / uint8 [P] on the device (check_selection), or None = rasterize_gaussians;
     selection_invert: render the Gaussians whose byte is 0 instead.  Same return tuple; radii stays [P] (0 for an unselected
     Gaussian) and the workspaces serve the same backward calls."""
@@ -952,9 +952,8 @@ def _launch_exact(fa, dev, P, S, selection, invert, into=None):
                                                   torch.cuda.current_stream(dev).cuda_stream)
         sc, _keep = _prepared_scene(dev, P, S, **fa._asdict())
         alloc = _BinningAllocator(dev)
-        # (without a selection this is goi_raster_forward: keep == NULL is the plain call, include/goi_raster.h)
-        n = lib.goi_raster_forward_selected(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, *[_ptr(o) for o in outs],
-                                            _ptr(radii), _ptr(selection), int(invert), C.c_void_p(stream))
+        n = lib.goi_raster_forward(C.byref(sc), _ptr(geom), _ptr(img), alloc.cb, None, *[_ptr(o) for o in outs], _ptr(radii),
+                                   _ptr(selection), int(invert), C.c_void_p(stream))
     if alloc.error is not None:
         raise alloc.error
     _lib.check(n)
@@ -975,11 +974,8 @@ def _launch_async(fa, dev, P, S, cap, z_in, z_out, selection, invert):
         geom, img, radii, outs = (*_new_workspaces(dev, P, H, W), _new_outputs(dev, S, H, W))
         sc, _keep = _prepared_scene(dev, P, S, **fa._asdict())
         binning = _binning_tensor(dev, lib.goi_raster_binning_bytes(cap))
-        frame = (C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap, *[_ptr(o) for o in outs], _ptr(radii))
-        if selection is not None:
-            ticket = lib.goi_raster_forward_async_selected(*frame, _ptr(selection), int(invert), _lib.stream(dev))
-        else:
-            ticket = lib.goi_raster_forward_async_cut(*frame, _ptr(z_in), _ptr(z_out), _lib.stream(dev))
+        ticket = lib.goi_raster_forward_async(C.byref(sc), _ptr(geom), _ptr(img), _ptr(binning), cap, *[_ptr(o) for o in outs],
+                                              _ptr(radii), _ptr(z_in), _ptr(z_out), _ptr(selection), int(invert), _lib.stream(dev))
     _lib.check(ticket)
     return (ticket,) + outs + (radii, geom, binning, img)
 
@@ -992,7 +988,7 @@ def _backward_impl(background, means3D, radii, colors, semantics, scales, rotati
     dL_dcov3D[P,6], dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])
 
     accumulate_into (compiled binding only): the dL_dmeans3D an earlier call of the same batch returned -- this view's gradients
-    are ADDED to that call's tensors (goi_raster_backward3, GOI_BACKWARD_ACCUMULATE) and the same tensors are returned.
+    are ADDED to that call's tensors (goi_raster_backward, GOI_BACKWARD_ACCUMULATE) and the same tensors are returned.
 
     sh_factored (not in the reference's pybind module; FACTORED mode of goi_raster_backward): dL_dsh is not formed
     (returned as None) and dL_dcolors is the clamp-masked colour gradient g, the factor of
@@ -1065,7 +1061,7 @@ def _backward_impl(background, means3D, radii, colors, semantics, scales, rotati
             R_scratch = _scratch_instances(R, R_layout)
             scratch = _backward_scratch(lib.goi_raster_backward_scratch_bytes(R_scratch or R_layout, S), dev)
             # (no buffer pool on this path: every row is written, no mask is kept)
-            r = lib.goi_raster_backward4(
+            r = lib.goi_raster_backward(
                 C.byref(sc), R_layout, R_scratch, 0, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(radii_c),
                 _ptr(alphas_c), *[_ptr(g) for g in ups],
                 _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dsemantics),
@@ -1089,7 +1085,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, semantics, 
 def rasterize_gaussians_backward_accumulate(accumulate_into, *args):
     """rasterize_gaussians_backward(*args) (not in the reference's pybind module) whose gradients are ADDED, on the device, to the
     tensors an earlier call of the same batch returned: accumulate_into = that call's dL_dmeans3D (None: a plain call, the
-    batch's first).  Returns the same nine tensors.  goi_raster_backward3 / GOI_BACKWARD_ACCUMULATE; compiled binding only."""
+    batch's first).  Returns the same nine tensors.  goi_raster_backward / GOI_BACKWARD_ACCUMULATE; compiled binding only."""
     return _backward_impl(*args, accumulate_into=accumulate_into)
 
 

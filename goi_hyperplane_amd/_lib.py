@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgoi_raster.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 STAGES = ("preprocess", "depth_sort", "scan", "emit", "tile_sort", "ranges", "blend_fwd", "blend_bwd",
           "preprocess_bwd")
@@ -41,28 +41,15 @@ SYMBOLS = {
     "goi_raster_binning_bytes": (C.c_size_t, [C.c_int]),
     "goi_raster_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "goi_raster_forward": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, ALLOC_FN, C.c_void_p]
-                           + [C.c_void_p] * 5 + [C.c_void_p]),
+                           + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
     "goi_raster_forward_async": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-                                 + [C.c_void_p] * 5 + [C.c_void_p]),
-    "goi_raster_forward_selected": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, ALLOC_FN, C.c_void_p]
-                                    + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
-    "goi_raster_forward_async_selected": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-                                          + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
-    "goi_raster_ticket_result": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
-    "goi_raster_forward_async_cut": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-                                     + [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "goi_raster_ticket_result2": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
+                                 + [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "goi_raster_ticket_result": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "goi_raster_forward_redo": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
                                 + [C.c_void_p] * 5 + [C.c_void_p]),
     "goi_raster_forward_reblend": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int] + [C.c_void_p] * 9),
-    "goi_raster_backward": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int] + [C.c_void_p] * 3 + [C.c_void_p] * 6
-                            + [C.c_void_p] * 11 + [C.c_void_p, C.c_void_p]),
-    "goi_raster_backward2": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int] + [C.c_void_p] * 3 + [C.c_void_p] * 6
-                             + [C.c_void_p] * 11 + [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "goi_raster_backward3": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_void_p] * 6
-                             + [C.c_void_p] * 11 + [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "goi_raster_backward4": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_void_p] * 6
-                             + [C.c_void_p] * 11 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "goi_raster_backward": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_void_p] * 6
+                            + [C.c_void_p] * 11 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "goi_raster_debug_backward_contrib_offset": (C.c_size_t, [C.c_int, C.c_int]),
     "goi_raster_backward_semantics": (C.c_int, [C.POINTER(GoiRasterScene), C.c_int] + [C.c_void_p] * 9),
     "goi_raster_trace": (C.c_int, [C.POINTER(GoiRasterScene), C.c_void_p, C.c_void_p, C.c_void_p, ALLOC_FN,

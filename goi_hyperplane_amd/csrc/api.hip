@@ -270,8 +270,7 @@ int enqueue_readback(const GeomView& g, int ticket, hipStream_t s, bool head_onl
 // ticket < 0: no read-back here (the speculative forward queues it behind the blend instead: nobody is waiting for it,
 // and a device-to-host copy in the middle of the frame costs the stream a ~10 us bubble)
 int enqueue_front(const GoiRasterScene& sc, GeomView& g, ImageView& im, int* radii, int ticket, const uint32_t** order_out,
-                  hipStream_t s, const float* zcut = nullptr, uint32_t* zlearn = nullptr, const uint8_t* keep = nullptr,
-                  int keep_invert = 0) {
+                  hipStream_t s, const float* zcut, uint32_t* zlearn, const uint8_t* keep, int keep_invert) {
     const int P = sc.P;
     const int gx = (sc.W + TILE - 1) / TILE, gy = (sc.H + TILE - 1) / TILE;
     // one memset: the counters and, right behind them, the control words of the depth sort
@@ -538,10 +537,10 @@ size_t goi_raster_debug_backward_contrib_offset(int N, int S) {
     return (size_t)(reinterpret_cast<char*>(v.contrib) - base);  // the offset in a 256-byte aligned scratch
 }
 
-// keep (or NULL) / invert: the per-Gaussian selection of the _selected entry points -- the plain ones pass NULL
-static int forward_exact(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
-                         void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                         int* radii, const uint8_t* keep, int invert, void* stream) {
+// keep (or NULL) / invert: the per-Gaussian selection
+int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
+                       void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                       int* radii, const uint8_t* keep, int invert, void* stream) {
     refresh_options();
     if (validate(scene, true)) return -1;
     const GoiRasterScene& sc = *scene;
@@ -572,48 +571,9 @@ static int forward_exact(const GoiRasterScene* scene, void* geom_buffer, void* i
     return N;
 }
 
-int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
-                       void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                       int* radii, void* stream) {
-    return forward_exact(scene, geom_buffer, image_buffer, binning_alloc, alloc_user, out_color, out_semantic, out_depth,
-                         out_alpha, radii, nullptr, 0, stream);
-}
-
-int goi_raster_forward_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, goi_alloc_fn binning_alloc,
-                                void* alloc_user, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                                int* radii, const uint8_t* keep, int invert, void* stream) {
-    return forward_exact(scene, geom_buffer, image_buffer, binning_alloc, alloc_user, out_color, out_semantic, out_depth,
-                         out_alpha, radii, keep, invert, stream);
-}
-
-static int forward_speculative(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
-                               int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                               int* radii, const float* zcut_in, float* zcut_out, const uint8_t* keep, int invert, void* stream);
-
 int goi_raster_forward_async(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
                              int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                             int* radii, void* stream) {
-    return forward_speculative(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic, out_depth,
-                               out_alpha, radii, /*zcut_in=*/nullptr, /*zcut_out=*/nullptr, /*keep=*/nullptr, /*invert=*/0, stream);
-}
-
-int goi_raster_forward_async_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
-                                      int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                                      int* radii, const uint8_t* keep, int invert, void* stream) {
-    return forward_speculative(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic, out_depth,
-                               out_alpha, radii, nullptr, nullptr, keep, invert, stream);
-}
-
-int goi_raster_forward_async_cut(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
-                                 int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                                 int* radii, const float* zcut_in, float* zcut_out, void* stream) {
-    return forward_speculative(scene, geom_buffer, image_buffer, binning_buffer, capacity, out_color, out_semantic, out_depth,
-                               out_alpha, radii, zcut_in, zcut_out, nullptr, 0, stream);
-}
-
-static int forward_speculative(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
-                               int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                               int* radii, const float* zcut_in, float* zcut_out, const uint8_t* keep, int invert, void* stream) {
+                             int* radii, const float* zcut_in, float* zcut_out, const uint8_t* keep, int invert, void* stream) {
     refresh_options();
     if (validate(scene, true)) return -1;
     const GoiRasterScene& sc = *scene;
@@ -623,6 +583,7 @@ static int forward_speculative(const GoiRasterScene* scene, void* geom_buffer, v
     if (g_options.sort_variant != 1) return fail("goi_raster_forward_async needs the onesweep sort (sort_variant 1)");
     if (capacity <= 0) return fail("goi_raster_forward_async: capacity must be positive");
     if (!geom_buffer || !image_buffer || !binning_buffer) return fail("workspace pointer is NULL");
+    if (keep && (zcut_in || zcut_out)) return fail("goi_raster_forward_async: a selection (keep) cannot be combined with a depth cut");
     GeomView g;
     ImageView im;
     BinView bv;
@@ -678,11 +639,7 @@ static int forward_speculative(const GoiRasterScene* scene, void* geom_buffer, v
     return ticket;
 }
 
-int goi_raster_ticket_result(int ticket, int wait, int* num_rendered) {
-    return goi_raster_ticket_result2(ticket, wait, num_rendered, nullptr);
-}
-
-int goi_raster_ticket_result2(int ticket, int wait, int* num_rendered, unsigned* frame_flags) {
+int goi_raster_ticket_result(int ticket, int wait, int* num_rendered, unsigned* frame_flags) {
     long long n = 0;
     unsigned fl = 0;
     const int r = ticket_result(ticket, wait, &n, &fl);
@@ -784,13 +741,13 @@ int goi_raster_trace(const GoiRasterScene* scene, const float* img_sem, void* ge
     return N;
 }
 
-int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
-                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
-                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
-                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, const uint8_t* prev_mask,
-                         uint8_t* row_mask, void* stream) {
+int goi_raster_backward(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
+                        const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
+                        const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
+                        const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                        float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                        float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, const uint8_t* prev_mask,
+                        uint8_t* row_mask, void* stream) {
     refresh_options();
     if (validate(scene, true, false)) return -1;  // opacity lives in the forward's records
     const GoiRasterScene& sc = *scene;
@@ -866,43 +823,6 @@ int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instanc
     if (check_stage(sc, s, "backward preprocess")) return -1;
     GOI_HIP(hipGetLastError());
     return 0;
-}
-
-// The older entries: the same backward without the arguments that came later.
-int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
-                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
-                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
-                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, void* stream) {
-    return goi_raster_backward4(scene, R, scratch_instances, flags, geom_buffer, binning_buffer, image_buffer, radii, out_alpha,
-                                dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic, dL_dopacity,
-                                dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch,
-                                prev_radii, /*prev_mask=*/nullptr, /*row_mask=*/nullptr, stream);
-}
-
-int goi_raster_backward2(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,
-                         const void* image_buffer, const int* radii, const float* out_alpha, const float* dL_dout_color,
-                         const float* dL_dout_semantic, const float* dL_dout_depth, const float* dL_dout_alpha,
-                         float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
-                         float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                         float* dL_drot, void* scratch, const int* prev_radii, void* stream) {
-    return goi_raster_backward4(scene, R, /*scratch_instances=*/0, /*flags=*/0, geom_buffer, binning_buffer, image_buffer, radii,
-                                out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic,
-                                dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                                scratch, prev_radii, /*prev_mask=*/nullptr, /*row_mask=*/nullptr, stream);
-}
-
-int goi_raster_backward(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,
-                        const void* image_buffer, const int* radii, const float* out_alpha, const float* dL_dout_color,
-                        const float* dL_dout_semantic, const float* dL_dout_depth, const float* dL_dout_alpha,
-                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
-                        float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                        float* dL_drot, void* scratch, void* stream) {
-    return goi_raster_backward4(scene, R, /*scratch_instances=*/0, /*flags=*/0, geom_buffer, binning_buffer, image_buffer, radii,
-                                out_alpha, dL_dout_color, dL_dout_semantic, dL_dout_depth, dL_dout_alpha, dL_dmean2D, dL_dconic,
-                                dL_dopacity, dL_dcolor, dL_dsemantic, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                                scratch, /*prev_radii=*/nullptr, /*prev_mask=*/nullptr, /*row_mask=*/nullptr, stream);
 }
 
 int goi_raster_backward_semantics(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,

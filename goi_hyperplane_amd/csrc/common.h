@@ -231,7 +231,7 @@ void launch_emit_counting(int P, int W, int H, const GeomView& g, const uint32_t
                           uint32_t* vals, uint2* ranges, uint32_t* clear, size_t clear_words, uint32_t cap, hipStream_t s);
 void launch_tile_ranges_hist(int W, int H, uint2* ranges, uint32_t* ghist, uint32_t* counters, hipStream_t s);
 void launch_ranges(int N, const uint32_t* n_dev, const uint32_t* sorted_keys, uint2* ranges, int T, hipStream_t s);
-// zcut / zlearn: the speculative depth cut-off (goi_raster_forward_async_cut): per tile, the cut this frame's lists were built
+// zcut / zlearn: the speculative depth cut-off (goi_raster_forward_async): per tile, the cut this frame's lists were built
 // with (or NULL) and what the frame learns for the camera's next visit (float bits, max over the tile's quadrants; or NULL)
 void launch_render_fwd(const GoiRasterScene& sc, const GeomView& g, const ImageView& im, const uint32_t* point_list,
                        float* out_color, float* out_sem, float* out_depth, float* out_alpha, hipStream_t s,

@@ -33,17 +33,17 @@ struct BwdArgs {
     const float* campos_p;
     // radii of the backward that LAST WROTE these very output buffers (nothing has touched them since), or NULL: a Gaussian that
     // was invisible then and is invisible now already has zeros in every output row -- nothing is written for it (half of the
-    // headline scene: 170 MB of zeros per step).  goi_raster_backward2, csrc/torch_binding.cpp: the gradient-buffer pool.
+    // headline scene: 170 MB of zeros per step).  goi_raster_backward (prev_radii), csrc/torch_binding.cpp: the gradient-buffer pool.
     const int* prev_radii;
     // The same knowledge per ROW, which can also say "visible then, but the chain did not run" (an IDLE Gaussian, see RecArgs::contrib):
     // prev_mask[id] == 0 -- the backward that last wrote these buffers left zeros in the row (and nothing has touched it since);
     // it takes precedence over prev_radii.  row_mask (or NULL): this kernel writes 1 for every id whose row the chain wrote and 0
     // for every other id < P, whatever it did about that row (zeros, or nothing where they were there already).  The two may be
     // the SAME array: a thread reads the byte of an id before it writes it, and no other thread touches that byte.
-    // goi_raster_backward4; csrc/torch_binding.cpp keeps the mask with the pooled allocation.
+    // goi_raster_backward (prev_mask, row_mask); csrc/torch_binding.cpp keeps the mask with the pooled allocation.
     const uint8_t* prev_mask;
     uint8_t* row_mask;
-    // ACCUMULATE (goi_raster_backward3, flags bit 0; the record path only): the outputs already hold the gradients of earlier
+    // ACCUMULATE (goi_raster_backward, flags bit 0; the record path only): the outputs already hold the gradients of earlier
     // views of the same batch -- a visible Gaussian's rows are read, added to and written back, an invisible one's are left
     // alone.  The sum of K views then costs each view its visible rows once more instead of a dense [P, 75 + S] addition
     // (dist.backward_views).

@@ -31,12 +31,12 @@ struct PreArgs {
     const float* view_p;    // device, [16]
     const float* proj_p;    // device, [16]
     const float* campos_p;  // device, [3]
-    // speculative depth cut-off of the tile lists (api.hip, goi_raster_forward_async_cut): zcut[t] = view depth beyond which
+    // speculative depth cut-off of the tile lists (api.hip, goi_raster_forward_async): zcut[t] = view depth beyond which
     // tile t's list was never walked when this camera was rendered last (NULL: no cut); zlearn[t]: what this frame learns
     // (cleared here, written by the forward blend)
     const float* zcut;
     uint32_t* zlearn;
-    // per-Gaussian SELECTION (goi_raster_forward_selected; read by preprocess_fwd_k<true> only): keep[id] is one byte per Gaussian,
+    // per-Gaussian SELECTION (goi_raster_forward, keep; read by preprocess_fwd_k<true> only): keep[id] is one byte per Gaussian,
     // and Gaussian id is UNSELECTED when (keep[id] != 0) == (keep_invert != 0) -- keep_invert = 0 renders the Gaussians whose byte
     // is set, keep_invert = 1 the others.  NULL: no selection (preprocess_fwd_k<false>).
     const uint8_t* keep;

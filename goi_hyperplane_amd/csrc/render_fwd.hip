@@ -247,7 +247,7 @@ __global__ __launch_bounds__(64) void render_fwd_k(const uint2* __restrict__ ran
         __builtin_amdgcn_wave_barrier();
     }
 
-    // Speculative depth cut-off (api.hip, goi_raster_forward_async_cut).  LEARN: the view depth up to which this tile's list
+    // Speculative depth cut-off (api.hip, goi_raster_forward_async).  LEARN: the view depth up to which this tile's list
     // is worth listing the next time this camera is rendered -- the depth of the entry an eighth (and 32 positions) beyond
     // the last entry that ended a pixel of the tile (max over its four quadrant waves); +inf when a pixel reached the end of its list
     // unsaturated (such a tile is never cut).  CHECK: a pixel that reaches the end of a list that WAS cut (zcut finite) without

@@ -160,7 +160,7 @@ Prepared prepare(GOI_FORWARD_ARGS, bool need_semantics) {
     return f;
 }
 
-// The per-Gaussian selection of the _selected operators (include/goi_raster.h, goi_raster_forward_selected): P bytes on the
+// The per-Gaussian selection of the _selected operators (include/goi_raster.h, goi_raster_forward: keep): P bytes on the
 // frame's device, handed over by pointer -- never copied or converted.
 const uint8_t* selection_ptr(const Tensor& selection, const Prepared& f) {
     TORCH_CHECK_TYPE(selection.scalar_type() == torch::kBool || selection.scalar_type() == torch::kByte,
@@ -203,9 +203,9 @@ FrameTuple forward_frame(GOI_FORWARD_ARGS, const Tensor* selection, bool invert)
     Prepared f = prepare(GOI_FORWARD_PASS, true);
     const uint8_t* keep = selection ? selection_ptr(*selection, f) : nullptr;
     Frame o(f, means3D);
-    const int n = goi_raster_forward_selected(&f.sc, ptr(o.geom), ptr(o.img), grow, &o.binning, o.color.data_ptr<float>(),
-                                              o.sem.data_ptr<float>(), o.depth.data_ptr<float>(), o.alpha.data_ptr<float>(),
-                                              static_cast<int*>(ptr(o.radii)), keep, invert ? 1 : 0, stream_of(f.dev));
+    const int n = goi_raster_forward(&f.sc, ptr(o.geom), ptr(o.img), grow, &o.binning, o.color.data_ptr<float>(),
+                                     o.sem.data_ptr<float>(), o.depth.data_ptr<float>(), o.alpha.data_ptr<float>(),
+                                     static_cast<int*>(ptr(o.radii)), keep, invert ? 1 : 0, stream_of(f.dev));
     if (n < 0) raise_last();
     return o.result(n);
 }
@@ -221,7 +221,7 @@ FrameTuple rasterize_gaussians_selected(GOI_FORWARD_ARGS, const Tensor& selectio
 }
 
 // speculative forward: nothing waits; returns the read-back ticket instead of num_rendered (include/goi_raster.h)
-// zcut_in / zcut_out: the speculative depth cut-off of the tile lists (goi_raster_forward_async_cut): per-tile float32 arrays on
+// zcut_in / zcut_out: the speculative depth cut-off of the tile lists (goi_raster_forward_async): per-tile float32 arrays on
 // the device, either may be absent (None)
 // selection (or NULL) / invert: rasterize_gaussians_async_selected -- a selected frame takes no depth cut
 FrameTuple forward_frame_async(GOI_FORWARD_ARGS, const int capacity, const c10::optional<Tensor>& zcut_in,
@@ -240,13 +240,10 @@ FrameTuple forward_frame_async(GOI_FORWARD_ARGS, const int capacity, const c10::
         if (k == 0) zin = z->data_ptr<float>();
         else zout = z->data_ptr<float>();
     }
-    float *color = o.color.data_ptr<float>(), *sem = o.sem.data_ptr<float>(), *depth = o.depth.data_ptr<float>();
-    float* alpha = o.alpha.data_ptr<float>();
-    const int ticket =
-        keep ? goi_raster_forward_async_selected(&f.sc, o.geom.data_ptr(), o.img.data_ptr(), o.binning.data_ptr(), capacity, color,
-                                                 sem, depth, alpha, o.radii.data_ptr<int>(), keep, invert ? 1 : 0, stream_of(f.dev))
-             : goi_raster_forward_async_cut(&f.sc, o.geom.data_ptr(), o.img.data_ptr(), o.binning.data_ptr(), capacity, color,
-                                            sem, depth, alpha, o.radii.data_ptr<int>(), zin, zout, stream_of(f.dev));
+    const int ticket = goi_raster_forward_async(&f.sc, o.geom.data_ptr(), o.img.data_ptr(), o.binning.data_ptr(), capacity,
+                                                o.color.data_ptr<float>(), o.sem.data_ptr<float>(), o.depth.data_ptr<float>(),
+                                                o.alpha.data_ptr<float>(), o.radii.data_ptr<int>(), zin, zout, keep,
+                                                invert ? 1 : 0, stream_of(f.dev));
     if (ticket < 0) raise_last();
     return o.result(ticket);
 }
@@ -280,7 +277,7 @@ void* backward_scratch(size_t bytes, const c10::Device& dev, void* stream, const
     return it->second.data_ptr();
 }
 
-// ---- gradient-buffer pool (goi_raster_backward4: rows that already hold zeros are not written again) -------------------------
+// ---- gradient-buffer pool (goi_raster_backward, prev_mask: rows that already hold zeros are not written again) ---------------
 // The reference hands autograd eleven freshly zero-filled [P, ..] tensors per backward (rasterize_points.cu:252-262); on the
 // headline scene half of the Gaussians are invisible in any one view: 170 MB of zeros per step.  The binding keeps the ONE
 // allocation all outputs of a backward are views of, together with a byte per Gaussian the kernel writes (1: the chain of that
@@ -349,7 +346,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     const c10::optional<Tensor>& dL_dout_depth, const c10::optional<Tensor>& dL_dout_alpha, const Tensor& sh,
     const int degree, const Tensor& campos, const Tensor& geomBuffer, const int R, const Tensor& binningBuffer,
     const Tensor& imageBuffer, const Tensor& alphas, const bool debug, const bool sh_factored_in,
-    const int scratch_instances /* 0: the row scratch is laid out for R (goi_raster_backward3) */,
+    const int scratch_instances /* 0: the row scratch is laid out for R (goi_raster_backward) */,
     const c10::optional<Tensor>& accumulate_into /* the dL_dmeans3D an earlier call of the same batch returned: this view's
                                                     gradients are ADDED to that call's buffer (GOI_BACKWARD_ACCUMULATE) */) {
     const c10::Device dev = check_device(means3D);
@@ -435,7 +432,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
         // the mask travels with the buffer it describes; read (a clean pooled buffer) and rewritten in place
         const bool pooled = g_pool_on && !debug && !accumulate;
         if (pooled && !mask.defined()) mask = torch::empty({(long long)P}, means3D.options().dtype(torch::kByte));
-        const int r = goi_raster_backward4(
+        const int r = goi_raster_backward(
             &sc, R, scratch_instances, accumulate ? GOI_BACKWARD_ACCUMULATE : 0, geomBuffer.data_ptr(), ptr(binningBuffer),
             imageBuffer.data_ptr(), rad.data_ptr<int>(), al.p, gc.p, gs.p, gd.p, ga.p, dL_dmeans2D.data_ptr<float>(),
             dL_dconic.data_ptr<float>(), dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),

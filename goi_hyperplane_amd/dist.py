@@ -476,7 +476,7 @@ def backward_views(views, render_view, upstream, params, streams: int = 1, accum
     Two things can make a batch cheaper than K steps.  (1) Independent views overlap: one view's latency-bound kernels (sorts, scans,
     kernel tails) run beside the other's blends.  (2) on_device: the K views share their operands (the activations of the same
     parameters), so the rasterizer's backward of view 2, 3, ... ADDS its per-Gaussian gradients to view 1's tensors inside the
-    per-Gaussian kernel (rasterizer.accumulate_gradients -> goi_raster_backward3, GOI_BACKWARD_ACCUMULATE: a view reads and rewrites
+    per-Gaussian kernel (rasterizer.accumulate_gradients -> goi_raster_backward, GOI_BACKWARD_ACCUMULATE: a view reads and rewrites
     the rows of the Gaussians it sees -- half of the scene -- instead of a dense [P, 75 + S] addition per view, and no row of an
     invisible Gaussian is zero-filled or touched), one sum per stream; the per-stream sums are added once and back-propagated
     through the activations ONCE instead of K times.  The result equals the serial sum up to the association of fp32 additions

@@ -302,7 +302,7 @@ _ACCUM = {"state": None}  # process-wide on purpose: Function.backward runs on a
 
 class accumulate_gradients:
     """Context of a MULTI-VIEW BATCH (dist.backward_views): while it is active, the full backward of every rasterizer call adds
-    its per-Gaussian gradients ON THE DEVICE to the tensors the first such call returned (goi_raster_backward3 with
+    its per-Gaussian gradients ON THE DEVICE to the tensors the first such call returned (goi_raster_backward with
     GOI_BACKWARD_ACCUMULATE: a view reads and rewrites the rows of the Gaussians it sees, nothing else) and hands autograd no
     gradient; `state` collects {"grads": the nine tensors in the op's order (dL_dmeans2D, dL_dcolors, dL_dsemantics, dL_dopacity,
     dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations), "inputs": the operands of the last call (means3D, sh,

@@ -49,7 +49,12 @@
 extern "C" {
 #endif
 
-/* 8: + goi_raster_forward_selected, goi_raster_forward_async_selected (a per-Gaussian selection the forward itself honours);
+/* 9: ONE ENTRY PER OPERATION of the rasterizer's frame (signatures change: nothing is added).  goi_raster_forward,
+ *    goi_raster_forward_async, goi_raster_ticket_result and goi_raster_backward take the widest parameter list there was, and the
+ *    seven names that carried the history are REMOVED: goi_raster_forward_selected, goi_raster_forward_async_selected,
+ *    goi_raster_forward_async_cut, goi_raster_ticket_result2, goi_raster_backward2, goi_raster_backward3, goi_raster_backward4;
+ *    goi_raster_forward_async refuses a selection together with a depth cut
+ * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
  *    goi_field_iso_count, goi_field_iso_emit; goi_mesh_components_workspace_bytes, goi_mesh_components,
@@ -59,11 +64,12 @@ extern "C" {
  *    goi_texture_resolve, goi_texture_grid_put_workspace_bytes, goi_texture_grid_put, goi_texture_accumulate,
  *    goi_texture_normalize, goi_texture_fill_workspace_bytes, goi_texture_fill; goi_edit_bounds_workspace_bytes,
  *    goi_edit_bounds, goi_edit_transform; goi_raster_contrib_frame
- * 7: + goi_raster_backward4 (per-row mask of the rows a backward's chain wrote), goi_raster_debug_backward_contrib_offset, option
- *    bwd_skip_idle; the backward scratch grew by one byte per instance (contribution bytes: sizes come from
- *    goi_raster_backward_scratch_bytes as ever);
+ * 7: + the backward with prev_mask / row_mask (per-row mask of the rows a backward's chain wrote; folded by 9),
+ *    goi_raster_debug_backward_contrib_offset, option bwd_skip_idle; the backward scratch grew by one byte per instance
+ *    (contribution bytes: sizes come from goi_raster_backward_scratch_bytes as ever);
  *    later additions: goi_semantic_frame_workspace_bytes, goi_semantic_frame_compose
- * 6: + goi_raster_backward3 (row scratch sized by the frame's count instead of its capacity), goi_raster_blend_stats;
+ * 6: + the backward with scratch_instances / flags (row scratch sized by the frame's count instead of its capacity; folded by 9),
+ *    goi_raster_blend_stats;
  *    later additions: goi_semantic_osh_counts, goi_semantic_osh_fit, goi_semantic_dbscan_workspace_bytes, goi_semantic_dbscan,
  *    goi_semantic_mask_pack, goi_semantic_mask_dilate, goi_semantic_mask_unpack, goi_semantic_mask_confusion,
  *    goi_raster_debug_sort_workspace_bytes, goi_raster_debug_sort_pairs, goi_raster_debug_scan_workspace_bytes,
@@ -72,11 +78,12 @@ extern "C" {
  *    goi_codebook_unique_rows_workspace_bytes, goi_codebook_unique_rows, goi_codebook_kmeans_workspace_bytes, goi_codebook_kmeans,
  *    goi_raster_photometric_workspace_bytes, goi_raster_photometric_forward, goi_raster_photometric_backward,
  *    goi_raster_debug_preprocess_backward, goi_raster_debug_pair_eval, goi_raster_debug_backward_blend
- * 5: + goi_raster_forward_async_cut, goi_raster_ticket_result2 (speculative depth cut-off of the tile lists), goi_raster_backward2; the binning and
- *    backward-scratch workspaces grew (member masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
+ * 5: + the _async forward with zcut_in / zcut_out and the ticket entry with the flag word (speculative depth cut-off of the tile
+ *    lists), the backward with prev_radii (all three folded by 9); the binning and backward-scratch workspaces grew (member
+ *    masks; descriptors of big Gaussians): sizes come from goi_raster_*_bytes as ever
  * 4: + goi_raster_truncated_flag, goi_adam_step_guarded; a truncated speculative frame back-propagates ZERO gradients
  * (3: + goi_raster_forward_reblend, goi_codebook_sim, goi_codebook_fused; 2: + the asynchronous forward; additions only) */
-#define GOI_RASTER_ABI_VERSION 8
+#define GOI_RASTER_ABI_VERSION 9
 
 typedef struct GoiRasterScene {
     int P;                       /* number of Gaussians */
@@ -117,11 +124,28 @@ size_t goi_raster_image_bytes(int W, int H);
 size_t goi_raster_binning_bytes(int num_rendered);
 size_t goi_raster_backward_scratch_bytes(int num_rendered, int S);
 
-/* Forward: color[3,H,W], semantic[S,H,W], depth[H,W], alpha[H,W], radii[P] (int32). */
+/* Forward: color[3,H,W], semantic[S,H,W], depth[H,W], alpha[H,W], radii[P] (int32).  Returns num_rendered.
+ *   geom_buffer, image_buffer : workspaces of goi_raster_geom_bytes(P) / goi_raster_image_bytes(W, H) bytes, uninitialised;
+ *   binning_alloc, alloc_user : called once, with goi_raster_binning_bytes(num_rendered), when the host has read the count;
+ *   keep, invert              : a SELECTION of the Gaussians, rendered in place (below); keep == NULL renders all of them.
+ *
+ * A SELECTION (the reference's viewer index-selects every per-Gaussian tensor by a boolean mask before it calls the rasterizer,
+ * gui/gs_renderer.py:315-321: a host synchronisation, a second copy of the selected set, and outputs of the subset's length):
+ *   keep   : [P] device bytes, one per Gaussian (never written; a torch.bool or torch.uint8 tensor as it is), or NULL;
+ *   invert : 0 -- Gaussian i is rendered iff keep[i] != 0;  non-zero -- iff keep[i] == 0 (the complement, without forming it).
+ * The frame is the frame of the selected Gaussians alone, bit for bit what a call with keep == NULL produces for the
+ * index-selected arrays (outputs, num_rendered, and -- scattered to their ids -- radii and every gradient).  An unselected
+ * Gaussian is dropped by the first kernel before anything of it but its selection byte is read, exactly where a Gaussian
+ * behind the near plane is dropped: radii[i] = 0, no tile, no instance, zero gradient rows; it does not trip the
+ * `prefiltered` check.  All arrays stay [P]-long and are indexed by the caller's own ids.
+ * Everything that reads the geometry workspace -- goi_raster_forward_redo, _reblend, goi_raster_backward,
+ * goi_raster_backward_semantics -- works behind a selected forward unchanged and takes no selection (a reblend shows the
+ * selection of the frame that filled the workspaces).  goi_raster_forward_async takes the same pair; there is no selection
+ * together with a depth cut, and no selected trace or mark_visible. */
 int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer,
                        goi_alloc_fn binning_alloc, void* alloc_user,
                        float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                       int* radii, void* stream);
+                       int* radii, const uint8_t* keep, int invert, void* stream);
 
 /* ---- Speculative forward: the same frame WITHOUT the host round trip -----------------------------------------------
  * (no counterpart in the reference: CudaRasterizer::Rasterizer::forward blocks on num_rendered at
@@ -132,7 +156,7 @@ int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* ima
  * the largest count seen so far); on the device every kernel takes the true count from the geometry workspace and
  * clamps it to `capacity`.  The return value is a TICKET (>= 0) for the asynchronous read-back of the count:
  *
- *   goi_raster_ticket_result(ticket, wait, &n): 1 = the count has arrived (n = num_rendered; the ticket is released),
+ *   goi_raster_ticket_result(ticket, wait, &n, &flags): 1 = the count has arrived (n = num_rendered; the ticket is released),
  *       0 = not yet (only with wait == 0), -1 = error (e.g. the "prefiltered" trap; ticket released).
  *   n <= capacity : the frame is exactly what goi_raster_forward would have produced (bit-identical outputs; the
  *       tile lists are identical, only the workspace is larger).  Pass R = capacity to goi_raster_backward.
@@ -151,17 +175,14 @@ int goi_raster_forward(const GoiRasterScene* scene, void* geom_buffer, void* ima
  * A resolved ticket means the COUNT has arrived -- it is final before the frame's blend kernel starts -- not that the frame's
  * kernels have finished: the outputs are ordered on `stream` like any other kernel's.  A blocking wait spins on host memory;
  * after two seconds it synchronises the frame's stream (not the device) and fails loudly rather than hang.
- * Not available with scene->debug (which synchronises after every stage) or for P == 0. */
-int goi_raster_forward_async(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
-                             int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                             int* radii, void* stream);
-int goi_raster_ticket_result(int ticket, int wait, int* num_rendered);
-
-/* SPECULATIVE DEPTH CUT-OFF of the tile lists (no counterpart in the reference, which lists every Gaussian in every tile of its
- * rectangle, CR/rasterizer_impl.cu:70-111, although a pixel stops at T < 1e-4, CR/forward.cu:352-357: on an opaque scene three
- * quarters of the instances lie behind their tile's saturation front and are emitted, sorted and never looked at).
+ * Not available with scene->debug (which synchronises after every stage) or for P == 0.
  *
- * goi_raster_forward_async_cut is goi_raster_forward_async with two per-TILE arrays (ceil(W/16) * ceil(H/16) floats, row-major):
+ * keep, invert: the selection of goi_raster_forward (NULL, 0: every Gaussian).
+ *
+ * zcut_in, zcut_out: the SPECULATIVE DEPTH CUT-OFF of the tile lists (no counterpart in the reference, which lists every Gaussian
+ * in every tile of its rectangle, CR/rasterizer_impl.cu:70-111, although a pixel stops at T < 1e-4, CR/forward.cu:352-357: on an
+ * opaque scene three quarters of the instances lie behind their tile's saturation front and are emitted, sorted and never looked
+ * at).  Two per-TILE arrays (ceil(W/16) * ceil(H/16) floats, row-major); both NULL is the frame without a cut:
  *   zcut_out (or NULL): LEARNT by this frame -- for every tile, the view depth up to which its list is worth listing the next
  *       time the same camera is rendered: the depth of the list entry a quarter (+ 64 positions) beyond the last position any
  *       pixel of the tile looked at; +inf for a tile in which some pixel reached the end of its list unsaturated.
@@ -171,16 +192,19 @@ int goi_raster_ticket_result(int ticket, int wait, int* num_rendered);
  * A frame whose pixels all saturate inside their cut lists is bit-identical to the uncut frame: outputs, n_contrib, every
  * gradient (the dropped instances were never looked at).  If a pixel of a cut tile reaches the end of its list unsaturated, or
  * looks at an entry DEEPER than its tile's cut (a rectangle of more than 64 tiles has no tile mask and stays listed at every
- * depth: the Gaussians that were dropped in between would have come first), the
- * cut was TOO TIGHT for this frame (the geometry has moved since it was learnt): the forward blend raises bit 2 of the frame's
- * flag word (goi_raster_truncated_flag; bit 0 = the instance list was truncated, bit 1 = a sort timed out), the frame's
- * backward writes ZERO gradients like a truncated frame's, and goi_raster_ticket_result2 hands the word to the host, which
- * renders the frame again without a cut (goi_raster_forward) and forgets what the camera had learnt.
- * goi_raster_ticket_result2: as goi_raster_ticket_result, plus the frame's flag word (0 for a frame of goi_raster_forward). */
-int goi_raster_forward_async_cut(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
-                                 int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                                 int* radii, const float* zcut_in, float* zcut_out, void* stream);
-int goi_raster_ticket_result2(int ticket, int wait, int* num_rendered, unsigned* frame_flags);
+ * depth: the Gaussians that were dropped in between would have come first), the cut was TOO TIGHT for this frame (the geometry
+ * has moved since it was learnt): the forward blend raises bit 2 of the frame's flag word (goi_raster_truncated_flag; bit 0 = the
+ * instance list was truncated, bit 1 = a sort timed out), the frame's backward writes ZERO gradients like a truncated frame's,
+ * and goi_raster_ticket_result hands the word to the host, which renders the frame again without a cut (goi_raster_forward) and
+ * forgets what the camera had learnt.
+ * A selection and a cut do not go together: keep != NULL with zcut_in or zcut_out is refused.
+ *
+ * goi_raster_ticket_result: num_rendered (or NULL) receives the count, frame_flags (or NULL) the frame's flag word (GOI_FRAME_*;
+ * 0 for a frame of goi_raster_forward); both are written only when the call returns 1. */
+int goi_raster_forward_async(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
+                             int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
+                             int* radii, const float* zcut_in, float* zcut_out, const uint8_t* keep, int invert, void* stream);
+int goi_raster_ticket_result(int ticket, int wait, int* num_rendered, unsigned* frame_flags);
 #define GOI_FRAME_TRUNCATED 1u
 #define GOI_FRAME_MISSORTED 2u
 #define GOI_FRAME_CUT_TOO_TIGHT 4u
@@ -193,36 +217,12 @@ int goi_raster_forward_redo(const GoiRasterScene* scene, int num_rendered, void*
                             void* binning_buffer, float* out_color, float* out_semantic, float* out_depth,
                             float* out_alpha, const int* radii, void* stream);
 
-/* ---- A SELECTION of the Gaussians, rendered in place (ABI 8) ----------------------------------------------------------------
- * (the reference's viewer index-selects every per-Gaussian tensor by a boolean mask before it calls the rasterizer,
- * gui/gs_renderer.py:315-321: a host synchronisation, a second copy of the selected set, and outputs of the subset's length)
- *
- * goi_raster_forward_selected / goi_raster_forward_async_selected are goi_raster_forward / goi_raster_forward_async with
- *   keep   : [P] device bytes, one per Gaussian (never written; a torch.bool or torch.uint8 tensor as it is), or NULL;
- *   invert : 0 -- Gaussian i is rendered iff keep[i] != 0;  non-zero -- iff keep[i] == 0 (the complement, without forming it).
- * The frame is the frame of the selected Gaussians alone, bit for bit what the plain entry points produce for the
- * index-selected arrays (outputs, num_rendered, and -- scattered to their ids -- radii and every gradient).  An unselected
- * Gaussian is dropped by the first kernel before anything of it but its selection byte is read, exactly where a Gaussian
- * behind the near plane is dropped: radii[i] = 0, no tile, no instance, zero gradient rows; it does not trip the
- * `prefiltered` check.  All arrays stay [P]-long and are indexed by the caller's own ids.
- * keep == NULL is the plain call.  Everything that reads the geometry workspace -- goi_raster_forward_redo, _reblend, every
- * goi_raster_backward*, goi_raster_backward_semantics -- works behind a selected forward unchanged and takes no selection
- * (a reblend shows the selection of the frame that filled the workspaces).  There is no selected _async_cut, trace or
- * mark_visible. */
-int goi_raster_forward_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer,
-                                goi_alloc_fn binning_alloc, void* alloc_user,
-                                float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                                int* radii, const uint8_t* keep, int invert, void* stream);
-int goi_raster_forward_async_selected(const GoiRasterScene* scene, void* geom_buffer, void* image_buffer, void* binning_buffer,
-                                      int capacity, float* out_color, float* out_semantic, float* out_depth, float* out_alpha,
-                                      int* radii, const uint8_t* keep, int invert, void* stream);
-
 /* The blend of a frame whose geometry and tile lists are already in workspaces filled by an earlier goi_raster_forward /
  * _async / _redo of the SAME camera over the SAME Gaussian geometry (positions, covariances, opacities, colours): only the
  * semantic rows and the background may have changed.  Runs the forward blend alone (no preprocess, sort or emit), writes the
  * four outputs and a fresh image workspace (`image_buffer`, goi_raster_image_bytes; the tile ranges are copied from
  * `cached_image_buffer`), and leaves geometry and binning workspaces untouched, so the result is what goi_raster_forward
- * would produce for the current semantics, bit for bit, and goi_raster_backward* can follow with (geom, binning, the NEW
+ * would produce for the current semantics, bit for bit, and goi_raster_backward / _backward_semantics can follow with (geom, binning, the NEW
  * image workspace, R).  R as for goi_raster_backward.  Reads only P, S, W, H, semantics and bg from `scene`.  What it cannot
  * check is the premise: the caller vouches that nothing but the semantics changed (goi_hyperplane_amd: opt-in geometry cache,
  * DESIGN.md 7c).  No counterpart in the reference, which redoes the whole frame (CR/rasterizer_impl.cu:198-344). */
@@ -239,8 +239,49 @@ int goi_raster_forward_reblend(const GoiRasterScene* scene, int R, const void* g
  * between the two passes inside the scratch instead and these two arrays are left unwritten.
  * FACTORED mode: dL_dsh == NULL while the scene has SH colours.  dL/dSH is not formed (192 of the 300 bytes of
  * gradient per Gaussian at degree 3); dL_dcolor returns the colour gradient with the forward's clamp mask applied
- * (CR/backward.cu:44-47), the factor g of dL/dSH[k] = basis_k(view direction) * g -- see goi_raster_sh_grad_from_views. */
-int goi_raster_backward(const GoiRasterScene* scene, int R,
+ * (CR/backward.cu:44-47), the factor g of dL/dSH[k] = basis_k(view direction) * g -- see goi_raster_sh_grad_from_views.
+ *
+ * scratch: goi_raster_backward_scratch_bytes(scratch_instances ? scratch_instances : R, S) bytes, uninitialised; NULL selects the
+ * float-atomic accumulation path (not bit-reproducible).
+ *
+ * scratch_instances (0 = R): the row scratch laid out for FEWER instances than the binning workspace.  `R` stays what the
+ * binning buffer was laid out for (a speculative frame: its capacity); `scratch_instances` is what the scratch --
+ * goi_raster_backward_scratch_bytes(scratch_instances, S) bytes -- holds rows for.  It must be >= the frame's num_rendered: a
+ * caller that has READ the count of a speculative frame by the time it enqueues the backward (the loss usually sits in between)
+ * passes the count and needs half the scratch of a frame sized by its capacity (headroom 2: 2.1 instead of 4.3 GB on the
+ * headline view, 6.4 instead of 12.9 GB at 3 M Gaussians).  Same results bit for bit.
+ *
+ * flags: bit 0, GOI_BACKWARD_ACCUMULATE: the eleven output arrays already hold the gradients of earlier views of the same batch
+ * (written by a call without the bit, then possibly added to by calls with it) and this view's gradients are ADDED: the rows of a
+ * Gaussian that is visible in this view are read, added to and written back, all other rows are left alone -- the sum over the K
+ * views of a batch costs each view its visible rows once more instead of a dense [P, 75 + S] addition per view.  Default (record)
+ * path with dL_dsh formed or no SH at all; prev_radii, prev_mask and row_mask must be NULL (an idle Gaussian then costs nothing
+ * at all).  (Not in the reference: its loop back-propagates one view per optimiser step, train.py:96-198; dist.backward_views
+ * uses it for multi-view batches.)
+ *
+ * prev_radii (or NULL): the radii array of the backward that LAST WROTE these very output buffers -- all eleven of them, e.g.
+ * views of one allocation a binding keeps and reuses once its consumers have let go of it -- provided nothing else has written to
+ * them since.  A Gaussian with prev_radii == 0 that is invisible in this frame as well already has zeros in every output row, and
+ * nothing is written for it: on the headline scene half of the Gaussians are invisible in any one view and the dense gradient
+ * tensors of the reference's interface (rasterize_points.cu:252-262: eleven zero-filled [P, ..] tensors per call) are 170 MB of
+ * zeros per step.  The results are those of a call with prev_radii == NULL bit for bit.  (Honoured on the default path -- row
+ * records; the other backward variants write every row.)  csrc/torch_binding.cpp keeps such a pool and checks refcount and
+ * version counter before a reuse.
+ *
+ * prev_mask, row_mask: a per-ROW record of what a backward left in the eleven output arrays.  On the default path (row records,
+ * option bwd_skip_idle 1) the per-Gaussian chain runs only for a Gaussian that reached a pixel: the row reduction publishes one
+ * CONTRIBUTION byte per listed Gaussian ("owns at least one valid row") in the scratch, and a visible Gaussian whose byte is 0 --
+ * it sits behind the saturation front in every tile it touches -- or that has no tiles is handled like an invisible one: its rows
+ * get zeros.  On a scene with depth complexity that is two thirds of the visible Gaussians.  "The row already holds zeros" can
+ * then no longer be told from a radii array, so:
+ *   row_mask  [P] bytes, written (or NULL): 1 -- this call's chain wrote the row of that Gaussian, 0 -- the row holds zeros now;
+ *   prev_mask [P] bytes, read (or NULL): the row_mask of the backward that LAST WROTE these very output buffers, nothing else
+ *             having written to them since: a row with prev_mask 0 that gets zeros again is not written.  Takes precedence over
+ *             prev_radii, which keeps its meaning.  prev_mask and row_mask may be the same array.
+ * The gradients are those of bwd_skip_idle 0 under IEEE equality: the chain on an all-zero record could write -0.0 where the zero
+ * path writes +0.0; the blend-gradient arrays are bit-identical.  csrc/torch_binding.cpp keeps the mask with its pooled buffer. */
+#define GOI_BACKWARD_ACCUMULATE 1
+int goi_raster_backward(const GoiRasterScene* scene, int R, int scratch_instances, int flags,
                         const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
                         const int* radii, const float* out_alpha,
                         const float* dL_dout_color, const float* dL_dout_semantic,
@@ -249,65 +290,7 @@ int goi_raster_backward(const GoiRasterScene* scene, int R,
                         float* dL_dcolor /*[P,3]*/, float* dL_dsemantic /*[P,S]*/, float* dL_ddepth /*[P]*/,
                         float* dL_dmean3D /*[P,3]*/, float* dL_dcov3D /*[P,6]*/, float* dL_dsh /*[P,M,3]*/,
                         float* dL_dscale /*[P,3]*/, float* dL_drot /*[P,4]*/,
-                        void* scratch /* goi_raster_backward_scratch_bytes(R, S) bytes, uninitialised; NULL selects
-                                         the float-atomic accumulation path (not bit-reproducible) */,
-                        void* stream);
-
-/* goi_raster_backward with one more pointer (ABI 5).  prev_radii (or NULL = goi_raster_backward): the radii array of the
- * backward that LAST WROTE these very output buffers -- all eleven of them, e.g. views of one allocation a binding keeps and
- * reuses once its consumers have let go of it -- provided nothing else has written to them since.  A Gaussian with
- * prev_radii == 0 that is invisible in this frame as well already has zeros in every output row, and nothing is written for it:
- * on the headline scene half of the Gaussians are invisible in any one view and the dense gradient tensors of the reference's
- * interface (rasterize_points.cu:252-262: eleven zero-filled [P, ..] tensors per call) are 170 MB of zeros per step.  The
- * results are those of goi_raster_backward bit for bit.  (Honoured on the default path -- row records; the other backward
- * variants write every row.)  csrc/torch_binding.cpp keeps such a pool and checks refcount and version counter before a reuse. */
-int goi_raster_backward2(const GoiRasterScene* scene, int R, const void* geom_buffer, const void* binning_buffer,
-                         const void* image_buffer, const int* radii, const float* out_alpha, const float* dL_dout_color,
-                         const float* dL_dout_semantic, const float* dL_dout_depth, const float* dL_dout_alpha,
-                         float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dsemantic,
-                         float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                         float* dL_drot, void* scratch, const int* prev_radii, void* stream);
-
-/* goi_raster_backward2 with the row scratch laid out for FEWER instances than the binning workspace (ABI 6).  `R` stays what the
- * binning buffer was laid out for (a speculative frame: its capacity); `scratch_instances` (0 = R) is what the scratch --
- * goi_raster_backward_scratch_bytes(scratch_instances, S) bytes -- holds rows for.  It must be >= the frame's num_rendered: a
- * caller that has READ the count of a speculative frame by the time it enqueues the backward (the loss usually sits in between)
- * passes the count and needs half the scratch of a frame sized by its capacity (headroom 2: 2.1 instead of 4.3 GB on the
- * headline view, 6.4 instead of 12.9 GB at 3 M Gaussians).  Same results bit for bit.
- * `flags` bit 0, ACCUMULATE: the eleven output arrays already hold the gradients of earlier views of the same batch (written by a
- * call without the bit, then possibly added to by calls with it) and this view's gradients are ADDED: the rows of a Gaussian that
- * is visible in this view are read, added to and written back, all other rows are left alone -- the sum over the K views of a batch
- * costs each view its visible rows once more instead of a dense [P, 75 + S] addition per view.  Default (record) path with dL_dsh
- * formed or no SH at all; prev_radii must be NULL.  (Not in the reference: its loop back-propagates one view per optimiser step,
- * train.py:96-198; dist.backward_views uses it for multi-view batches.) */
-#define GOI_BACKWARD_ACCUMULATE 1
-int goi_raster_backward3(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
-                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
-                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
-                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, void* stream);
-
-/* goi_raster_backward3 with a per-ROW record of what a backward left in the eleven output arrays (ABI 7).  On the default path
- * (row records, option bwd_skip_idle 1) the per-Gaussian chain runs only for a Gaussian that reached a pixel: the row reduction
- * publishes one CONTRIBUTION byte per listed Gaussian ("owns at least one valid row") in the scratch, and a visible Gaussian whose
- * byte is 0 -- it sits behind the saturation front in every tile it touches -- or that has no tiles is handled like an invisible
- * one: its rows get zeros.  On a scene with depth complexity that is two thirds of the visible Gaussians.  "The row already holds
- * zeros" can then no longer be told from a radii array, so:
- *   row_mask  [P] bytes, written (or NULL): 1 -- this call's chain wrote the row of that Gaussian, 0 -- the row holds zeros now;
- *   prev_mask [P] bytes, read (or NULL): the row_mask of the backward that LAST WROTE these very output buffers, nothing else
- *             having written to them since: a row with prev_mask 0 that gets zeros again is not written.  Takes precedence over
- *             prev_radii, which keeps its meaning.  prev_mask and row_mask may be the same array.
- * Both NULL: goi_raster_backward3.  With GOI_BACKWARD_ACCUMULATE both must be NULL (an idle Gaussian then costs nothing at all).
- * The gradients are those of bwd_skip_idle 0 under IEEE equality: the chain on an all-zero record could write -0.0 where the zero
- * path writes +0.0; the blend-gradient arrays are bit-identical.  csrc/torch_binding.cpp keeps the mask with its pooled buffer. */
-int goi_raster_backward4(const GoiRasterScene* scene, int R, int scratch_instances, int flags, const void* geom_buffer,
-                         const void* binning_buffer, const void* image_buffer, const int* radii, const float* out_alpha,
-                         const float* dL_dout_color, const float* dL_dout_semantic, const float* dL_dout_depth,
-                         const float* dL_dout_alpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                         float* dL_dsemantic, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscale, float* dL_drot, void* scratch, const int* prev_radii, const uint8_t* prev_mask,
-                         uint8_t* row_mask, void* stream);
+                        void* scratch, const int* prev_radii, const uint8_t* prev_mask, uint8_t* row_mask, void* stream);
 
 /* Tests only: byte offset, in a 256-byte aligned scratch of goi_raster_backward_scratch_bytes(num_rendered, S), of the contribution
  * bytes the default backward leaves there: [num_rendered] bytes indexed by a listed Gaussian's first emit-order instance (word 0 of
@@ -626,7 +609,7 @@ int goi_raster_profile_collect(double* ms, int* calls);
  *                  2 EXPERIMENT (128-byte rows: S = 5 .. 20): the per-Gaussian pass sums its Gaussians' rows itself -- no record,
  *                  no reduce_rows_k; bit-identical, measured slower
  *   "bwd_skip_idle" (bwd_records 1) 1 (default) a visible Gaussian that reached no pixel -- no valid row in any tile it touches, or
- *                  no tiles -- skips the per-Gaussian chain and its rows get zeros (goi_raster_backward4); 0 every visible
+ *                  no tiles -- skips the per-Gaussian chain and its rows get zeros (goi_raster_backward, row_mask); 0 every visible
  *                  Gaussian goes through the chain.  Equal gradients (zeros may differ in sign)
  *   "osh_path"     goi_semantic_osh_fit: 0 (default) z in registers where the shape allows it (D = 256, n_codes <= 320),
  *                  1 always the generic path (z re-formed from the LUT every epoch); bit-identical (285 -> 437 us on the headline view: DESIGN.md 9.3)
@@ -892,7 +875,7 @@ int goi_raster_debug_preprocess_backward(const GoiRasterScene* scene, int source
 int goi_raster_debug_pair_eval(int P, int W, int H, const void* geom_buffer, const uint32_t* requests, long long n_requests,
                                float* E, float* alpha, uint8_t* guards, void* stream);
 
-/* The backward BLEND stage alone, on a real frame (tests only), asynchronously on `stream`: what goi_raster_backward3 /
+/* The backward BLEND stage alone, on a real frame (tests only), asynchronously on `stream`: what goi_raster_backward /
  * goi_raster_backward_semantics run before the row reduction -- the quadrant-order launch (or the memsets) and one blend kernel,
  * through the product's launchers -- and copies of what it left.  From `scene`: P, S, W, H, bg, semantics.  R, the three
  * workspaces, radii, out_alpha: as for goi_raster_backward of the same frame (R > 0).  The four upstream gradients may each be

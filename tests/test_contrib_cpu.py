@@ -186,7 +186,7 @@ def test_header_table_and_abi_version(lib):
     assert decl, "the entry is not declared with the documented signature"
     version = re.search(r"#define GOI_RASTER_ABI_VERSION (\d+)", hdr)
     assert hdr.index(NAME) < version.start() < decl.start(), "must be named among ABI 8's later additions, above the version"
-    assert int(version.group(1)) == 8 == _lib.ABI_VERSION == lib.goi_raster_abi_version()
+    assert int(version.group(1)) == 9 == _lib.ABI_VERSION == lib.goi_raster_abi_version()
     restype, argtypes = _lib.SYMBOLS[NAME]
     assert restype is C.c_int and argtypes == [C.c_int] * 4 + [C.c_void_p] * 7
     assert hasattr(lib, NAME)

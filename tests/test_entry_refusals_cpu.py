@@ -6,6 +6,10 @@ were recorded from the library as it was when every one of these entries still l
 
 The same for the rasterizer's direct-test and diagnostic entries that live beside their kernels (the RASTER tables below): for
 those, every refusal and every return of 0 that comes before the entry's first HIP call.
+
+And for the entries of the rasterizer's frame in csrc/api.hip (the FRAME table): forward, asynchronous forward and its ticket,
+redo, reblend, backward, semantics-only backward, trace, truncated flag.  Recorded from the library of ABI 8 through the widest
+entry of each operation, before ABI 9 folded the narrower ones into it.
 """
 import ctypes as C
 import threading
@@ -20,7 +24,7 @@ WS = object()  # where a workspace case puts the workspace under test
 _COUNTS = (C.c_longlong * 1)()
 _FLAGS = C.c_uint(0)
 _MAPS = (C.c_void_p * 1)(F.value)
-_ALLOC = None  # made with the library's callback type in the fixture
+_ALLOC = _NO_ALLOC = None  # made with the library's callback type in the fixture: a callback, and the NULL one
 
 
 @pytest.fixture(scope="module")
@@ -28,13 +32,14 @@ def lib():
     from goi_hyperplane_amd import build
     build.build()
     from goi_hyperplane_amd import _lib
-    global _ALLOC
+    global _ALLOC, _NO_ALLOC
     _ALLOC = _lib.ALLOC_FN(lambda user, nbytes: None)
+    _NO_ALLOC = _lib.ALLOC_FN()
     return _lib.load()
 
 
 def _call(lib, fn, args, ws=None):
-    args = tuple(ws if a is WS else _ALLOC if a == "alloc" else a for a in args)
+    args = tuple(ws if a is WS else _ALLOC if a == "alloc" else _NO_ALLOC if a == "no alloc" else a for a in args)
     return getattr(lib, fn)(*args)
 
 
@@ -408,6 +413,136 @@ RASTER_SIZES = [
 ]
 
 
+# ---- the entries of the rasterizer's frame (csrc/api.hip).  Per entry every path that returns before its first HIP call, in the
+# order of its checks: each row passes all earlier checks and fails exactly this one.  (A forward or a trace over P == 0 Gaussians
+# clears its outputs on the stream: not such a path.)  Each entry's arguments are a passing call with fields replaced.
+_FWD = dict(geom=F, image=F, alloc="alloc", user=N, color=F, sem=F, depth=F, alpha=F, radii=F, keep=N, invert=0, stream=N)
+_ASYNC = dict(geom=F, image=F, binning=F, capacity=64, color=F, sem=F, depth=F, alpha=F, radii=F, zcut_in=N, zcut_out=N, keep=N,
+              invert=0, stream=N)
+_REDO = dict(num_rendered=8, geom=F, image=F, binning=F, color=F, sem=F, depth=F, alpha=F, radii=F, stream=N)
+_REBLEND = dict(R=8, geom=F, binning=F, cached_image=F, image=F, color=F, sem=F, depth=F, alpha=F, stream=N)
+_TRACE = dict(img_sem=F, geom=F, image=F, alloc="alloc", user=N, color=F, gau_sem=F, num_gsem=F, radii=F, stream=N)
+_BWD = dict(R=8, scratch_instances=0, flags=0, geom=F, binning=F, image=F, radii=F, out_alpha=F, dL_dout_color=F, dL_dout_semantic=F,
+            dL_dout_depth=F, dL_dout_alpha=F, dL_dmean2D=F, dL_dconic=F, dL_dopacity=F, dL_dcolor=F, dL_dsemantic=F, dL_ddepth=F,
+            dL_dmean3D=F, dL_dcov3D=F, dL_dsh=F, dL_dscale=F, dL_drot=F, scratch=F, prev_radii=N, prev_mask=N, row_mask=N, stream=N)
+_BSEM = dict(R=8, geom=F, binning=F, image=F, radii=F, out_alpha=F, dL_dout_semantic=F, dL_dsemantic=F, scratch=F, stream=N)
+_FRAME_ARGS = {"goi_raster_forward": _FWD, "goi_raster_forward_async": _ASYNC, "goi_raster_forward_redo": _REDO,
+               "goi_raster_forward_reblend": _REBLEND, "goi_raster_trace": _TRACE, "goi_raster_backward": _BWD,
+               "goi_raster_backward_semantics": _BSEM}
+
+
+def _frame(fn, message, scene=None, rc=-1, **over):
+    """A FRAME row: entry `fn` called with its passing arguments, scene fields (`scene`: a dict, or "null") and arguments replaced."""
+    base = _FRAME_ARGS[fn]
+    assert set(over) <= set(base) and (scene == "null" or set(scene or {}) <= set(_SCENE))
+
+    def args():
+        from goi_hyperplane_amd import _lib
+        sc = N
+        if scene != "null":
+            fields = dict(_SCENE, **(scene or {}))
+            sc = C.byref(_lib.GoiRasterScene(**{k: (v.value if isinstance(v, C.c_void_p) else v) for k, v in fields.items()}))
+        return (sc,) + tuple(dict(base, **over).values())
+    return (fn, args, rc, message)
+
+
+_SH_MSG2 = "Please provide excatly one of either SHs or precomputed colors!"
+_COV_MSG = "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!"
+_DEG_MSG = "SH degree must be 0..3 and (D+1)^2 <= M <= 16"
+
+
+def _validate_rows(fn, need_sem=True, need_opacity=True):
+    """The refusals of validate() (csrc/api.hip), which every entry that takes a whole scene starts with, through `fn`."""
+    rows = [_frame(fn, "scene is NULL", "null")]
+    rows += [_frame(fn, "bad P/W/H", dict([f])) for f in (("P", -1), ("W", 0), ("H", 0), ("W", -1))]
+    rows += [_frame(fn, "semantic channels S must be in 1..32", dict(S=v)) for v in (0, 33)]
+    if need_opacity:
+        rows += [_frame(fn, "opacities is NULL", dict(opacities=N))]
+    rows += [_frame(fn, "a required input pointer is NULL", {f: N}) for f in ("means3D", "viewmatrix", "projmatrix", "campos", "bg")]
+    if need_sem:
+        rows += [_frame(fn, "semantics is required (the reference dereferences it unconditionally)", dict(semantics=N))]
+    rows += [_frame(fn, "semantics must be 16-byte aligned when S is a multiple of 4 (its rows are moved as 16-byte words)",
+                    dict(semantics=A16, S=v)) for v in (16, 4)]
+    rows += [_frame(fn, _SH_MSG2, dict(colors_precomp=F)), _frame(fn, _SH_MSG2, dict(shs=N))]
+    rows += [_frame(fn, "shs must be 16-byte aligned when 3 M is a multiple of 4 (its rows are moved as 16-byte words)",
+                    dict(shs=A16, **m)) for m in (dict(M=16), dict(D=1, M=4))]
+    rows += [_frame(fn, _COV_MSG, sc) for sc in (dict(scales=N), dict(rotations=N), dict(scales=N, rotations=N), dict(cov3D_precomp=F),
+                                                 dict(scales=N, cov3D_precomp=F))]
+    rows += [_frame(fn, _DEG_MSG, sc) for sc in (dict(D=-1), dict(D=4, M=25), dict(D=3, M=15), dict(D=0, M=17))]
+    return rows
+
+
+_FA, _RD, _RB = "goi_raster_forward_async", "goi_raster_forward_redo", "goi_raster_forward_reblend"
+_BW, _BS = "goi_raster_backward", "goi_raster_backward_semantics"
+_ACC_MSG = ("GOI_BACKWARD_ACCUMULATE needs the default backward (scratch given, bwd_variant 0 / 2, bwd_records 1), dL_dsh when "
+            "the colours are SH, prev_radii NULL and debug off")
+_P0 = dict(P=0, means3D=N, opacities=N, shs=N, scales=N)  # (P == 0: nothing else of the scene is looked at)
+
+# entry, arguments (a function that makes them once the library is there), return value, message (None: no refusal)
+FRAME = (
+    _validate_rows("goi_raster_forward")
+    + [_frame("goi_raster_forward", "workspace pointer / allocator is NULL", **kw)
+       for kw in (dict(geom=N), dict(image=N), dict(alloc="no alloc"))]
+    + _validate_rows(_FA)
+    + [_frame(_FA, _FA + ": P == 0 has nothing to speculate on; use goi_raster_forward", _P0),
+       _frame(_FA, _FA + ": debug mode synchronises after every stage; use goi_raster_forward", dict(debug=1)),
+       _frame(_FA, _FA + ": capacity must be positive", capacity=0),
+       _frame(_FA, _FA + ": capacity must be positive", capacity=-1)]
+    + [_frame(_FA, "workspace pointer is NULL", **{k: N}) for k in ("geom", "image", "binning")]
+    + [_frame(_FA, _FA + ": a selection (keep) cannot be combined with a depth cut", keep=F, **z)
+       for z in (dict(zcut_in=F), dict(zcut_out=F), dict(zcut_in=F, zcut_out=F))]
+    + [("goi_raster_ticket_result", (t, w, N, N), -1, "invalid or already resolved ticket")
+       for t, w in ((-1, 0), (-1, 1), (0, 0), (4095, 1), (1 << 20, 0))]  # (no ticket was ever issued in this process)
+    + [_frame(_RD, "scene is NULL", "null")]
+    + [_frame(_RD, _RD + ": bad P/W/H/S", dict([f])) for f in (("P", 0), ("P", -1), ("W", 0), ("H", 0), ("S", 0), ("S", 33))]
+    + [_frame(_RD, _RD + ": semantics, bg and radii are required", dict(semantics=N)),
+       _frame(_RD, _RD + ": semantics, bg and radii are required", dict(bg=N)),
+       _frame(_RD, _RD + ": semantics, bg and radii are required", radii=N),
+       _frame(_RD, _RD + ": nothing to redo", num_rendered=-1),
+       _frame(_RD, "workspace pointer is NULL", geom=N),
+       _frame(_RD, "workspace pointer is NULL", image=N),
+       _frame(_RD, "workspace pointer is NULL", binning=N),
+       _frame(_RD, "workspace pointer is NULL", num_rendered=0, binning=N, image=N)]
+    + [_frame(_RB, "scene is NULL", "null")]
+    + [_frame(_RB, _RB + ": bad P/W/H/S", dict([f])) for f in (("P", 0), ("P", -1), ("W", 0), ("H", 0), ("S", 0), ("S", 33))]
+    + [_frame(_RB, _RB + ": semantics and bg are required", dict(semantics=N)),
+       _frame(_RB, _RB + ": semantics and bg are required", dict(bg=N)),
+       _frame(_RB, _RB + ": bad R", R=-1)]
+    + [_frame(_RB, "workspace pointer is NULL", **{k: N}) for k in ("geom", "cached_image", "image", "binning")]
+    + [_frame(_RB, "workspace pointer is NULL", R=0, binning=N, geom=N)]
+    + [_frame(_RB, "output pointer is NULL", **{k: N}) for k in ("color", "sem", "depth", "alpha")]
+    + [_frame(_RB, "output pointer is NULL", R=0, binning=N, alpha=N)]  # (R == 0 needs no binning workspace)
+    + _validate_rows(_BW, need_opacity=False)
+    + [_frame(_BW, None, _P0, rc=0, geom=N, image=N, binning=N, scratch=N),  # P == 0: nothing to do, nothing looked at
+       # (the forward's records hold the opacities: a scene without them gets as far as the workspaces)
+       _frame(_BW, "workspace pointer is NULL", dict(opacities=N), geom=N),
+       _frame(_BW, "workspace pointer is NULL", image=N),
+       _frame(_BW, "workspace pointer is NULL", binning=N),
+       _frame(_BW, "workspace pointer is NULL", R=0, binning=N, image=N),
+       _frame(_BW, "scratch_instances must be in 0..R (0: the scratch is laid out for R)", scratch_instances=-1),
+       _frame(_BW, "scratch_instances must be in 0..R (0: the scratch is laid out for R)", scratch_instances=9),
+       _frame(_BW, "scratch_instances must be in 0..R (0: the scratch is laid out for R)", R=0, binning=N, scratch_instances=1),
+       _frame(_BW, _ACC_MSG, flags=1, scratch=N),
+       _frame(_BW, _ACC_MSG, flags=1, prev_radii=F),
+       _frame(_BW, _ACC_MSG, flags=1, dL_dsh=N),
+       _frame(_BW, _ACC_MSG, dict(debug=1), flags=1),
+       _frame(_BW, "GOI_BACKWARD_ACCUMULATE: prev_mask and row_mask must be NULL", flags=1, prev_mask=F),
+       _frame(_BW, "GOI_BACKWARD_ACCUMULATE: prev_mask and row_mask must be NULL", flags=1, row_mask=F),
+       _frame(_BW, "GOI_BACKWARD_ACCUMULATE: prev_mask and row_mask must be NULL", flags=1, scratch_instances=8, prev_mask=F,
+              row_mask=F)]
+    + _validate_rows(_BS, need_opacity=False)
+    + [_frame(_BS, None, _P0, rc=0, geom=N, image=N, binning=N, scratch=N),
+       _frame(_BS, "workspace pointer is NULL", dict(opacities=N), geom=N),
+       _frame(_BS, "workspace pointer is NULL", image=N),
+       _frame(_BS, "workspace pointer is NULL", binning=N),
+       _frame(_BS, _BS + " needs the scratch of goi_raster_backward_scratch_bytes", scratch=N),
+       _frame(_BS, _BS + " needs the scratch of goi_raster_backward_scratch_bytes", R=0, binning=N, scratch=N)]
+    + [_frame(_BS, "a required pointer is NULL", **{k: N}) for k in ("dL_dout_semantic", "dL_dsemantic", "out_alpha", "radii")]
+    + _validate_rows("goi_raster_trace", need_sem=False)
+    + [("goi_raster_truncated_flag", a, None, None) for a in ((N, 4), (F, 0), (F, -1), (N, 0))]
+)
+
+
 def _ids(table):
     seen = {}
     out = []
@@ -448,6 +583,27 @@ def test_raster_size_out_of_range_is_zero(lib, fn, args):
     assert getattr(lib, fn)(*args) == 0
 
 
+@pytest.mark.parametrize("fn,args,rc,message", FRAME, ids=_ids(FRAME))
+def test_frame_entry_refusals_and_early_returns(lib, fn, args, rc, message):
+    assert lib.goi_knn_dist2(-1, F, F, F, N) < 0  # (a message of another unit's: a return without a refusal must leave it alone)
+    assert _call(lib, fn, args() if callable(args) else args) == rc
+    assert _err(lib) == (message if message is not None else "goi_knn_dist2: bad P")
+
+
+def test_async_forward_refuses_without_the_onesweep_sort(lib):
+    """The speculative forward takes its counts on the device, which only the onesweep sort does: with sort_variant 0 it is
+    refused, behind the debug check and before it looks at the capacity or the workspaces."""
+    fn, args, _rc, _message = _frame(_FA, None, capacity=0, geom=N)
+    assert lib.goi_raster_set_option(b"sort_variant", 0) == 0
+    try:
+        assert _call(lib, fn, args()) == -1
+        assert _err(lib) == "goi_raster_forward_async needs the onesweep sort (sort_variant 1)"
+    finally:
+        assert lib.goi_raster_set_option(b"sort_variant", 1) == 0
+    assert _call(lib, fn, args()) == -1
+    assert _err(lib) == _FA + ": capacity must be positive"
+
+
 def test_sort_entry_refuses_device_counts_without_the_onesweep_sort(lib):
     """n_dev and ghist belong to the onesweep sort: with sort_variant 0 the entry refuses them, behind its flags check and
     before it looks at n, the pointers or the workspace."""
@@ -472,6 +628,15 @@ def test_every_raster_test_entry_is_covered():
     assert len(beside_kernels) == 13
     assert beside_kernels == {row[0] for row in RASTER + RASTER_SIZES}
     assert {n for n in beside_kernels if n.endswith("_bytes")} == {row[0] for row in RASTER_SIZES}
+
+
+def test_every_frame_entry_is_covered():
+    from goi_hyperplane_amd import _lib
+    frame = {n for n in _lib.SYMBOLS if n.startswith(("goi_raster_forward", "goi_raster_backward", "goi_raster_ticket_",
+                                                       "goi_raster_trace", "goi_raster_truncated_"))}
+    frame -= {"goi_raster_backward_scratch_bytes"}  # (a size function: any int has an answer)
+    assert len(frame) == 9
+    assert frame == {row[0] for row in FRAME}
 
 
 def test_every_moved_entry_is_covered():

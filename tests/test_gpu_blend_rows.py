@@ -47,7 +47,9 @@ import torch
 
 from tests import blend_cases as BC
 from tests import blend_reference as BR
+from tests import raw_frame
 from tests import reduce_rows_reference as RR
+from tests.raw_frame import ptr as _ptr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,50 +80,21 @@ def _L():
     return _lib
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _dev(a, dtype=None):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype))).to(DEV)
 
 
 # ---- a frame on the device -------------------------------------------------------------------------------------------------
-class DeviceFrame:
+class DeviceFrame(raw_frame.RawFrame):
     """One exact forward of the product through the C ABI, its workspaces kept, and what the reference needs of it."""
 
     def __init__(self, sc, cam, bg):
-        from goi_hyperplane_amd import _C
-        L = _L()
-        lib = L.load()
-        self.lib, self.sc_np, self.cam = lib, sc, cam
-        P, S, W, H = sc.P, sc.S, cam.image_width, cam.image_height
-        self.P, self.S, self.W, self.H = P, S, W, H
-        self.t = dict(bg=_dev(bg, np.float32), means3D=_dev(sc.means3D), shs=_dev(sc.shs), semantics=_dev(sc.semantics),
-                      opacity=_dev(sc.opacities), scales=_dev(sc.scales), rotations=_dev(sc.rotations),
-                      view=_dev(cam.world_view_transform), proj=_dev(cam.full_proj_transform), campos=_dev(cam.camera_center))
-        t = self.t
-        self.scene = _C._scene(P, S, H, W, t["bg"], t["means3D"], t["shs"], None, t["semantics"], t["opacity"], t["scales"],
-                               t["rotations"], 1.0, None, t["view"], t["proj"], cam.tanfovx, cam.tanfovy, sc.sh_degree, t["campos"],
-                               False, False)
-        f32 = dict(dtype=torch.float32, device=DEV)
-        self.color, self.semmap = torch.empty((3, H, W), **f32), torch.empty((S, H, W), **f32)
-        self.depth, self.alpha = torch.empty((H, W), **f32), torch.empty((H, W), **f32)
-        self.radii = torch.empty((P,), dtype=torch.int32, device=DEV)
-        self.geom = torch.empty(lib.goi_raster_geom_bytes(P), dtype=torch.uint8, device=DEV)
-        self.img = torch.empty(lib.goi_raster_image_bytes(W, H), dtype=torch.uint8, device=DEV)
-        alloc = _C._BinningAllocator(torch.device(DEV))
-        n = lib.goi_raster_forward(C.byref(self.scene), _ptr(self.geom), _ptr(self.img), alloc.cb, None, _ptr(self.color),
-                                   _ptr(self.semmap), _ptr(self.depth), _ptr(self.alpha), _ptr(self.radii), None)
-        if alloc.error is not None:
-            raise alloc.error
-        assert n >= 0, L.last_error()
-        self.N, self.binning = int(n), alloc.tensor
-        torch.cuda.synchronize()
+        super().__init__(sc, cam, bg, DEV)
+        lib, P, S, W, H = self.lib, self.P, self.S, self.W, self.H
         self.frame = self.quads = None
         if self.N == 0:
             return
-        v = {k: x.cpu().numpy() for k, x in _C.debug_views(P, W, H, self.N, self.geom, self.binning, self.img).items()}
+        v = {k: x.cpu().numpy() for k, x in self.views().items()}
         self.frame = BR.Frame(W, H, S, v["means2D"], v["conic_opacity"], v["rgb"], v["depths"], np.asarray(sc.semantics, np.float32),
                               v["point_list"].astype(np.uint32), v["ranges"].astype(np.uint32), v["n_contrib"].astype(np.uint32),
                               self.alpha.cpu().numpy().reshape(-1), np.asarray(bg, np.float32))
@@ -382,7 +355,7 @@ def test_per_tile_kernel_arrays():
 
 @pytest.mark.parametrize("name", ["S10", "S17", "huge-64x48", "stack-129"])
 def test_chain_link_rows_reduce_to_the_backward_outputs_bit_for_bit(name):
-    """bwd_records 0: dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic and dL_ddepth of goi_raster_backward3 are the
+    """bwd_records 0: dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic and dL_ddepth of goi_raster_backward are the
     dumped rows added up in reduce_rows_k's order (tests/reduce_rows_reference.py), bit for bit."""
     L = _L()
     lib = L.load()
@@ -402,10 +375,10 @@ def test_chain_link_rows_reduce_to_the_backward_outputs_bit_for_bit(name):
     before = dict(L.OPTIONS)
     try:
         L.set_option("bwd_records", 0)
-        r = lib.goi_raster_backward3(C.byref(df.scene), N, 0, 0, _ptr(df.geom), _ptr(df.binning), _ptr(df.img), _ptr(df.radii),
-                                     _ptr(df.alpha), *[_ptr(u) for u in ups],
-                                     *[_ptr(g[k]) for k in ("mean2D", "conic", "opacity", "color", "semantic", "depth", "mean3D", "cov3D",
-                                                            "sh", "scale", "rot")], _ptr(scratch), None, None)
+        r = lib.goi_raster_backward(C.byref(df.scene), N, 0, 0, _ptr(df.geom), _ptr(df.binning), _ptr(df.img), _ptr(df.radii),
+                                    _ptr(df.alpha), *[_ptr(u) for u in ups],
+                                    *[_ptr(g[k]) for k in ("mean2D", "conic", "opacity", "color", "semantic", "depth", "mean3D", "cov3D",
+                                                           "sh", "scale", "rot")], _ptr(scratch), None, None, None, None)
         assert r >= 0, L.last_error()
         torch.cuda.synchronize()
     finally:

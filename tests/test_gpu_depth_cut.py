@@ -1,4 +1,4 @@
-"""Speculative depth cut-off of the tile lists (include/goi_raster.h: goi_raster_forward_async_cut; _C._depth_cut_for).
+"""Speculative depth cut-off of the tile lists (include/goi_raster.h: goi_raster_forward_async, zcut_in / zcut_out; _C._depth_cut_for).
 
 A speculative training frame of a camera that was rendered before lists, per tile, only Gaussians up to the depth that camera's
 previous frame found worth listing.  What must hold:

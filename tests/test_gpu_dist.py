@@ -231,7 +231,7 @@ print("OK", rank, hits, dirty, fresh)
 def test_views_of_a_batch_in_flight_sum_to_the_serial_gradient(K, streams, on_device):
     """dist.backward_views: the K views of a multi-view batch alternate over several HIP streams of one GPU and the sum of their
     gradients lands in p.grad.  on_device (default): views 2, 3, ... of a stream ADD their per-Gaussian gradients to view 1's inside
-    the per-Gaussian backward kernel (goi_raster_backward3, GOI_BACKWARD_ACCUMULATE) and the sums go through the activations once:
+    the per-Gaussian backward kernel (goi_raster_backward, GOI_BACKWARD_ACCUMULATE) and the sums go through the activations once:
     the serial sum up to the association of fp32 additions.  on_device False: K dense sums of leaf gradients -- K = 2 on two
     streams is g0 + g1, bit-identical to two serial backward calls; with more views per stream (g0 + g2) + (g1 + g3).  The per-view
     outputs are those of the serial renders, bit for bit, either way."""
@@ -290,7 +290,7 @@ def test_views_of_a_batch_in_flight_sum_to_the_serial_gradient(K, streams, on_de
 
 @pytest.mark.gpu
 def test_accumulating_backward_adds_exactly_the_visible_rows():
-    """goi_raster_backward3 with GOI_BACKWARD_ACCUMULATE through the binding: the second view's call adds to the first view's
+    """goi_raster_backward with GOI_BACKWARD_ACCUMULATE through the binding: the second view's call adds to the first view's
     tensors -- equal to the sum of two plain calls to an ulp of the larger term, rows of Gaussians neither view sees stay exactly
     zero, and the pooled-buffer bookkeeping does not hand the accumulated buffer out as "zero rows known" afterwards."""
     import torch

@@ -1,4 +1,4 @@
-"""Gradient-buffer pool of the compiled binding (csrc/torch_binding.cpp; goi_raster_backward2 in include/goi_raster.h).
+"""Gradient-buffer pool of the compiled binding (csrc/torch_binding.cpp; goi_raster_backward, prev_radii / prev_mask, in include/goi_raster.h).
 
 The reference hands autograd eleven zero-filled [P, ..] tensors per backward (rasterize_points.cu:252-262).  The binding keeps the
 one allocation all outputs of a backward are views of and reuses it once nobody holds it and nothing wrote to it in place; the

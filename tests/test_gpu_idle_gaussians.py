@@ -1,4 +1,4 @@
-"""Visible Gaussians that reached no pixel skip the per-Gaussian backward (option bwd_skip_idle, goi_raster_backward4).
+"""Visible Gaussians that reached no pixel skip the per-Gaussian backward (option bwd_skip_idle; goi_raster_backward: row_mask).
 
 A listed Gaussian that sits behind the saturation front in every tile it touches owns slots but no valid row: its record is all +0
 and every gradient preprocess_bwd_k would form from it is zero.  The record-mode row reduction publishes one CONTRIBUTION byte per
@@ -18,6 +18,8 @@ import pytest
 import torch
 
 from goi_hyperplane_amd.scene import make_camera, make_clustered_scene, make_scene
+from tests import raw_frame
+from tests.raw_frame import ptr as _ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -88,41 +90,14 @@ def _assert_equal(got, want, what=""):
             assert torch.equal(a, b), (what, i)
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-class RawFrame:
-    """One exact forward through the C ABI with its workspaces kept, and goi_raster_backward4 on a scratch of the test's own."""
+class RawFrame(raw_frame.RawFrame):
+    """One exact forward through the C ABI with its workspaces kept, and goi_raster_backward on a scratch of the test's own."""
 
     def __init__(self, sc, cam, dev):
-        from goi_hyperplane_amd import _C, _lib
-        self.lib = lib = _lib.load()
-        P, S, W, H = sc.P, sc.S, cam.image_width, cam.image_height
-        self.P, self.S, self.W, self.H, self.dev, self.M = P, S, W, H, dev, int(np.asarray(sc.shs).shape[1])
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-        self.t = dict(bg=torch.zeros(3, device=dev), means3D=t(sc.means3D), shs=t(sc.shs), semantics=t(sc.semantics),
-                      opacity=t(sc.opacities), scales=t(sc.scales), rotations=t(sc.rotations), view=t(cam.world_view_transform),
-                      proj=t(cam.full_proj_transform), campos=t(cam.camera_center))
-        x = self.t
-        self.scene = _C._scene(P, S, H, W, x["bg"], x["means3D"], x["shs"], None, x["semantics"], x["opacity"], x["scales"],
-                               x["rotations"], 1.0, None, x["view"], x["proj"], cam.tanfovx, cam.tanfovy, sc.sh_degree, x["campos"],
-                               False, False)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.color, self.semmap = torch.empty((3, H, W), **f32), torch.empty((S, H, W), **f32)
-        self.depth, self.alpha = torch.empty((H, W), **f32), torch.empty((H, W), **f32)
-        self.radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        self.geom = torch.empty(lib.goi_raster_geom_bytes(P), dtype=torch.uint8, device=dev)
-        self.img = torch.empty(lib.goi_raster_image_bytes(W, H), dtype=torch.uint8, device=dev)
-        alloc = _C._BinningAllocator(dev)
-        n = lib.goi_raster_forward(C.byref(self.scene), _ptr(self.geom), _ptr(self.img), alloc.cb, None, _ptr(self.color),
-                                   _ptr(self.semmap), _ptr(self.depth), _ptr(self.alpha), _ptr(self.radii), None)
-        if alloc.error is not None:
-            raise alloc.error
-        assert n > 0, _lib.last_error()
-        self.N, self.binning = int(n), alloc.tensor
-        torch.cuda.synchronize()
-        self.tiles_touched = _C.debug_views(P, W, H, self.N, self.geom, self.binning, self.img)["tiles_touched"].cpu().numpy()
+        super().__init__(sc, cam, np.zeros(3, np.float32), dev)
+        assert self.N > 0, "the scene renders nothing"
+        self.M = int(np.asarray(sc.shs).shape[1])
+        self.tiles_touched = self.views()["tiles_touched"].cpu().numpy()
 
     def blend_flags(self, ups):
         """the backward blend alone (the default kernel: split-f16 flush, member masks) -> validity bytes [4 N], aux [P, 4]"""
@@ -147,7 +122,7 @@ class RawFrame:
         return flags.cpu().numpy(), aux.cpu().numpy().view(np.uint32)
 
     def backward(self, ups, masks=True):
-        """goi_raster_backward4 on outputs and a scratch filled with 0xFF -> (dict of the eleven arrays, contribution bytes [N]
+        """goi_raster_backward on outputs and a scratch filled with 0xFF -> (dict of the eleven arrays, contribution bytes [N]
         as they lie in the scratch, row mask [P] or None)"""
         from goi_hyperplane_amd import _lib
         lib, P, S, N, M = self.lib, self.P, self.S, self.N, self.M
@@ -157,7 +132,7 @@ class RawFrame:
         scratch = torch.full((lib.goi_raster_backward_scratch_bytes(N, S),), 0xFF, dtype=torch.uint8, device=self.dev)
         assert scratch.data_ptr() % 256 == 0
         mask = torch.full((P,), 0xEE, dtype=torch.uint8, device=self.dev) if masks else None
-        r = lib.goi_raster_backward4(
+        r = lib.goi_raster_backward(
             C.byref(self.scene), N, 0, 0, _ptr(self.geom), _ptr(self.binning), _ptr(self.img), _ptr(self.radii), _ptr(self.alpha),
             *[_ptr(u) for u in ups], *[_ptr(o[k]) for k in ("mean2D", "conic", "opacity", "color", "semantic", "depth", "mean3D",
                                                             "cov3D", "sh", "scale", "rot")],

@@ -1,4 +1,4 @@
-"""A per-Gaussian selection rendered IN PLACE (render(..., gaussian_mask=m, in_place=True); goi_raster_forward_selected;
+"""A per-Gaussian selection rendered IN PLACE (render(..., gaussian_mask=m, in_place=True); goi_raster_forward, keep / invert;
 DESIGN.md 4.18) against the yardstick: the index-select path render(..., gaussian_mask=m), which restates the reference's
 gui/gs_renderer.py:315-321 and is untouched by the selection.
 

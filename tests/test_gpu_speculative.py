@@ -517,7 +517,7 @@ def test_a_much_larger_image_starts_the_capacity_policy_over(dev):
 
 @pytest.mark.parametrize("P,S,W,H,mu", [(20000, 16, 400, 300, -3.3), (3000, 10, 160, 120, -2.8)])
 def test_row_scratch_is_sized_by_the_count_once_it_has_arrived(dev, P, S, W, H, mu):
-    """goi_raster_backward3: a speculative frame's workspaces are laid out for its CAPACITY, but the backward's row scratch (129
+    """goi_raster_backward, scratch_instances: a speculative frame's workspaces are laid out for its CAPACITY, but the backward's row scratch (129
     bytes per instance and quadrant: the largest workspace of a step) only has to hold the COUNT -- and the count has usually
     reached the host by the time the backward is enqueued.  The binding polls (no wait) and lays the scratch out for whichever
     is known: the gradients are bit-identical either way, and identical to those of an exact frame."""

@@ -1,8 +1,8 @@
-"""CPU-only checks of the in-place selection's surface (no GPU, no compute calls): the two C entry points are declared,
-exported and mirrored in the ctypes table; the ABI version is the same in the header, the loader and the compiled binding; the
-selection argument of GaussianRasterizer.forward is checked by the project's rules (wrong dtype: TypeError, wrong length or
-not contiguous: ValueError, a CPU tensor: RuntimeError -- never converted, never copied); and in_place=True without a mask is
-the plain call."""
+"""CPU-only checks of the in-place selection's surface (no GPU, no compute calls): the two forward entries declare, export and
+mirror in the ctypes table the selection pair (const uint8_t* keep, int invert) in front of the stream; the ABI version is the
+same in the header, the loader, the library and the compiled binding; the selection argument of GaussianRasterizer.forward is
+checked by the project's rules (wrong dtype: TypeError, wrong length or not contiguous: ValueError, a CPU tensor: RuntimeError --
+never converted, never copied); and in_place=True without a mask is the plain call."""
 import ctypes as C
 import os
 import re
@@ -11,7 +11,10 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRIES = ("goi_raster_forward_selected", "goi_raster_forward_async_selected")
+ENTRIES = ("goi_raster_forward", "goi_raster_forward_async")
+# ABI 9 folded these into ENTRIES, goi_raster_ticket_result and goi_raster_backward
+REMOVED = ("goi_raster_forward_selected", "goi_raster_forward_async_selected", "goi_raster_forward_async_cut",
+           "goi_raster_ticket_result2", "goi_raster_backward2", "goi_raster_backward3", "goi_raster_backward4")
 
 
 @pytest.fixture(scope="module")
@@ -26,30 +29,34 @@ def _header():
     return open(os.path.join(ROOT, "include", "goi_raster.h")).read()
 
 
-def test_header_declares_the_selected_entries():
+def test_header_declares_the_selection_of_both_forwards():
     hdr = _header()
-    for name, plain in zip(ENTRIES, ("goi_raster_forward", "goi_raster_forward_async")):
+    for name in ENTRIES:
         decl = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, hdr)
-        base = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % plain, hdr)
-        assert decl and base, name
-        args, args0 = [" ".join(a.split()) for a in decl.group(1).split(",")], [" ".join(a.split()) for a in base.group(1).split(",")]
-        # the plain entry's parameters, with (const uint8_t* keep, int invert) in front of the stream
-        assert args == args0[:-1] + ["const uint8_t* keep", "int invert"] + args0[-1:], name
+        assert decl, name
+        args = [" ".join(a.split()) for a in decl.group(1).split(",")]
+        # (const uint8_t* keep, int invert) immediately in front of the stream
+        assert args[-3:] == ["const uint8_t* keep", "int invert", "void* stream"], name
+    for name in REMOVED:
+        assert not re.search(r"\b%s\s*\(" % name, hdr), name
 
 
 def test_ctypes_table_has_their_signatures_and_the_library_exports_them(lib):
     from goi_hyperplane_amd import _lib
-    for name, plain in zip(ENTRIES, ("goi_raster_forward", "goi_raster_forward_async")):
+    for name in ENTRIES:
         res, args = _lib.SYMBOLS[name]
-        res0, args0 = _lib.SYMBOLS[plain]
-        assert res is C.c_int and args == args0[:-1] + [C.c_void_p, C.c_int] + args0[-1:], name
+        assert res is C.c_int and args[-3:] == [C.c_void_p, C.c_int, C.c_void_p], name
         assert getattr(lib, name).argtypes == args
+    for name in REMOVED:
+        assert name not in _lib.SYMBOLS and not hasattr(lib, name), name
 
 
 def test_abi_version_is_consistent(lib):
     from goi_hyperplane_amd import _C, _lib
     version = int(re.search(r"#define GOI_RASTER_ABI_VERSION (\d+)", _header()).group(1))
-    assert version >= 8 and re.search(r"/\* %d: \+ goi_raster_forward_selected, goi_raster_forward_async_selected" % 8, _header())
+    assert version == 9
+    line9 = re.search(r"/\* 9: (.*?)\n \* 8: ", _header(), re.S)
+    assert line9 and all(re.search(r"\b%s\b" % name, line9.group(1)) for name in REMOVED)
     assert _lib.ABI_VERSION == version == lib.goi_raster_abi_version()
     _C.set_binding("compiled")
     ext = _C._ext()
