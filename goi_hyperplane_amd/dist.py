@@ -440,6 +440,29 @@ def allreduce_gradients_sh_factored_async(params, sh_leaves, means3D, factor, di
     return h
 
 
+# operands (means3D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp) <- positions of their gradients in
+# the op's result (dL_dmeans2D, dL_dcolors, dL_dsemantics, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
+_OPERAND_GRADIENT = (4, 6, 1, 2, 3, 7, 8, 5)
+
+
+def accumulated_gradients(state, params):
+    """The last step of a multi-view batch (rasterizer.accumulate_gradients): from the rasterizer's gradients, summed on the device
+    in `state["grads"]`, to the gradients of `params` -- ONE pass through whatever produced the operands of the batch's last view
+    (`state["inputs"]`: the activations of the parameters), which must still hold its graph: a per-view
+    `torch.autograd.grad(outputs, params, ...)` inside the batch needs retain_graph=True, or it frees what those nodes saved.
+    Returns a list with one entry per parameter: its gradient, or None where the operands do not depend on it (or where nothing
+    was accumulated: a batch whose backwards all took a mode that does not accumulate)."""
+    params = list(params)
+    grads, inputs = state.get("grads"), state.get("inputs")
+    if grads is None or inputs is None or not params:
+        return [None] * len(params)
+    pairs = [(inp, grads[j]) for inp, j in zip(inputs, _OPERAND_GRADIENT)
+             if torch.is_tensor(inp) and inp.requires_grad and grads[j] is not None and grads[j].numel() == inp.numel()]
+    if not pairs:
+        return [None] * len(params)
+    return list(torch.autograd.grad([a for a, _b in pairs], params, [b.view_as(a) for a, b in pairs], allow_unused=True))
+
+
 # ---- a multi-view batch on ONE rank: the K views of a rank's share of a batch, in flight on several HIP streams -----------------
 _VIEW_STREAMS = {}  # (device index, n) -> list of side streams (created once: a stream owns its allocator pool and its scratch)
 
@@ -482,7 +505,13 @@ def backward_views(views, render_view, upstream, params, streams: int = 1, accum
     through the activations ONCE instead of K times.  The result equals the serial sum up to the association of fp32 additions
     (tests/test_gpu_dist.py).  Gradients that do not come through the rasterizer, and backward modes that do not accumulate
     (semantics-only, factored, ctypes binding), are summed as leaf gradients, per stream in view order, then in stream order.
-    Returns the list of per-view outputs (detached)."""
+    Returns the list of per-view outputs (detached).
+
+    `viewspace_points` (the screen-space gradient sink of each returned dictionary; returned as the leaf it is, every other tensor
+    detached): with on_device=False its `.grad` is what the serial backward of that view leaves there.  With on_device=True the
+    accumulating backward hands autograd no gradient, so every returned `viewspace_points.grad` is None (the summed dL/dmeans2D of the batch is `state["grads"][0]` of
+    rasterizer.accumulate_gradients for a caller who runs the protocol by hand); a loop that feeds densification statistics from
+    it uses on_device=False."""
     import contextlib
 
     from . import rasterizer
@@ -498,7 +527,6 @@ def backward_views(views, render_view, upstream, params, streams: int = 1, accum
     # that ran on, so the accumulating kernels never meet -- what overlaps is view k + 1's forward (front end, forward blend) with
     # view k's backward; no per-stream sums to add at the end, one zero-fill per batch.
     shared = dict(grads=None, inputs=None, views=0)
-    states = [shared if on_device else dict(grads=None, inputs=None, views=0) for _ in range(n)]
     bwd_done = None
     outs = [None] * len(views)
     for s_ in side:
@@ -507,13 +535,20 @@ def backward_views(views, render_view, upstream, params, streams: int = 1, accum
     for k, view in enumerate(views):
         si = k % n
         with torch.cuda.stream(side[si]):
-            ctx = rasterizer.accumulate_gradients(states[si]) if on_device else contextlib.nullcontext()
+            ctx = rasterizer.accumulate_gradients(shared) if on_device else contextlib.nullcontext()
             with ctx:
                 out = render_view(view)
                 tensors, grads = upstream(out, k)
                 if on_device and n > 1 and bwd_done is not None:
                     side[si].wait_event(bwd_done)
-                g = torch.autograd.grad(tensors, params, grads, allow_unused=True)
+                # on_device: the accumulating backward hands autograd nothing, and a walk with undefined gradients still frees what
+                # the nodes between the parameters and the operands (exp, sigmoid, normalize, cat, the mask product) saved -- which
+                # the pass at the batch's end needs.  The graph is kept here and dies with the view's outputs, below.
+                # (the leaves among the view's outputs -- render()'s screen-space sink -- receive their gradient as from backward())
+                sinks = [(key, v) for key, v in out.items() if torch.is_tensor(v) and v.is_leaf and v.requires_grad]
+                g = torch.autograd.grad(tensors, params + [v for _key, v in sinks], grads, allow_unused=True,
+                                        retain_graph=bool(on_device))
+                g, g_sinks = g[:len(params)], g[len(params):]
                 if on_device and n > 1:
                     bwd_done = torch.cuda.Event()
                     bwd_done.record(side[si])
@@ -530,36 +565,25 @@ def backward_views(views, render_view, upstream, params, streams: int = 1, accum
                     # (out of place: a gradient may be a view of the rasterizer's pooled buffer)
                     sums[si][i] = t if sums[si][i] is None else sums[si][i] + t
             outs[k] = {key: (v.detach() if torch.is_tensor(v) else v) for key, v in out.items()}
-            for t in g:  # the caching allocator must not hand these blocks to another stream before this one is done with them
+            for (key, v), t in zip(sinks, g_sinks):
+                outs[k][key] = v  # (a leaf: no graph behind it)
+                v.grad = t
+            for t in g + g_sinks:  # the caching allocator must not hand these blocks to another stream before this one is done with them
                 if t is not None and side[si] is not cur:
                     t.record_stream(side[si])
+                    t.record_stream(cur)
+            # the view's graph -- the rasterizer's node with the frame's workspaces -- goes now, not when the next view has rendered;
+            # the graph from the parameters to the last view's operands stays alive through shared["inputs"]
+            del out, tensors, grads, g, g_sinks
     for s_ in side:
         if s_ is not cur:
             cur.wait_stream(s_)
-    # ---- the rasterizer's gradients, summed on the device per stream: add the streams' sums, then through the activations once
-    op_total, op_inputs = None, None
-    for si in range(n):
-        st = states[si]
-        if st["grads"] is None or (on_device and si > 0):  # (on_device: the one shared sum)
-            continue
-        if side[si] is not cur:
-            for t in st["grads"]:
-                if t is not None:
-                    t.record_stream(cur)
-        if op_total is None:
-            op_total, op_inputs = list(st["grads"]), st["inputs"]
-        else:
-            for i, t in enumerate(st["grads"]):
-                if t is not None and op_total[i] is not None:
-                    op_total[i].add_(t)
-    from_op = [None] * len(params)
-    if op_total is not None:
-        # operands (means3D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp) <- positions of their
-        # gradients in the op's result (dL_dmeans2D, dL_dcolors, dL_dsemantics, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, ...)
-        pairs = [(inp, op_total[j]) for inp, j in zip(op_inputs, (4, 6, 1, 2, 3, 7, 8, 5))
-                 if torch.is_tensor(inp) and inp.requires_grad and op_total[j] is not None and op_total[j].numel() == inp.numel()]
-        if pairs:
-            from_op = torch.autograd.grad([a_ for a_, _b in pairs], params, [b_.view_as(a_) for a_, b_ in pairs], allow_unused=True)
+    # ---- the rasterizer's gradients, summed on the device (on_device: the one sum all streams shared), through the activations once
+    if shared["grads"] is not None and n > 1:
+        for t in shared["grads"]:
+            if t is not None:
+                t.record_stream(cur)
+    from_op = accumulated_gradients(shared, params)
     for i, p in enumerate(params):
         tot = from_op[i]
         for si in range(n):

@@ -307,8 +307,12 @@ class accumulate_gradients:
     gradient; `state` collects {"grads": the nine tensors in the op's order (dL_dmeans2D, dL_dcolors, dL_dsemantics, dL_dopacity,
     dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations), "inputs": the operands of the last call (means3D, sh,
     colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp), "views": how many views are summed}.  The caller
-    back-propagates the sums through whatever produced the operands (the activations), once.  Valid only while the parameters do
-    not change between the views of the batch.  One batch at a time per process; the semantics-only, factored and debug
+    back-propagates the sums through whatever produced the operands (the activations), once: dist.accumulated_gradients(state,
+    params).  That pass walks the graph between the parameters and the LAST view's operands, so a per-view
+    `torch.autograd.grad(outputs, params, ...)` inside the context must pass retain_graph=True (without it the walk, although it
+    carries no gradient, frees what exp / sigmoid / normalize / cat saved, and the final pass raises "backward through the graph a
+    second time").  The screen-space sink gets nothing either: `viewspace_points.grad` of a view rendered in here stays None; the
+    batch's summed dL/dmeans2D is state["grads"][0].  Valid only while the parameters do not change between the views of the batch.  One batch at a time per process; the semantics-only, factored and debug
     backwards, and the ctypes binding, do not accumulate (they return gradients as usual: state["views"] stays put)."""
 
     def __init__(self, state: dict):

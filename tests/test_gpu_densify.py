@@ -319,20 +319,8 @@ def test_add_densification_stats_without_a_host_sync(dev):
 
 
 def _scene_model(dev, P=20000, seed=4):
-    from goi_hyperplane_amd.scene import make_scene
-    sc = make_scene(P, S=16, seed=seed, log_scale_mean=-3.0)
-    m = ref.Model()
-    t = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device=dev)  # noqa: E731
-    op = np.clip(sc.opacities, 1e-4, 1 - 1e-4)
-    raw = {"_xyz": t(sc.means3D), "_scaling": torch.log(t(sc.scales)), "_rotation": t(sc.rotations),
-           "_opacity": t(np.log(op / (1 - op))), "_features_dc": t(sc.shs[:, :1]), "_features_rest": t(sc.shs[:, 1:]),
-           "_semantics": t(sc.semantics)}
-    for attr, v in raw.items():
-        setattr(m, attr, nn.Parameter(v.contiguous()))
-    m.xyz_gradient_accum = torch.zeros(P, 1, device=dev)
-    m.denom = torch.zeros(P, 1, device=dev)
-    m.max_radii2D = torch.zeros(P, device=dev)
-    return m
+    from tests import activated_model
+    return activated_model.make(dev, P, S=16, seed=seed, rotation_norm=None, log_scale_mean=-3.0)
 
 
 def test_goi_delete_and_extract_render_as_the_gaussian_mask(dev):

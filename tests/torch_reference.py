@@ -196,3 +196,22 @@ def float64_gradients(sc, cam, bg, upstream, sh_degree):
     return dict(means3D=inp["means3D"].grad.numpy(), opacity=inp["opacities"].grad.numpy(),
                 semantics=inp["semantics"].grad.numpy(), means2D=sink.grad.numpy(), sh=inp["shs"].grad.numpy(),
                 scales=inp["scales"].grad.numpy(), rotations=inp["rotations"].grad.numpy())
+
+
+def float64_raw_gradients(raw, cam, bg, upstream, sh_degree, dtype=torch.float64):
+    """float64_gradients one level up: gradients with respect to the reference GaussianModel's RAW parameters (`raw`: {"_xyz",
+    "_scaling", "_rotation", "_opacity", "_features_dc", "_features_rest", "_semantics"} as arrays), through the activations the
+    model applies before the rasterizer (scene/gaussian_model.py:90-117: exp, normalize, sigmoid, cat) evaluated in `dtype` too.
+    dtype=torch.float32 is the yardstick's own error: the same restatement in the precision of the implementation under test."""
+    import numpy as np
+    T = lambda a: torch.tensor(np.asarray(a), dtype=dtype)  # noqa: E731
+    p = {k: T(v).requires_grad_() for k, v in raw.items()}
+    r = render(means3D=p["_xyz"], opacities=torch.sigmoid(p["_opacity"]), semantics=p["_semantics"],
+               shs=torch.cat((p["_features_dc"], p["_features_rest"]), dim=1), scales=torch.exp(p["_scaling"]),
+               rotations=torch.nn.functional.normalize(p["_rotation"]), viewmatrix=T(cam.world_view_transform),
+               projmatrix=T(cam.full_proj_transform), campos=T(cam.camera_center), tan_fovx=cam.tanfovx, tan_fovy=cam.tanfovy,
+               W=cam.image_width, H=cam.image_height, bg=T(bg), sh_degree=sh_degree)
+    gc, gs, gd, ga = upstream
+    loss = (r["color"] * T(gc)).sum() + (r["semantic"] * T(gs)).sum() + (r["depth"] * T(gd)).sum() + (r["alpha"] * T(ga)).sum()
+    loss.backward()
+    return {k: v.grad.numpy() for k, v in p.items()}
