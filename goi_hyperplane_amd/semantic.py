@@ -495,7 +495,7 @@ def fit_hyperplane(sem_chw: torch.Tensor, mlp: SemanticModel, lut: torch.Tensor,
 def select_gaussians(pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float = 0.5) -> torch.Tensor:
     """The Gaussians of interest (gui/main.py:400-405, compute_relative_gs_index): the fused decode of every Gaussian's
     own semantic feature pc.get_semantics [P, S], scored by score_fn and thresholded; bool [P], ready for
-    render(..., gaussian_mask=...)."""
+    render(..., gaussian_mask=...).  (It also returns Gaussians no camera shows: contrib.lift_mask selects by the blend instead.)"""
     sem = pc.get_semantics.detach().float().t().contiguous()  # [S, P]: the decode's channel-major layout, one "pixel" per Gaussian
     return compute_similarity(sem, mlp, lut, score_fn, thresh) > 0
 
@@ -522,7 +522,8 @@ def group_points(pc, selected: torch.Tensor, viewpoint_camera, bg_color: torch.T
     accumulated on the device: host synchronisations are the index gather of `selected` and dbscan's one read of the
     cluster count, none per cluster.  With rasterizer.set_geometry_cache on, the K renders of one camera share the
     geometry: renders 2..K are blend-only.  in_place / mask_invert: how gaussian_mask is applied (render.render): handed to
-    the rasterizer as a selection instead of index-selecting the model for every cluster's render -- the same result."""
+    the rasterizer as a selection instead of index-selecting the model for every cluster's render -- the same result.
+    (contrib.lift_mask lifts res_mask, or the masks of several views, onto the Gaussians directly, without clustering.)"""
     from . import cluster
     from .render import render_gui
 

@@ -53,7 +53,8 @@ extern "C" {
  *    goi_raster_forward_async, goi_raster_ticket_result and goi_raster_backward take the widest parameter list there was, and the
  *    seven names that carried the history are REMOVED: goi_raster_forward_selected, goi_raster_forward_async_selected,
  *    goi_raster_forward_async_cut, goi_raster_ticket_result2, goi_raster_backward2, goi_raster_backward3, goi_raster_backward4;
- *    goi_raster_forward_async refuses a selection together with a depth cut
+ *    goi_raster_forward_async refuses a selection together with a depth cut;
+ *    later additions: goi_raster_contrib_votes
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -776,6 +777,21 @@ int goi_raster_blend_stats(int P, int W, int H, int R, const void* geom_buffer, 
  * A truncated frame (goi_raster_truncated_flag) merges nothing into peak and writes -1 / 0; so does R == 0, without a launch. */
 int goi_raster_contrib_frame(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
                              const void* image_buffer, float* peak, int* top_id, float* top_w, void* stream);
+
+/* Lifts a 2D label map onto the Gaussians by exact blend-weight votes: the same replay as goi_raster_contrib_frame, and for
+ * every pair that CONTRIBUTES to a pixel inside the image (both guards passed on a live pixel and T (1 - alpha) >= 1e-4; the
+ * pair that ended a pixel added nothing to the picture and is excluded, which also makes the sums those of the backward with a
+ * one-hot upstream) with l = labels[pixel] in [0, K):
+ *     votes[id * K + l] += q,   q = w * 2^24 rounded half-to-even to an integer,  w = alpha * T
+ * (the product is exact in fp32; w >= 1e-4 / 255 > 2^-25, so q >= 1: a Gaussian's total is non-zero exactly when it contributed
+ * to a validly labelled pixel).  One vote unit is 2^-24 of a pixel's full weight.
+ *   labels [H*W] int32, DEVICE: any value outside [0, K) (negative, K, INT_MAX ...) is ignored -- the "don't know" band.
+ *   votes  [P*K] int64, DEVICE: ADDED TO on `stream` (zero it once, sweep any number of views and label maps).  Integer sums
+ *          by 64-bit integer atomics, one per (8x8 quadrant, Gaussian, label) after a wave sum: the same bits in any order.
+ * R / the three buffers: as for goi_raster_contrib_frame.  A truncated frame adds nothing; so does R == 0, without a launch. */
+int goi_raster_contrib_votes(int P, int W, int H, int R, const void* geom_buffer, const void* binning_buffer,
+                             const void* image_buffer, const int* labels /*[H*W]*/, int K,
+                             int64_t* votes /*[P*K], added to*/, void* stream);
 
 /* Inspection of the opaque workspaces (tests only): copies device -> caller DEVICE buffers.
  * Any pointer may be NULL.  point_list is in final sorted order. */
