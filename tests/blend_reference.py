@@ -567,15 +567,18 @@ def pooled_stats(S_list, err_list) -> dict:
 
 
 # The YARDSTICK's normalised error |x - f64| / M per element class -- (median, 99th percentile, maximum), pooled over the 47 runs of
-# tests/blend_cases.py::all_runs() -- measured on the CPU with tools/blend_yardstick.py (float32 direct-form alphas standing in for
-# the device's): docs/MEASUREMENT_LOG.md, "Direct test of the blend kernels".  The gate is 4 x the first two and 16 x the third
-# (check_gate, element_tolerance): the 4 x covers the 2^-22 per product of the split operands against fp32's 2^-24.
+# tests/blend_cases.py::all_runs() and the 32 frames of tests/channel_count_cases.py -- measured on the CPU with
+# tools/blend_yardstick.py --all (float32 direct-form alphas standing in for the device's): docs/MEASUREMENT_LOG.md, "Direct test of
+# the blend kernels" and "Every semantic width 1..32 through the frame kernels" (the figures over the 47 runs alone, which stood
+# here before the 32 frames existed, are kept there; the three maxima did not move, so no element's tolerance did).  The gate is
+# 4 x the first two and 16 x the third (check_gate, element_tolerance): the 4 x covers the 2^-22 per product of the split operands
+# against fp32's 2^-24.
 GATE = {
-    "features": (0.406 * U, 3.801 * U, 39.316 * U),
-    "colour_depth": (0.394 * U, 3.572 * U, 36.859 * U),
-    "mean2D": (0.043 * U, 0.599 * U, 4.899 * U),
-    "conic": (0.055 * U, 0.602 * U, 4.832 * U),
-    "opacity": (0.082 * U, 1.207 * U, 7.054 * U),
+    "features": (0.451 * U, 3.825 * U, 39.316 * U),
+    "colour_depth": (0.442 * U, 3.682 * U, 36.859 * U),
+    "mean2D": (0.044 * U, 0.544 * U, 4.899 * U),
+    "conic": (0.054 * U, 0.569 * U, 4.832 * U),
+    "opacity": (0.094 * U, 1.155 * U, 7.054 * U),
 }
 
 

@@ -7,6 +7,9 @@ import numpy as np
 import torch
 
 
+GUARD = 64  # floats: 256 bytes, so that what lies between two guard bands keeps the allocation's alignment
+
+
 def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -29,7 +32,9 @@ class RawFrame:
                                x["rotations"], 1.0, None, x["view"], x["proj"], cam.tanfovx, cam.tanfovy, sc.sh_degree, x["campos"],
                                False, False)
         f32 = dict(dtype=torch.float32, device=dev)
-        self.color, self.semmap = torch.empty((3, H, W), **f32), torch.empty((S, H, W), **f32)
+        # (the semantic map sits between two NaN guard bands of GUARD floats: a channel written beyond the S-th is seen)
+        self.semmap_guarded = torch.full((S * H * W + 2 * GUARD,), float("nan"), **f32)
+        self.color, self.semmap = torch.empty((3, H, W), **f32), self.semmap_guarded[GUARD:GUARD + S * H * W].view(S, H, W)
         self.depth, self.alpha = torch.empty((H, W), **f32), torch.empty((H, W), **f32)
         self.radii = torch.empty((P,), dtype=torch.int32, device=dev)
         self.geom = torch.empty(lib.goi_raster_geom_bytes(P), dtype=torch.uint8, device=dev)

@@ -32,6 +32,11 @@ semantic-only rows and the per-tile kernel's per-id arrays on a subset.
 CHAIN LINK.  At bwd_records 0 the per-id outputs of the ordinary backward equal, bit for bit, the dumped rows added up in the order of
 tests/reduce_rows_reference.py: the three direct tests (blend rows, row reduction, per-Gaussian backward) meet.
 
+EVERY SEMANTIC WIDTH.  The frame of tests/channel_count_cases.py at each S = 1..32 (every S4 instantiation, the 16-byte and the
+scalar row path, 1 and 2 accumulator blocks, rows of 16 / 32 / 48 floats): pair evaluation, forward and default rows at every width;
+the other forms of the row kernel, the semantic-only rows in all four forms and the per-tile kernel at 4 S4 - 1 and 4 S4; the chain
+link and the record paths (bwd_records 1, 2 against 0) at every width.  Same reference, same tolerances.
+
 Nothing here is built to make a kernel fault: every frame is a valid forward of the product.
 """
 from __future__ import annotations
@@ -47,6 +52,7 @@ import torch
 
 from tests import blend_cases as BC
 from tests import blend_reference as BR
+from tests import channel_count_cases as CC
 from tests import raw_frame
 from tests import reduce_rows_reference as RR
 from tests.raw_frame import ptr as _ptr
@@ -274,13 +280,17 @@ def test_forward_and_default_backward_rows_on_every_case():
 SUBSET = ("S3", "S16", "S17", "ragged-123x77", "huge-64x48", "stack-33", "stack-129", "opaque-65")
 
 
-@pytest.mark.parametrize("mode,what", [(1, "exact-fp32 flush"), (2, "candidate testing"), (3, "exact-fp32 flush, candidate testing")])
-def test_other_forms_of_the_row_kernel(mode, what):
-    pooled_S, pooled_e = [], []
-    for name in SUBSET:
+def _subset_cases(names=SUBSET):
+    """(tag, scene, frame, upstream gradients) of the named row cases under random gradients"""
+    for name in names:
         sc, cam = BC.ROW_CASES[name]()
         up, bg = BC.upstream("random", sc.S, cam.image_height, cam.image_width, name)
-        df = _frame(name, bg)
+        yield name, sc, _frame(name, bg), up
+
+
+def _other_form(mode, what, cases, key):
+    pooled_S, pooled_e = [], []
+    for name, sc, df, up in cases:
         fr, qd = df.frame, df.quads
         out = df.blend(mode, up)
         ref = BR.backward_rows(fr, qd, up, df.E, df.al, df.hit)
@@ -296,39 +306,41 @@ def test_other_forms_of_the_row_kernel(mode, what):
             a, b = _rows_of(d, slots[ref.member], ncol), _rows_of(out, slots[ref.member], ncol)
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"{name}: bwd_masks 0 and 1 differ"
     pooled = BR.pooled_stats(pooled_S, pooled_e)
-    STATS[f"pooled/mode{mode}"] = {c: [x / BR.U for x in v[:3]] + [v[3]] for c, v in pooled.items()}
-    print(what, STATS[f"pooled/mode{mode}"])
+    STATS[key] = {c: [x / BR.U for x in v[:3]] + [v[3]] for c, v in pooled.items()}
+    print(what, STATS[key])
     BR.check_gate(pooled, BR.GATE, f"{what}: ")
 
 
-def test_semantic_only_rows():
-    """render_bwd_sem_k: rows of the padded semantic channels alone, same slots, same validity bytes, the feature tolerance."""
-    for name in SUBSET:
-        sc, cam = BC.ROW_CASES[name]()
-        up, bg = BC.upstream("random", sc.S, cam.image_height, cam.image_width, name)
-        df = _frame(name, bg)
+OTHER_FORMS = [(1, "exact-fp32 flush"), (2, "candidate testing"), (3, "exact-fp32 flush, candidate testing")]
+
+
+@pytest.mark.parametrize("mode,what", OTHER_FORMS)
+def test_other_forms_of_the_row_kernel(mode, what):
+    _other_form(mode, what, _subset_cases(), f"pooled/mode{mode}")
+
+
+def _semantic_only_rows(cases, modes):
+    for name, sc, df, up in cases:
         fr, qd = df.frame, df.quads
         n = BR.nsem_of(sc.S)
         ref = BR.backward_rows(fr, qd, dict(sem=up["sem"]), df.E, df.al, df.hit)
-        for mode in (4, 5):
+        for mode in modes:
             out = df.blend(mode, dict(sem=up["sem"]))
             slots = BR.slots_reference(fr, qd, out["aux"])
             BR.check_flags(slots, ref.member, out["flags"], df.N)
             got = np.zeros((qd.npairs, n + 10), np.float32)
             got[ref.member, :n] = _rows_of(out, slots[ref.member], n)
             got[ref.member, n:] = ref.rows[ref.member, n:]  # (not produced by this kernel)
-            BR.check_rows(sc.S, qd, ref, got, BR.GATE, f"{name}/mode {mode}", split=mode == 4)
+            BR.check_rows(sc.S, qd, ref, got, BR.GATE, f"{name}/mode {mode}", split=(mode & 1) == 0)
 
 
-def test_per_tile_kernel_arrays():
-    """render_bwd_tile_k: the six per-id arrays against the per-Gaussian float64 sums of the reference's rows.  The kernel adds the
-    quadrants' partial sums with atomics (any order) and expands its moments around the TILE centre (|u|, |v| <= 7.5): an element
-    may be off by the sum of its rows' tolerances, the moment-derived ones by 4.6 times that ((7.5 / 3.5)^2 < 4.6: the squares of the
-    basis; the companions here carry the quadrant-centred basis)."""
-    for name in ("S3", "S16", "ragged-123x77", "stack-33"):
-        sc, cam = BC.ROW_CASES[name]()
-        up, bg = BC.upstream("random", sc.S, cam.image_height, cam.image_width, name)
-        df = _frame(name, bg)
+def test_semantic_only_rows():
+    """render_bwd_sem_k: rows of the padded semantic channels alone, same slots, same validity bytes, the feature tolerance."""
+    _semantic_only_rows(_subset_cases(), (4, 5))
+
+
+def _per_tile_arrays(cases):
+    for name, sc, df, up in cases:
         fr, qd = df.frame, df.quads
         out = df.blend(8, up)
         ref = BR.backward_rows(fr, qd, up, df.E, df.al, df.hit)
@@ -343,6 +355,7 @@ def test_per_tile_kernel_arrays():
         tol += (nrows[:, None] + 4) * BR.U * mag  # (the atomic additions themselves)
         emap, _ = RR.element_map(sc.S, 0, BR.row_floats(sc.S))
         arrays = {k: out[k].reshape(fr.P, -1) for k in ("mean2D", "conic", "opacity", "color", "semantic", "depth")}
+        assert arrays["semantic"].shape == (fr.P, sc.S)
         for el in range(n + 10):
             if emap[el] is None:
                 continue
@@ -353,19 +366,22 @@ def test_per_tile_kernel_arrays():
         assert not arrays["mean2D"][:, 2].any() and not arrays["conic"][:, 2].any()
 
 
-@pytest.mark.parametrize("name", ["S10", "S17", "huge-64x48", "stack-129"])
-def test_chain_link_rows_reduce_to_the_backward_outputs_bit_for_bit(name):
-    """bwd_records 0: dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic and dL_ddepth of goi_raster_backward are the
-    dumped rows added up in reduce_rows_k's order (tests/reduce_rows_reference.py), bit for bit."""
+def test_per_tile_kernel_arrays():
+    """render_bwd_tile_k: the six per-id arrays against the per-Gaussian float64 sums of the reference's rows.  The kernel adds the
+    quadrants' partial sums with atomics (any order) and expands its moments around the TILE centre (|u|, |v| <= 7.5): an element
+    may be off by the sum of its rows' tolerances, the moment-derived ones by 4.6 times that ((7.5 / 3.5)^2 < 4.6: the squares of the
+    basis; the companions here carry the quadrant-centred basis)."""
+    _per_tile_arrays(_subset_cases(("S3", "S16", "ragged-123x77", "stack-33")))
+
+
+_GRAD_NAMES = ("mean2D", "conic", "opacity", "color", "semantic", "depth", "mean3D", "cov3D", "sh", "scale", "rot")
+
+
+def _raw_backward(df, sc, up, records):
+    """goi_raster_backward of the frame at bwd_records `records`, every output NaN before the call -> dict of host arrays"""
     L = _L()
     lib = L.load()
-    sc, cam = BC.ROW_CASES[name]()
-    up, bg = BC.upstream("random", sc.S, cam.image_height, cam.image_width, name)
-    df = _frame(name, bg)
-    fr, qd = df.frame, df.quads
     P, S, N = df.P, df.S, df.N
-    out = df.blend(0, up)
-    rf = BR.row_floats(S)
     M = sc.shs.shape[1]
     shapes = dict(mean2D=(P, 3), conic=(P, 4), opacity=(P,), color=(P, 3), semantic=(P, S), depth=(P,), mean3D=(P, 3), cov3D=(P, 6),
                   sh=(P, M, 3), scale=(P, 3), rot=(P, 4))
@@ -374,22 +390,134 @@ def test_chain_link_rows_reduce_to_the_backward_outputs_bit_for_bit(name):
     ups = [_dev(up[k]) for k in ("color", "sem", "depth", "alpha")]
     before = dict(L.OPTIONS)
     try:
-        L.set_option("bwd_records", 0)
+        L.set_option("bwd_records", records)
         r = lib.goi_raster_backward(C.byref(df.scene), N, 0, 0, _ptr(df.geom), _ptr(df.binning), _ptr(df.img), _ptr(df.radii),
-                                    _ptr(df.alpha), *[_ptr(u) for u in ups],
-                                    *[_ptr(g[k]) for k in ("mean2D", "conic", "opacity", "color", "semantic", "depth", "mean3D", "cov3D",
-                                                           "sh", "scale", "rot")], _ptr(scratch), None, None, None, None)
+                                    _ptr(df.alpha), *[_ptr(u) for u in ups], *[_ptr(g[k]) for k in _GRAD_NAMES], _ptr(scratch),
+                                    None, None, None, None)
         assert r >= 0, L.last_error()
         torch.cuda.synchronize()
     finally:
         L.set_option("bwd_records", before.get("bwd_records", 1))
+    return {k: g[k].cpu().numpy() for k in _GRAD_NAMES}
+
+
+def _chain_link(df, sc, up):
+    """-> the outputs of the ordinary backward at bwd_records 0, checked against the dumped rows of the default blend"""
+    fr = df.frame
+    P, S, N = df.P, df.S, df.N
+    out = df.blend(0, up)
+    g = _raw_backward(df, sc, up, 0)
     count = np.bincount(fr.point_list.astype(np.int64), minlength=P)
     first = out["aux"][:, 0].astype(np.int64)
     listed = np.flatnonzero(count)
     order = listed[np.argsort(first[listed], kind="stable")]
     frm = RR.Frame(P, S, N, N, order.astype(np.uint32), first[order].astype(np.uint32), count.astype(np.uint32), out["flags"], 0)
-    K = RR.kernel_constants()
-    ref = RR.frame_reference(frm, K)
+    ref = RR.frame_reference(frm, RR.kernel_constants())
     exp = RR.expected_sums(ref, out["rows"][ref.slots])
-    arrays = {k: g[k].cpu().numpy() for k in ("mean2D", "conic", "opacity", "color", "semantic", "depth")}
-    RR.check_arrays(arrays, frm, ref, exp, 0, rf)
+    RR.check_arrays({k: g[k] for k in ("mean2D", "conic", "opacity", "color", "semantic", "depth")}, frm, ref, exp, 0, BR.row_floats(S))
+    return g
+
+
+@pytest.mark.parametrize("name", ["S10", "S17", "huge-64x48", "stack-129"])
+def test_chain_link_rows_reduce_to_the_backward_outputs_bit_for_bit(name):
+    """bwd_records 0: dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantic and dL_ddepth of goi_raster_backward are the
+    dumped rows added up in reduce_rows_k's order (tests/reduce_rows_reference.py), bit for bit."""
+    (_name, sc, df, up), = _subset_cases((name,))
+    _chain_link(df, sc, up)
+
+
+# ---- every semantic width S = 1..32 (tests/channel_count_cases.py) ---------------------------------------------------------------
+# The kernels above are compiled per S4 = ceil(S / 4) and take the 16-byte row path (LDS-DMA in the backward) for S % 4 == 0 only;
+# the row cases of blend_cases.py reach S in {1, 3, 4, 10, 16, 17, 20, 32}.  One small frame per width -- two staging rounds,
+# saturated and untouched pixels, ragged and empty quadrants (tests/test_channel_counts_cpu.py) -- through the same checks with
+# the same tolerances.  The float32 yardstick over these 32 frames is part of the pooled GATE (docs/MEASUREMENT_LOG.md, "Every
+# semantic width 1..32 through the frame kernels").
+_WIDTH_FRAMES, _WIDTH_ROWS = {}, {}
+
+
+def _width_case(S):
+    """(tag, scene, frame, upstream gradients) of width S; the frames are small and kept for the module"""
+    sc, _cam = CC.case(S)
+    if S not in _WIDTH_FRAMES:
+        _WIDTH_FRAMES[S] = DeviceFrame(sc, _cam, CC.BG)
+    return f"width{S}", sc, _WIDTH_FRAMES[S], CC.upstream_dict(S)
+
+
+def _width_default_rows(S):
+    """the default backward rows of width S against the float64 reference: every element, validity byte and padded column;
+    -> (normalised errors for the pooled gate, the yardstick's on the device's alphas); computed once per width"""
+    if S not in _WIDTH_ROWS:
+        tag, sc, df, up = _width_case(S)
+        fr, qd = df.frame, df.quads
+        out = df.blend(0, up)
+        ref = BR.backward_rows(fr, qd, up, df.E, df.al, df.hit)
+        slots = BR.slots_reference(fr, qd, out["aux"])
+        BR.check_flags(slots, ref.member, out["flags"], df.N)
+        ncol = BR.nsem_of(S) + 10
+        got = np.zeros((qd.npairs, ncol), np.float32)
+        got[ref.member] = _rows_of(out, slots[ref.member], ncol)
+        err = BR.check_rows(S, qd, ref, got, BR.GATE, tag)
+        y = BR.backward_rows(fr, qd, up, df.E, df.al, df.hit, dtype=np.float32)
+        _WIDTH_ROWS[S] = (err, BR.normalised_errors(S, ref, y.rows)[0], int(ref.member.sum()), int(ref.depth.max()))
+    return _WIDTH_ROWS[S]
+
+
+@pytest.mark.parametrize("S", CC.WIDTHS)
+def test_every_width_forward_and_default_backward_rows(S):
+    """Pair evaluation of every candidate pair, qcost, member masks, n_contrib, out_alpha and the four maps, then slots, validity
+    bytes and every element of every default-mode row, the padded semantic columns exactly 0."""
+    tag, sc, df, up = _width_case(S)
+    assert df.N > 0 and df.S == S
+    fr, qd = df.frame, df.quads
+    st = dict(N=df.N, pairs=qd.npairs, pair_eval=_check_pairs_chunked(fr, qd, df.E, df.al, df.guards))
+    out = df.blend(0, up)
+    BR.check_masks(qd, df.hit, out["qmask0"], out["qmask"], out["qcost"])
+    assert (qd.qmax > 64).any() and (qd.nc.max(axis=1) < qd.length).any() and (~qd.inside).all(axis=1).any()
+    st["forward"] = BR.check_forward(fr, qd, BR.forward_reference(fr, qd, df.al, df.hit), df.maps(), BR.GATE)
+    err, _y, st["rows"], st["depth"] = _width_default_rows(S)
+    st["kernel"] = {c: [x / BR.U for x in v[:3]] for c, v in BR.class_stats(S, err).items()}
+    STATS[tag] = st
+    print(tag, json.dumps(st, default=float), flush=True)
+
+
+def test_every_width_default_rows_pass_the_pooled_gate():
+    S_list = list(CC.WIDTHS)
+    res = [_width_default_rows(S) for S in S_list]
+    pooled = BR.pooled_stats(S_list, [r[0] for r in res])
+    py = BR.pooled_stats(S_list, [r[1] for r in res])
+    STATS["pooled/widths/kernel"] = {c: [x / BR.U for x in v[:3]] + [v[3]] for c, v in pooled.items()}
+    STATS["pooled/widths/yardstick_device_alphas"] = {c: [x / BR.U for x in v[:3]] + [v[3]] for c, v in py.items()}
+    print("pooled/widths", json.dumps({k: v for k, v in STATS.items() if k.startswith("pooled/widths")}, default=float), flush=True)
+    BR.check_gate(pooled, BR.GATE, "every width, default mode: ")
+
+
+@pytest.mark.parametrize("mode,what", OTHER_FORMS)
+def test_other_forms_of_the_row_kernel_at_both_row_paths_of_every_S4(mode, what):
+    """S = 4 S4 - 1 (rows through registers, one padded column) and 4 S4 (16-byte rows, LDS-DMA) for S4 = 1..8"""
+    _other_form(mode, what, (_width_case(S) for S in CC.PAIRED_WIDTHS), f"pooled/widths/mode{mode}")
+
+
+@pytest.mark.parametrize("S", CC.PAIRED_WIDTHS)
+def test_semantic_only_rows_and_per_tile_kernel_at_both_row_paths_of_every_S4(S):
+    """render_bwd_sem_k in its four forms (modes 4..7: either flush, member masks or candidate testing) and render_bwd_tile_k"""
+    _semantic_only_rows([_width_case(S)], (4, 5, 6, 7))
+    _per_tile_arrays([_width_case(S)])
+
+
+@pytest.mark.parametrize("S", CC.WIDTHS)
+def test_chain_link_and_record_paths_at_every_width(S):
+    """The chain link at bwd_records 0, and the nine gradients the operator returns at bwd_records 1 (records in the row scratch:
+    the default) and 2 (rows summed inside the per-Gaussian backward where a row has 32 floats, S = 5..20; the records elsewhere)
+    equal to it element for element: the relation tests/test_gpu_parity.py asserts for these options on its own shapes.  (dL_dconic and
+    dL_ddepth are inputs of the per-Gaussian backward that only the six-array path writes out.)"""
+    _tag, sc, df, up = _width_case(S)
+    g0 = _chain_link(df, sc, up)
+    assert g0["semantic"].shape == (df.P, S) and np.isfinite(g0["semantic"]).all()
+    for records in (1, 2):
+        g = _raw_backward(df, sc, up, records)
+        for k in ("mean2D", "color", "semantic", "opacity", "mean3D", "cov3D", "sh", "scale", "rot"):
+            # (equality of VALUES, torch.equal's as in the parity suite: a zero gradient may leave either path as +0 or -0)
+            assert np.isfinite(g[k]).all() and np.isfinite(g0[k]).all(), f"width {S}: dL_d{k} was not written everywhere"
+            differ = g[k] != g0[k]
+            assert not differ.any(), (f"width {S}: dL_d{k} at bwd_records {records} differs from 0 in {int(differ.sum())} elements, by up to "
+                                      f"{float(np.abs(g[k].astype(np.float64) - g0[k])[differ].max()):.3e}")

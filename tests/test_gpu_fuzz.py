@@ -13,6 +13,11 @@ from tests.test_gpu_parity import check_backward, check_forward, dev, run_hip  #
 pytestmark = pytest.mark.gpu
 
 
+# (8, 12, 28: 16-byte rows at S4 = 2, 3, 7; 13, 26, 27, 31: the scalar path at S4 = 4, 7, 8 -- tests/test_gpu_channel_counts.py runs
+# every width on one scene, this sweep mixes them with random sizes.  The committed 60 draws differ from the earlier list's in S alone.)
+S_CHOICES = [1, 2, 3, 4, 7, 8, 10, 12, 13, 16, 17, 24, 26, 27, 28, 31, 32]
+
+
 def configs(n=None, seed=None):
     # GOI_FUZZ_N / GOI_FUZZ_SEED widen the sweep for a soak run (default: the 60 committed configurations)
     import os
@@ -24,7 +29,7 @@ def configs(n=None, seed=None):
         P = int(rng.choice([1, 2, 7, 63, 64, 65, 255, 257, 600, 1500, 3000]))
         W = int(rng.integers(17, 220))
         H = int(rng.integers(17, 160))
-        S = int(rng.choice([1, 2, 3, 4, 7, 10, 16, 17, 24, 32]))
+        S = int(rng.choice(S_CHOICES))
         deg = int(rng.integers(0, 4))
         mu = float(rng.uniform(-4.2, -0.8))
         yaw, pitch = float(rng.uniform(-0.5, 0.5)), float(rng.uniform(-0.3, 0.3))
@@ -110,12 +115,18 @@ def check_configuration(oracle_mod, dev, k, P, S, W, H, mu, deg, yaw, pitch):  #
 #   its terms, and the two-plane split-bf16 flush (products to ~1e-5) left 2.1e-3 there; the moments now get a third
 #   plane.
 SOAK_REGRESSIONS = [(201, 1500, 8102)]
+# The soak draws below were made with the S list of that time ([1, 2, 3, 4, 7, 10, 16, 17, 24, 32]); they are written out so that a
+# change of the sweep's draw does not move them: (k, n, seed) -> (k, P, S, W, H, mu, deg, yaw, pitch)
+SOAK_CONFIGS = {
+    (201, 1500, 8102): (201, 1, 16, 119, 70, -2.400713130181625, 3, -0.3549261207503315, -0.18873906689270756),
+    (1185, 1500, 66001): (1185, 257, 17, 173, 157, -2.8536901499675658, 3, 0.27756263262567726, 0.2396198647018623),
+}
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("k,n,seed", SOAK_REGRESSIONS)
 def test_soak_regression_is_within_the_plain_tolerance(oracle_mod, dev, k, n, seed):  # noqa: F811
-    cfg = [c for c in configs(n, seed) if c[0] == k][0]
+    cfg = SOAK_CONFIGS[(k, n, seed)]
     _k, P, S, W, H, mu, deg, yaw, pitch = cfg
     sc = make_scene(P, S=S, sh_degree=deg, seed=100 + k, log_scale_mean=mu)
     cam = make_camera(W, H, yaw=yaw, pitch=pitch)
@@ -145,5 +156,5 @@ KNOWN_OUTLIERS = [(1185, 1500, 66001)]
                                        "element (tolerance 2.74e-3 = 3 x the oracle builds' own spread); float64 figures above")
 @pytest.mark.parametrize("k,n,seed", KNOWN_OUTLIERS)
 def test_known_soak_outlier_stays_visible(oracle_mod, dev, k, n, seed):  # noqa: F811
-    cfg = [c for c in configs(n, seed) if c[0] == k][0]
+    cfg = SOAK_CONFIGS[(k, n, seed)]
     check_configuration(oracle_mod, dev, *cfg)

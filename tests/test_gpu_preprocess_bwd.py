@@ -466,10 +466,10 @@ def test_accumulate_adds_to_visible_rows_only(oracle_mod, S, max_blocks):
     run(sp, oracle_mod)
 
 
-@pytest.mark.parametrize("S", [1, 3, 10, 16, 17, 32])
+@pytest.mark.parametrize("S", list(range(1, 33)))
 def test_records_listed_and_unlisted(oracle_mod, S):
     """Source 1: visible Gaussians with a record and without (tiles_touched == 0: zero blend gradients, the chain still runs);
-    dL_dsemantic leaves as float4 (S = 16, 32) or scalar copies."""
+    dL_dsemantic leaves as float4 (S % 4 == 0) or scalar copies, from records of 16, 32 and 48 floats: every width admitted."""
     sp = spec(oracle_mod, 3000, "outside", f"records/{S}", visible=PATTERNS["frac51"], source=1, S=S, listed=0.6, max_blocks=3)
     got = run(sp, oracle_mod)
     vis, listed = sp.radii > 0, sp.extra["listed"]
@@ -480,11 +480,12 @@ def test_records_listed_and_unlisted(oracle_mod, S):
     assert np.abs(got["sh"][vis & listed]).max() > 0
 
 
-@pytest.mark.parametrize("S", [5, 10, 16, 20])
+@pytest.mark.parametrize("S", list(range(5, 21)))
 @pytest.mark.parametrize("dense", [False, True])
 def test_rows_summed_in_the_kernel(oracle_mod, S, dense):
     """Source 2: unflagged rows, rows past the count and the padding hold NaN; Gaussians on both sides of the frame's
-    big-instance threshold (a big one's record is read instead of its rows), on a sparse and on a dense frame."""
+    big-instance threshold (a big one's record is read instead of its rows), on a sparse and on a dense frame; every width the
+    source admits (128-byte rows: S = 5 .. 20; the float2 store of an even S and the scalar one of an odd S)."""
     sparse, big = K["SPARSE_INST"], K["BIG_INST"]
     counts = (big, big + 1, big + 40) if dense else (sparse, sparse + 1, big + 1, 700)
     sp = spec(oracle_mod, 2500, "outside", f"rows/{S}/{dense}", visible=PATTERNS["frac51"], source=2, S=S, listed=0.7,

@@ -228,8 +228,10 @@ def threshold_frame(kind: str, S: int) -> tuple[R.Frame, np.ndarray]:
 
 
 # ---- 1. every row width and mode ------------------------------------------------------------------------------------
-WIDTH_CASES = ([(0, S) for S in (1, 3, 4, 5, 10, 16, 20, 21, 24, 32)] + [(1, S) for S in (1, 3, 4, 5, 10, 16, 20, 21, 24, 32)]
-               + [(3, S) for S in (1, 10, 16, 17, 32)] + [(2, S) for S in (5, 16, 20)])
+# every semantic width the rasterizer admits (the 16-byte output path of S % 4 == 0 and the scalar one at every row width;
+# tests/test_channel_counts_cpu.py counts the classes); mode 2 exists for the 128-byte rows only (S = 5 .. 20)
+WIDTH_CASES = ([(0, S) for S in range(1, 33)] + [(1, S) for S in range(1, 33)] + [(3, S) for S in range(1, 33)]
+               + [(2, S) for S in range(5, 21)])
 
 
 @pytest.mark.parametrize("mode,S", WIDTH_CASES, ids=lambda x: str(x))

@@ -6,6 +6,8 @@ the 3-sigma rectangles, float32 direct-form alphas standing in for the device's)
 Prints, per element class, median / p99 / max of |x - f64| / M in units of 2^-24, pooled over the runs.
 
     python tools/blend_yardstick.py [case ...]
+    python tools/blend_yardstick.py --widths     (the 32 frames of tests/channel_count_cases.py, S = 1..32)
+    python tools/blend_yardstick.py --all        (both sets, pooled: what tests/blend_reference.py::GATE records)
 """
 import os
 import sys
@@ -16,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from tests import blend_cases as BC  # noqa: E402
 from tests import blend_reference as BR  # noqa: E402
+from tests import channel_count_cases as CC  # noqa: E402
 
 
 def oracle_frame(sc, cam, bg):
@@ -34,11 +37,20 @@ def oracle_frame(sc, cam, bg):
 
 
 def main(names):
-    runs = [r for r in BC.all_runs() if not names or r[0] in names]
+    # --widths: the 32 frames of tests/channel_count_cases.py instead of blend_cases.all_runs(); --all: both, pooled
+    width_runs = [(f"width{S}", S) for S in CC.WIDTHS]
+    if names in (["--widths"], ["--all"]):
+        runs = width_runs + (BC.all_runs() if names == ["--all"] else [])
+    else:
+        runs = [r for r in BC.all_runs() if not names or r[0] in names]
     S_list, y_err, d_err = [], [], []
     for name, kind in runs:
-        sc, cam = BC.ROW_CASES[name]()
-        up, bg = BC.upstream(kind, sc.S, cam.image_height, cam.image_width, name)
+        if isinstance(kind, int):
+            sc, cam = CC.case(kind)
+            up, bg, kind = CC.upstream_dict(kind), CC.BG, "random"
+        else:
+            sc, cam = BC.ROW_CASES[name]()
+            up, bg = BC.upstream(kind, sc.S, cam.image_height, cam.image_width, name)
         fr, qd, E, alpha, hit = oracle_frame(sc, cam, bg)
         ref = BR.backward_rows(fr, qd, up, E, alpha, hit)
         if not ref.member.any():
