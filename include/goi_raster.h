@@ -54,7 +54,7 @@ extern "C" {
  *    seven names that carried the history are REMOVED: goi_raster_forward_selected, goi_raster_forward_async_selected,
  *    goi_raster_forward_async_cut, goi_raster_ticket_result2, goi_raster_backward2, goi_raster_backward3, goi_raster_backward4;
  *    goi_raster_forward_async refuses a selection together with a depth cut;
- *    later additions: goi_raster_contrib_votes
+ *    later additions: goi_raster_contrib_votes; goi_knn_graph_workspace_bytes, goi_knn_graph, goi_knn_majority
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -635,6 +635,26 @@ int goi_raster_sh_grad_from_views(int P, int D, int M, int V, const float* means
  * radix sort of the Morton codes is exact below 2^30 keys. */
 size_t goi_knn_workspace_bytes(int P);
 int goi_knn_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream);
+
+/* ---- exact k-NN graph (csrc/knn.hip; the reference has no counterpart).  queries [Pq,3], refs [Pr,3] fp32;
+ * query_keep [Pq] / ref_keep [Pr]: one byte per point, non-zero = in, NULL = all.  With
+ *     dist2(i, j) = fmaf(dz, dz, fmaf(dx, dx, dy * dy)),  d = refs[j] - queries[i]  in fp32
+ * row i of idx [Pq,k] (int32) / dist2 [Pq,k] holds the k smallest (dist2, j) pairs over the kept references in ascending
+ * lexicographic order: ties in distance go to the lower j.  Nothing else enters the result: not the boxes, the visiting order
+ * or the order of the input.  Ids are the caller's.  A masked-out reference is never a neighbour; the row of a masked-out query,
+ * and the tail of a row with fewer than k kept references, is idx = -1, dist2 = +inf.  exclude_self = 1 skips reference j == i
+ * (by id: whatever the two masks are) and is refused unless queries == refs and Pq == Pr.  1 <= k <= 16; Pq, Pr < 2^30 (the workspace size is 0 beyond).
+ * workspace: goi_knn_graph_workspace_bytes(Pq, Pr) bytes of device memory, 256-byte aligned.  Asynchronous on `stream`; no host
+ * read-back: the kept counts stay on the device. */
+size_t goi_knn_graph_workspace_bytes(int Pq, int Pr);
+int goi_knn_graph(int Pq, const float* queries, const uint8_t* query_keep, int Pr, const float* refs, const uint8_t* ref_keep,
+                  int k, int exclude_self, int32_t* idx /*[Pq,k]*/, float* dist2 /*[Pq,k]*/, void* workspace, void* stream);
+/* A label per row of such a graph from its neighbours' labels [Pr] (int64): an entry counts with 0 <= idx < Pr, labels[idx] >= 0
+ * and dist2 <= max_dist2 (+inf allowed; dist2 == NULL: no cut).  label_out [Pq] = the label most entries carry, the LOWEST
+ * among equals (the rule of contrib.assign), count_out [Pq] (int32) its count; -1 and 0 for a row without an entry.  Labels are
+ * compared as values: any int64 >= 0, no histogram, no limit on the number of classes; integer arithmetic only.  k >= 1. */
+int goi_knn_majority(int Pq, int k, const int32_t* idx, const float* dist2, float max_dist2, int Pr, const int64_t* labels,
+                     int64_t* label_out, int32_t* count_out, void* stream);
 
 /* ---- training losses of the semantic head, row pass (train.py:142-163; see csrc/codebook_loss.hip).
  * Inputs: sim_raw [HW][C] = <g_p, LUT_c/|LUT_c|> with g NOT normalised, inv_gnorm [HW] = 1/|g_p|,
