@@ -185,13 +185,18 @@ KNN_GRAPH_SYMBOLS = {
     "goi_knn_graph": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
     "goi_knn_majority": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int] + [C.c_void_p] * 4),
 }
+# the goi_pose_* family (csrc/pose.hip: the pose gradient of a selection from one backward's gradients)
+POSE_SYMBOLS = {
+    "goi_pose_gradient_workspace_bytes": (C.c_size_t, [_LL]),
+    "goi_pose_gradient": (C.c_int, [_LL, _I, _P, _I] + [_P] * 14),
+}
 # every symbol include/goi_raster.h declares under the goi_raster / semantic / knn / adam / codebook prefixes
 SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS}
 # The entries that were MOVED out of csrc/api.hip into their families' units, with the frame's own: the set whose refusals
 # tests/test_entry_refusals_cpu.py records as they were before the move.  Entries added since are in LATER_TABLES and bring
-# their refusals in their own test files (tests/test_knn_graph_cpu.py).  load() binds both.
+# their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py).  load() binds both.
 SYMBOL_TABLES = (BASE_SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)
-LATER_TABLES = (KNN_GRAPH_SYMBOLS,)
+LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS)
 
 _lib = None
 

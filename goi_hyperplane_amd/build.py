@@ -53,6 +53,7 @@ UNITS = {
     "mesh.hip": ["-ffp-contract=off"],  # null faces, cells, means and normals are compared bit for bit: one rounding per operation
     "texture.hip": ["-ffp-contract=off"],  # barycentrics, splat weights and upsampling are compared bit for bit: no FMA
     "edit.hip": ["-ffp-contract=off"],  # the edit is compared bit for bit with its numpy restatement: one rounding per operation
+    "pose.hip": ["-ffp-contract=off"],  # the per-row pieces are held to their numpy restatement: one rounding per operation
 }
 
 

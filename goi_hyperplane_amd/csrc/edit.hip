@@ -21,6 +21,7 @@
 // order of tests/edit_reference.py.  No float atomics, no inline assembly.
 // C entries, with the limits they enforce, at the end of the file: goi_edit_* (declared in include/goi_raster.h).
 #include "entry.h"
+#include "rest_row.h"
 #include "wave_util.h"
 
 namespace goi {
@@ -42,10 +43,6 @@ struct BoundsPartial {
     unsigned long long n;
     float lo[3], hi[3];
 };
-
-__device__ __forceinline__ bool edit_selected(const uint8_t* __restrict__ sel, int invert, long long i) {
-    return !sel || ((sel[i] != 0) != (invert != 0));
-}
 
 __device__ __forceinline__ void bounds_add(BoundsPartial& a, const BoundsPartial& b) {
 #pragma unroll
@@ -162,11 +159,6 @@ __device__ __forceinline__ void rotate_band(const float* D, const float* c, floa
         }
     }
 }
-
-template <int R>
-struct RestRow {
-    static constexpr int STRIDE = (R % 2) ? R : R + 1;  // odd: 64 lanes reading their own rows hit 64 different banks
-};
 
 // One [P][R] tensor (the parameter or its first moment): the wave's rows through LDS; only the rows in `ballot` are written.
 template <int R>

@@ -54,7 +54,8 @@ extern "C" {
  *    seven names that carried the history are REMOVED: goi_raster_forward_selected, goi_raster_forward_async_selected,
  *    goi_raster_forward_async_cut, goi_raster_ticket_result2, goi_raster_backward2, goi_raster_backward3, goi_raster_backward4;
  *    goi_raster_forward_async refuses a selection together with a depth cut;
- *    later additions: goi_raster_contrib_votes; goi_knn_graph_workspace_bytes, goi_knn_graph, goi_knn_majority
+ *    later additions: goi_raster_contrib_votes; goi_knn_graph_workspace_bytes, goi_knn_graph, goi_knn_majority;
+ *    goi_pose_gradient_workspace_bytes, goi_pose_gradient
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -1128,6 +1129,36 @@ int goi_edit_bounds(long long P, const float* xyz, const unsigned char* selectio
 int goi_edit_transform(long long P, int M, const unsigned char* selection, int invert, const GoiEditTransform* t, float* xyz,
                        float* rotation, float* scaling, float* features_rest, float* m_xyz, float* m_rotation,
                        float* m_features_rest, const float* pivot_dev, void* stream);
+
+/* ---- Pose gradients of a selection (csrc/pose.hip) ----------------------------------------------------------
+ * The inverse of goi_edit_transform: the gradient of a loss with respect to the twist tau = (omega[3], t[3], sigma) of the
+ * similarity x' = p + t + e^sigma Exp(omega) (x - p), r' = q(omega) (x) r, l' = l + sigma, c'_l = D_l(Exp(omega)) c_l applied to the
+ * selected rows, at tau = 0, from the gradients a backward left for the raw parameters.  With d = x - p, r = (w, v), g_r = (g_w, g_v):
+ *     out[0..2] = dL/domega = sum [ d x g_x  +  1/2 ((w g_v - g_w v) + v x g_v)  +  (sum_ch g_c[:, ch]^T G_k c[:, ch])_k ]
+ *     out[3..5] = dL/dt     = sum g_x
+ *     out[6]    = dL/dsigma = sum [ g_x . d  +  ((g_l0 + g_l1) + g_l2) ]
+ * over the selected rows; *count = their number.  Minus the whole-model result is the gradient of moving the camera (omega, t only).
+ *
+ * goi_pose_gradient: P rows, 0 <= P < 2^31; M in {1, 4, 9, 16} SH coefficients (features_rest and g_features_rest [P][M-1][3]).
+ *   selection [P] bytes (non-zero selects; with `invert` a zero byte does) or NULL = every row.  xyz [P][3], rotation [P][4] raw
+ *   (w, x, y, z), features_rest: the parameters.  g_xyz, g_rotation, g_scaling [P][3], g_features_rest: their gradients; ANY may
+ *   be NULL (not trained): its pieces are omitted and its parameter tensor is not read (scaling itself is never read).  Refused:
+ *   all four NULL (with P > 0), a gradient whose parameter is NULL, g_features_rest with M = 1, NULL out / count / generators, a
+ *   NULL or misaligned workspace.  generators: HOST pointer to the 48 non-zero entries of the SH rotation generators G_x (18),
+ *   G_y (18), G_z (12) over bands 1..3, row-major within each (pose.py: sh_generators, generator_entries); where they sit is
+ *   compiled in.  pivot_host: HOST float[3] (NULL: the origin), used unless pivot_dev (device float[3]) is given.  out: device
+ *   double[7]; count: device int[1].  workspace: goi_pose_gradient_workspace_bytes(P) bytes (0: P out of range), 256-byte aligned.
+ *   Every piece of a row is formed in fp32, one rounding per operation, as written above with d first (products before their sum,
+ *   dot products in index order, the entries of a generator left to right); each piece -- three for omega, two for sigma, g_x for
+ *   t -- is converted to double and summed in float64 in a fixed order: per thread over its rows, the wave butterfly, the waves in
+ *   order, then at most 1024 per-workgroup partials by one workgroup in the same way.  No float atomics: two calls give the same
+ *   bits.  P = 0 or an empty selection gives zeros and count 0.  Two launches on `stream`, no read-back; returns 0 (or -1:
+ *   goi_raster_last_error). */
+size_t goi_pose_gradient_workspace_bytes(long long P);
+int goi_pose_gradient(long long P, int M, const unsigned char* selection, int invert, const float* xyz, const float* rotation,
+                      const float* features_rest, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                      const float* g_features_rest, const float* generators, const float* pivot_host, const float* pivot_dev,
+                      int* count, double* out, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
