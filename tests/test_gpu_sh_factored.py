@@ -14,7 +14,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.mark.parametrize("P,S,deg", [(5000, 8, 3), (1200, 16, 1), (3000, 4, 0)])
+@pytest.mark.parametrize("P,S,deg", [(5000, 8, 3), (1200, 16, 1), (3000, 4, 0), (800, 4, 2)])
 def test_factored_sh_gradient_is_bit_identical_to_the_sum_over_views(dev, P, S, deg):
     from goi_hyperplane_amd import _C, rasterizer
     from goi_hyperplane_amd.render import GaussianSet, PipelineParams, TorchCamera, render
