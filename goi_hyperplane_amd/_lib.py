@@ -190,13 +190,22 @@ POSE_SYMBOLS = {
     "goi_pose_gradient_workspace_bytes": (C.c_size_t, [_LL]),
     "goi_pose_gradient": (C.c_int, [_LL, _I, _P, _I] + [_P] * 14),
 }
+# the neighbour-consistency loss and feature diffusion on a k-NN graph (csrc/smooth.hip)
+SMOOTH_SYMBOLS = {
+    "goi_knn_transpose_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "goi_knn_transpose": (C.c_int, [_I, _I] + [_P] * 5),
+    "goi_knn_smooth_loss_workspace_bytes": (C.c_size_t, [_I]),
+    "goi_knn_smooth_loss": (C.c_int, [_I, _I, _I] + [_P] * 11),
+    "goi_knn_diffuse": (C.c_int, [_I, _I, _I] + [_P] * 4 + [C.c_float, _P, _P]),
+}
 # every symbol include/goi_raster.h declares under the goi_raster / semantic / knn / adam / codebook prefixes
-SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS}
+SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS, **SMOOTH_SYMBOLS}
 # The entries that were MOVED out of csrc/api.hip into their families' units, with the frame's own: the set whose refusals
 # tests/test_entry_refusals_cpu.py records as they were before the move.  Entries added since are in LATER_TABLES and bring
-# their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py).  load() binds both.
+# their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py, tests/test_smooth_entry_refusals_cpu.py).
+# load() binds both.
 SYMBOL_TABLES = (BASE_SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)
-LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS)
+LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS)
 
 _lib = None
 

@@ -55,7 +55,8 @@ extern "C" {
  *    goi_raster_forward_async_cut, goi_raster_ticket_result2, goi_raster_backward2, goi_raster_backward3, goi_raster_backward4;
  *    goi_raster_forward_async refuses a selection together with a depth cut;
  *    later additions: goi_raster_contrib_votes; goi_knn_graph_workspace_bytes, goi_knn_graph, goi_knn_majority;
- *    goi_pose_gradient_workspace_bytes, goi_pose_gradient
+ *    goi_pose_gradient_workspace_bytes, goi_pose_gradient; goi_knn_transpose_workspace_bytes, goi_knn_transpose,
+ *    goi_knn_smooth_loss_workspace_bytes, goi_knn_smooth_loss, goi_knn_diffuse
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -656,6 +657,45 @@ int goi_knn_graph(int Pq, const float* queries, const uint8_t* query_keep, int P
  * compared as values: any int64 >= 0, no histogram, no limit on the number of classes; integer arithmetic only.  k >= 1. */
 int goi_knn_majority(int Pq, int k, const int32_t* idx, const float* dist2, float max_dist2, int Pr, const int64_t* labels,
                      int64_t* label_out, int32_t* count_out, void* stream);
+
+/* ---- Neighbour consistency of per-Gaussian features on such a graph (csrc/smooth.hip) ----------------
+ * f [P,S] fp32, 1 <= S <= 32; idx [P,k] int32 as goi_knn_graph returns it, k >= 1, P * k < 2^30; weight [P,k] fp32 or NULL (= 1);
+ * rows [P] bytes or NULL (= all).  Entry (i, m) is an EDGE iff 0 <= idx[i,m] < P (goi_knn_majority's rule: -1 tails and ids out
+ * of range are skipped) and the edge COUNTS iff rows[i] != 0; N_E is the number of counting edges (a self edge counts and adds
+ * zero).  With j = idx[i,m]:
+ *     L        = (1 / N_E) sum_{counting (i,m)} w[i,m] sum_c (f[i,c] - f[j,c])^2                       (0 when N_E = 0)
+ *     dL/df[a] = (2 / N_E) [ sum_{m: (a,m) counts} w[a,m] (f[a] - f[idx[a,m]])  +  sum_{(i,m) counts, idx[i,m] = a} w[i,m] (f[a] - f[i]) ]
+ * The second sum runs over the TRANSPOSE of the graph, which makes the gradient a gather: no float atomics, the same bits on
+ * every call.
+ *
+ * goi_knn_transpose: from ALL edges (it knows neither rows nor weight: one transpose serves a run that redraws rows every
+ *   iteration).  in_ptr [P+1] int32, in_edge [P*k] int32: the flat edge numbers e = i * k + m in ascending (idx[e], e) order, those
+ *   that point at row a in in_edge[in_ptr[a] .. in_ptr[a+1]); in_ptr[P] is the number of edges and in_edge is -1 from there on.
+ *   From e the source row is e / k and the weight weight[e].  In-degrees by integer atomics, an exclusive scan, a stable radix
+ *   sort over the key bits P needs (a skipped entry sorts behind every edge).  P = 0 writes in_ptr[0] = 0.
+ * goi_knn_smooth_loss: *loss (fp32), *n_edges (int64) and, with grad != NULL, grad [P,S] = dL/df, all on the device; in_ptr and
+ *   in_edge are read only with grad (values outside their arrays are clamped or skipped: never an access out of bounds).  Per
+ *   gradient element: acc = 0; over row a's k slots in slot order, then over its in-list in stored order, for every counting
+ *   edge t = f[a,c] - f[other,c], acc = acc + w * t; then acc * scale with scale = float(2.0 / N_E) formed in float64 -- every
+ *   operation rounded once, no FMA.  The loss of a row: per edge q = t_c^2 (+ t_{c+16}^2) per lane c < 16, summed over the 16 lanes
+ *   pairwise (offsets 8, 4, 2, 1), r = r + w * q in slot order, all fp32; rows and workgroups are summed in float64 in a fixed
+ *   order and *loss = float(sum / N_E).  N_E = 0 gives exact zeros.  N_E is counted on the device before the gradient is
+ *   scaled: nothing is read back.
+ * goi_knn_diffuse: one Jacobi step over the out-lists: W = sum_m w[i,m] and m_c = (sum_m w[i,m] f[j,c]) / W over row i's edges
+ *   in slot order (acc = acc + w * f), out[i,c] = f[i,c] + lam * (m_c - f[i,c]), one rounding per operation.  A row with
+ *   fixed[i] != 0 (fixed [P] bytes or NULL), without an edge or with W == 0 is copied bit for bit.  out [P,S] must not be f.
+ * Refused: P < 0, S outside 1..32, k < 1, P * k >= 2^30 (the workspace size is then 0), a NULL required pointer, a NULL or
+ * misaligned workspace (goi_knn_*_workspace_bytes bytes, 256-byte aligned).  P = 0 is a valid empty call.  Asynchronous on
+ * `stream`; returns 0 (or -1: goi_raster_last_error). */
+size_t goi_knn_transpose_workspace_bytes(int P, int k);
+int goi_knn_transpose(int P, int k, const int32_t* idx, int32_t* in_ptr /*[P+1]*/, int32_t* in_edge /*[P*k]*/, void* workspace,
+                      void* stream);
+size_t goi_knn_smooth_loss_workspace_bytes(int P);
+int goi_knn_smooth_loss(int P, int S, int k, const float* f, const int32_t* idx, const float* weight, const uint8_t* rows,
+                        const int32_t* in_ptr, const int32_t* in_edge, float* loss, long long* n_edges, float* grad /*[P,S] or NULL*/,
+                        void* workspace, void* stream);
+int goi_knn_diffuse(int P, int S, int k, const float* f, const int32_t* idx, const float* weight, const uint8_t* fixed, float lam,
+                    float* out /*[P,S]*/, void* stream);
 
 /* ---- training losses of the semantic head, row pass (train.py:142-163; see csrc/codebook_loss.hip).
  * Inputs: sim_raw [HW][C] = <g_p, LUT_c/|LUT_c|> with g NOT normalised, inv_gnorm [HW] = 1/|g_p|,
