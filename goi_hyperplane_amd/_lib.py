@@ -198,14 +198,21 @@ SMOOTH_SYMBOLS = {
     "goi_knn_smooth_loss": (C.c_int, [_I, _I, _I] + [_P] * 11),
     "goi_knn_diffuse": (C.c_int, [_I, _I, _I] + [_P] * 4 + [C.c_float, _P, _P]),
 }
+# the edge gate and the connected components of a k-NN graph (csrc/segment.hip)
+SEGMENT_SYMBOLS = {
+    "goi_knn_segment_edges": (C.c_int, [_I, _I, _I, _P, _P, C.c_float, _P, C.c_float, _I, _P, _P, _P, _P]),
+    "goi_knn_segment_components_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "goi_knn_segment_components": (C.c_int, [_I, _I, _P, _P, _P, _I] + [_P] * 7),
+}
 # every symbol include/goi_raster.h declares under the goi_raster / semantic / knn / adam / codebook prefixes
-SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS, **SMOOTH_SYMBOLS}
+SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS, **SMOOTH_SYMBOLS, **SEGMENT_SYMBOLS}
 # The entries that were MOVED out of csrc/api.hip into their families' units, with the frame's own: the set whose refusals
 # tests/test_entry_refusals_cpu.py records as they were before the move.  Entries added since are in LATER_TABLES and bring
-# their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py, tests/test_smooth_entry_refusals_cpu.py).
+# their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py, tests/test_smooth_entry_refusals_cpu.py,
+# tests/test_segment_entry_refusals_cpu.py).
 # load() binds both.
 SYMBOL_TABLES = (BASE_SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)
-LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS)
+LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS)
 
 _lib = None
 

@@ -40,6 +40,7 @@ UNITS = {
     "semantic_head.hip": [],
     "knn.hip": ["-ffp-contract=off"],
     "smooth.hip": ["-ffp-contract=off"],  # the gradient is compared bit for bit with its numpy restatement: t = a - b, acc + w * t, no FMA
+    "segment.hip": ["-ffp-contract=off"],  # the feature gate is compared bit for bit: e = a - b, then the fmaf that is written out
     "adam.hip": ["-ffp-contract=off"],
     "codebook_loss.hip": [],
     "osh.hip": [],

@@ -56,7 +56,8 @@ extern "C" {
  *    goi_raster_forward_async refuses a selection together with a depth cut;
  *    later additions: goi_raster_contrib_votes; goi_knn_graph_workspace_bytes, goi_knn_graph, goi_knn_majority;
  *    goi_pose_gradient_workspace_bytes, goi_pose_gradient; goi_knn_transpose_workspace_bytes, goi_knn_transpose,
- *    goi_knn_smooth_loss_workspace_bytes, goi_knn_smooth_loss, goi_knn_diffuse
+ *    goi_knn_smooth_loss_workspace_bytes, goi_knn_smooth_loss, goi_knn_diffuse; goi_knn_segment_edges,
+ *    goi_knn_segment_components_workspace_bytes, goi_knn_segment_components
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -696,6 +697,47 @@ int goi_knn_smooth_loss(int P, int S, int k, const float* f, const int32_t* idx,
                         void* workspace, void* stream);
 int goi_knn_diffuse(int P, int S, int k, const float* f, const int32_t* idx, const float* weight, const uint8_t* fixed, float lam,
                     float* out /*[P,S]*/, void* stream);
+
+/* ---- Instance segmentation on such a graph (csrc/segment.hip) -----------------------------------------
+ * idx [P,k] int32 as goi_knn_graph returns it, k >= 1, P * k < 2^30.
+ *
+ * goi_knn_segment_edges: join [P,k] bytes.  With j = idx[i,m], join[i,m] = 1 iff ALL of
+ *     0 <= j < P and j != i                                  (-1 tails, ids out of range and self edges never join)
+ *     rows == NULL, or rows[i] != 0 && rows[j] != 0          (rows [P] bytes)
+ *     labels == NULL, or labels[i] >= 0 && labels[i] == labels[j]      (labels [P] int64)
+ *     GOI_SEGMENT_MAX_DIST2 is not in flags, or dist2[i,m] <= max_dist2      (dist2 [P,k] fp32; the flag needs dist2)
+ *     features == NULL, or d <= tau, where d = 0 and d = fmaf(e_c, e_c, d) for c = 0 .. S-1 in that order with
+ *         e_c = features[i,c] - features[j,c] in fp32 (features [P,S], 1 <= S <= 32; S is not looked at without features).  The
+ *         comparison is taken as written: a NaN d never joins, tau = +inf joins every other d.  d is symmetric in (i, j) bit for
+ *         bit and does not depend on the launch geometry: one lane owns the chain.
+ *     GOI_SEGMENT_MUTUAL is not in flags, or idx[j,m'] == i for some m'
+ *   Refused: P < 0, k < 1, P * k >= 2^30, S outside 1..32 (with features), a NaN tau, unknown flags, GOI_SEGMENT_MAX_DIST2 without
+ *   dist2 or with a NaN max_dist2, a NULL idx or join, idx / features / dist2 not 4-byte or labels not 8-byte aligned.
+ *
+ * goi_knn_segment_components: the connected components of the UNDIRECTED graph whose edges are the entries (i, m) with
+ *   0 <= j < P, j != i, join == NULL or join[i,m] != 0, and rows == NULL or rows[i] != 0 && rows[j] != 0 -- an edge that only
+ *   one endpoint lists unites both.  All outputs on the device, nothing is read back:
+ *     root  [P] int32   the smallest id of the row's component; -1 where rows[i] == 0 (such a row is in no component)
+ *     size  [P] int32   the number of rows of the row's component; 0 where root is -1
+ *     label [P] int32   the dense rank 0 .. C-1, in ascending root, of the component among those with size >= min_size; else -1
+ *     count [1] int32   C
+ *     status [1] int32  GOI_SEGMENT_STATUS_* bits, 0 after a good call (the convention of GOI_MESH_STATUS_*)
+ *   Union-find with the larger root hooked under the smaller (atomicCAS) and path halving (atomicMin), so every output is
+ *   independent of the schedule; sizes by integer atomics, combined per wave first; ranks by an exclusive scan.
+ *   Refused: P < 0, k < 1, P * k >= 2^30 (the workspace size is then 0), min_size < 1, a NULL or misaligned required pointer, a
+ *   NULL or misaligned workspace (goi_knn_segment_components_workspace_bytes bytes, 256-byte aligned).
+ * P = 0 is a valid empty call of either: it returns 0 and touches nothing.  Asynchronous on `stream`; returns 0 (or -1:
+ * goi_raster_last_error). */
+#define GOI_SEGMENT_MUTUAL 1     /* flags of goi_knn_segment_edges */
+#define GOI_SEGMENT_MAX_DIST2 2
+#define GOI_SEGMENT_STATUS_UNION 4 /* a union-find walk or retry loop ran out of its bound (cannot happen: parents only decrease) */
+int goi_knn_segment_edges(int P, int S, int k, const int32_t* idx, const float* features, float tau, const float* dist2,
+                          float max_dist2, int flags, const int64_t* labels, const uint8_t* rows, uint8_t* join /*[P,k]*/,
+                          void* stream);
+size_t goi_knn_segment_components_workspace_bytes(int P, int k);
+int goi_knn_segment_components(int P, int k, const int32_t* idx, const uint8_t* join, const uint8_t* rows, int min_size,
+                               int32_t* root, int32_t* size, int32_t* label, int32_t* count, int32_t* status, void* workspace,
+                               void* stream);
 
 /* ---- training losses of the semantic head, row pass (train.py:142-163; see csrc/codebook_loss.hip).
  * Inputs: sim_raw [HW][C] = <g_p, LUT_c/|LUT_c|> with g NOT normalised, inv_gnorm [HW] = 1/|g_p|,
