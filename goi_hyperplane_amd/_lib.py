@@ -204,15 +204,23 @@ SEGMENT_SYMBOLS = {
     "goi_knn_segment_components_workspace_bytes": (C.c_size_t, [_I, _I]),
     "goi_knn_segment_components": (C.c_int, [_I, _I, _P, _P, _P, _I] + [_P] * 7),
 }
+# the partition as member lists and the per-instance statistics (csrc/instance.hip); like the goi_pose_* family
+# these names carry a prefix of their own, so they are bound through LATER_TABLES and are not part of SYMBOLS below
+INSTANCE_SYMBOLS = {
+    "goi_instance_members_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "goi_instance_members": (C.c_int, [_I, _I] + [_P] * 5),
+    "goi_instance_stats_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "goi_instance_stats": (C.c_int, [_I, _I, _I] + [_P] * 16),
+}
 # every symbol include/goi_raster.h declares under the goi_raster / semantic / knn / adam / codebook prefixes
 SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS, **SMOOTH_SYMBOLS, **SEGMENT_SYMBOLS}
 # The entries that were MOVED out of csrc/api.hip into their families' units, with the frame's own: the set whose refusals
 # tests/test_entry_refusals_cpu.py records as they were before the move.  Entries added since are in LATER_TABLES and bring
 # their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py, tests/test_smooth_entry_refusals_cpu.py,
-# tests/test_segment_entry_refusals_cpu.py).
+# tests/test_segment_entry_refusals_cpu.py, tests/test_instance_entry_refusals_cpu.py).
 # load() binds both.
 SYMBOL_TABLES = (BASE_SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)
-LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS)
+LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS, INSTANCE_SYMBOLS)
 
 _lib = None
 

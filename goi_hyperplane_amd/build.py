@@ -41,6 +41,7 @@ UNITS = {
     "knn.hip": ["-ffp-contract=off"],
     "smooth.hip": ["-ffp-contract=off"],  # the gradient is compared bit for bit with its numpy restatement: t = a - b, acc + w * t, no FMA
     "segment.hip": ["-ffp-contract=off"],  # the feature gate is compared bit for bit: e = a - b, then the fmaf that is written out
+    "instance.hip": ["-ffp-contract=off"],  # the float64 sums are compared bit for bit with their numpy restatement: t = w * d, acc + t * d, no FMA
     "adam.hip": ["-ffp-contract=off"],
     "codebook_loss.hip": [],
     "osh.hip": [],

@@ -8,6 +8,7 @@ checkpoints load unchanged:
     LinearSVM                networks.py:12-67               (x / 0.3438 -> Linear(256, 1), hinge loss, SGD)
     fit_hyperplane           gui/main.py:1673-1763           (the OSH fine-tune against a mask: one HIP kernel)
     select_gaussians         gui/main.py:400-405             (Gaussians of interest)
+    select_instances         --                              (the same mask voted into whole objects: instance.py)
     group_points             gui/main.py:1595-1665           (DBSCAN refinement of the selection: cluster.py)
     relevant_cameras         gui/main.py:407-478             (relevant-camera precompute: masks.py on the device)
     evaluate_cameras         gui/main.py:1957-2016           (eval_epoch's IoU / mPA / mP, utils/image_utils.py:59-102)
@@ -498,6 +499,18 @@ def select_gaussians(pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh
     render(..., gaussian_mask=...).  (It also returns Gaussians no camera shows: contrib.lift_mask selects by the blend instead.)"""
     sem = pc.get_semantics.detach().float().t().contiguous()  # [S, P]: the decode's channel-major layout, one "pixel" per Gaussian
     return compute_similarity(sem, mlp, lut, score_fn, thresh) > 0
+
+
+@torch.no_grad()
+def select_instances(pc, mlp: SemanticModel, lut: torch.Tensor, score_fn, thresh: float, segments, min_fraction=0.5,
+                     min_hits: int = 1, capacity=None) -> torch.Tensor:
+    """The OBJECTS of interest: select_gaussians' per-Gaussian prompt mask -- which has holes inside objects and speckle outside
+    them -- voted over the instances of `segments` (segment.instances of the same model): an instance is returned whole when at
+    least min_hits of its Gaussians and at least min_fraction of them were selected (instance.select).  bool [P], ready for
+    render(..., gaussian_mask=..., in_place=True), edit.transform and prune_points.  capacity as in instance.members: None
+    reads the number of instances back once, an int synchronises nothing."""
+    from . import instance
+    return instance.select(segments, select_gaussians(pc, mlp, lut, score_fn, thresh), min_fraction, min_hits, capacity)
 
 
 @torch.no_grad()

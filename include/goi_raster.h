@@ -57,7 +57,8 @@ extern "C" {
  *    later additions: goi_raster_contrib_votes; goi_knn_graph_workspace_bytes, goi_knn_graph, goi_knn_majority;
  *    goi_pose_gradient_workspace_bytes, goi_pose_gradient; goi_knn_transpose_workspace_bytes, goi_knn_transpose,
  *    goi_knn_smooth_loss_workspace_bytes, goi_knn_smooth_loss, goi_knn_diffuse; goi_knn_segment_edges,
- *    goi_knn_segment_components_workspace_bytes, goi_knn_segment_components
+ *    goi_knn_segment_components_workspace_bytes, goi_knn_segment_components; goi_instance_members_workspace_bytes,
+ *    goi_instance_members, goi_instance_stats_workspace_bytes, goi_instance_stats
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -738,6 +739,39 @@ size_t goi_knn_segment_components_workspace_bytes(int P, int k);
 int goi_knn_segment_components(int P, int k, const int32_t* idx, const uint8_t* join, const uint8_t* rows, int min_size,
                                int32_t* root, int32_t* size, int32_t* label, int32_t* count, int32_t* status, void* workspace,
                                void* stream);
+
+/* ---- Per-instance statistics over a partition (csrc/instance.hip) ------------------------------------
+ * label [P] int32 as goi_knn_segment_components writes it; K >= 0 instances.  A row is in instance label[i] iff
+ * 0 <= label[i] < K; every other value (-1, a label at or above K) is "in no instance".  0 <= P < 2^30, 0 <= K < 2^30.
+ *
+ * goi_instance_members: the partition as lists.  member_ptr [K+1] int32, member [P] int32: the rows of instance k are
+ *   member[member_ptr[k] .. member_ptr[k+1]) in ascending row id, member_ptr[K] is the number of rows in an instance, member is
+ *   -1 from there on.  Counts by integer atomics, an exclusive scan, a stable radix sort over the key bits K + 1 needs.
+ *   P = 0 writes member_ptr = 0 and needs no workspace.
+ *
+ * goi_instance_stats: every statistic of every instance in one pass over the lists.  xyz [P,3] fp32 or NULL (every position is then the origin: a caller that wants the counts alone); features [P,S] fp32 or
+ *   NULL (S is then not looked at), 1 <= S <= 32; weight [P] fp32 or NULL (1); hit [P] bytes or NULL (0), eight independent
+ *   flag bits.  Outputs, on the device:
+ *     n [K] int32            number of members                 hits [K,8] int32     members with bit b of hit set
+ *     wsum [K] fp32          W = sum w                         centroid [K,3] fp32  sum w x / W
+ *     lo, hi [K,3] fp32      exact minimum / maximum of the members' positions; a NaN is skipped, -0 < +0; +inf / -inf when
+ *                            there is no number
+ *     cov [K,6] fp32         sum w (x-c)(x-c)^T / W: xx xy xz yy yz zz        feature [K,S] fp32 (NULL without features)  sum w f / W
+ *   Float64 sums of positions relative to the instance's first member, in an order that is a fixed function of the instance's own
+ *   member sequence (chunks of 256 members, four interleaved accumulators per chunk, chunk partials in ascending order: the
+ *   header comment of csrc/instance.hip spells it out), one rounding to fp32 at the end; W == 0 writes 0 for centroid, cov and
+ *   feature.  No float atomics, the same bits on every call.  member_ptr and member are clamped before use.
+ *   K = 0 returns 0 and touches nothing; P = 0 with K > 0 writes every instance's empty values.
+ * Refused by both, before any device call: P < 0, K < 0, P or K >= 2^30 (the workspace size is then 0), S outside 1..32 with
+ * features, a NULL required pointer, a pointer (hit apart) that is not 4-byte aligned, a NULL or misaligned workspace
+ * (goi_instance_*_workspace_bytes bytes, 256-byte aligned).  Asynchronous on `stream`; returns 0 (or -1: goi_raster_last_error). */
+size_t goi_instance_members_workspace_bytes(int P, int K);
+int goi_instance_members(int P, int K, const int32_t* label, int32_t* member_ptr /*[K+1]*/, int32_t* member /*[P]*/, void* workspace,
+                         void* stream);
+size_t goi_instance_stats_workspace_bytes(int P, int K);
+int goi_instance_stats(int P, int K, int S, const int32_t* member_ptr, const int32_t* member, const float* xyz, const float* features,
+                       const float* weight, const uint8_t* hit, int32_t* n, int32_t* hits, float* wsum, float* centroid, float* lo,
+                       float* hi, float* cov, float* feature, void* workspace, void* stream);
 
 /* ---- training losses of the semantic head, row pass (train.py:142-163; see csrc/codebook_loss.hip).
  * Inputs: sim_raw [HW][C] = <g_p, LUT_c/|LUT_c|> with g NOT normalised, inv_gnorm [HW] = 1/|g_p|,
