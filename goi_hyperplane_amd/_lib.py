@@ -212,15 +212,21 @@ INSTANCE_SYMBOLS = {
     "goi_instance_stats_workspace_bytes": (C.c_size_t, [_I, _I]),
     "goi_instance_stats": (C.c_int, [_I, _I, _I] + [_P] * 16),
 }
+# the mask-contrast loss of a rendered feature map against one view's 2D instance masks (csrc/grouping.hip); a prefix
+# of its own again: bound through LATER_TABLES, not part of SYMBOLS below
+GROUPING_SYMBOLS = {
+    "goi_mask_contrast_workspace_bytes": (C.c_size_t, [_I] * 4),
+    "goi_mask_contrast": (C.c_int, [_I] * 4 + [_P, _P, C.c_float, C.c_float, C.c_float, _I, C.c_float] + [_P] * 10),
+}
 # every symbol include/goi_raster.h declares under the goi_raster / semantic / knn / adam / codebook prefixes
 SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS, **SMOOTH_SYMBOLS, **SEGMENT_SYMBOLS}
 # The entries that were MOVED out of csrc/api.hip into their families' units, with the frame's own: the set whose refusals
 # tests/test_entry_refusals_cpu.py records as they were before the move.  Entries added since are in LATER_TABLES and bring
 # their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py, tests/test_smooth_entry_refusals_cpu.py,
-# tests/test_segment_entry_refusals_cpu.py, tests/test_instance_entry_refusals_cpu.py).
+# tests/test_segment_entry_refusals_cpu.py, tests/test_instance_entry_refusals_cpu.py, tests/test_grouping_entry_refusals_cpu.py).
 # load() binds both.
 SYMBOL_TABLES = (BASE_SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)
-LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS, INSTANCE_SYMBOLS)
+LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS, INSTANCE_SYMBOLS, GROUPING_SYMBOLS)
 
 _lib = None
 

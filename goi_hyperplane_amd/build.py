@@ -42,6 +42,7 @@ UNITS = {
     "smooth.hip": ["-ffp-contract=off"],  # the gradient is compared bit for bit with its numpy restatement: t = a - b, acc + w * t, no FMA
     "segment.hip": ["-ffp-contract=off"],  # the feature gate is compared bit for bit: e = a - b, then the fmaf that is written out
     "instance.hip": ["-ffp-contract=off"],  # the float64 sums are compared bit for bit with their numpy restatement: t = w * d, acc + t * d, no FMA
+    "grouping.hip": ["-ffp-contract=off"],  # the float64 means, pair terms and residual are held to their numpy restatement: one rounding per operation
     "adam.hip": ["-ffp-contract=off"],
     "codebook_loss.hip": [],
     "osh.hip": [],

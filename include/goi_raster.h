@@ -58,7 +58,8 @@ extern "C" {
  *    goi_pose_gradient_workspace_bytes, goi_pose_gradient; goi_knn_transpose_workspace_bytes, goi_knn_transpose,
  *    goi_knn_smooth_loss_workspace_bytes, goi_knn_smooth_loss, goi_knn_diffuse; goi_knn_segment_edges,
  *    goi_knn_segment_components_workspace_bytes, goi_knn_segment_components; goi_instance_members_workspace_bytes,
- *    goi_instance_members, goi_instance_stats_workspace_bytes, goi_instance_stats
+ *    goi_instance_members, goi_instance_stats_workspace_bytes, goi_instance_stats; goi_mask_contrast_workspace_bytes,
+ *    goi_mask_contrast
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -772,6 +773,32 @@ size_t goi_instance_stats_workspace_bytes(int P, int K);
 int goi_instance_stats(int P, int K, int S, const int32_t* member_ptr, const int32_t* member, const float* xyz, const float* features,
                        const float* weight, const uint8_t* hit, int32_t* n, int32_t* hits, float* wsum, float* centroid, float* lo,
                        float* hi, float* cov, float* feature, void* workspace, void* stream);
+
+/* ---- The mask-contrast loss of a feature map against one view's 2D instance masks (csrc/grouping.hip) ----
+ * feat [S,H,W] fp32, channel-major as the rasterizer writes `semantics`; labels [H,W] int32; K >= 0 an upper bound on the view's
+ * mask ids.  Pixel p is in mask m = labels[p] iff 0 <= m < K; every other value (-1, >= K, INT32_MIN) is ignored.
+ * 1 <= S <= 32, H, W >= 1, H * W <= 2^22, 0 <= K <= 65536.  With n_m the pixels of mask m, N = sum n_m, M the masks with n_m > 0,
+ * mu_m the mean feature of mask m:
+ *     L_intra = sum_m a_m sum_{p in m} |f_p - mu_m|^2        a_m = 1/N (balance 0: "pixel")   1/(M n_m) (balance 1: "mask")
+ *     L_inter = 1/(M(M-1)) sum_{m != m', both non-empty} max(0, margin - |mu_m - mu_m'|)^2
+ *     L = w_intra L_intra + w_inter L_inter;  M == 0: L = 0 and a zero gradient;  M == 1: L_inter = 0;  a pair whose means are
+ *     equal adds margin^2 and no gradient.
+ * Outputs, on the device: loss, intra (L_intra), inter (L_inter) fp32 scalars; grad [S,H,W] fp32 = dL/dfeat (0 for an ignored
+ * pixel), or NULL: then no gradient is stored; count [K] int64 = n_m; qsum [K,S] int64 = sum over the mask's pixels of
+ * rint(f * 2^q) (float64, ties to even) -- exact and free of any order; qexp int32 = q = 40 - e, e the smallest integer with
+ * max|f| < 2^e over the WHOLE map (0 for an all-zero map); status int32, 0 or bit 0.  max_abs < 0: the maximum is found by a pass
+ * over feat.  max_abs >= 0: e is the smallest integer with max_abs < 2^e and that pass is skipped; a pixel with |f| >= 2^e then
+ * counts as +-2^40 and raises bit 0 of status.  Means, pair terms and the residual are float64 in a fixed order; no float
+ * atomics, the same bits on every call.  Non-finite features are the caller's error (the call terminates, the numbers mean
+ * nothing).  count and qsum may be NULL when K == 0.
+ * Refused before any device call: S outside 1..32, H or W < 1, H * W > 2^22, K outside 0..65536 (the workspace size is then 0), a
+ * balance other than 0 or 1, a margin that is negative or not finite, a weight that is not finite, a max_abs that is not finite, a
+ * NULL required pointer, a pointer that is not 4-byte (count, qsum: 8-byte) aligned, a NULL or misaligned workspace
+ * (goi_mask_contrast_workspace_bytes bytes, 256-byte aligned).  Asynchronous on `stream`; returns 0 (or -1: goi_raster_last_error). */
+size_t goi_mask_contrast_workspace_bytes(int S, int H, int W, int K);
+int goi_mask_contrast(int S, int H, int W, int K, const float* feat, const int32_t* labels, float margin, float w_intra, float w_inter,
+                      int balance, float max_abs, float* loss, float* intra, float* inter, float* grad /*[S,H,W] or NULL*/,
+                      int64_t* count /*[K]*/, int64_t* qsum /*[K,S]*/, int32_t* qexp, int32_t* status, void* workspace, void* stream);
 
 /* ---- training losses of the semantic head, row pass (train.py:142-163; see csrc/codebook_loss.hip).
  * Inputs: sim_raw [HW][C] = <g_p, LUT_c/|LUT_c|> with g NOT normalised, inv_gnorm [HW] = 1/|g_p|,
