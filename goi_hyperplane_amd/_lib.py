@@ -218,15 +218,24 @@ GROUPING_SYMBOLS = {
     "goi_mask_contrast_workspace_bytes": (C.c_size_t, [_I] * 4),
     "goi_mask_contrast": (C.c_int, [_I] * 4 + [_P, _P, C.c_float, C.c_float, C.c_float, _I, C.c_float] + [_P] * 10),
 }
+# the fixed-budget densification (csrc/mcmc.hip); a prefix of its own: bound through LATER_TABLES
+MCMC_SYMBOLS = {
+    "goi_mcmc_relocate_workspace_bytes": (C.c_size_t, [_LL]),
+    "goi_mcmc_relocate": (C.c_int, [_LL, _P, _P, _LL, _P, C.c_double, _LL, _LL, _LL, _I, _P, _I] + [_P] * 5),
+    "goi_mcmc_noise": (C.c_int, [_LL] + [_P] * 6 + [C.c_double] * 3 + [_P]),
+    "goi_mcmc_debug_relocation_sum": (C.c_int, [_I] + [_P] * 4),
+}
 # every symbol include/goi_raster.h declares under the goi_raster / semantic / knn / adam / codebook prefixes
 SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS, **SMOOTH_SYMBOLS, **SEGMENT_SYMBOLS}
 # The entries that were MOVED out of csrc/api.hip into their families' units, with the frame's own: the set whose refusals
 # tests/test_entry_refusals_cpu.py records as they were before the move.  Entries added since are in LATER_TABLES and bring
 # their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py, tests/test_smooth_entry_refusals_cpu.py,
-# tests/test_segment_entry_refusals_cpu.py, tests/test_instance_entry_refusals_cpu.py, tests/test_grouping_entry_refusals_cpu.py).
+# tests/test_segment_entry_refusals_cpu.py, tests/test_instance_entry_refusals_cpu.py, tests/test_grouping_entry_refusals_cpu.py,
+# tests/test_mcmc_entry_refusals_cpu.py).
 # load() binds both.
 SYMBOL_TABLES = (BASE_SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)
-LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS, INSTANCE_SYMBOLS, GROUPING_SYMBOLS)
+LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS, INSTANCE_SYMBOLS, GROUPING_SYMBOLS,
+                MCMC_SYMBOLS)
 
 _lib = None
 
@@ -322,6 +331,15 @@ class GoiDensifyRows(C.Structure):
 
 
 DENSIFY_MAX_GROUPS = 24
+
+
+class GoiMcmcRows(C.Structure):
+    """include/goi_raster.h: GoiMcmcRows"""
+    _fields_ = [("data", C.c_void_p), ("row_len", C.c_int), ("mode", C.c_int)]
+
+
+MCMC_MAX_GROUPS = 24
+MCMC_PARAM, MCMC_OPACITY, MCMC_SCALING, MCMC_MOMENT = 0, 1, 2, 3  # GOI_MCMC_* of include/goi_raster.h
 
 
 class GoiEditTransform(C.Structure):

@@ -59,7 +59,7 @@ extern "C" {
  *    goi_knn_smooth_loss_workspace_bytes, goi_knn_smooth_loss, goi_knn_diffuse; goi_knn_segment_edges,
  *    goi_knn_segment_components_workspace_bytes, goi_knn_segment_components; goi_instance_members_workspace_bytes,
  *    goi_instance_members, goi_instance_stats_workspace_bytes, goi_instance_stats; goi_mask_contrast_workspace_bytes,
- *    goi_mask_contrast
+ *    goi_mask_contrast; goi_mcmc_relocate_workspace_bytes, goi_mcmc_relocate, goi_mcmc_noise, goi_mcmc_debug_relocation_sum
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -910,6 +910,66 @@ int goi_raster_densify_plan(long long P, const float* accum, const float* denom,
 int goi_raster_densify_prune_plan(long long P, const unsigned char* mask, unsigned* counts, void* workspace, void* stream);
 int goi_raster_densify_apply(long long P, const GoiDensifyRows* groups, int n_groups, const float* rotation, const float* scaling,
                              const float* z, long long n_split, long long kept_children, const void* workspace, void* stream);
+
+/* ---- Fixed-budget densification: MCMC relocation and position noise in place (csrc/mcmc.hip) --------------
+ * "3D Gaussian Splatting as Markov Chain Monte Carlo" (Kheradmand et al., 2024).  P never changes; everything is a device pointer
+ * and asynchronous on `stream`; nothing is read back.  0 <= P < 2^30.
+ *
+ * goi_mcmc_relocate.  opacity [P] fp32 ACTIVATED (sigmoid of the raw one), read only; draws [n_draws] int64 in [0, 2^32), read
+ *   only; selection [P] bytes or NULL (every row): a row with 0 is FROZEN -- never dead, never a source, never written.
+ *     dead_i    selected and (double)opacity_i <= min_opacity;  alive_i: selected and (double)opacity_i > min_opacity (a NaN
+ *               opacity is neither);  d_0 < d_1 < ... the dead rows in ascending id
+ *     w_i       (uint32)(min(opacity_i, 1) * 2^24) for alive rows (exact), 0 otherwise;  C_i = w_0 + ... + w_i (uint64), T = C_{P-1}
+ *     moves     min(n_dead, n_draws, max_moves, floor(n_alive * frac_num / frac_den)), in integers on the device; 0 when T == 0
+ *     t_j       floor(u_j * T / 2^32) for j < moves, u_j = draws[j] (the high half of the 64 x 64-bit product (u_j << 32) * T)
+ *     s_j       min{ i : C_i > t_j } (binary search, at most 32 steps);  r_i = #{ j < moves : s_j = i };  N_i = min(r_i + 1, n_max)
+ *   For every source (r_i >= 1), float64 with one rounding to fp32 at the store:
+ *     o  = min((double)opacity_i, 1 - 2^-24);   o' = 1 - pow(1 - o, 1 / N)   (N == 1: o' = o)
+ *     D  = sum_{m=1..N} sum_{k=0..m-1} (-1)^k (C(m-1, k) * Q[k]) * o'^(k+1): one accumulator in exactly this order, o'^(k+1) a
+ *          running product restarted at 1 for each m, odd k subtracted, Q[k] = 1 / sqrt((double)(k + 1)), C(n, k) exact in float64
+ *     c  = o / D;   new raw opacity = log(x / (1 - x)), x = min(max(o', min_opacity), 1 - 2^-24);   new raw log-scale = old + log(c)
+ *   Written, through the row groups (each `data` holds P rows of row_len floats, in place): dead row d_j receives row s_j of every
+ *   GOI_MCMC_PARAM group, and the new opacity / log-scale of s_j in the GOI_MCMC_OPACITY (row_len 1) / GOI_MCMC_SCALING (row_len 3)
+ *   group; source i receives the same new opacity and log-scale; every GOI_MCMC_MOMENT row of a SOURCE is zeroed, the dead rows'
+ *   moments stay as they were.  Every copy and the source itself see the source's OLD values: the new ones are staged in the
+ *   workspace by one kernel and written by a later one.  Nothing else is touched.
+ *   Outputs: counts [4] = {moves, n_dead, n_alive, sources hit}; status [1] int32, GOI_MCMC_STATUS_* bits, 0 after a good call;
+ *   hits [P] uint32 = r_i, or NULL (they stay in the workspace).  Integer atomics only: the same bits on every call.
+ *   P = 0 returns 0 and touches nothing.
+ *   Refused before any device call: P or n_draws outside [0, 2^30), max_moves < 0, frac_num outside [0, 2^32], frac_den outside
+ *   [1, 2^32], n_max outside 1..51, min_opacity outside [0, 1) (a NaN included), more than GOI_MCMC_MAX_GROUPS groups, a group with
+ *   row_len outside [1, 2^20], an unknown mode, a NULL or misaligned pointer, a second opacity or log-scale group or one of another
+ *   row length; then, with P > 0: a NULL required pointer, a misaligned one, a NULL or misaligned workspace
+ *   (goi_mcmc_relocate_workspace_bytes(P) bytes, 256-byte aligned; 0: P out of range).
+ *
+ * goi_mcmc_noise: xyz_i += Sigma_i (z_i g_i step) for every selected row, in place, one launch, no workspace.  Float64 throughout,
+ *   one rounding at the store: R from the raw quaternion rotation [P,4] normalised as build_rotation does it, s = exp(scaling [P,3]),
+ *   Sigma = (R diag s)(R diag s)^T, g = 1 / (1 + exp(-k ((1 - opacity) - x0))) with opacity [P] ACTIVATED, z [P,3] the caller's normal
+ *   draws, step = noise_lr * lr_xyz.  A frozen row (selection 0) is not written.  Refused: P out of range, a k, x0 or step that is
+ *   not finite, a NULL or misaligned pointer.
+ *
+ * goi_mcmc_debug_relocation_sum: D[i] for o_new[i] (float64) and N[i] (clamped to 1..51), n <= 2^24: the device function the
+ *   relocation uses, for a test that holds the sum to its restatement bit for bit. */
+#define GOI_MCMC_MAX_GROUPS 24
+#define GOI_MCMC_PARAM 0   /* a plain parameter: dead rows receive their source's row */
+#define GOI_MCMC_OPACITY 1 /* the raw opacity (row_len 1) */
+#define GOI_MCMC_SCALING 2 /* the raw log-scale (row_len 3) */
+#define GOI_MCMC_MOMENT 3  /* an Adam moment: the sources' rows are zeroed */
+#define GOI_MCMC_STATUS_DRAW 1   /* a draw outside [0, 2^32): its low 32 bits were used */
+#define GOI_MCMC_STATUS_SEARCH 2 /* a search ran out of its bound (cannot happen: t_j < T = C_{P-1}) */
+typedef struct GoiMcmcRows {
+    float* data;
+    int row_len;
+    int mode; /* GOI_MCMC_* */
+} GoiMcmcRows;
+size_t goi_mcmc_relocate_workspace_bytes(long long P);
+int goi_mcmc_relocate(long long P, const float* opacity, const int64_t* draws, long long n_draws, const unsigned char* selection,
+                      double min_opacity, long long max_moves, long long frac_num, long long frac_den, int n_max,
+                      const GoiMcmcRows* groups, int n_groups, unsigned* hits /*[P] or NULL*/, unsigned* counts /*[4]*/,
+                      int32_t* status, void* workspace, void* stream);
+int goi_mcmc_noise(long long P, float* xyz, const float* rotation, const float* scaling, const float* opacity, const float* z,
+                   const unsigned char* selection, double k, double x0, double step, void* stream);
+int goi_mcmc_debug_relocation_sum(int n, const double* o_new, const int32_t* N, double* D, void* stream);
 
 /* Lane utilisation of the blend kernels, counted on the device from what the forward of a frame left in its workspaces
  * (member masks, n_contrib, per-quadrant walk lengths): a diagnostic of the execution mapping, not part of the reference's
