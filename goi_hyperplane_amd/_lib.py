@@ -225,17 +225,25 @@ MCMC_SYMBOLS = {
     "goi_mcmc_noise": (C.c_int, [_LL] + [_P] * 6 + [C.c_double] * 3 + [_P]),
     "goi_mcmc_debug_relocation_sum": (C.c_int, [_I] + [_P] * 4),
 }
+# the as-rigid-as-possible deformation of a selection (csrc/deform.hip); a prefix of its own: bound through LATER_TABLES
+DEFORM_SYMBOLS = {
+    "goi_deform_solve_workspace_bytes": (C.c_size_t, [_I]),
+    "goi_deform_solve": (C.c_int, [_I, _I] + [_P] * 7 + [_I, _I, C.c_float] + [_P] * 4),
+    "goi_deform_energy_workspace_bytes": (C.c_size_t, [_I]),
+    "goi_deform_energy": (C.c_int, [_I, _I] + [_P] * 8),
+    "goi_deform_apply": (C.c_int, [_LL, _I, _I, _I, _P, _I, _P, _P, C.c_float] + [_P] * 10 + [_I, _P]),
+}
 # every symbol include/goi_raster.h declares under the goi_raster / semantic / knn / adam / codebook prefixes
 SYMBOLS = {**BASE_SYMBOLS, **KNN_GRAPH_SYMBOLS, **SMOOTH_SYMBOLS, **SEGMENT_SYMBOLS}
 # The entries that were MOVED out of csrc/api.hip into their families' units, with the frame's own: the set whose refusals
 # tests/test_entry_refusals_cpu.py records as they were before the move.  Entries added since are in LATER_TABLES and bring
 # their refusals in their own test files (tests/test_knn_graph_cpu.py, tests/test_pose_cpu.py, tests/test_smooth_entry_refusals_cpu.py,
 # tests/test_segment_entry_refusals_cpu.py, tests/test_instance_entry_refusals_cpu.py, tests/test_grouping_entry_refusals_cpu.py,
-# tests/test_mcmc_entry_refusals_cpu.py).
+# tests/test_mcmc_entry_refusals_cpu.py, tests/test_deform_entry_refusals_cpu.py).
 # load() binds both.
 SYMBOL_TABLES = (BASE_SYMBOLS, FIELD_SYMBOLS, MESH_SYMBOLS, TEXTURE_SYMBOLS, EDIT_SYMBOLS)
 LATER_TABLES = (KNN_GRAPH_SYMBOLS, POSE_SYMBOLS, SMOOTH_SYMBOLS, SEGMENT_SYMBOLS, INSTANCE_SYMBOLS, GROUPING_SYMBOLS,
-                MCMC_SYMBOLS)
+                MCMC_SYMBOLS, DEFORM_SYMBOLS)
 
 _lib = None
 
@@ -340,6 +348,12 @@ class GoiMcmcRows(C.Structure):
 
 MCMC_MAX_GROUPS = 24
 MCMC_PARAM, MCMC_OPACITY, MCMC_SCALING, MCMC_MOMENT = 0, 1, 2, 3  # GOI_MCMC_* of include/goi_raster.h
+
+
+class GoiDeformSH(C.Structure):
+    """include/goi_raster.h: GoiDeformSH"""
+    _fields_ = [("dirs1", C.c_float * 9), ("dirs2", C.c_float * 15), ("dirs3", C.c_float * 21), ("inv1", C.c_float * 9),
+                ("inv2", C.c_float * 25), ("inv3", C.c_float * 49)]
 
 
 class GoiEditTransform(C.Structure):

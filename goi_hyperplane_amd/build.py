@@ -52,6 +52,7 @@ UNITS = {
     "photometric.hip": [],
     "densify.hip": ["-ffp-contract=off"],  # the reference's elementwise torch ops, one rounding each
     "mcmc.hip": ["-ffp-contract=off"],  # the relocation sum and the noise are held to their float64 restatement: one rounding per operation
+    "deform.hip": ["-ffp-contract=off"],  # the solve and the apply are held to their float32 restatement: one rounding per operation
     "display.hip": ["-ffp-contract=off"],  # the viewer's blend a*b + c*d is compared bit for bit: no FMA
     "pca.hip": ["-ffp-contract=off"],  # the projection and its normalisations are one rounding per operation
     "field.hip": ["-ffp-contract=off"],  # the iso-surface's vertices are one rounding per operation (the density loop names its FMAs)

@@ -59,7 +59,8 @@ extern "C" {
  *    goi_knn_smooth_loss_workspace_bytes, goi_knn_smooth_loss, goi_knn_diffuse; goi_knn_segment_edges,
  *    goi_knn_segment_components_workspace_bytes, goi_knn_segment_components; goi_instance_members_workspace_bytes,
  *    goi_instance_members, goi_instance_stats_workspace_bytes, goi_instance_stats; goi_mask_contrast_workspace_bytes,
- *    goi_mask_contrast; goi_mcmc_relocate_workspace_bytes, goi_mcmc_relocate, goi_mcmc_noise, goi_mcmc_debug_relocation_sum
+ *    goi_mask_contrast; goi_mcmc_relocate_workspace_bytes, goi_mcmc_relocate, goi_mcmc_noise, goi_mcmc_debug_relocation_sum;
+ *    goi_deform_solve_workspace_bytes, goi_deform_solve, goi_deform_energy_workspace_bytes, goi_deform_energy, goi_deform_apply
  * 8: + the two _selected forward entries (a per-Gaussian selection the forward itself honours; folded by 9);
  *    later additions: goi_semantic_pca_workspace_bytes, goi_semantic_pca_accumulate, goi_semantic_pca_solve,
  *    goi_semantic_pca_apply; goi_field_density_workspace_bytes, goi_field_density, goi_field_iso_workspace_bytes,
@@ -970,6 +971,58 @@ int goi_mcmc_relocate(long long P, const float* opacity, const int64_t* draws, l
 int goi_mcmc_noise(long long P, float* xyz, const float* rotation, const float* scaling, const float* opacity, const float* z,
                    const unsigned char* selection, double k, double x0, double step, void* stream);
 int goi_mcmc_debug_relocation_sum(int n, const double* o_new, const int32_t* N, double* D, void* stream);
+
+/* ---- Non-rigid edits: as-rigid-as-possible deformation of a selection (csrc/deform.hip) --------------------
+ * Control nodes with rest positions x [M,3] on a graph idx [M,k] int32 (what goi_knn_graph returns), optional weight [M,k] (NULL: 1),
+ * and the graph's transpose in_ptr [M+1] / in_edge [M*k] (goi_knn_transpose).  Entry (i, m) is an edge iff 0 <= idx[i,m] < M and
+ * idx[i,m] != i; anything else is skipped and never used as an address.  Everything is a device pointer and asynchronous on `stream`;
+ * nothing is read back; no float atomics: the same bits on every call.  M * k < 2^30.
+ *
+ *     E = sum_i sum_{edges (i, m), j = idx[i,m]} w[i,m] |(y_i - y_j) - R(q_i) (x_i - x_j)|^2
+ *
+ * goi_deform_solve: y [M,3] and q [M,4] (w, x, y, z) hold the warm start on entry and the result on return.  `iterations` times:
+ *   POSITIONS (Jacobi, from the old y and q): a node with constrained[i] != 0 takes target[i]; a free node with
+ *   W = sum_out w + sum_in w > 0 takes (1 - relax) y_i + relax yhat_i, computed as y_i + relax (yhat_i - y_i) with
+ *   yhat_i - y_i = [sum_out w ((y_j - y_i) + R_i (x_i - x_j)) + sum_in w ((y_m - y_i) - R_m (x_m - x_i))] / W, out-edges in row order,
+ *   then in-edges in in_edge order, one accumulator (an undeformed graph gives exact zeros and keeps y's bits); W <= 0 keeps y_i.
+ *   Then ROTATIONS: A_i = sum_out w ((y_i - y_j)(x_i - x_j)^T) (symmetric bit for bit when y = x: no torque) and polar_iters
+ *   steps of omega = (sum_c r_c x a_c) / (|sum_c r_c . a_c| + 1e-9), q <- normalize(exp(omega) (x) q) over the columns r_c of R(q),
+ *   a_c of A_i; a zero omega, or one whose length is not finite, leaves q bit for bit.  constrained NULL: no node is constrained.  iterations = 0 or M = 0 returns 0 and
+ *   touches nothing.  Refused: M < 0, k < 1, M * k >= 2^30, iterations < 0, polar_iters < 0, relax outside (0, 1] (a NaN included);
+ *   then a NULL required pointer, a misaligned one, a NULL or misaligned workspace (goi_deform_solve_workspace_bytes(M) bytes).
+ *
+ * goi_deform_energy: *energy (float64, device) = E, every term formed in float64 and summed in a fixed order.
+ *
+ * goi_deform_apply: one launch over the P Gaussians.  A row takes part iff it is selected (selection [P] bytes, NULL: every row;
+ *   invert: the rows whose byte is 0) and its binding row bind_idx [P,kb] / bind_dist2 [P,kb] (the rows goi_knn_graph writes for the Gaussians as queries
+ *   and the nodes as references: knn.query) has a USED entry: 0 <= id < n_nodes and a finite distance.  With d_0^2 the first used entry's distance,
+ *   w_a = exp(-(d_a^2 - d_0^2) * (1 / (2 sigma^2))) normalised by their sum in entry order.  moments = 0 (source: the REST tensors
+ *   src_*, destination: the model, which may be the same memory):
+ *     xyz      = x + sum_a w_a [(y_a - x_a) + (R(q_a) - I)(x - x_a)]   (R - I from the quaternion's terms; a zero sum keeps x's bits)
+ *     q_g      = normalize(sum_a w_a s_a q_a), s_a = -1 where q_a . q_first < 0;  rotation = q_g (x) src_rotation
+ *     features_rest [P, M - 1, 3]: every stored band l = 1..3 times D_l(R(q_g)) per channel, built per row as
+ *              D_l c = inv_l (Y_l(R^T dirs_l) c) from the constants of GoiDeformSH
+ *     a row whose q_g has a zero vector part gets src_rotation's and src_features_rest's bits.
+ *   moments = 1 (in place; src_* are not read; any of xyz, rotation, features_rest may be NULL): the rows' Adam first moments
+ *     turned by the same q_g: xyz <- R(q_g) m, rotation <- q_g (x) m, features_rest <- D_l m; a row with the identity is not written.
+ *   Rows that do not take part are neither read nor written.  P = 0 or n_nodes = 0 returns 0 and touches nothing.
+ *   Refused: P outside [0, 2^31), M not in 1, 4, 9, 16, n_nodes outside [0, 2^30), kb outside 1..8, P * kb >= 2^31, a sigma that is
+ *   not finite and > 0, moments not 0 or 1, sh NULL; then a NULL required pointer or a misaligned one. */
+typedef struct GoiDeformSH {
+    float dirs1[9], dirs2[15], dirs3[21]; /* 2 l + 1 unit directions per band, [n][3] */
+    float inv1[9], inv2[25], inv3[49];    /* the inverse of the band's basis at those directions, row-major */
+} GoiDeformSH;
+size_t goi_deform_solve_workspace_bytes(int M);
+int goi_deform_solve(int M, int k, const float* x, const int32_t* idx, const float* weight, const int32_t* in_ptr,
+                     const int32_t* in_edge, const unsigned char* constrained, const float* target, int iterations, int polar_iters,
+                     float relax, float* y, float* q, void* workspace, void* stream);
+size_t goi_deform_energy_workspace_bytes(int M);
+int goi_deform_energy(int M, int k, const float* x, const int32_t* idx, const float* weight, const float* y, const float* q,
+                      double* energy, void* workspace, void* stream);
+int goi_deform_apply(long long P, int M, int n_nodes, int kb, const unsigned char* selection, int invert, const int32_t* bind_idx,
+                     const float* bind_dist2, float sigma, const float* node_x, const float* node_y, const float* node_q,
+                     const GoiDeformSH* sh, const float* src_xyz, const float* src_rotation, const float* src_features_rest,
+                     float* xyz, float* rotation, float* features_rest, int moments, void* stream);
 
 /* Lane utilisation of the blend kernels, counted on the device from what the forward of a frame left in its workspaces
  * (member masks, n_contrib, per-quadrant walk lengths): a diagnostic of the execution mapping, not part of the reference's
